@@ -12,11 +12,16 @@ A "step" = one pass of the hot path (brutus_fit_batch: star vectors resident in
 HBM -> compact per-star survivor records in HBM) over one batch of `--batch`
 (default 512) DISTINCT synthetic stars against the 750k-model x 12-band grid, in
 sub-batches of `--sub-batch` stars.  Workload = BASELINE.json configs[1]
-(Av-only: rvlim=(3.32, 3.32), no parallax) -> `value`; configs[2] (Av+Rv free,
-parallax prior) is timed the same way in the same run -> `other_config`
-(`--config 3` swaps them).  `roofline.frac` = stars/s x 108 MB / 8 TB/s for the
-whole step; `roofline.kernels` lists every kernel with its own
-algorithmic bytes.
+(Av-only: rvlim=(3.32, 3.32), no parallax) -> `value` (`--config 3`: configs[2],
+Av+Rv free, parallax prior).  `roofline.frac` = stars/s x 108 MB / 8 TB/s for the
+whole step.
+
+A plain run sets up, warms up, times exactly `--steps` steps once and prints the
+line.  `--full` adds everything else: 5 timed repeats (median / min / max), the other
+configuration -> `other_config`, the SURVEY 8(d) and sharp-posterior grids, parity
+blocks, per-kernel timing (`roofline.kernels`, every kernel with its own algorithmic
+bytes), end-to-end fit() legs, CPU baselines and cluster mode.  `--dump-outputs DIR`
+writes what the last timed step computed to DIR/*.npy (dump_last_step).
 """
 import argparse
 import json
@@ -58,11 +63,20 @@ def parse():
                          "4: configs[3], the sharded 1M-star catalogue = configs[2] with "
                          "--scaling strong --steps 250 --batch 4000 (the same line); "
                          "5: cluster.isochrone_loglike (configs[4], supplementary line)")
-    ap.add_argument("--repeats", type=int, default=5,
-                    help="timed repeats of the K steps (SURVEY 8(d): >= 5 repeats of the whole "
-                         "star set): every repeat times EXACTLY `--steps` steps between two "
-                         "barrier + synchronize fences; `value` is the median, min / max and "
-                         "every repeat's time ride along")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: 5 timed repeats, the second configuration, "
+                         "the SURVEY 8(d) and sharp-posterior grids, parity blocks, per-kernel timing "
+                         "and roofline tables, end-to-end fit() legs, CPU baselines, cluster mode.  "
+                         "Without it a run sets up, warms up, times the `--steps` steps once and "
+                         "prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed to DIR/<name>.npy "
+                         "(float32 / float64, < 64 MB; see dump_last_step)")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed repeats of the K steps (default 1; 5 with --full, SURVEY 8(d): >= 5 "
+                         "repeats of the whole star set): every repeat times EXACTLY `--steps` steps "
+                         "between two barrier + synchronize fences; `value` is the median, min / max "
+                         "and every repeat's time ride along")
     ap.add_argument("--no-parity", action="store_true",
                     help="skip the parity block (a few timed stars re-checked against the C "
                          "restatement, 16 end-to-end objects against the oracle)")
@@ -421,32 +435,9 @@ def bench_cluster(args, emit=True):
         tt = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
-    # the same with the plug-in's time taken out, and with a point table that is revisited
-    t_plug = 0.
-    for k in range(min(args.steps, 16)):
-        th = theta0 + np.array([1e-3, 1e-3, 1e-3, 0., 0.5, 1e-3]) * walk[k]
-        t1 = time.perf_counter()
-        iso.get_seds_grid(smf_grid=iso.smf_grid, feh=th[0], loga=th[1], av=th[2], rv=th[3],
-                          eep=np.linspace(202., 808., 2000), dist=th[4])
-        t_plug += time.perf_counter() - t1
-    t_plug /= min(args.steps, 16)
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    for k in range(args.steps):
-        call(0)
-    torch.cuda.synchronize()
-    dt_hit = (time.perf_counter() - t1) / args.steps
-    # device block alone (HIP events on the launch stream)
-    L.brutus_enable_timing(1)
-    call(1)
-    n = C.c_int(0)
-    names = (C.c_char_p * 8)()
-    ms = (C.c_float * 8)()
-    L.brutus_last_timing(C.byref(n), names, ms, 8)
-    L.brutus_enable_timing(0)
-    k_ms = dict((names[j].decode(), float(ms[j])) for j in range(n.value)).get("k_cluster")
+    if rank == 0 and emit and args.dump_outputs:
+        _save_outputs(args.dump_outputs, {"lnl_tot": np.array([val], dtype=np.float64)})
     npts = 2000 + 14 * int(np.sum(iso.eep_grid <= 480.))     # evolved points only in slice 0
-    npts_run = 15 * 2000                                     # the kernel walks the dropped ones too
     pairs = float(nobj) * npts
     line = {
         "metric": "isochrone_loglike evaluations/s (5k stars x 12 bands x 15 SMF x 2000 EEP)",
@@ -459,33 +450,59 @@ def bench_cluster(args, emit=True):
                    "parallelism": "replicas only, %d rank(s)" % world,
                    "timed_region": "whole isochrone_loglike call: host arrays in, lnl_tot out"},
         "star_points_per_s": world * pairs * args.steps / dt,
-        "plugin_ms_per_step": 1e3 * t_plug,
-        "library_ms_per_step": 1e3 * (dt / args.steps - t_plug),
-        "revisited_table_evaluations_per_s": 1. / dt_hit,
     }
-    if k_ms:
-        # the block re-reads only the 2.9 MB point table per 64-object workgroup:
-        # it is bound by f64 VALU issue, the HBM figure is shown for completeness
-        alg = 8. * (npts * (args.nfilt + 1) + nobj * (2 * args.nfilt + 3))
-        flops = pairs * (3. * args.nfilt + 40.)
-        tf = flops / (k_ms * 1e-3) / 1e12
-        line["roofline"] = {"bound": "vector f64 (the block re-reads a 2.9 MB point table per 64-object "
-                                     "workgroup: HBM sees next to nothing)",
-                            "kernel": "k_cluster", "achieved": tf, "peak": 78.6, "unit": "TFLOP/s",
-                            "frac": tf / 78.6, "traffic": None, "avg_launch_ms": k_ms,
-                            "hbm_algorithmic_gbs": alg / (k_ms * 1e-3) / 1e9,
-                            "device_star_points_per_s": pairs / (k_ms * 1e-3)}
-    if rank == 0 and world == 1 and args.cpu_seconds > 0:
-        from oracle import brutus_oracle as O
-        sub = max(16, min(nobj, int(100 * args.cpu_seconds / 10.)))
-        t0 = time.perf_counter()
-        O.isochrone_loglike(theta0, iso, phot[:sub], err[:sub], parallax=par[:sub],
-                            parallax_err=perr[:sub])
-        dc = time.perf_counter() - t0
-        line["cpu_baseline"] = {"value": (sub / dc) / nobj, "unit": "evaluations/s",
-                                "cores": 1, "kind": "port",
-                                "sample": "oracle numpy restatement on %d of the %d objects "
-                                          "(%.1f s), scaled to a full evaluation" % (sub, nobj, dc)}
+    if args.full:
+        # beside the headline: the step without the plug-in's time, a revisited point table, the
+        # device block alone against the vector float64 peak, the CPU leg
+        t_plug = 0.
+        for k in range(min(args.steps, 16)):
+            th = theta0 + np.array([1e-3, 1e-3, 1e-3, 0., 0.5, 1e-3]) * walk[k]
+            t1 = time.perf_counter()
+            iso.get_seds_grid(smf_grid=iso.smf_grid, feh=th[0], loga=th[1], av=th[2], rv=th[3],
+                              eep=np.linspace(202., 808., 2000), dist=th[4])
+            t_plug += time.perf_counter() - t1
+        t_plug /= min(args.steps, 16)
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        for k in range(args.steps):
+            call(0)
+        torch.cuda.synchronize()
+        dt_hit = (time.perf_counter() - t1) / args.steps
+        # device block alone (HIP events on the launch stream)
+        L.brutus_enable_timing(1)
+        call(1)
+        n = C.c_int(0)
+        names = (C.c_char_p * 8)()
+        ms = (C.c_float * 8)()
+        L.brutus_last_timing(C.byref(n), names, ms, 8)
+        L.brutus_enable_timing(0)
+        k_ms = dict((names[j].decode(), float(ms[j])) for j in range(n.value)).get("k_cluster")
+        line.update(plugin_ms_per_step=1e3 * t_plug,
+                    library_ms_per_step=1e3 * (dt / args.steps - t_plug),
+                    revisited_table_evaluations_per_s=1. / dt_hit)
+        if k_ms:
+            # the block re-reads only the 2.9 MB point table per 64-object workgroup:
+            # it is bound by f64 VALU issue, the HBM figure is shown for completeness
+            alg = 8. * (npts * (args.nfilt + 1) + nobj * (2 * args.nfilt + 3))
+            flops = pairs * (3. * args.nfilt + 40.)
+            tf = flops / (k_ms * 1e-3) / 1e12
+            line["roofline"] = {"bound": "vector f64 (the block re-reads a 2.9 MB point table per 64-object "
+                                         "workgroup: HBM sees next to nothing)",
+                                "kernel": "k_cluster", "achieved": tf, "peak": 78.6, "unit": "TFLOP/s",
+                                "frac": tf / 78.6, "traffic": None, "avg_launch_ms": k_ms,
+                                "hbm_algorithmic_gbs": alg / (k_ms * 1e-3) / 1e9,
+                                "device_star_points_per_s": pairs / (k_ms * 1e-3)}
+        if rank == 0 and world == 1 and args.cpu_seconds > 0:
+            from oracle import brutus_oracle as O
+            sub = max(16, min(nobj, int(100 * args.cpu_seconds / 10.)))
+            t0 = time.perf_counter()
+            O.isochrone_loglike(theta0, iso, phot[:sub], err[:sub], parallax=par[:sub],
+                                parallax_err=perr[:sub])
+            dc = time.perf_counter() - t0
+            line["cpu_baseline"] = {"value": (sub / dc) / nobj, "unit": "evaluations/s",
+                                    "cores": 1, "kind": "port",
+                                    "sample": "oracle numpy restatement on %d of the %d objects "
+                                              "(%.1f s), scaled to a full evaluation" % (sub, nobj, dc)}
     if rank == 0 and emit:
         emit_line(line)
     if world > 1 and emit:
@@ -608,10 +625,72 @@ def TIMER_OF(kernel):
     return k
 
 
-def run_config(config, args, L, grid, models, dev, world, rank, dist, torch, star_kw=None):
+def _save_outputs(d, arrays):
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), a)
+
+
+DUMP_BYTES = 48 << 20       # what --dump-outputs writes at most (the limit is 64 MB)
+
+
+def dump_last_step(d, one, idxs, torch):
+    """--dump-outputs: what brutus_fit_batch returned for the stars of the last timed step
+    (sub-batches `idxs` of the job), recomputed after the clock stopped: every engine's record
+    buffers are overwritten by its next call, and the path is deterministic.  Per star:
+    `n_selected` (records kept), `ndim`, `k1`, `k2`, and `lnlike_sum` over all of its records.
+    A fixed sample of the records themselves (as many as DUMP_BYTES allows, evenly spaced over
+    each sub-batch's records in the order a caller receives them: star by star, ascending model
+    index): `record_star` (star of the step), `record_model`, `lnlike`, `chi2`, `scale`, `av`,
+    `rv` and `icov6` (00, 01, 02, 11, 12, 22)."""
+    per_sub = DUMP_BYTES // ((2 + 11) * 8) // max(1, len(idxs))
+    per_star = {k: [] for k in ("n_selected", "ndim", "k1", "k2")}
+    sums, stars, models, vals = [], [], [], []
+    base = 0
+    for i in idxs:
+        rec, ndim, k1, k2 = one(i)
+        off = rec.off.cpu().numpy()
+        total = int(off[-1])
+        per_star["n_selected"].append(np.diff(off))
+        per_star["ndim"].append(ndim.cpu().numpy())
+        per_star["k1"].append(k1)
+        per_star["k2"].append(k2)
+        slot = rec.slot[:total].long()
+        lnl = rec.vals[0].index_select(0, slot)
+        for s in range(len(off) - 1):
+            sums.append(lnl[int(off[s]):int(off[s + 1])].sum())
+        k = min(per_sub, total)
+        if k:
+            dev = rec.idx.device
+            pos = ((torch.arange(k, dtype=torch.float64, device=dev) + 0.5) * (total / k)).long()
+            stars.append(torch.searchsorted(rec.off, pos, right=True) - 1 + base)
+            models.append(rec.idx.index_select(0, pos))
+            v = rec.vals.index_select(1, slot.index_select(0, pos))
+            if rec.rv_const is not None:
+                v[4] = rec.rv_const
+            vals.append(v)
+        base += len(off) - 1
+    out = {k: np.concatenate(v).astype(np.float64) for k, v in per_star.items()}
+    out["lnlike_sum"] = torch.stack(sums).cpu().numpy()
+    if vals:
+        vals = torch.cat(vals, dim=1).cpu().numpy()           # (11, records)
+        out["record_star"] = torch.cat(stars).cpu().numpy().astype(np.float64)
+        out["record_model"] = torch.cat(models).cpu().numpy().astype(np.float64)
+    else:
+        vals = np.zeros((11, 0))
+        out["record_star"] = out["record_model"] = np.zeros(0)
+    for j, name in enumerate(("lnlike", "chi2", "scale", "av", "rv")):
+        out[name] = np.ascontiguousarray(vals[j])
+    out["icov6"] = np.ascontiguousarray(vals[5:11].T)
+    _save_outputs(d, out)
+
+
+def run_config(config, args, L, grid, models, dev, world, rank, dist, torch, star_kw=None,
+               dump=None):
     """Time `args.steps` steps of configs[config - 1] on this rank; returns a dict with
     the whole-job rate and the per-kernel durations.  A step = `args.batch` DISTINCT
-    stars, pushed through brutus_fit_batch in sub-batches of `args.sub_batch`."""
+    stars, pushed through brutus_fit_batch in sub-batches of `args.sub_batch`.  `dump`: the
+    directory --dump-outputs names."""
     from brutus_amd import _lib, fitting, synth
     nmodel, nfilt = args.nmodel, args.nfilt
     kw = dict(rvlim=(3.32, 3.32)) if config == 2 else dict()
@@ -714,6 +793,8 @@ def run_config(config, args, L, grid, models, dev, world, rank, dist, torch, sta
     if [en.regrown for en in engines] != grown:
         raise SystemExit("record buffers grew inside the timed region: timing invalid")
     nsel_total = int(out[0].counts[0])
+    if dump and rank == 0:
+        dump_last_step(dump, one, range(max(0, len(subs) - nsub), len(subs)), torch)
     med = int(np.argsort(job)[len(job) // 2])          # the median repeat
     dt = job[med]
     per_rank = [own[med]]
@@ -860,6 +941,13 @@ def main():
     global FULL_LINE
     args = parse()
     FULL_LINE = bool(args.full_line)
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    if not args.full:
+        # a plain run measures the headline and nothing else
+        args.single_config = args.no_survey_grid = args.no_sharp = args.no_cluster = True
+        args.no_parity = args.no_kernel_timing = True
+        args.e2e_stars, args.cpu_seconds = 0, 0.
     if args.config == 5:
         return bench_cluster(args)
     cfg4 = args.config == 4
@@ -908,7 +996,8 @@ def main():
 
     main_cfg = args.config
     other_cfg = 3 if main_cfg == 2 else 2
-    res = run_config(main_cfg, args, L, grid, models, dev, world, rank, dist, torch)
+    res = run_config(main_cfg, args, L, grid, models, dev, world, rank, dist, torch,
+                     dump=args.dump_outputs)
     res_other = None
     if not args.single_config:
         res_other = run_config(other_cfg, args, L, grid, models, dev, world, rank, dist, torch)

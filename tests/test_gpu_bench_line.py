@@ -1,6 +1,7 @@
 """The bench line's contract on a small grid (GPU): one JSON line with the driver's keys, the
 SURVEY 8(d) protocol (timed repeats, median / min / max), the `roofline` and `cpu_baseline`
-objects and the parity blocks -- all of them green."""
+objects and the parity blocks -- all of them green (`--full`); a plain run times exactly
+`--steps` steps and nothing else, and `--dump-outputs` writes the same arrays on every run."""
 import json
 import os
 import subprocess
@@ -60,7 +61,7 @@ def test_compact_line_of_a_full_size_record_fits_the_driver():
 
 @pytest.mark.gpu
 def test_bench_line_contract_small_grid():
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--nmodel", "60000", "--steps", "3",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--nmodel", "60000", "--steps", "3",
            "--warmup", "1", "--batch", "128", "--sub-batch", "64", "--repeats", "3",
            "--e2e-stars", "64", "--cpu-seconds", "1", "--cluster-stars", "300"]
     out = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
@@ -131,7 +132,7 @@ def test_bench_two_ranks_on_one_device_over_gloo():
     env = dict(os.environ, BRUTUS_BENCH_ONE_DEVICE="1", BRUTUS_BENCH_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--config", "3", "--scaling", "strong",
+           os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--config", "3", "--scaling", "strong",
            "--nmodel", "60000", "--steps", "4", "--warmup", "1", "--batch", "128", "--sub-batch", "64",
            "--repeats", "2", "--streams", "2", "--single-config", "--no-survey-grid", "--no-sharp",
            "--no-cluster", "--e2e-stars", "0", "--cpu-seconds", "0"]
@@ -146,3 +147,49 @@ def test_bench_two_ranks_on_one_device_over_gloo():
     assert "2 rank(s)" in d["config"]["parallelism"]
     p = d["parity"]
     assert p["sel_equal"] and p["k1_k2_equal"] and p["max_rel"] < 1e-8, p
+
+
+PLAIN_KEYS = {
+    "metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
+    "scaling", "vs_baseline", "dtype", "data", "config", "ranks_seen", "statistic", "repeats",
+    "value_min", "value_max", "repeat_s", "per_rank_s", "timed_region_s", "roofline", "detail"}
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_steps_once_and_dumps_its_outputs(tmp_path):
+    """Without --full: one timed pass of exactly `--steps` steps, the headline keys only, and
+    --dump-outputs writes float32 / float64 arrays under 64 MB -- identical from run to run."""
+    import numpy as np
+    dumps = []
+    for run in range(2):
+        d = tmp_path / ("out%d" % run)
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--nmodel", "60000",
+               "--steps", "3", "--warmup", "1", "--batch", "128", "--sub-batch", "64",
+               "--dump-outputs", str(d)]
+        out = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+        assert out.returncode == 0, out.stderr.decode("utf-8", "replace")[-3000:]
+        d_line = json.loads(out.stdout.decode().strip().splitlines()[-1])
+        assert set(d_line) == PLAIN_KEYS, sorted(set(d_line) ^ PLAIN_KEYS)
+        assert d_line["steps"] == 3 and d_line["repeats"] == 1 and len(d_line["repeat_s"]) == 1
+        assert d_line["ms_per_step"] * 3 == pytest.approx(1e3 * d_line["repeat_s"][0], rel=1e-4)
+        assert d_line["unit"] == "stars/s" and d_line["higher_is_better"] and d_line["dtype"] == "f64"
+        files = sorted(os.listdir(str(d)))
+        arrays = {f[:-4]: np.load(str(d / f)) for f in files}
+        assert sum(os.path.getsize(str(d / f)) for f in files) < 64 << 20
+        for name, a in arrays.items():
+            assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+            assert np.isfinite(a).all(), name
+        assert arrays["n_selected"].shape == (128,) and arrays["n_selected"].sum() > 0
+        n = arrays["record_star"].size
+        assert 0 < n <= arrays["n_selected"].sum()
+        for name in ("record_model", "lnlike", "chi2", "scale", "av", "rv"):
+            assert arrays[name].shape == (n,), name
+        assert arrays["icov6"].shape == (n, 6)
+        # sampled records in the order a caller receives them: star by star, ascending model
+        st, mo = arrays["record_star"], arrays["record_model"]
+        assert np.all((np.diff(st) > 0) | ((np.diff(st) == 0) & (np.diff(mo) > 0)))
+        assert np.all(arrays["n_selected"][st.astype(int)] > 0)
+        dumps.append(arrays)
+    assert sorted(dumps[0]) == sorted(dumps[1])
+    for name in dumps[0]:
+        assert np.array_equal(dumps[0][name], dumps[1][name], equal_nan=True), name

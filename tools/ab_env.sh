@@ -10,7 +10,7 @@ cd $R
 for rep in 1 2; do
 for v in $a $b; do
   for cfg in $cfgs; do
-    env $var=$v python bench.py --config $cfg --single-config --no-survey-grid --no-sharp --no-cluster \
+    env $var=$v python bench.py --full --config $cfg --single-config --no-survey-grid --no-sharp --no-cluster \
         --e2e-stars 0 --cpu-seconds 0 --steps 10 --warmup 2 --repeats 3 "$@" > $O/${tag}_line.json 2> $O/${tag}_err.txt || tail -5 $O/${tag}_err.txt >> $O/${tag}_ab.txt
     python - "$var=$v" $cfg $rep >> $O/${tag}_ab.txt <<'PY'
 import json, sys

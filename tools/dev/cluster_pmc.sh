@@ -2,7 +2,7 @@
 # SQ counters of k_cluster on the bench's cluster workload:  tools/dev/cluster_pmc.sh <tag>
 tag=${1:-clsq}
 R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out; mkdir -p $O
-W="python $R/bench.py --config 5 --steps 20 --warmup 2 --cpu-seconds 0"
+W="python $R/bench.py --full --config 5 --steps 20 --warmup 2 --cpu-seconds 0"
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_SMEM SQ_INSTS_VMEM SQ_INSTS_LDS -d $O/${tag}_a -o p -- $W > $O/${tag}_a.log 2>&1
 rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY -d $O/${tag}_b -o p -- $W > $O/${tag}_b.log 2>&1

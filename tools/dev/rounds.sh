@@ -5,7 +5,7 @@ BRUTUS_FLUX_ROUNDS=$r python - <<PY
 import os, sys, json, subprocess, ctypes as C
 sys.path.insert(0, os.getcwd())
 import bench
-sys.argv = ["bench.py", "--single-config", "--steps", "20", "--warmup", "4", "--repeats", "3", "--cpu-seconds", "0",
+sys.argv = ["bench.py", "--full", "--single-config", "--steps", "20", "--warmup", "4", "--repeats", "3", "--cpu-seconds", "0",
             "--e2e-stars", "0", "--no-survey-grid", "--no-cluster", "--no-parity", "--no-kernel-timing", "--config", os.environ.get("CFG", "2")]
 import io, contextlib
 buf = io.StringIO()

@@ -650,6 +650,37 @@ def gen_psd():
           % (bad0.sum(), n, len(sel)))
 
 
+def gen_fresh():
+    """Inputs and reference outputs of tests/test_oracle_vs_reference.py: `loglike` (all seven
+    return values) and one `_fit` yield per star, RandomState(7 + i), on a 700 x 6 MIST-like grid."""
+    models, labels, lmask = synth.make_mist_like_grid(700, 6, seed=99)
+    st = synth.make_stars(models, 3, seed=98)
+    st["mask"][1, 2] = False
+    m64 = models.astype(np.float64)
+    BF = F.BruteForce(m64, labels, lmask)
+    from oracle import brutus_oracle as O
+    lnprior = O.static_lnprior(labels, lmask)
+    res = {}
+    for i in range(3):
+        ref = F.loglike(st["flux"][i].copy(), st["err"][i].copy(), st["mask"][i].copy(),
+                        m64.copy(), parallax=st["parallax"][i],
+                        parallax_err=st["parallax_err"][i], return_vals=True)
+        for j, v in enumerate(ref):
+            res["loglike_%d_%d" % (i, j)] = np.asarray(v)
+        sl = slice(i, i + 1)
+        r = next(BF._fit(st["flux"][sl].copy(), st["err"][sl].copy(), st["mask"][sl].copy(),
+                         parallax=st["parallax"][sl], parallax_err=st["parallax_err"][sl],
+                         Nmc_prior=20, lnprior=lnprior.copy(), lngalprior=galprior,
+                         data_coords=st["coords"][sl], rstate=np.random.RandomState(7 + i),
+                         Ndraws=50))
+        for j, v in enumerate(r):
+            res["fit_%d_%d" % (i, j)] = np.asarray(v)
+    np.savez_compressed(os.path.join(OUT, "oracle_fresh.npz"), grid_nmodel=700, grid_nfilt=6,
+                        grid_seed=99, flux=st["flux"], err=st["err"], mask=st["mask"],
+                        parallax=st["parallax"], parallax_err=st["parallax_err"],
+                        coords=st["coords"], lnprior=lnprior, seed0=7, **res)
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     which = sys.argv[1:] or ["loglike", "fit", "helpers", "setup", "galprior",
@@ -684,4 +715,6 @@ if __name__ == "__main__":
         gen_loglike()
     if "fit" in which:
         gen_fit()
+    if "fresh" in which:
+        gen_fresh()
 

@@ -2,9 +2,8 @@
 under shims for the third-party modules that are absent from this image.
 
 This module is test-infrastructure tooling.  It is used ONLY by
-`tools/gen_golden.py` and by the optional `tests/test_oracle_vs_reference.py`
-(which skips itself when `/root/reference` is not present, e.g. on the GPU box).
-Nothing in the product package imports it.
+`tools/gen_golden.py`, which stores the reference's outputs under tests/golden/.
+Nothing in the product package or the test suite imports it.
 
 Shims:
   * `numba.jit` -> identity decorator, so the four `@jit(nopython=True)` loops

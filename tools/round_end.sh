@@ -26,7 +26,7 @@ python tools/sq_to_json.py $O/${tag}_sq_cfg2_a.txt 2 128 3 $O/${tag}_sq_valu.jso
 python tools/sq_to_json.py $O/${tag}_sq_cfg3_a.txt 3 128 3 $O/${tag}_sq_valu.json $S >> $O/${tag}_tables.log 2>&1
 cp $O/${tag}_sq_valu.json profiles/sq_valu.json
 cp $O/${tag}_pmc_traffic.json profiles/pmc_traffic.json
-python bench.py > $O/${tag}_bench_default.json 2> $O/${tag}_bench.err
+python bench.py --full > $O/${tag}_bench_default.json 2> $O/${tag}_bench.err
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats -d $O/${tag}_np -o p -- python $R/tools/e2e_np.py 2048 > $O/${tag}_np.log 2>&1
 rocprofv3 --kernel-trace --stats -d $O/${tag}_ph -o p -- python $R/tools/e2e_seq.py > $O/${tag}_ph.log 2>&1
