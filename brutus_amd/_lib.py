@@ -79,6 +79,10 @@ SIGNATURES = {
     "brutus_fit_batch": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp,
                                    _i32, C.POINTER(Params), _vp, _sz, _i64, _vp, _vp,
                                    _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "brutus_cut_workspace_bytes": (_sz, [_i64, _i32]),
+    "brutus_cut_batch": (C.c_int, [_i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32,
+                                   _vp, _vp, _dbl, _vp, _sz, _i64, _i64, _vp, _vp, _vp, _vp, _vp,
+                                   _vp]),
     "brutus_last_timing": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_char_p),
                                      C.POINTER(C.c_float), C.c_int]),
     "brutus_enable_timing": (None, [C.c_int]),

@@ -60,6 +60,7 @@
 #include "mt_kernels.hpp"
 #include "post_kernels.hpp"
 #include "offsets_kernels.hpp"
+#include "cut_kernels.hpp"
 
 namespace {
 
@@ -1410,6 +1411,137 @@ int brutus_fit_batch(const float *d_grid_soa, int64_t nmodel, int nfilt, int nst
     (void)hipStreamSynchronize(st);
     if (rc) return rc;
     fix_k2(h_k2, nstar);
+    tm.collect();
+    return 0;
+}
+
+}  // extern "C"
+
+namespace {
+
+struct CutWs {
+    double *lnprob;       // (nstar, stride) first-cut statistic
+    double *part;         // (nstar, CUT_NCH) partial maxima
+    double *thr;          // (nstar) ln(wt_thresh) + max
+    int32_t *counts;      // (nstar, CUT_NCH) selected models per chunk
+    int64_t *offsets;     // (nstar, CUT_NCH) first record row of the chunk
+    int64_t *total;       // (1) selected models of the call
+    int64_t stride;       // row stride of lnprob: nmodel rounded up to even
+    size_t bytes;
+};
+
+CutWs carve_cut(char *base, int64_t nmodel, int nstar) {
+    CutWs w;
+    size_t off = 0;
+    auto take = [&](size_t n) {
+        char *q = base ? base + off : nullptr;
+        off += align_up(n);
+        return q;
+    };
+    w.stride = nmodel + (nmodel & 1);
+    w.lnprob = (double *)take(sizeof(double) * (size_t)nstar * (size_t)w.stride);
+    w.part = (double *)take(sizeof(double) * nstar * CUT_NCH);
+    w.thr = (double *)take(sizeof(double) * nstar);
+    w.counts = (int32_t *)take(sizeof(int32_t) * nstar * CUT_NCH);
+    w.offsets = (int64_t *)take(sizeof(int64_t) * nstar * CUT_NCH);
+    w.total = (int64_t *)take(sizeof(int64_t));
+    w.bytes = off + 256;      // (room to align a base that is not)
+    return w;
+}
+
+bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
+
+}  // namespace
+
+extern "C" {
+
+size_t brutus_cut_workspace_bytes(int64_t nmodel, int nstar) {
+    if (nmodel <= 0 || nmodel > (int64_t)1 << 31 || nstar < 1 || nstar > BRUTUS_MAX_BATCH) return 0;
+    return carve_cut(nullptr, nmodel, nstar).bytes;
+}
+
+int brutus_cut_batch(int64_t nmodel, int nstar, double *d_lnl, const double *d_chi2,
+                     const double *d_scale, const double *d_av, const double *d_rv,
+                     const double *d_icov, const double *d_parallax, const double *d_parallax_err,
+                     int has_parallax, int next, const double *d_ext_labels,
+                     const double *d_ext_par, double wt_thresh, void *d_workspace,
+                     size_t workspace_bytes, int64_t capacity, int64_t rec_base,
+                     int32_t *d_rec_idx, int32_t *d_rec_slot, double *d_rec_vals,
+                     int64_t *d_rec_off, int64_t *h_counts, void *stream) {
+    if (nmodel <= 0 || nmodel > (int64_t)1 << 31) return fail(BRUTUS_EINVAL, "bad nmodel");
+    if (nstar < 1 || nstar > BRUTUS_MAX_BATCH)
+        return fail(BRUTUS_EINVAL, "nstar=%d outside [1, %d]", nstar, BRUTUS_MAX_BATCH);
+    if (next < 0) return fail(BRUTUS_EINVAL, "next=%d is negative", next);
+    if (next > 0 && (!d_ext_labels || !d_ext_par))
+        return fail(BRUTUS_EINVAL, "next=%d but the label columns or their parameters are NULL", next);
+    if (!(wt_thresh > 0.) || !isfinite(wt_thresh))
+        return fail(BRUTUS_EINVAL, "wt_thresh must be positive and finite");
+    if (!d_lnl || !d_chi2 || !d_scale || !d_av || !d_rv || !d_icov || !d_workspace || !d_rec_idx ||
+        !d_rec_slot || !d_rec_vals || !d_rec_off || !h_counts)
+        return fail(BRUTUS_EINVAL, "NULL pointer");
+    if (capacity < 0 || capacity > INT32_MAX || rec_base < 0 || rec_base > capacity)
+        return fail(BRUTUS_EINVAL, "capacity outside [0, 2^31) or rec_base outside [0, capacity]");
+    char *base = (char *)(((uintptr_t)d_workspace + 255) & ~(uintptr_t)255);
+    CutWs w = carve_cut(base, nmodel, nstar);
+    if (w.bytes > workspace_bytes)
+        return fail(BRUTUS_ENOMEM, "workspace too small: need %zu bytes, got %zu", w.bytes,
+                    workspace_bytes);
+    const int has_par = (d_parallax && d_parallax_err) ? has_parallax : 0;
+    const double ln_wt = log(wt_thresh);
+    // chunks of whole workgroup steps (2 models per lane), CUT_NCH of them cover the grid
+    int64_t span = (nmodel + CUT_NCH - 1) / CUT_NCH;
+    span = (span + 2 * TILE - 1) / (2 * TILE) * (2 * TILE);
+    const bool vec = (nmodel & 1) == 0 && aligned16(d_lnl) && aligned16(d_scale) &&
+                     aligned16(d_icov) && (next == 0 || aligned16(d_ext_labels));
+    hipStream_t st = (hipStream_t)stream;
+    Timer tm(st);
+    const dim3 grid(CUT_NCH, nstar), block(TILE);
+    tm.begin("cut_stat");
+    if (vec)
+        hipLaunchKernelGGL(k_cut_stat<true>, grid, block, 0, st, nmodel, w.stride, span, nstar, d_lnl,
+                           d_scale, d_icov, d_parallax, d_parallax_err, has_par, next, d_ext_labels,
+                           d_ext_par, w.lnprob, w.part);
+    else
+        hipLaunchKernelGGL(k_cut_stat<false>, grid, block, 0, st, nmodel, w.stride, span, nstar, d_lnl,
+                           d_scale, d_icov, d_parallax, d_parallax_err, has_par, next, d_ext_labels,
+                           d_ext_par, w.lnprob, w.part);
+    tm.end();
+    tm.begin("cut_count");
+    hipLaunchKernelGGL(k_cut_count, grid, block, 0, st, nmodel, w.stride, span, w.lnprob, w.part,
+                       ln_wt, w.thr, w.counts);
+    hipLaunchKernelGGL(k_cut_offsets, dim3(1), dim3(CUT_OFF_T), 0, st, nstar, w.counts, rec_base,
+                       w.offsets, d_rec_off, w.total);
+    tm.end();
+    HIP_TRY(hipGetLastError());
+    int64_t total = 0;
+    HIP_TRY(hipMemcpyAsync(&total, w.total, sizeof(total), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    h_counts[0] = total;
+    h_counts[1] = rec_base + total;
+    if (rec_base + total > capacity) {
+        tm.collect();
+        return fail(BRUTUS_ENOMEM, "record buffer too small: %lld rows needed, capacity %lld",
+                    (long long)(rec_base + total), (long long)capacity);
+    }
+    CutPlanes pl;
+    pl.v[0] = d_lnl;
+    pl.v[1] = d_chi2;
+    pl.v[2] = d_scale;
+    pl.v[3] = d_av;
+    pl.v[4] = d_rv;
+    for (int q = 0; q < 6; ++q) pl.v[5 + q] = d_icov + (size_t)q * nstar * nmodel;
+    tm.begin("cut_scatter");
+    if (vec)
+        hipLaunchKernelGGL(k_cut_scatter<true>, grid, block, 0, st, nmodel, w.stride, span, nstar,
+                           w.lnprob, w.thr, w.counts, w.offsets, d_lnl, pl, next, d_ext_labels,
+                           d_ext_par, capacity, d_rec_idx, d_rec_slot, d_rec_vals);
+    else
+        hipLaunchKernelGGL(k_cut_scatter<false>, grid, block, 0, st, nmodel, w.stride, span, nstar,
+                           w.lnprob, w.thr, w.counts, w.offsets, d_lnl, pl, next, d_ext_labels,
+                           d_ext_par, capacity, d_rec_idx, d_rec_slot, d_rec_vals);
+    tm.end();
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
     tm.collect();
     return 0;
 }

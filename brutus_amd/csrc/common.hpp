@@ -1,7 +1,7 @@
 // common.hpp -- constants, error helper, per-star / per-model device structs, reductions
 // Part of the single translation unit brutus_kernels.hip (included there, in
 // this order: common, fastmath, grid_kernels, fit_kernels, cluster_kernels,
-// post_kernels); everything lives in that unit's anonymous namespace.
+// post_kernels, ..., cut_kernels); everything lives in that unit's anonymous namespace.
 #pragma once
 
 namespace {

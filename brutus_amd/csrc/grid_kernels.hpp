@@ -184,6 +184,27 @@ __device__ __forceinline__ void store_mle(const Planes &pl, int64_t o, const Mle
 // kernels
 // ---------------------------------------------------------------------------
 
+// The parallax fields of a star's StarPrep: the measurement for the cull (fitting.py:749-756)
+// and the scale-space Gaussian of the first cut (pdf.py:209, 252-255).  Shared by k_prep and
+// by the prologue of the cut kernels (cut_kernels.hpp), so both routes clip alike.
+__device__ __forceinline__ void prep_parallax(StarPrep &sp, int has_parallax,
+                                              const double *__restrict__ par,
+                                              const double *__restrict__ perr, int s) {
+    double p = nan(""), pe = nan("");
+    if (has_parallax) {
+        p = par[s];
+        pe = perr[s];
+    }
+    const bool fin = isfinite(p) && isfinite(pe);
+    sp.has_par = fin ? 1 : 0;
+    sp.par = fin ? p : 0.;
+    sp.par_ivar = fin ? 1. / (pe * pe) : 0.;
+    sp.sp_on = (fin && p / pe > 4.) ? 1 : 0;                  // pdf.py:209
+    const double pm = p > 0. ? p : 0.;                        // pdf.py:252-255
+    sp.sp_mean = sp.sp_on ? pm * pm + pe * pe : 0.;
+    sp.sp_var = sp.sp_on ? 2. * pe * pe * pe * pe + 4. * pm * pm * pe * pe : 0.;
+}
+
 // Per-star preparation (fitting.py:706-725).  One thread per star.
 __global__ void __launch_bounds__(64)
 k_prep(int nstar, int nfilt, const double *__restrict__ flux,
@@ -250,19 +271,7 @@ k_prep(int nstar, int nfilt, const double *__restrict__ flux,
     const double df = (double)(ndim - 3);
     sp.c0 = -log(exp2(df / 2.) * tgamma(df / 2.));
     sp.c1 = df / 2. - 1.;
-    double p = nan(""), pe = nan("");
-    if (has_parallax) {
-        p = par[s];
-        pe = perr[s];
-    }
-    const bool fin = isfinite(p) && isfinite(pe);
-    sp.has_par = fin ? 1 : 0;
-    sp.par = fin ? p : 0.;
-    sp.par_ivar = fin ? 1. / (pe * pe) : 0.;
-    sp.sp_on = (fin && p / pe > 4.) ? 1 : 0;                  // pdf.py:209
-    const double pm = p > 0. ? p : 0.;                        // pdf.py:252-255
-    sp.sp_mean = sp.sp_on ? pm * pm + pe * pe : 0.;
-    sp.sp_var = sp.sp_on ? 2. * pe * pe * pe * pe + 4. * pm * pm * pe * pe : 0.;
+    prep_parallax(sp, has_parallax, par, perr, s);
     sp.pad_ = 0;
     ndim_out[s] = ndim;
 }

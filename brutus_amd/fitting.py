@@ -153,6 +153,23 @@ class DeviceGrid(object):
         return self
 
 
+def ext_constraint_params(mean_std):
+    """`lnprior_ext` values (..., 2) = (mean, std) -> (..., 3) = (mean, 1 / std^2, ln(2 pi std^2)),
+    what `brutus_cut_batch` takes per (constraint, object); formed like the reference forms them
+    (fitting.py:2002-2008), one Python float at a time.  A constraint the reference skips
+    (non-finite mean or std <= 0) is (NaN, 0, 0)."""
+    ms = np.asarray(mean_std, dtype=np.float64)
+    out = np.zeros(ms.shape[:-1] + (3,), dtype=np.float64)
+    flat_in, flat_out = ms.reshape(-1, 2), out.reshape(-1, 3)
+    for i in range(flat_in.shape[0]):
+        mean, std = float(flat_in[i, 0]), float(flat_in[i, 1])
+        if np.isfinite(mean) and std > 0:
+            flat_out[i] = (mean, 1. / std ** 2, float(np.log(2. * np.pi * std ** 2)))
+        else:
+            flat_out[i, 0] = np.nan
+    return out
+
+
 class Records(object):
     """Indexed first-cut records of one `brutus_fit_batch` call, device resident
     (include/brutus_amd.h): record r of the batch = model `idx[r]` with values
@@ -208,6 +225,7 @@ class _Engine(object):
         self.torch = _torch()
         self.L = _lib.lib()
         self.grid = grid
+        self.mem_budget = mem_budget
         per_star = 104 * grid.nmodel + 65536       # workspace + records / full-grid outputs
         nb = int(max(1, min(_lib.MAX_BATCH, mem_budget // per_star)))
         if nb >= 64:
@@ -351,77 +369,123 @@ class _Engine(object):
                     if params.rvlim[0] == params.rvlim[1] == params.rv_gauss[0] else None)
         return Records(idx, slot, vals, off, rv_const, counts), ndim, k1, k2
 
-    def _fit_batch_device_full_grid(self, f, e, m, p, pe, has_par, params, chunk=8, ext=None):
+    def _fit_batch_device_full_grid(self, f, e, m, p, pe, has_par, params, chunk=None, ext=None):
         """`fit_batch_device` for more than 32 bands (33 - 64): the hot path's list kernels stop at
         32, the full-grid pipeline (`brutus_loglike_batch`: every model in float64) does not.  Its
-        outputs stay on the device, the parallax clip + first `wt_thresh` cut of `lnpost`
-        (reference fitting.py:976-991, pdf.py:209-218) are taken there too, and the selected models
-        come back as dense `Records` in ascending model order -- everything downstream (device
-        `lnpost`, host stage, HDF5) is the same code as for any other band count.  Slower per star
-        by the work the float32 proof saves, not by a different result.
+        outputs stay on the device, and `brutus_cut_batch` takes the parallax clip + first
+        `wt_thresh` cut of `lnpost` (reference fitting.py:976-991, pdf.py:209-218) there: per chunk
+        of stars the eleven planes are filled and cut straight into the engine's record buffers,
+        in ascending model order -- everything downstream (device `lnpost`, host stage, HDF5) is
+        the same code as for any other band count.  Slower per star by the work the float32 proof
+        saves, not by a different result.  The only host read per chunk is the row count.
 
-        `ext` = [(label column (Nmodel,) float64 on the device, means (S,), stds (S,))]: external
-        per-object Gaussian constraints on model labels (`lnprior_ext`, reference
-        fitting.py:1995-2009) -- they change lnlike over the WHOLE grid before the cut, which is
-        why they take this route at any band count: `lnlike += -((label - mean)^2 / std^2 + ln(2
-        pi std^2)) / 2` on the device, then the cut; the records carry the sum like the
-        reference's `results`."""
+        `ext` = (label columns (next, Nmodel) float64 on the device, `ext_constraint_params` of
+        the batch (next, S, 3)): external per-object Gaussian constraints on model labels
+        (`lnprior_ext`, reference fitting.py:1995-2009) -- they change lnlike over the WHOLE grid
+        before the cut, which is why they take this route at any band count; the records carry
+        the sum like the reference's `results`."""
         torch, L, g = self.torch, self.L, self.grid
         S = f.shape[0]
         dev = g.device
-        kw = dict(dtype=torch.float64, device=dev)
-        ln_wt = float(np.log(params.wt_thresh))
+        if chunk is None:
+            # eleven planes + the cut's statistic, float64, per star and model
+            chunk = self.mem_budget // 4 // (96 * g.nmodel)
+        chunk = int(max(1, min(chunk, S, _lib.MAX_BATCH)))
         k1 = np.zeros(S, dtype=np.int32)
         k2 = np.zeros(S, dtype=np.int32)
         ndim = torch.empty(S, dtype=torch.int32, device=dev)
-        par_h = p.cpu().numpy() if p is not None else np.full(S, np.nan)
-        perr_h = pe.cpu().numpy() if pe is not None else np.full(S, np.nan)
-        idx_parts, val_parts, counts = [], [], np.zeros(S, dtype=np.int64)
+        off = torch.empty(S + 1, dtype=torch.int64, device=dev)
+        counts = np.zeros(2, dtype=np.int64)
+        labels_t = ext_t = None
+        n_ext = 0
+        if ext is not None:
+            labels_t, ext_par = ext
+            n_ext = int(labels_t.shape[0])
+            if ext_par.shape != (n_ext, S, 3) or labels_t.shape[1] != g.nmodel:
+                raise ValueError("`ext` does not match the batch or the grid")
+        buffers = getattr(self, "_rec_bufs", None)
+        if buffers is None:
+            buffers = self._record_buffers(max(1 << 20, (S * g.nmodel) // 8))
+        base = 0
+        # `wt_thresh` None or -inf (`_make_params` stores 0): the first cut keeps every model
+        keep_all = not params.wt_thresh > 0
+        if keep_all and n_ext:
+            raise ValueError("external constraints need a positive `wt_thresh` on this route")
+
+        def grow(old, rows, need, done):
+            """Larger record buffers (sized for the whole batch at the rate of the `done` stars
+            so far) with the finished chunks' `rows` rows carried over."""
+            self.regrown += 1
+            self._rec_bufs = None
+            new = self._record_buffers(max(need, int(need * S / done * 1.25) + 4096))
+            new[0][:rows] = old[0][:rows]
+            new[1][:rows] = old[1][:rows]
+            new[2][:, :rows] = old[2][:, :rows]
+            return new
+
         with torch.cuda.device(dev):
+            fg = getattr(self, "_fg_planes", None)
+            if fg is None or fg.shape[1] < chunk:
+                self._fg_planes = fg = None
+                self._fg_planes = fg = torch.empty((_lib.NVALS, chunk, g.nmodel),
+                                                   dtype=torch.float64, device=dev)
+            nbytes = L.brutus_cut_workspace_bytes(g.nmodel, chunk)
+            cws = getattr(self, "_cut_ws", None)
+            if cws is None or cws.numel() < nbytes:
+                self._cut_ws = cws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
             for a in range(0, S, chunk):
                 b = min(S, a + chunk)
                 n = b - a
                 ws = self._workspace(n)
-                out = torch.empty((5 + 6, n, g.nmodel), **kw)      # lnl chi2 scale av rv | icov[6]
+                out = fg.view(-1)[:_lib.NVALS * n * g.nmodel].view(_lib.NVALS, n, g.nmodel)   # lnl chi2 scale av rv | icov[6]
                 k1c, k2c = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+                pa = p[a:b].data_ptr() if p is not None else None
+                pea = pe[a:b].data_ptr() if pe is not None else None
                 _lib.check(L.brutus_loglike_batch(
                     g.soa.data_ptr(), g.nmodel, g.nfilt, n, f[a:b].data_ptr(), e[a:b].data_ptr(),
-                    m[a:b].data_ptr(), p[a:b].data_ptr() if p is not None else None,
-                    pe[a:b].data_ptr() if pe is not None else None, has_par, params,
+                    m[a:b].data_ptr(), pa, pea, has_par, params,
                     ws.data_ptr(), ws.numel(), out[0].data_ptr(), out[1].data_ptr(),
                     out[2].data_ptr(), out[3].data_ptr(), out[4].data_ptr(), out[5].data_ptr(),
                     ndim[a:b].data_ptr(), k1c.ctypes.data, k2c.ctypes.data, None, None,
                     _stream_ptr(torch)))
                 k1[a:b], k2[a:b] = k1c, k2c
-                for s in range(n):
-                    for lab, means, stds in (ext or ()):
-                        mean, std = float(means[a + s]), float(stds[a + s])
-                        if np.isfinite(mean) and std > 0:
-                            ivar = 1. / std ** 2
-                            out[0, s] += -0.5 * ((lab - mean) ** 2 * ivar + float(np.log(2. * np.pi * std ** 2)))
-                    lnprob = out[0, s]
-                    pm, ps = float(par_h[a + s]), float(perr_h[a + s])
-                    if has_par and np.isfinite(pm) and np.isfinite(ps) and pm / ps > 4.:
-                        s_mean, s_std = parallax_to_scale(pm, ps)
-                        serr = 1. / torch.sqrt(out[5, s].abs())               # fitting.py:976-981
-                        var = float(s_std) ** 2 + serr ** 2
-                        lnprob = lnprob - 0.5 * ((out[2, s] - float(s_mean)) ** 2 / var
-                                                 + torch.log(2. * np.pi * var))
-                    lnprob = torch.where(torch.isfinite(lnprob), lnprob,
-                                         torch.full_like(lnprob, -1e300))
-                    sel = torch.nonzero(lnprob > ln_wt + lnprob.max()).reshape(-1)
-                    counts[a + s] = int(sel.numel())
-                    idx_parts.append(sel.to(torch.int32))
-                    val_parts.append(out[:, s, :].index_select(1, sel))
-                del out
-        off = torch.zeros(S + 1, dtype=torch.int64, device=dev)
-        off[1:] = torch.from_numpy(np.cumsum(counts)).to(dev)
-        idx = torch.cat(idx_parts) if idx_parts else torch.empty(0, dtype=torch.int32, device=dev)
-        vals = torch.cat(val_parts, dim=1).contiguous() if val_parts else torch.empty((_lib.NVALS, 0), **kw)
-        rec = Records.dense(idx, vals, off)
-        ntot = int(counts.sum())
-        rec.counts = np.array([ntot, ntot, ntot], dtype=np.int64)
-        return rec, ndim, k1, k2
+                if n_ext:
+                    ext_t = torch.from_numpy(np.ascontiguousarray(ext_par[:, a:b])).to(dev)
+                if keep_all:
+                    # no cut was asked for: every model is a record, the planes are the values
+                    counts[1] = base + n * g.nmodel
+                    if counts[1] > buffers[0].numel():
+                        buffers = grow(buffers, base, int(counts[1]), b)
+                    idx, slot, vals = buffers
+                    capacity = idx.numel()
+                    rows = slice(base, int(counts[1]))
+                    idx[rows].view(n, g.nmodel)[:] = torch.arange(g.nmodel, dtype=torch.int32, device=dev)
+                    slot[rows] = torch.arange(rows.start, rows.stop, dtype=torch.int32, device=dev)
+                    vals[:, rows] = out.reshape(_lib.NVALS, n * g.nmodel)
+                    off[a:b + 1] = base + g.nmodel * torch.arange(n + 1, dtype=torch.int64, device=dev)
+                while not keep_all:
+                    idx, slot, vals = buffers
+                    capacity = idx.numel()
+                    rc = L.brutus_cut_batch(
+                        g.nmodel, n, out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(),
+                        out[3].data_ptr(), out[4].data_ptr(), out[5].data_ptr(), pa, pea, has_par,
+                        n_ext, labels_t.data_ptr() if n_ext else None,
+                        ext_t.data_ptr() if n_ext else None, float(params.wt_thresh),
+                        cws.data_ptr(), cws.numel(), capacity, base, idx.data_ptr(),
+                        slot.data_ptr(), vals.data_ptr(), off[a:].data_ptr(), counts.ctypes.data,
+                        _stream_ptr(torch))
+                    if rc == -2 and b"record buffer too small" in L.brutus_last_error():
+                        # the planes are untouched: larger buffers, then the cut of this chunk again
+                        idx = slot = vals = None
+                        buffers = grow(buffers, base, int(counts[1]), b)
+                        continue
+                    _lib.check(rc)
+                    break
+                base = int(counts[1])
+        if getattr(self, "_rec_bufs", None) is None or self._rec_bufs[0].numel() <= capacity:
+            self._rec_bufs = buffers
+        return (Records(idx, slot, vals, off, None, np.array([base, base, base], dtype=np.int64)),
+                ndim, k1, k2)
 
     def records_device(self, f, e, m, p, pe, has_par, params, ext=None):
         """`fit_batch_device` plus the host copies the callers need:
@@ -1328,10 +1392,12 @@ class BruteForce(object):
                 # external per-object constraints on labels (fitting.py:1995-2009): the label
                 # columns go to the device once, the cut follows the full-grid pipeline there
                 torch = eng.torch
-                ext = [(torch.from_numpy(np.ascontiguousarray(self.models_labels[k], dtype=np.float64)
-                                         ).to(eng.grid.device),
-                        np.asarray(lnprior_ext[k], dtype=np.float64).reshape(-1, 2))
-                       for k in lnprior_ext.keys()]
+                keys = list(lnprior_ext.keys())
+                ext = (torch.from_numpy(np.ascontiguousarray(
+                           np.stack([self.models_labels[k] for k in keys]), dtype=np.float64)
+                       ).to(eng.grid.device),
+                       np.stack([np.asarray(lnprior_ext[k], dtype=np.float64).reshape(-1, 2)
+                                 for k in keys]))
             for out in self._fit_device_post(
                     eng, params, step_device, data, data_err, data_mask, parallax,
                     parallax_err, data_coords, lnprior, lngalprior, dlabels,
@@ -1486,7 +1552,7 @@ class BruteForce(object):
             en = engines[k % nE]
             with torch.cuda.device(dev):
                 # (external label constraints of the batch's objects: the full-grid route)
-                ext_b = None if ext is None else [(t, v[a:b, 0], v[a:b, 1]) for t, v in ext]
+                ext_b = None if ext is None else (ext[0], ext_constraint_params(ext[1][:, a:b]))
                 if streams[k % nE] is None:
                     f, e, m, p, pe, hp = en._upload(data[a:b], data_err[a:b], data_mask[a:b],
                                                     parallax[a:b], parallax_err[a:b])

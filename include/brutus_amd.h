@@ -145,6 +145,47 @@ int brutus_fit_batch(const float *d_grid_soa, int64_t nmodel, int nfilt,
                      int64_t *d_rec_off, int32_t *d_ndim, int32_t *h_k1, int32_t *h_k2,
                      int64_t *h_counts, void *stream);
 
+/* The same first cut for the fits brutus_fit_batch does not take -- more than BRUTUS_MAX_FILT_FIT
+ * bands, or external per-object Gaussian constraints on model labels (`lnprior_ext`,
+ * fitting.py:1995-2009) -- from the full-grid planes brutus_loglike_batch wrote for `nstar` stars
+ * (each (nstar, nmodel), d_icov (6, nstar, nmodel)); d_parallax / d_parallax_err / has_parallax
+ * as there.  Per star s:
+ *   1. for each constraint k < next, in order, that applies to the star:
+ *        lnl[m] += -0.5 * ((label_k[m] - mean)^2 * ivar + lnc)
+ *      d_ext_labels (next, nmodel) holds the label columns, d_ext_par (next, nstar, 3) holds
+ *      (mean, ivar = 1 / std^2, lnc = ln(2 pi std^2)) per (constraint, star), computed by the
+ *      caller in host doubles -- no logarithm or division happens on the device.  A constraint
+ *      the reference skips (non-finite mean, std <= 0; fitting.py:2002) is passed as mean = NaN.
+ *      The operations are performed in exactly this order (subtract, square, times ivar, plus
+ *      lnc, times -0.5, add to lnl), each rounded on its own, never contracted to a fused
+ *      multiply-add: the sum equals the reference's to the bit.  It is written back into
+ *      d_lnl, so the records carry lnlike + constraints like the reference's `results`;
+ *   2. lnprob = lnl, plus the scale-space parallax Gaussian when the parallax is finite with
+ *      p / err > 4 (fitting.py:976-983, pdf.py:209-220), non-finite -> -1e300 (fitting.py:984);
+ *      the same device function as brutus_fit_batch's exact first cut;
+ *   3. model m is selected iff lnprob[m] > ln(wt_thresh) + max_m lnprob (strict,
+ *      fitting.py:985-991); a star with nothing selected has an empty range.
+ * Output: records in brutus_fit_batch's layout, dense (d_rec_slot[r] = r), ascending model
+ * index per star, starting at row `rec_base` of the caller's buffers; d_rec_off (nstar + 1)
+ * entries are absolute rows (d_rec_off[0] = rec_base), so a batch can be cut in several
+ * calls into one set of buffers: pass the previous call's h_counts[1] as rec_base and
+ * d_rec_off advanced by that call's nstar.
+ * h_counts (host, 2 x int64): [0] models selected by this call, [1] rows needed = rec_base +
+ * [0].  BRUTUS_ENOMEM if [1] > capacity: nothing has been written to the planes or the
+ * record buffers then (d_rec_off excepted), repeat the call with buffers of at least [1]
+ * rows (rows below rec_base carried over by the caller).
+ * BRUTUS_EINVAL: nstar outside [1, BRUTUS_MAX_BATCH], next < 0, next > 0 with a NULL
+ * d_ext_labels / d_ext_par, wt_thresh not positive and finite. */
+size_t brutus_cut_workspace_bytes(int64_t nmodel, int nstar);
+int brutus_cut_batch(int64_t nmodel, int nstar, double *d_lnl, const double *d_chi2,
+                     const double *d_scale, const double *d_av, const double *d_rv,
+                     const double *d_icov, const double *d_parallax,
+                     const double *d_parallax_err, int has_parallax, int next,
+                     const double *d_ext_labels, const double *d_ext_par, double wt_thresh,
+                     void *d_workspace, size_t workspace_bytes, int64_t capacity,
+                     int64_t rec_base, int32_t *d_rec_idx, int32_t *d_rec_slot,
+                     double *d_rec_vals, int64_t *d_rec_off, int64_t *h_counts, void *stream);
+
 /* ---- lnpost on the device ------------------------------------------------------
  * Everything of fitting.lnpost after the first cut (fitting.py:1000-1107) and
  * the resampling tail of BruteForce._fit (fitting.py:2021-2061), for the
