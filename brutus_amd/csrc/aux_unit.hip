@@ -1,0 +1,267 @@
+// aux_unit.hip -- translation unit of libbrutus_amd.so: the cluster likelihood
+// (brutus_cluster_*; cluster.py:336-414 isochrone_loglike hot block, cluster_kernels.hpp) and the
+// photometric offsets (brutus_offsets_*; offsets_kernels.hpp).
+
+#include <hip/hip_runtime.h>
+#include <rocprim/device/device_segmented_radix_sort.hpp>
+#include <math.h>
+#include <stdint.h>
+
+#include "../../include/brutus_amd.h"
+
+#include "host.hpp"
+#include "common.hpp"
+#include "fastmath.hpp"
+#include "cluster_kernels.hpp"
+#include "offsets_kernels.hpp"
+
+extern "C" {
+
+constexpr int CLUSTER_CHUNKS = 256;
+
+size_t brutus_cluster_workspace_bytes(int nobj) {
+    if (nobj <= 0) return 0;
+    return 2 * align_up(sizeof(double) * (size_t)nobj * CLUSTER_CHUNKS);
+}
+
+int brutus_cluster_chunks(void) { return CLUSTER_CHUNKS; }
+
+extern "C++" {
+template <bool MAGS>
+static int cluster_part(int nobj, int nfilt, int npts, const double *d_pts_flux,
+                        const double *d_pts_lnw, ClusterMags mg, const double *d_phot,
+                        const double *d_ivar, const double *d_chi2_p, const double *d_lnorm,
+                        const int32_t *d_ndim, int dim_prior, void *d_workspace,
+                        size_t workspace_bytes, int chunk_lo, int chunk_n, void *stream) {
+    const int nb = padded_nb(nfilt);
+    if (nobj <= 0 || npts < 0 || nb < 0)
+        return fail(BRUTUS_EINVAL, "bad cluster dimensions (nobj=%d, npts=%d, nfilt=%d)", nobj,
+                    npts, nfilt);
+    if (chunk_lo < 0 || chunk_n < 1 || chunk_lo + chunk_n > CLUSTER_CHUNKS)
+        return fail(BRUTUS_EINVAL, "bad chunk range [%d, %d) of %d", chunk_lo, chunk_lo + chunk_n,
+                    CLUSTER_CHUNKS);
+    if (!d_phot || !d_ivar || !d_chi2_p || !d_lnorm || !d_ndim || !d_workspace)
+        return fail(BRUTUS_EINVAL, "NULL device pointer");
+    if (npts > 0 && (MAGS ? (!mg.src || !mg.mags || !mg.lnw_eep || !mg.lnw_smf || mg.neep <= 0)
+                          : (!d_pts_flux || !d_pts_lnw)))
+        return fail(BRUTUS_EINVAL, "NULL device pointer (isochrone points)");
+    if (workspace_bytes < brutus_cluster_workspace_bytes(nobj))
+        return fail(BRUTUS_ENOMEM, "cluster workspace too small");
+    double *pm = (double *)d_workspace + (size_t)chunk_lo * nobj;
+    double *ps = (double *)((char *)d_workspace + align_up(sizeof(double) * (size_t)nobj * CLUSTER_CHUNKS)) +
+                 (size_t)chunk_lo * nobj;
+    hipStream_t st = (hipStream_t)stream;
+    // every chunk of the range is written: one without points holds (-inf, 0)
+    const int ppb = npts > 0 ? (npts + chunk_n - 1) / chunk_n : 1;
+    const dim3 g((nobj + CL_T - 1) / CL_T, chunk_n);
+    Timer tm(st);
+    tm.begin("k_cluster");
+#define BRUTUS_CL(N)                                                                              \
+    case N:                                                                                       \
+        hipLaunchKernelGGL((k_cluster<N, MAGS>), g, dim3(CL_T), 0, st, nobj, nfilt, npts,         \
+                           d_pts_flux, d_pts_lnw, mg, d_phot, d_ivar, d_chi2_p, d_lnorm, d_ndim,  \
+                           dim_prior, ppb, pm, ps);                                               \
+        break;
+    switch (nb) {
+        BRUTUS_CL(12)
+#ifndef BRUTUS_DEV_NB12_ONLY
+        BRUTUS_CL(8)
+        BRUTUS_CL(16)
+        BRUTUS_CL(24)
+        BRUTUS_CL(32)
+#endif
+        default:
+            return fail(BRUTUS_EINVAL, "cluster likelihood: at most %d bands (%d given)", BRUTUS_MAX_FILT_FIT, nfilt);
+    }
+#undef BRUTUS_CL
+    tm.end();
+    HIP_TRY(hipGetLastError());
+    tm.collect();
+    return 0;
+}
+}  // extern "C++"
+
+int brutus_cluster_lnl_part(int nobj, int nfilt, int npts, const double *d_pts_flux,
+                            const double *d_pts_lnw, const double *d_phot, const double *d_ivar,
+                            const double *d_chi2_p, const double *d_lnorm, const int32_t *d_ndim,
+                            int dim_prior, void *d_workspace, size_t workspace_bytes, int chunk_lo,
+                            int chunk_n, void *stream) {
+    return cluster_part<false>(nobj, nfilt, npts, d_pts_flux, d_pts_lnw, ClusterMags{}, d_phot,
+                               d_ivar, d_chi2_p, d_lnorm, d_ndim, dim_prior, d_workspace,
+                               workspace_bytes, chunk_lo, chunk_n, stream);
+}
+
+int brutus_cluster_lnl_part_mags(int nobj, int nfilt, int npts, int neep, const int32_t *d_src,
+                                 const double *d_mags, const double *d_lnw_eep,
+                                 const double *d_lnw_smf, const double *d_phot,
+                                 const double *d_ivar, const double *d_chi2_p,
+                                 const double *d_lnorm, const int32_t *d_ndim, int dim_prior,
+                                 void *d_workspace, size_t workspace_bytes, int chunk_lo,
+                                 int chunk_n, void *stream) {
+    ClusterMags mg;
+    mg.src = d_src;
+    mg.mags = d_mags;
+    mg.lnw_eep = d_lnw_eep;
+    mg.lnw_smf = d_lnw_smf;
+    mg.neep = neep;
+    return cluster_part<true>(nobj, nfilt, npts, nullptr, nullptr, mg, d_phot, d_ivar, d_chi2_p,
+                              d_lnorm, d_ndim, dim_prior, d_workspace, workspace_bytes, chunk_lo,
+                              chunk_n, stream);
+}
+
+int brutus_cluster_lnl_merge(int nobj, int nchunk, void *d_workspace, size_t workspace_bytes,
+                             double *d_lnl, void *stream) {
+    if (nobj <= 0 || nchunk < 1 || nchunk > CLUSTER_CHUNKS || !d_workspace || !d_lnl)
+        return fail(BRUTUS_EINVAL, "bad cluster merge (nobj=%d, nchunk=%d)", nobj, nchunk);
+    if (workspace_bytes < brutus_cluster_workspace_bytes(nobj))
+        return fail(BRUTUS_ENOMEM, "cluster workspace too small");
+    double *pm = (double *)d_workspace;
+    double *ps = (double *)((char *)d_workspace + align_up(sizeof(double) * (size_t)nobj * CLUSTER_CHUNKS));
+    hipLaunchKernelGGL(k_cluster_merge, dim3((nobj + CM_O - 1) / CM_O), dim3(CM_O * CM_J), 0,
+                       (hipStream_t)stream, nobj, nchunk, pm, ps, d_lnl);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int brutus_cluster_mix(int nobj, const double *d_lnl, const double *d_lnl_outlier, double ln_fin,
+                       double ln_fout, double *d_lnl_mix, double *d_lnl_tot, void *stream) {
+    if (nobj <= 0 || !d_lnl || !d_lnl_outlier || !d_lnl_mix || !d_lnl_tot)
+        return fail(BRUTUS_EINVAL, "bad cluster mixture arguments (nobj=%d)", nobj);
+    hipLaunchKernelGGL(k_cluster_mix, dim3(1), dim3(CX_T), 0, (hipStream_t)stream, nobj, d_lnl,
+                       d_lnl_outlier, ln_fin, ln_fout, d_lnl_mix, d_lnl_tot);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int brutus_cluster_lnl(int nobj, int nfilt, int npts, const double *d_pts_flux,
+                       const double *d_pts_lnw, const double *d_phot, const double *d_ivar,
+                       const double *d_chi2_p, const double *d_lnorm, const int32_t *d_ndim,
+                       int dim_prior, void *d_workspace, size_t workspace_bytes, double *d_lnl,
+                       void *stream) {
+    if (npts <= 0) return fail(BRUTUS_EINVAL, "bad cluster dimensions (npts=%d)", npts);
+    if (!d_lnl) return fail(BRUTUS_EINVAL, "NULL device pointer");
+    static const int want_chunks = env_int("BRUTUS_CLUSTER_CHUNKS", CLUSTER_CHUNKS);
+    const int use_chunks = want_chunks < 1 ? 1 : (want_chunks > CLUSTER_CHUNKS ? CLUSTER_CHUNKS : want_chunks);
+    const int rc = brutus_cluster_lnl_part(nobj, nfilt, npts, d_pts_flux, d_pts_lnw, d_phot, d_ivar,
+                                           d_chi2_p, d_lnorm, d_ndim, dim_prior, d_workspace,
+                                           workspace_bytes, 0, use_chunks, stream);
+    if (rc) return rc;
+    return brutus_cluster_lnl_merge(nobj, use_chunks, d_workspace, workspace_bytes, d_lnl, stream);
+}
+
+int brutus_cluster_points(int64_t npts, int nfilt, const int32_t *d_src, const double *d_mags,
+                          const double *d_lnw_in, double *d_pts_flux, double *d_pts_lnw,
+                          void *stream) {
+    if (npts <= 0 || nfilt <= 0) return fail(BRUTUS_EINVAL, "bad point-table dimensions");
+    if (!d_mags || !d_lnw_in || !d_pts_flux || !d_pts_lnw) return fail(BRUTUS_EINVAL, "NULL device pointer");
+    hipLaunchKernelGGL(k_cluster_points, dim3((unsigned)((npts + 255) / 256)), dim3(256), 0,
+                       (hipStream_t)stream, npts, nfilt, d_src, d_mags, d_lnw_in, 0,
+                       (const double *)nullptr, d_pts_flux, d_pts_lnw);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int brutus_cluster_points_grid(int64_t npts, int nfilt, int neep, const int32_t *d_src,
+                               const double *d_mags, const double *d_lnw_eep,
+                               const double *d_lnw_smf, double *d_pts_flux, double *d_pts_lnw,
+                               void *stream) {
+    if (npts <= 0 || nfilt <= 0 || neep <= 0) return fail(BRUTUS_EINVAL, "bad point-table dimensions");
+    if (!d_mags || !d_lnw_eep || !d_lnw_smf || !d_pts_flux || !d_pts_lnw)
+        return fail(BRUTUS_EINVAL, "NULL device pointer");
+    hipLaunchKernelGGL(k_cluster_points, dim3((unsigned)((npts + 255) / 256)), dim3(256), 0,
+                       (hipStream_t)stream, npts, nfilt, d_src, d_mags, d_lnw_eep, neep, d_lnw_smf,
+                       d_pts_flux, d_pts_lnw);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// ---- utils.photometric_offsets on the device (offsets_kernels.hpp) ----------
+int brutus_offsets_weights(int nobj, int nsamps, int nfilt, int64_t nmodel, const float *d_models,
+                           const int64_t *d_idxs, const double *d_reds, const double *d_dreds,
+                           const double *d_dists, const double *d_phot, const double *d_err,
+                           const uint8_t *d_mask, const double *d_weights,
+                           const double *d_old_offsets, const uint8_t *d_use,
+                           const uint8_t *d_mask_fit, int dim_prior, double *d_flux, double *d_cdf,
+                           void *stream) {
+    if (nobj <= 0 || nsamps <= 0 || nfilt <= 0 || nfilt > NBMAX || nmodel <= 0)
+        return fail(BRUTUS_EINVAL, "bad photometric-offset dimensions (nobj=%d, nsamps=%d, nfilt=%d)",
+                    nobj, nsamps, nfilt);
+    if (!d_models || !d_idxs || !d_reds || !d_dreds || !d_dists || !d_phot || !d_err || !d_mask ||
+        !d_weights || !d_old_offsets || !d_use || !d_mask_fit || !d_flux || !d_cdf)
+        return fail(BRUTUS_EINVAL, "NULL device pointer");
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t nt = (int64_t)nobj * nsamps;
+    hipLaunchKernelGGL(k_po_flux, dim3((unsigned)((nt + PO_T - 1) / PO_T)), dim3(PO_T), 0, st, nobj,
+                       nsamps, nfilt, nmodel, d_models, d_idxs, d_reds, d_dreds, d_dists, d_phot,
+                       d_err, d_mask, d_old_offsets, d_use, d_mask_fit, dim_prior, d_flux, d_cdf);
+    hipLaunchKernelGGL(k_po_cdf, dim3(nobj, nfilt), dim3(PO_T), 0, st, nobj, nsamps, d_weights,
+                       d_use, d_mask_fit, d_cdf);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+namespace {
+// [vals | sorted | segment offsets | rocPRIM scratch]
+struct OffsetsWs {
+    double *vals, *sorted;
+    int32_t *seg;
+    void *tmp;
+    size_t tmp_bytes, bytes;
+};
+static int carve_offsets(char *base, int n, int nmc, OffsetsWs &w) {
+    const size_t nv = (size_t)n * nmc;
+    size_t off = 0;
+    w.vals = (double *)(base + off);
+    off += align_up(sizeof(double) * nv);
+    w.sorted = (double *)(base + off);
+    off += align_up(sizeof(double) * nv);
+    w.seg = (int32_t *)(base + off);
+    off += align_up(sizeof(int32_t) * ((size_t)nmc + 1));
+    w.tmp = base + off;
+    w.tmp_bytes = 0;
+    hipError_t e = rocprim::segmented_radix_sort_keys(
+        nullptr, w.tmp_bytes, (const double *)nullptr, (double *)nullptr, (unsigned int)nv,
+        (unsigned int)nmc, (const int32_t *)nullptr, (const int32_t *)nullptr);
+    if (e != hipSuccess) return -1;
+    off += align_up(w.tmp_bytes);
+    w.bytes = off;
+    return 0;
+}
+}  // namespace
+
+size_t brutus_offsets_workspace_bytes(int n, int nmc) {
+    if (n <= 0 || nmc <= 0 || (int64_t)n * nmc >= (int64_t)1 << 31) return 0;
+    OffsetsWs w;
+    if (carve_offsets(nullptr, n, nmc, w)) return 0;
+    return w.bytes;
+}
+
+int brutus_offsets_bootstrap(int band, int nobj, int nsamps, int nfilt, int n, int nmc,
+                             const int32_t *d_subset, const double *d_cdf_obj, const double *d_u,
+                             const double *d_flux, const double *d_cdf, const double *d_phot,
+                             void *d_workspace, size_t workspace_bytes, double *d_meds,
+                             void *stream) {
+    if (band < 0 || band >= nfilt || nobj <= 0 || nsamps <= 0 || n <= 0 || n > nobj || nmc <= 0 ||
+        (int64_t)n * nmc >= (int64_t)1 << 31)
+        return fail(BRUTUS_EINVAL, "bad bootstrap dimensions (band=%d, n=%d, nmc=%d)", band, n, nmc);
+    if (!d_subset || !d_cdf_obj || !d_u || !d_flux || !d_cdf || !d_phot || !d_workspace || !d_meds)
+        return fail(BRUTUS_EINVAL, "NULL device pointer");
+    OffsetsWs w;
+    if (carve_offsets((char *)d_workspace, n, nmc, w)) return fail(BRUTUS_EHIP, "rocPRIM sizing failed");
+    if (workspace_bytes < w.bytes) return fail(BRUTUS_ENOMEM, "photometric-offset workspace too small");
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t nv = (int64_t)n * nmc;
+    hipLaunchKernelGGL(k_po_segments, dim3((nmc + 1 + 255) / 256), dim3(256), 0, st, n, nmc, w.seg);
+    hipLaunchKernelGGL(k_po_boot, dim3((unsigned)((nv + PO_T - 1) / PO_T)), dim3(PO_T), 0, st, band,
+                       nobj, nsamps, nfilt, n, nmc, d_subset, d_cdf_obj, d_u, d_flux, d_cdf, d_phot,
+                       w.vals);
+    HIP_TRY(rocprim::segmented_radix_sort_keys(w.tmp, w.tmp_bytes, (const double *)w.vals, w.sorted,
+                                               (unsigned int)nv, (unsigned int)nmc, w.seg, w.seg + 1,
+                                               0, 64, st));
+    hipLaunchKernelGGL(k_po_median, dim3((nmc + 255) / 256), dim3(256), 0, st, n, nmc, w.sorted,
+                       d_meds);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+}  // extern "C"

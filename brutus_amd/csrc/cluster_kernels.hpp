@@ -1,8 +1,9 @@
 // cluster_kernels.hpp -- cluster.isochrone_loglike hot block behind brutus_cluster_lnl
-// Part of the single translation unit brutus_kernels.hip (included there, in
-// this order: common, fastmath, grid_kernels, fit_kernels, cluster_kernels,
-// post_kernels); everything lives in that unit's anonymous namespace.
+// Included by aux_unit.hip only (it defines kernels); needs common.hpp and fastmath.hpp.
 #pragma once
+
+#include "common.hpp"
+#include "fastmath.hpp"
 
 namespace {
 

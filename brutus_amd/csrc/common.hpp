@@ -1,8 +1,13 @@
-// common.hpp -- constants, error helper, per-star / per-model device structs, reductions
-// Part of the single translation unit brutus_kernels.hip (included there, in
-// this order: common, fastmath, grid_kernels, fit_kernels, cluster_kernels,
-// post_kernels, ..., cut_kernels); everything lives in that unit's anonymous namespace.
+// common.hpp -- constants, per-star / per-model device structs, reductions and prefix sums
+// Included by every translation unit of the library except pre32s_unit.hip; defines no kernel.
+// Everything lives in the including unit's anonymous namespace (the host side the units
+// share is host.hpp).
 #pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/brutus_amd.h"
 
 namespace {
 
@@ -12,29 +17,6 @@ constexpr int STAR_GROUP = 16;   // stars per workgroup (grid.y = ceil(S / STAR_
 constexpr int KCAP = 16;         // max sweeps probed by one k_mag_stats launch
 constexpr int NCHUNK = 64;       // model-range chunks for ordered compaction
 constexpr double BIG = 1e300;
-
-thread_local std::string g_err;
-bool g_timing = false;
-struct TimingEntry { std::string name; float ms; int count; };
-thread_local std::vector<TimingEntry> g_last_timing;   // per calling thread (scan-ahead + lnpost threads time concurrently)
-
-int fail(int code, const char *fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return code;
-}
-
-#define HIP_TRY(expr)                                                          \
-    do {                                                                       \
-        hipError_t e_ = (expr);                                                \
-        if (e_ != hipSuccess)                                                  \
-            return fail(BRUTUS_EHIP, "%s failed: %s (%s:%d)", #expr,           \
-                        hipGetErrorString(e_), __FILE__, __LINE__);            \
-    } while (0)
 
 // ---------------------------------------------------------------------------
 // device-side data

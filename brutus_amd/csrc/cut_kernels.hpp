@@ -1,7 +1,7 @@
 // cut_kernels.hpp -- brutus_cut_batch: external label constraints, parallax clip and first
 // `wt_thresh` cut on the full-grid planes of brutus_loglike_batch, emitting indexed records
-// (reference fitting.py:1995-2009, :976-991, pdf.py:209-220).  Included by brutus_kernels.hip
-// after fit_kernels.hpp (first_cut_lnprob) and grid_kernels.hpp (prep_parallax).
+// (reference fitting.py:1995-2009, :976-991, pdf.py:209-220).  Included by brutus_kernels.hip only
+// (it defines kernels); needs fit_kernels.hpp (first_cut_lnprob) and grid_kernels.hpp (prep_parallax).
 //
 // Four streaming passes over (star, model); a star's models are cut into CUT_NCH contiguous
 // chunks of `span` models, one workgroup per (chunk, star), each lane two adjacent models:
@@ -17,6 +17,9 @@
 // to be large enough, so a call that fails with BRUTUS_ENOMEM leaves its inputs as they were
 // and is simply repeated.
 #pragma once
+
+#include "grid_kernels.hpp"
+#include "fit_kernels.hpp"
 
 namespace {
 

@@ -1,7 +1,7 @@
 // fastmath.hpp -- table / series forms of 10^x, e^x, ln x, 1/x, sqrt x for the hot kernels
-// Part of the single translation unit brutus_kernels.hip (included there, in
-// this order: common, fastmath, grid_kernels, fit_kernels, cluster_kernels,
-// post_kernels); everything lives in that unit's anonymous namespace.
+// Included by every translation unit of the library except pre32s_unit.hip (each gets its own
+// copy of the __constant__ tables); defines no kernel, needs no other header.  Everything lives in
+// the including unit's anonymous namespace.
 #pragma once
 
 namespace {

@@ -1,6 +1,6 @@
 // fit2_kernels.hpp -- the hot path behind brutus_fit_batch: float32 proof pass, exact
-// thresholds, selection.  Part of the single translation unit brutus_kernels.hip (included
-// after fit_kernels.hpp); everything lives in that unit's anonymous namespace.
+// thresholds, selection.  Included by brutus_kernels.hip only (it defines kernels); needs
+// fit_kernels.hpp and pre32_types.hpp.
 //
 // Why.  The reference's per-star control flow hangs on maxima over the whole grid
 // (fitting.py:246-264 K1, :758-759 cull, :798-799 K2, :988-991 first cut), but
@@ -13,7 +13,7 @@
 //              lnprob~ (4 + 4 B per pair), float32 maxima per 2048-model block, and the
 //              sweep statistics that decide K1 when they are clear of the tolerances
 //              (else k_k1probe, exact).
-//   k_top      float64 re-evaluation of the models within 2 eps of the float32 maximum
+//   k_top1     float64 re-evaluation of the models within 2 eps of the float32 maximum
 //              (only the blocks whose float32 maximum is that high are touched)
 //              ->  EXACT max lnl_p, i.e. the exact cull threshold.
 //   k_cmp_count32 + k_offsets + k_items + k_cmp_scatter
@@ -24,7 +24,7 @@
 //              straight into the caller's record planes (full-line writes) -- that is the
 //              survivors' final storage; the list position is also left as a tag in the
 //              lnprob~ plane (surv_tag).
-//   k_top (B)  exact maximum of lnprob over the non-survivors that could exceed the
+//   k_top1 (B) exact maximum of lnprob over the non-survivors that could exceed the
 //              survivors' maximum  ->  EXACT first-cut threshold.
 //   k_sel_classify + k_sel_band
 //              two bit-masks: selected, and selected-but-not-a-survivor ("derived").
@@ -44,6 +44,7 @@
 // and in tests/test_gpu_fit2.py).
 #pragma once
 
+#include "fit_kernels.hpp"
 #include "pre32_types.hpp"
 
 namespace {
@@ -577,135 +578,19 @@ __device__ __forceinline__ int64_t mword(int s, int ntile, int t, int w) {
 }
 
 // ---------------------------------------------------------------------------
-// k_top: exact maxima over nominees
+// k_hot_list + k_top1: exact maxima over nominees, from a LIST of the hot (block, star) pairs
 // ---------------------------------------------------------------------------
 // mode 0: nominees = !(lnlp32 < nom[s])                          -> max lnl_p
 // mode 1: nominees = non-survivors with !(lnpr32 < nom[s])       -> max lnprob (mag-phase value)
 //         (survivors carry a tag in that plane, see surv_tag)
-// A (block, star) whose float32 block maximum (part32 column 6 + mode) is below nom[s]
-// and that holds no NaN lane is skipped outright.
 // part[(bx * nstar + s)] = block maximum (-inf if no nominee)
-template <int NB, bool RVF, int G>
-__global__ void __launch_bounds__(TILE, top_waves(NB))
-k_top(const float *__restrict__ grid, int64_t nmodel, int64_t nmodel_pad, int nstar, int nrun,
-      const int32_t *__restrict__ star_ids, const StarPrep *__restrict__ stars, DevParams p,
-      const int32_t *__restrict__ k1, int ntile, int mode, const float *__restrict__ plane32,
-      const double *__restrict__ nom, const float *__restrict__ surv32,
-      const float *__restrict__ part32, double *__restrict__ part, float *__restrict__ aud) {
-    __shared__ double slot[4][G];
-    __shared__ double s_tbl[64];
-    const int g0 = blockIdx.y * G;
-    const int ng = min(G, nrun - g0);
-    const int t0 = blockIdx.x * F2_T;
-    const int t1 = min(ntile, t0 + F2_T);
-    const int lane = threadIdx.x & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    bool hot[G];
-    bool anyhot = false;
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-        hot[g] = false;
-        if (g < ng) {
-            const int s = star_ids[g0 + g];
-            const float *pp = part32 + ((int64_t)blockIdx.x * nstar + s) * NV32;
-            hot[g] = !((double)pp[6 + mode] < nom[s]) || pp[9] > 0.f;
-            anyhot = anyhot || hot[g];
-        }
-    }
-    // (all but a few per cent of the workgroups end here: before the table staging, its
-    // barrier and everything else -- a launch is ~12 000 workgroups for some hundred hot ones)
-    if (!anyhot) {
-        if ((int)threadIdx.x < ng) part[(int64_t)blockIdx.x * nstar + star_ids[g0 + threadIdx.x]] = -INFINITY;
-        return;
-    }
-    stage_exp_table(s_tbl);
-    __syncthreads();
-    if (lane < G) slot[wv][lane] = -INFINITY;      // wave-private row: no barrier needed
-    // nominee masks of the block's tiles for its hot stars: all float32 values are requested
-    // first (clamped addresses, no guards: every load of the batch is in flight at once;
-    // one guarded load per (tile, star) made each a round trip of its own), the masks wait
-    // in a wave-private LDS row
-    __shared__ unsigned long long s_need[4][G][F2_T];
-    const float *__restrict__ tagp = mode == 1 ? surv32 : plane32;     // (mode 0: value unused)
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-        if (g < ng && hot[g]) {
-            const int s = star_ids[g0 + g];
-            const double nm_s = nom[s];
-            float v[F2_T], tg[F2_T];
-#pragma unroll
-            for (int u = 0; u < F2_T; ++u) {
-                const int64_t i = (int64_t)(t0 + u) * TILE + threadIdx.x;
-                const int64_t ic = i < nmodel ? i : nmodel - 1;
-                v[u] = plane32[(int64_t)s * nmodel + ic];
-                tg[u] = tagp[(int64_t)s * nmodel + ic];
-            }
-#pragma unroll
-            for (int u = 0; u < F2_T; ++u) {
-                const int64_t i = (int64_t)(t0 + u) * TILE + threadIdx.x;
-                bool nm = t0 + u < t1 && i < nmodel && !(v[u] < nm_s);
-                if (mode == 1 && nm) nm = !surv_is(tg[u]);
-                const unsigned long long b = __ballot(nm);
-                if (lane == 0) s_need[wv][g][u] = b;
-            }
-        } else if (lane < F2_T) {
-            s_need[wv][g][lane] = 0ull;
-        }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    for (int t = t0; anyhot && t < t1; ++t) {
-        const int64_t i = (int64_t)t * TILE + threadIdx.x;
-        unsigned long long need[G];
-        bool any = false;
-#pragma unroll
-        for (int g = 0; g < G; ++g) {
-            const unsigned long long b = s_need[wv][g][t - t0];
-            need[g] = ((unsigned long long)__builtin_amdgcn_readfirstlane((int)(b >> 32)) << 32) |
-                      (unsigned int)__builtin_amdgcn_readfirstlane((int)b);
-            any = any || need[g] != 0ull;
-        }
-        if (!any) continue;
-        Tile64<NB, RVF> tl;
-        tile_load<NB, RVF>(grid, nmodel_pad, i, p.rv_mean, tl);
-#pragma unroll
-        for (int g = 0; g < G; ++g) {
-            if (g >= ng || need[g] == 0ull) continue;
-            const int s = star_ids[g0 + g];
-            const StarPrep &sp = stars[s];
-            double av, rv;
-            mag_phase<NB, RVF>(tl, sp, p, k1[s], av, rv);
-            Mle m;
-            mle_at<NB, RVF, false>(tl, sp, p, av, rv, s_tbl, m);
-            double val;
-            if (mode == 0) val = cull_stat(sp, m);
-            else val = first_cut_lnprob(sp, final_lnl<false>(sp, p, m.chi2, false), m.scale, m.i00);
-            const bool mine = (need[g] >> lane) & 1ull;
-            if (mine) audit(aud, s, plane32[(int64_t)s * nmodel + i], val, nom[s]);
-            const double x = wave_max((mine && val == val) ? val : -INFINITY);
-            if (lane == 0 && x > slot[wv][g]) slot[wv][g] = x;
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x < ng) {
-        const int g = threadIdx.x;
-        double x = slot[0][g];
-        x = slot[1][g] > x ? slot[1][g] : x;
-        x = slot[2][g] > x ? slot[2][g] : x;
-        x = slot[3][g] > x ? slot[3][g] : x;
-        part[(int64_t)blockIdx.x * nstar + star_ids[g0 + g]] = x;
-    }
-}
-
-// ---------------------------------------------------------------------------
-// k_hot_list + k_top1: the same exact maxima from a LIST of the hot (block, star) pairs
-// ---------------------------------------------------------------------------
-// k_top is launched over every (block, star group) and all but a few per cent of its ~12 000
-// workgroups find nothing to do: 0.08 ms per launch, twice per call, for some hundred hot
-// pairs.  k_hot_list (one workgroup per star) lists the pairs whose float32 block maximum
-// reaches the nominee level (or that hold a NaN lane) and marks the others' partials -inf;
-// k_top1 walks the list with a fixed launch, one (block, star) per workgroup and turn.
-//   mode 0: nom = nomA (k_pre_decide);   mode 1: nomB[s] = maxsurv[s] - eps is formed here.
+// Of the ~12 000 (block, star group) pairs of a call all but some hundred have nothing to do.
+// k_hot_list (one workgroup per star) lists the pairs whose float32 block maximum (part32
+// column 6 + mode) reaches the nominee level (or that hold a NaN lane) and marks the others'
+// partials -inf; k_top1 walks the list with a fixed launch, one (block, star) per workgroup
+// and turn.
+//   mode 0: nom = nomA (k_pre_decide);   mode 1: nomB[s] = maxsurv[s] - eps is formed here
+//   (the non-survivors that could exceed the survivors' maximum).
 // An entry is  block * BRUTUS_MAX_BATCH + star.
 __global__ void __launch_bounds__(256)
 k_hot_list(int nblkx, int nstar, int mode, const float *__restrict__ part32,
@@ -780,7 +665,7 @@ k_top1(const float *__restrict__ grid, int64_t nmodel, int64_t nmodel_pad, int n
     }
 }
 
-// thresholds from k_top's partials.
+// thresholds from k_top1's partials.
 //   mode 0: thr_cull[s] = max + ln_init;  candS[s] = thr_cull - eps
 //   mode 1: thr_sel[s] = max(maxsurv[s], max) + ln_wt
 __global__ void k_top_decide(int nblkx, int nstar, const int32_t *__restrict__ star_ids, int mode,
@@ -807,13 +692,6 @@ __global__ void k_top_decide(int nblkx, int nstar, const int32_t *__restrict__ s
         const double m = maxsurv[s] > v ? maxsurv[s] : v;
         thr[s] = m + ln_thr;
     }
-}
-
-// nomB[s] = maxsurv[s] - eps: the non-survivors that could exceed the survivors' maximum
-__global__ void k_nomB(int nstar, const double *__restrict__ maxsurv, const Star32 *__restrict__ s32,
-                       double *__restrict__ nomB) {
-    const int s = blockIdx.x * blockDim.x + threadIdx.x;
-    if (s < nstar) nomB[s] = maxsurv[s] - (double)s32[s].eps;
 }
 
 // Ordered compaction of a float32 plane: {i : !(plane[s][i] < thr[s])} (NaN counts as a

@@ -1,12 +1,14 @@
 // fit_kernels.hpp -- float64 building blocks of brutus_fit_batch: Gram-form magnitude
 // sweeps, the MLE, the exact K1 probe, ordered compaction, the flux phase on the candidate
 // lists (k_fflux), the record index (k_rec_index) and the derived records (k_derive).
-// Part of the single translation unit brutus_kernels.hip (included there, in
-// this order: common, fastmath, grid_kernels, fit_kernels, fit2_kernels, cluster_kernels,
-// mt_kernels, post_kernels, offsets_kernels); everything lives in that unit's anonymous
-// namespace.  The pipeline that strings these kernels together is described at the top of
-// fit2_kernels.hpp.
+// Included by brutus_kernels.hip only (it defines kernels); needs common.hpp, fastmath.hpp and
+// the device functions at the head of grid_kernels.hpp.  The pipeline that strings these kernels
+// together is described at the top of fit2_kernels.hpp.
 #pragma once
+
+#include "common.hpp"
+#include "fastmath.hpp"
+#include "grid_kernels.hpp"
 
 namespace {
 
@@ -313,8 +315,8 @@ constexpr int fflux_waves(int nb, bool first) {
     return nb >= (first ? BRUTUS_FFLUX_OCC1_FROM : BRUTUS_LIST_OCC1_FROM) ? 1 : 2;
 }
 // (the tile kernels of fit2_kernels.hpp likewise: k_sel_band from 24 bands -- 0.16 -> 0.10,
-// 0.27 -> 0.13 ms --, k_top at 32 -- 2.19 -> 1.27 ms; k_top<24> is faster with two: 0.68
-// against 0.87 ms)
+// 0.27 -> 0.13 ms --, the exact-maxima kernel (k_top1; measured on its all-pairs predecessor) at
+// 32 -- 2.19 -> 1.27 ms; at 24 bands it is faster with two: 0.68 against 0.87 ms)
 constexpr int top_waves(int nb) { return nb > 24 ? 1 : 2; }
 constexpr int band_waves(int nb) { return nb > 16 ? 1 : 2; }
 // (an LDS pointer by address space: a volatile access through a generic pointer is a FLAT one)

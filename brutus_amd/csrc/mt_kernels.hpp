@@ -1,6 +1,5 @@
 // mt_kernels.hpp -- numpy's legacy random stream on the device
-// Part of the single translation unit brutus_kernels.hip (included before
-// post_kernels.hpp); everything lives in that unit's anonymous namespace.
+// Included by post_unit.hip only (it defines kernels); needs common.hpp.
 //
 // The reference draws everything from ONE `numpy.random.RandomState` (MT19937):
 //   rstate.normal(size = 3 Nmc Nsel)          utils.py:897   legacy polar Box-Muller
@@ -23,6 +22,8 @@
 // representation (key[624], pos, has_gauss, cached_gaussian) so the caller's RandomState
 // continues exactly where the reference's would.
 #pragma once
+
+#include "common.hpp"
 
 namespace {
 

@@ -1,6 +1,5 @@
 // offsets_kernels.hpp -- utils.photometric_offsets on the device
-// Part of the single translation unit brutus_kernels.hip; everything lives in that
-// unit's anonymous namespace.
+// Included by aux_unit.hip only (it defines kernels); needs common.hpp and fastmath.hpp.
 //
 // Reference utils.py:1218-1400.  The fit of every object left Nsamps resampled models
 // (grid index, Av, Rv, distance).  Per band b the reference
@@ -17,6 +16,9 @@
 //   k_po_boot    lane = (round, slot): two binary searches, one ratio
 //   segmented radix sort of the rounds (rocPRIM) + k_po_median
 #pragma once
+
+#include "common.hpp"
+#include "fastmath.hpp"
 
 namespace {
 

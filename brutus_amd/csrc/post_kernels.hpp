@@ -1,8 +1,11 @@
 // post_kernels.hpp -- device lnpost (second cut, MC prior integral, resampling) behind brutus_post_batch
-// Part of the single translation unit brutus_kernels.hip (included there, in
-// this order: common, fastmath, grid_kernels, fit_kernels, cluster_kernels,
-// post_kernels); everything lives in that unit's anonymous namespace.
+// Included by post_unit.hip only (it defines kernels); needs common.hpp, fastmath.hpp and
+// mt_kernels.hpp (ZMap: where the numpy stream left the normals).
 #pragma once
+
+#include "common.hpp"
+#include "fastmath.hpp"
+#include "mt_kernels.hpp"
 
 namespace {
 

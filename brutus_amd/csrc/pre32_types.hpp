@@ -1,6 +1,6 @@
-// pre32_types.hpp -- what the float32 proof pass shares between the two translation units of the
-// library: brutus_kernels.hip (everything else) and pre32s_unit.hip (the star-lane pass, built
-// with other compiler flags; see there).
+// pre32_types.hpp -- what the float32 proof pass shares between two translation units of the
+// library: brutus_kernels.hip (the hot path that drives it) and pre32s_unit.hip (the star-lane
+// pass, built with other compiler flags; see there).
 #pragma once
 
 #include <stdint.h>

@@ -1,4 +1,4 @@
-// pre32s_unit.hip -- second translation unit of libbrutus_amd.so: the star-lane float32 pass
+// pre32s_unit.hip -- translation unit of libbrutus_amd.so: the star-lane float32 pass
 // (pre32s_kernels.hpp) and its launcher, compiled with -fno-slp-vectorize.
 //
 // Why a unit of its own.  hipcc's SLP vectoriser pairs neighbouring float32 operations of the

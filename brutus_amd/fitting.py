@@ -12,7 +12,7 @@ per-star grid-likelihood path:
 The grid scan (everything that touches all Nmodel models: the magnitude-space
 and flux-space optimisation of (scale, Av, Rv), chi2 / log-likelihood, the
 dimensionality prior, the parallax clip and the first `wt_thresh` cut) runs in
-the hand-written HIP kernels of `csrc/brutus_kernels.hip`, reached through the
+the hand-written HIP kernels of `csrc/` (`brutus_kernels.hip`; `lnpost`: `post_unit.hip`), reached through the
 C ABI of `include/brutus_amd.h`.  The host keeps what the reference's plugin
 contract forces onto the host -- the user-supplied `lngalprior` / `lndustprior`
 Python callables and the legacy `numpy.random.RandomState` stream -- and only

@@ -53,6 +53,37 @@ def test_library_exports_nothing_outside_its_prefix():
     helpers = [n for n in names if not n.startswith(("__device_stub__", "void __device_stub__"))
                and "k_" not in n.split("(")[0]]
     assert not helpers, helpers[:10]
+    # what the library's translation units call across their boundaries (brutus_i_*) is hidden
+    internal = [ln.split()[-1] for ln in out.splitlines() if ln.split()[-1].startswith("brutus_i_")]
+    assert not internal, internal
+
+
+def test_error_state_is_shared_by_all_translation_units():
+    """The library is several translation units; the error string lives in one of them
+    (host_unit.hip) and brutus_last_error() has to carry the message of whichever subsystem
+    failed last.  Argument validation comes before any HIP call, so no GPU is needed: one
+    rejected call into the fit unit, the post unit and the auxiliary unit (cluster, offsets),
+    one after the other."""
+    import ctypes
+    from brutus_amd import _lib
+    L = _lib.lib()
+
+    def rejected(name, **ints):
+        """Call `name` with NULL pointers and zeros, except the integer arguments given by
+        position (a3=1: fourth argument = 1); return the message it left."""
+        args = []
+        for k, t in enumerate(_lib.SIGNATURES[name][1]):
+            v = ints.get("a%d" % k, 0)
+            args.append(None if t in (ctypes.c_void_p,) or hasattr(t, "contents") else v)
+        assert getattr(L, name)(*args) == -1, name          # BRUTUS_EINVAL
+        return L.brutus_last_error().decode()
+
+    # (nmodel = 0; nstar = 0; nobj = 0; nmc = 0 with every other dimension valid)
+    assert rejected("brutus_fit_batch", a2=8, a3=1) == "bad nmodel"
+    assert rejected("brutus_post_batch", a1=1) == "bad post dimensions"
+    assert rejected("brutus_cluster_lnl_part", a1=8, a2=1).startswith("bad cluster dimensions (nobj=0, ")
+    assert rejected("brutus_offsets_bootstrap", a1=1, a2=1, a3=1, a4=1).startswith("bad bootstrap dimensions (")
+    assert rejected("brutus_fit_batch", a2=8, a3=1) == "bad nmodel"
 
 
 def test_hot_kernels_do_not_spill():

@@ -1,14 +1,16 @@
 #!/bin/bash
 # Development aid: instruction mix of one kernel (mangled-name substring) from the ISA of a
 # 12-band-only build:   tools/isa_stats.sh k_ffluxILi12ELb1ELb1 [-DFLAG=1 ...]
+# (UNIT=post_unit ...: a kernel of another translation unit than brutus_kernels.hip)
 pat=${1:?kernel name substring}; shift
+U=${UNIT:-brutus_kernels}; R=$(cd $(dirname $0)/.. && pwd)
 D=/tmp/isa_stats_$$; mkdir -p $D; cd $D
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -c -Wno-unused-value -save-temps -DBRUTUS_DEV_NB12_ONLY "$@" \
-    /root/repo/brutus_amd/csrc/brutus_kernels.hip -o x.o 2>&1 | grep -E "error" | head
-python3 - "$pat" "$D" <<'PY'
+    $R/brutus_amd/csrc/$U.hip -o x.o 2>&1 | grep -E "error" | head
+python3 - "$pat" "$D/$U" <<'PY'
 import re, sys, collections
 pat, D = sys.argv[1], sys.argv[2]
-L = open(D + '/brutus_kernels-hip-amdgcn-amd-amdhsa-gfx950.s').read().split('\n')
+L = open(D + '-hip-amdgcn-amd-amdhsa-gfx950.s').read().split('\n')
 start = next(k for k, l in enumerate(L) if re.match(r'^_ZN\S*' + re.escape(pat) + r'\S*:', l))
 end = start
 while '.end_amdhsa_kernel' not in L[end]:

@@ -15,11 +15,13 @@ rm -rf $O/${tag}_trace_cfg2 $O/${tag}_trace_cfg3 $O/${tag}_pmc_FETCH_SIZE_cfg2 $
 bash tools/pmc_sq.sh ${tag}_sq_cfg2 2 128 > /dev/null 2>&1
 bash tools/pmc_sq.sh ${tag}_sq_cfg3 3 128 > /dev/null 2>&1
 bash tools/pmc_clock.sh ${tag}_cfg2 2 128 > /dev/null 2>&1
-# the static ISA of both translation units (12-band instantiations: what the workloads run)
-I=/tmp/isa_round; mkdir -p $I; ( cd $I
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -c -Wno-unused-value -save-temps -DBRUTUS_DEV_NB12_ONLY $R/brutus_amd/csrc/brutus_kernels.hip -o x.o > /dev/null 2>&1
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -c -Wno-unused-value -save-temps -fno-slp-vectorize -DBRUTUS_DEV_NB12_ONLY $R/brutus_amd/csrc/pre32s_unit.hip -o y.o > /dev/null 2>&1 )
-S="$I/brutus_kernels-hip-amdgcn-amd-amdhsa-gfx950.s $I/pre32s_unit-hip-amdgcn-amd-amdhsa-gfx950.s"
+# the static ISA of every translation unit (12-band instantiations: what the workloads run)
+I=/tmp/isa_round; mkdir -p $I; S=""
+for u in $R/brutus_amd/csrc/*.hip; do
+  fl=""; [ $(basename $u) = pre32s_unit.hip ] && fl=-fno-slp-vectorize
+  ( cd $I && /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -c -Wno-unused-value -save-temps $fl -DBRUTUS_DEV_NB12_ONLY $u -o $(basename $u).o > /dev/null 2>&1 ) &
+  S="$S $I/$(basename $u .hip)-hip-amdgcn-amd-amdhsa-gfx950.s"
+done; wait
 export PMC_COMMIT=$commit
 rm -f $O/${tag}_sq_valu.json
 python tools/sq_to_json.py $O/${tag}_sq_cfg2_a.txt 2 128 3 $O/${tag}_sq_valu.json $S > $O/${tag}_tables.log 2>&1
