@@ -56,24 +56,12 @@ static int cluster_part(int nobj, int nfilt, int npts, const double *d_pts_flux,
     const dim3 g((nobj + CL_T - 1) / CL_T, chunk_n);
     Timer tm(st);
     tm.begin("k_cluster");
-#define BRUTUS_CL(N)                                                                              \
-    case N:                                                                                       \
-        hipLaunchKernelGGL((k_cluster<N, MAGS>), g, dim3(CL_T), 0, st, nobj, nfilt, npts,         \
-                           d_pts_flux, d_pts_lnw, mg, d_phot, d_ivar, d_chi2_p, d_lnorm, d_ndim,  \
-                           dim_prior, ppb, pm, ps);                                               \
-        break;
-    switch (nb) {
-        BRUTUS_CL(12)
-#ifndef BRUTUS_DEV_NB12_ONLY
-        BRUTUS_CL(8)
-        BRUTUS_CL(16)
-        BRUTUS_CL(24)
-        BRUTUS_CL(32)
-#endif
-        default:
-            return fail(BRUTUS_EINVAL, "cluster likelihood: at most %d bands (%d given)", BRUTUS_MAX_FILT_FIT, nfilt);
-    }
-#undef BRUTUS_CL
+    if (!with_nb(nb, FitBands{}, [&](auto NB) {
+            hipLaunchKernelGGL((k_cluster<decltype(NB)::value, MAGS>), g, dim3(CL_T), 0, st, nobj, nfilt, npts,
+                               d_pts_flux, d_pts_lnw, mg, d_phot, d_ivar, d_chi2_p, d_lnorm, d_ndim,
+                               dim_prior, ppb, pm, ps);
+        }))
+        return fail(BRUTUS_EINVAL, "cluster likelihood: at most %d bands (%d given)", BRUTUS_MAX_FILT_FIT, nfilt);
     tm.end();
     HIP_TRY(hipGetLastError());
     tm.collect();
@@ -210,21 +198,17 @@ struct OffsetsWs {
 };
 static int carve_offsets(char *base, int n, int nmc, OffsetsWs &w) {
     const size_t nv = (size_t)n * nmc;
-    size_t off = 0;
-    w.vals = (double *)(base + off);
-    off += align_up(sizeof(double) * nv);
-    w.sorted = (double *)(base + off);
-    off += align_up(sizeof(double) * nv);
-    w.seg = (int32_t *)(base + off);
-    off += align_up(sizeof(int32_t) * ((size_t)nmc + 1));
-    w.tmp = base + off;
+    Carver cv(base);
+    w.vals = (double *)cv.take(sizeof(double) * nv);
+    w.sorted = (double *)cv.take(sizeof(double) * nv);
+    w.seg = (int32_t *)cv.take(sizeof(int32_t) * ((size_t)nmc + 1));
     w.tmp_bytes = 0;
     hipError_t e = rocprim::segmented_radix_sort_keys(
         nullptr, w.tmp_bytes, (const double *)nullptr, (double *)nullptr, (unsigned int)nv,
         (unsigned int)nmc, (const int32_t *)nullptr, (const int32_t *)nullptr);
     if (e != hipSuccess) return -1;
-    off += align_up(w.tmp_bytes);
-    w.bytes = off;
+    w.tmp = cv.take(w.tmp_bytes);
+    w.bytes = cv.off;
     return 0;
 }
 }  // namespace

@@ -28,6 +28,10 @@
 //   "not converged at sweep k"  <=>  max{logwt_i : step_i >= tol} > max_i logwt_i + ln(init_thresh)
 // turns the masked max-step test (fitting.py:246-264) into two plain maxima.
 //
+// Host side of brutus_fit_batch: one FitCall per call, handed through named stages (start_call,
+// classify_on_device / _on_host, cull_candidates, flux_on_device / _on_host, select_and_derive,
+// read_results, capacity_verdict); run_fit strings them into the device-driven or the host-driven driver.
+//
 // This is one of the library's translation units: the full-grid pipeline (brutus_loglike_batch),
 // the hot path (brutus_fit_batch) and the device first cut (brutus_cut_batch).  lnpost is
 // post_unit.hip, the cluster likelihood and the photometric offsets aux_unit.hip, the error /
@@ -57,6 +61,18 @@ namespace {
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
+// The result block of brutus_fit_batch (Workspace::res): what the host reads at the end of a call,
+// in ONE copy.  int64 totals[4] (selected, derived, candidates, -), then as int32 k1[S], k2[S],
+// n_unconv[4], ctr[8]; k_prep32 zeroes the last two, which is why they lie side by side.
+struct ResBlock {
+    enum { SELECTED, DERIVED, CANDIDATES, NTOTALS = 4, NUNCONV = 4, NCTR = 8, ZEROED = NUNCONV + NCTR };
+    int64_t *totals;
+    int32_t *k1, *k2, *n_unconv, *ctr;
+    ResBlock(int64_t *base, int nstar) : totals(base), k1((int32_t *)(base + NTOTALS)), k2(k1 + nstar),
+                                         n_unconv(k2 + nstar), ctr(n_unconv + NUNCONV) {}
+    static size_t bytes(int nstar) { return sizeof(int64_t) * NTOTALS + sizeof(int32_t) * (2 * (size_t)nstar + ZEROED); }
+};
+
 struct Workspace {
     Planes pl;          // brutus_loglike_batch only: the caller's output planes + lnlp, step
     StarPrep *stars;
@@ -73,9 +89,7 @@ struct Workspace {
     int32_t *ctr;       // (8,) device-driven call: [0] stars to probe, [1] stars to redo, [3] "host path needed";
                         //      both drivers: [4], [5] lengths of the hot (block, star) lists of the two k_top1 launches
     int32_t *hot;       // (nblk2 * S,) hot (block, star) pairs of a k_top1 launch
-    int64_t *res;       // brutus_fit_batch: what the host reads at the end of a call, in ONE copy --
-                        // totals[4] = selected, derived, candidates, -; then k1 (S), k2 (S),
-                        // n_unconv (4), ctr (8) as int32 (w.k1 / w.k2 / w.n_unconv / w.ctr point here)
+    int64_t *res;       // brutus_fit_batch: the result block (ResBlock; k1 / k2 / n_unconv / ctr point into it)
     int32_t *kfix;      // (S,)
     double *thr_cull, *maxsurv, *thr_sel;
     int32_t *surv_idx;  // (S * nmodel,) worst case: candidate lists, then band queues, then derived lists
@@ -105,86 +119,73 @@ struct Workspace {
 // brutus_loglike_batch (the caller supplies the output planes); fit = true: brutus_fit_batch.
 Workspace carve(char *base, int64_t nmodel, int nstar, bool fit) {
     Workspace w{};
-    size_t off = 0;
-    auto take = [&](size_t n) {
-        char *p = base ? base + off : nullptr;
-        off += align_up(n);
-        return p;
-    };
-    auto take_big = [&](size_t n) {       // plane-sized arrays: absolute 2 MiB alignment
-        off = align_big((size_t)base + off) - (size_t)base;
-        char *p = base ? base + off : nullptr;
-        off += n;
-        return p;
-    };
+    Carver cv(base);
     const size_t pairs = (size_t)nstar * (size_t)nmodel;
     const int64_t ntile = pad_models(nmodel) / TILE;
     w.pl.nmodel = nmodel;
-    w.stars = (StarPrep *)take(sizeof(StarPrep) * nstar);
+    w.stars = (StarPrep *)cv.take(sizeof(StarPrep) * nstar);
     w.part_doubles = (size_t)ntile * (size_t)(nstar * 2 * KCAP > 1024 ? nstar * 2 * KCAP : 1024);
-    w.part = (double *)take(sizeof(double) * w.part_doubles);
-    w.stars_tmp = (StarPrep *)take(sizeof(StarPrep));
-    w.vmax_lnlp = (double *)take(sizeof(double) * nstar);
-    w.k1 = (int32_t *)take(sizeof(int32_t) * nstar);
-    w.k2 = (int32_t *)take(sizeof(int32_t) * nstar);
-    w.n_unconv = (int32_t *)take(sizeof(int32_t) * 4);
-    w.counts = (int64_t *)take(sizeof(int64_t) * nstar * NCHUNK);
-    w.offsets = (int64_t *)take(sizeof(int64_t) * nstar * NCHUNK);
+    w.part = (double *)cv.take(sizeof(double) * w.part_doubles);
+    w.stars_tmp = (StarPrep *)cv.take(sizeof(StarPrep));
+    w.vmax_lnlp = (double *)cv.take(sizeof(double) * nstar);
+    w.k1 = (int32_t *)cv.take(sizeof(int32_t) * nstar);
+    w.k2 = (int32_t *)cv.take(sizeof(int32_t) * nstar);
+    w.n_unconv = (int32_t *)cv.take(sizeof(int32_t) * 4);
+    w.counts = (int64_t *)cv.take(sizeof(int64_t) * nstar * NCHUNK);
+    w.offsets = (int64_t *)cv.take(sizeof(int64_t) * nstar * NCHUNK);
     if (!fit) {
-        w.pl.lnlp = (double *)take_big(sizeof(double) * pairs);
-        w.pl.step = (double *)take_big(sizeof(double) * pairs);
+        w.pl.lnlp = (double *)cv.take_big(sizeof(double) * pairs);
+        w.pl.step = (double *)cv.take_big(sizeof(double) * pairs);
     } else {
-        w.ids = (int32_t *)take(sizeof(int32_t) * nstar);
-        w.ids2 = (int32_t *)take(sizeof(int32_t) * nstar);
-        w.res = (int64_t *)take(sizeof(int64_t) * 4 + sizeof(int32_t) * (2 * (size_t)nstar + 12));
+        w.ids = (int32_t *)cv.take(sizeof(int32_t) * nstar);
+        w.ids2 = (int32_t *)cv.take(sizeof(int32_t) * nstar);
+        w.res = (int64_t *)cv.take(ResBlock::bytes(nstar));
         if (base) {
-            int32_t *r32 = (int32_t *)(w.res + 4);
-            w.k1 = r32;
-            w.k2 = r32 + nstar;
-            w.n_unconv = r32 + 2 * nstar;
-            w.ctr = r32 + 2 * nstar + 4;
-        } else {
-            w.ctr = nullptr;
+            const ResBlock res(w.res, nstar);
+            w.k1 = res.k1;
+            w.k2 = res.k2;
+            w.n_unconv = res.n_unconv;
+            w.ctr = res.ctr;
         }
-        w.kfix = (int32_t *)take(sizeof(int32_t) * nstar);
-        w.thr_cull = (double *)take(sizeof(double) * nstar);
-        w.maxsurv = (double *)take(sizeof(double) * nstar);
-        w.thr_sel = (double *)take(sizeof(double) * nstar);
-        w.surv_off = (int64_t *)take(sizeof(int64_t) * (nstar + 1));
-        w.der_off = (int64_t *)take(sizeof(int64_t) * (nstar + 1));
-        w.coffsets = (int64_t *)take(sizeof(int64_t) * nstar * NCHUNK);
-        w.dcounts = (int64_t *)take(sizeof(int64_t) * nstar * NCHUNK);
-        w.doffsets = (int64_t *)take(sizeof(int64_t) * nstar * NCHUNK);
-        w.wbase_surv = (int32_t *)take(sizeof(int32_t) * ((size_t)NCHUNK * nstar + 1));
-        w.wbase_der = (int32_t *)take(sizeof(int32_t) * ((size_t)NCHUNK * nstar + 1));
+        w.kfix = (int32_t *)cv.take(sizeof(int32_t) * nstar);
+        w.thr_cull = (double *)cv.take(sizeof(double) * nstar);
+        w.maxsurv = (double *)cv.take(sizeof(double) * nstar);
+        w.thr_sel = (double *)cv.take(sizeof(double) * nstar);
+        w.surv_off = (int64_t *)cv.take(sizeof(int64_t) * (nstar + 1));
+        w.der_off = (int64_t *)cv.take(sizeof(int64_t) * (nstar + 1));
+        w.coffsets = (int64_t *)cv.take(sizeof(int64_t) * nstar * NCHUNK);
+        w.dcounts = (int64_t *)cv.take(sizeof(int64_t) * nstar * NCHUNK);
+        w.doffsets = (int64_t *)cv.take(sizeof(int64_t) * nstar * NCHUNK);
+        w.wbase_surv = (int32_t *)cv.take(sizeof(int32_t) * ((size_t)NCHUNK * nstar + 1));
+        w.wbase_der = (int32_t *)cv.take(sizeof(int32_t) * ((size_t)NCHUNK * nstar + 1));
         {
             const size_t nit = (size_t)nstar * ((size_t)(pad_models(nmodel) / TILE) + NCHUNK);
-            w.items_surv = (ItemGeom *)take(sizeof(ItemGeom) * nit);
-            w.items_der = (ItemGeom *)take(sizeof(ItemGeom) * nit);
+            w.items_surv = (ItemGeom *)cv.take(sizeof(ItemGeom) * nit);
+            w.items_der = (ItemGeom *)cv.take(sizeof(ItemGeom) * nit);
         }
-        w.bandn = (int32_t *)take(sizeof(int32_t) * (size_t)NCHUNK * nstar);
+        w.bandn = (int32_t *)cv.take(sizeof(int32_t) * (size_t)NCHUNK * nstar);
         const size_t words = (size_t)nstar * (size_t)(pad_models(nmodel) / 64);
-        w.mask = (unsigned long long *)take_big(sizeof(unsigned long long) * words);
-        w.dmask = (unsigned long long *)take_big(sizeof(unsigned long long) * words);
-        w.smask = (unsigned long long *)take_big(sizeof(unsigned long long) * words);
+        w.mask = (unsigned long long *)cv.take_big(sizeof(unsigned long long) * words);
+        w.dmask = (unsigned long long *)cv.take_big(sizeof(unsigned long long) * words);
+        w.smask = (unsigned long long *)cv.take_big(sizeof(unsigned long long) * words);
         const size_t nblk2 = (size_t)(ntile + F2_T - 1) / F2_T;
-        w.s32 = (Star32 *)take(sizeof(Star32) * nstar);
-        w.part32 = (float *)take(sizeof(float) * nblk2 * nstar * NV32);
-        w.hot = (int32_t *)take(sizeof(int32_t) * nblk2 * nstar);
-        w.st32 = (float *)take(sizeof(float) * nstar * NV32);
-        w.status = (int32_t *)take(sizeof(int32_t) * nstar);
-        w.ids_all = (int32_t *)take(sizeof(int32_t) * nstar);
-        w.nomA = (double *)take(sizeof(double) * nstar);
-        w.nomB = (double *)take(sizeof(double) * nstar);
-        w.candS = (double *)take(sizeof(double) * nstar);
-        w.aud = (float *)take(sizeof(float) * nstar * 4);
-        w.lnlp32 = (float *)take_big(sizeof(float) * pairs);
-        w.lnpr32 = (float *)take_big(sizeof(float) * pairs);
-        w.surv_idx = (int32_t *)take_big(sizeof(int32_t) * pairs);
-        w.step_st = (double *)take_big(sizeof(double) * pairs);
-        w.lnprob_st = (double *)take_big(sizeof(double) * pairs);
+        w.s32 = (Star32 *)cv.take(sizeof(Star32) * nstar);
+        w.part32 = (float *)cv.take(sizeof(float) * nblk2 * nstar * NV32);
+        w.hot = (int32_t *)cv.take(sizeof(int32_t) * nblk2 * nstar);
+        w.st32 = (float *)cv.take(sizeof(float) * nstar * NV32);
+        w.status = (int32_t *)cv.take(sizeof(int32_t) * nstar);
+        w.ids_all = (int32_t *)cv.take(sizeof(int32_t) * nstar);
+        w.nomA = (double *)cv.take(sizeof(double) * nstar);
+        w.nomB = (double *)cv.take(sizeof(double) * nstar);
+        w.candS = (double *)cv.take(sizeof(double) * nstar);
+        w.aud = (float *)cv.take(sizeof(float) * nstar * 4);
+        w.lnlp32 = (float *)cv.take_big(sizeof(float) * pairs);
+        w.lnpr32 = (float *)cv.take_big(sizeof(float) * pairs);
+        w.surv_idx = (int32_t *)cv.take_big(sizeof(int32_t) * pairs);
+        w.step_st = (double *)cv.take_big(sizeof(double) * pairs);
+        w.lnprob_st = (double *)cv.take_big(sizeof(double) * pairs);
     }
-    w.bytes = align_big(off) + (base ? 0 : (size_t)4 << 20);     // (sizing: room for the base's own offset)
+    w.bytes = align_big(cv.off) + (base ? 0 : (size_t)4 << 20);     // (sizing: room for the base's own offset)
     return w;
 }
 
@@ -215,11 +216,31 @@ int make_params(const brutus_params *in, DevParams &p) {
     return 0;
 }
 
-struct Workspace;
+// Exact number of magnitude sweeps of ONE star by probing kmax = 16, 32, ... sweeps
+// with the residual-carrying kernels (no cap but max_iter; fitting.py:173-264).
 template <int NB>
 int probe_k1_deep(const float *grid, int64_t nmodel, int star, const DevParams &p, int max_iter,
                   Workspace &w, int32_t *k1_out, hipStream_t st, const double *av_init = nullptr,
-                  const double *rv_init = nullptr);
+                  const double *rv_init = nullptr) {
+    const int64_t nmodel_pad = pad_models(nmodel);
+    const int ntile = (int)(nmodel_pad / TILE);
+    HIP_TRY(hipMemcpyAsync(w.stars_tmp, w.stars + star, sizeof(StarPrep), hipMemcpyDeviceToDevice, st));
+    const int cap = (int)(w.part_doubles / ((size_t)ntile * 2));
+    for (int kmax = 16;; kmax *= 2) {
+        if (kmax > max_iter) kmax = max_iter;
+        if (kmax > cap) kmax = cap;
+        hipLaunchKernelGGL(k_mag_stats<NB>, dim3(ntile, 1), dim3(TILE), 0, st, grid, nmodel,
+                           nmodel_pad, 1, w.stars_tmp, p, kmax, w.part, av_init, rv_init);
+        hipLaunchKernelGGL(k_k1_deep_decide, dim3(1), dim3(256), 0, st, ntile, kmax, w.part,
+                           p.ln_init, w.k1 + star);
+        HIP_TRY(hipMemcpyAsync(k1_out, w.k1 + star, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (*k1_out > 0) return 0;
+        if (kmax >= max_iter || kmax >= cap)
+            return fail(BRUTUS_ENOCONV, "magnitude phase of star %d not converged after %d sweeps",
+                        star, kmax);
+    }
+}
 
 template <int NB>
 int run_pipeline(const float *grid, int64_t nmodel, int nstar, const DevParams &p,
@@ -302,406 +323,412 @@ int run_pipeline(const float *grid, int64_t nmodel, int nstar, const DevParams &
 int dispatch_pipeline(int nb, const float *grid, int64_t nmodel, int nstar, const DevParams &p,
                       int max_iter, Workspace &w, int32_t *h_k1, int32_t *h_k2,
                       hipStream_t st, Timer &tm, const double *av_init, const double *rv_init) {
-    switch (nb) {
-        case 12: return run_pipeline<12>(grid, nmodel, nstar, p, max_iter, w, h_k1, h_k2, st, tm, av_init, rv_init);
-#ifndef BRUTUS_DEV_NB12_ONLY      // (tools/ab/build.sh: kernel A/B builds in seconds; never set for the product)
-        case 8: return run_pipeline<8>(grid, nmodel, nstar, p, max_iter, w, h_k1, h_k2, st, tm, av_init, rv_init);
-        case 16: return run_pipeline<16>(grid, nmodel, nstar, p, max_iter, w, h_k1, h_k2, st, tm, av_init, rv_init);
-        case 24: return run_pipeline<24>(grid, nmodel, nstar, p, max_iter, w, h_k1, h_k2, st, tm, av_init, rv_init);
-        case 32: return run_pipeline<32>(grid, nmodel, nstar, p, max_iter, w, h_k1, h_k2, st, tm, av_init, rv_init);
-        case 48: return run_pipeline<48>(grid, nmodel, nstar, p, max_iter, w, h_k1, h_k2, st, tm, av_init, rv_init);
-        case 64: return run_pipeline<64>(grid, nmodel, nstar, p, max_iter, w, h_k1, h_k2, st, tm, av_init, rv_init);
-#endif
-    }
+    int rc = 0;
+    if (with_nb(nb, GridBands{}, [&](auto NB) {
+            rc = run_pipeline<decltype(NB)::value>(grid, nmodel, nstar, p, max_iter, w, h_k1, h_k2, st, tm, av_init, rv_init);
+        }))
+        return rc;
     return fail(BRUTUS_EINVAL, "unsupported band count %d", nb);
 }
 
 // ---- hot path host orchestration (brutus_fit_batch) ----------------------------------
-thread_local int t_audit_call = 0;        // dispatch_fit: this call's float32 bound is audited and enforced
+// Two drivers for the same kernels.  DEVICE-DRIVEN (default): which stars need the exact K1
+// probe, which need their float32 planes redone and which iterate on in the flux phase is
+// decided and listed ON THE DEVICE (k_pre_decide, k_k1_decide, k_fflux_decide), the
+// follow-up launches are issued unconditionally with a size that fits any list (their
+// surplus workgroups leave at once), and the host sees the call once, at its end.  What
+// that cannot express -- a star that needs more than the eight probed sweeps, a flux phase
+// longer than FLUX_ROUNDS continuations -- raises a flag, and the batch is done again by
+// the HOST-DRIVEN driver (round 3's: a host decision after the float32 pass and after
+// every flux launch; each one idles the stream for a round trip).  Each driver is a sequence
+// of the stages below (run_fit); a stage issues its launches, copies and memsets on c.st.
 constexpr int BRUTUS_RETRY_HOSTDRIVEN = -1000;     // internal: never leaves dispatch_fit
 std::atomic<long long> g_fit_calls{0}, g_fit_retries{0};     // device-driven calls / repeated host-driven
-constexpr int FS_TILES_PER_BLOCK = 8;
-constexpr int PERSIST_BLOCKS = 4096;
+constexpr int FS_TILES_PER_BLOCK = 8, PERSIST_BLOCKS = 4096, CONT_BLOCKS = 2048, TOP_BLOCKS = 1024;
 
-// nact == 0: the opening launch (all stars); else a continuation over the `nact` stars listed
-// in w.ids (device) that are still iterating.
-// nact < 0: a continuation whose list (w.ids) and length (*nact_dev) were written by
-// k_fflux_decide on the device -- a launch of fixed size.
-constexpr int CONT_BLOCKS = 2048;
-template <int NB, bool RVF>
-void launch_fflux(hipStream_t st, int nact, const float *grid, int64_t nmodel, int64_t nmodel_pad,
-                  int nstar, const DevParams &p, const Workspace &w, const RecPlanes &rec,
-                  const int32_t *nact_dev = nullptr) {
-    if (nact == 0)
-        hipLaunchKernelGGL((k_fflux<NB, RVF, true>), dim3(PERSIST_BLOCKS), dim3(TILE), 0, st, grid,
-                           nmodel, nmodel_pad, nstar, w.stars, p, w.k1, w.k2, w.surv_idx, w.surv_off,
-                           w.wbase_surv, w.items_surv, rec, w.step_st, w.lnprob_st, w.part, w.lnpr32,
-                           w.thr_cull, (const int32_t *)nullptr, 0, (const int32_t *)nullptr);
-    else if (nact > 0)
-        hipLaunchKernelGGL((k_fflux<NB, RVF, false>), dim3(NCHUNK * nact * CONT_P), dim3(TILE), 0, st,
-                           grid, nmodel, nmodel_pad, nstar, w.stars, p, w.k1, w.k2, w.surv_idx,
-                           w.surv_off, w.wbase_surv, w.items_surv, rec, w.step_st, w.lnprob_st, w.part,
-                           w.lnpr32, w.thr_cull, w.ids, nact, (const int32_t *)nullptr);
-    else       // (nact = -r, the r-th continuation: a per cent of the stars reach the first, fewer every round)
-        hipLaunchKernelGGL((k_fflux<NB, RVF, false>), dim3(nact == -1 ? CONT_BLOCKS : CONT_BLOCKS / 8), dim3(TILE), 0, st,
-                           grid, nmodel, nmodel_pad, nstar, w.stars, p, w.k1, w.k2, w.surv_idx,
-                           w.surv_off, w.wbase_surv, w.items_surv, rec, w.step_st, w.lnprob_st, w.part,
-                           w.lnpr32, w.thr_cull, w.ids, 0, nact_dev);
+// What every stage of one brutus_fit_batch call passes along.
+struct FitCall {
+    const float *grid;
+    int64_t nmodel, nmodel_pad;
+    int ntile, nblkx;       // tiles of TILE models; blocks of F2_T tiles (float32 pass, partial maxima)
+    int nfilt, nstar;
+    DevParams p;
+    int max_iter;
+    Workspace w;
+    RecPlanes rec;
+    int64_t capacity;
+    int32_t *d_rec_idx, *d_rec_slot;
+    int64_t *d_rec_off;
+    int32_t *h_k1, *h_k2;
+    int64_t *h_counts;      // [0] selected models (= d_rec_off[nstar]), [1] candidates of the cull, [2] slots needed in all
+    hipStream_t st;
+    Timer tm;
+    // set by dispatch_fit
+    int flux_rounds = 4;    // BRUTUS_FLUX_ROUNDS (development switch): continuations of the device-driven flux phase
+    bool audited = false;   // this call's float32 bound is audited and ENFORCED (audit_verdict)
+    float *aud = nullptr;   // w.aud on an audited call and with BRUTUS_AUDIT=1 (recorded for the caller to read)
+};
+
+// Rv pinned by its limits at the value every fit starts from: the (offset, Av)
+// specialisation computes the same thing (SURVEY 8d, config 2)
+inline bool rv_pinned(const DevParams &p) { return p.rvmin == p.rvmax && p.rv_mean == p.rvmin; }
+
+P32 make_p32(const DevParams &p, int nfilt) {      // (in the order of P32's fields)
+    return P32{(float)p.avmin, (float)p.avmax, (float)p.rvmin, (float)p.rvmax, (float)p.av_mean, (float)p.av_ivar,
+               (float)p.rv_mean, (float)p.rv_ivar, (float)(p.mtol * 1.002 + 1e-4), (float)(p.mtol * 0.998 - 1e-4),
+               p.dim_prior, nfilt};
 }
 
-// Exact K1 of the stars in `ids` by probing KS = 8 sweeps in float64 (k1 = 0: more needed).
-// `ids` = nullptr: the probe list (w.ids2, length w.ctr[0]) was put together on the device by
-// k_pre_decide; k_k1_decide then appends to the redo list (w.ids, length w.ctr[1]) itself.
+// The float32 pass over the `nrun` stars of `list` (device) and its decision kernel.  nrun_dev: the list's
+// real length lives on the device.  ctr: k_pre_decide puts the probe list w.ids2 / ctr[0] and the redo list
+// w.ids / ctr[1] together.  two_sweeps: every listed star stands at two sweeps, or Rv is pinned.
 template <int NB, bool RVF>
-int launch_k1probe(const float *grid, int64_t nmodel, int nstar, const std::vector<int32_t> *ids,
-                   const DevParams &p, int max_iter, Workspace &w, hipStream_t st, Timer &tm) {
-    constexpr int KS = 8;
-    const int64_t nmodel_pad = pad_models(nmodel);
-    const int ntile = (int)(nmodel_pad / TILE);
-    const int nblkx = (ntile + FS_TILES_PER_BLOCK - 1) / FS_TILES_PER_BLOCK;
-    if (ids) {
-        const int nrun = (int)ids->size();
-        HIP_TRY(hipMemcpyAsync(w.ids, ids->data(), sizeof(int32_t) * nrun, hipMemcpyHostToDevice, st));
-        tm.begin("k_k1probe");
-        hipLaunchKernelGGL((k_k1probe<NB, KS, RVF>), dim3(nblkx, nrun), dim3(TILE), 0, st, grid, nmodel,
-                           nmodel_pad, nstar, nrun, w.ids, w.stars, p, FS_TILES_PER_BLOCK, ntile, w.part,
-                           (const int32_t *)nullptr);
-        tm.end();
-        hipLaunchKernelGGL(k_k1_decide, dim3(nrun), dim3(256), 0, st, nblkx, nstar, w.ids, KS, w.part,
-                           p.ln_init, w.k1, (const int32_t *)nullptr, (int32_t *)nullptr,
-                           (int32_t *)nullptr, (int32_t *)nullptr, RVF ? 1 : 0, max_iter);
-    } else {
-        tm.begin("k_k1probe");
-        hipLaunchKernelGGL((k_k1probe<NB, KS, RVF>), dim3(nblkx, nstar < 8 ? nstar : 8), dim3(TILE), 0, st,
-                           grid, nmodel, nmodel_pad, nstar, 0, w.ids2, w.stars, p, FS_TILES_PER_BLOCK,
-                           ntile, w.part, w.ctr + 0);
-        tm.end();
-        hipLaunchKernelGGL(k_k1_decide, dim3(nstar), dim3(256), 0, st, nblkx, nstar, w.ids2, KS, w.part,
-                           p.ln_init, w.k1, w.ctr + 0, w.kfix, w.ctr, w.ids, RVF ? 1 : 0, max_iter);
-    }
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-// Exact number of magnitude sweeps of ONE star by probing kmax = 16, 32, ... sweeps
-// with the residual-carrying kernels (no cap but max_iter; fitting.py:173-264).
-template <int NB>
-int probe_k1_deep(const float *grid, int64_t nmodel, int star, const DevParams &p, int max_iter,
-                  Workspace &w, int32_t *k1_out, hipStream_t st, const double *av_init,
-                  const double *rv_init) {
-    const int64_t nmodel_pad = pad_models(nmodel);
-    const int ntile = (int)(nmodel_pad / TILE);
-    HIP_TRY(hipMemcpyAsync(w.stars_tmp, w.stars + star, sizeof(StarPrep), hipMemcpyDeviceToDevice, st));
-    const int cap = (int)(w.part_doubles / ((size_t)ntile * 2));
-    for (int kmax = 16;; kmax *= 2) {
-        if (kmax > max_iter) kmax = max_iter;
-        if (kmax > cap) kmax = cap;
-        hipLaunchKernelGGL(k_mag_stats<NB>, dim3(ntile, 1), dim3(TILE), 0, st, grid, nmodel,
-                           nmodel_pad, 1, w.stars_tmp, p, kmax, w.part, av_init, rv_init);
-        hipLaunchKernelGGL(k_k1_deep_decide, dim3(1), dim3(256), 0, st, ntile, kmax, w.part,
-                           p.ln_init, w.k1 + star);
-        HIP_TRY(hipMemcpyAsync(k1_out, w.k1 + star, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        if (*k1_out > 0) return 0;
-        if (kmax >= max_iter || kmax >= cap)
-            return fail(BRUTUS_ENOCONV, "magnitude phase of star %d not converged after %d sweeps",
-                        star, kmax);
-    }
-}
-
-// mode 0: host-driven (`ids`, `kfix` from the host; k_pre_decide leaves k1 / status for the host)
-// mode 1: device-driven opening pass over all stars (`ids`, `kfix` uploaded; k_pre_decide puts
-//         the probe list w.ids2 / w.ctr[0] and the redo list w.ids / w.ctr[1] together)
-// mode 2: device-driven re-run over the redo list as it stands on the device (accept = 1)
-template <int NB, bool RVF>
-int launch_pre32(const float *grid, int64_t nmodel, int nfilt, int nstar,
-                 const std::vector<int32_t> &ids, const std::vector<int32_t> &kfix,
-                 const DevParams &p, Workspace &w, int accept, hipStream_t st, Timer &tm,
-                 int mode = 0) {
+int launch_pre32(FitCall &c, const int32_t *list, int nrun, const int32_t *nrun_dev, int accept,
+                 int32_t *ctr, bool two_sweeps) {
     constexpr int G = 4;
-    const int64_t nmodel_pad = pad_models(nmodel);
-    const int ntile = (int)(nmodel_pad / TILE);
-    const int nblkx = (ntile + F2_T - 1) / F2_T;
-    const int nrun = mode == 2 ? nstar : (int)ids.size();
-    const int32_t *list = mode == 1 ? w.ids_all : w.ids;
-    if (mode == 0) HIP_TRY(hipMemcpyAsync(w.ids, ids.data(), sizeof(int32_t) * nrun, hipMemcpyHostToDevice, st));
-    // (mode 1: kfix = 2 for every star, set on the device by k_prep32)
-    if (mode == 0) HIP_TRY(hipMemcpyAsync(w.kfix, kfix.data(), sizeof(int32_t) * nstar, hipMemcpyHostToDevice, st));
-    const int32_t *nrun_dev = mode == 2 ? w.ctr + 1 : nullptr;
-    P32 q;
-    q.avmin = (float)p.avmin;
-    q.avmax = (float)p.avmax;
-    q.rvmin = (float)p.rvmin;
-    q.rvmax = (float)p.rvmax;
-    q.av_mean = (float)p.av_mean;
-    q.av_ivar = (float)p.av_ivar;
-    q.rv_mean = (float)p.rv_mean;
-    q.rv_ivar = (float)p.rv_ivar;
-    q.mtol_hi = (float)(p.mtol * 1.002 + 1e-4);
-    q.mtol_lo = (float)(p.mtol * 0.998 - 1e-4);
-    q.dim_prior = p.dim_prior;
-    q.nfilt = nfilt;
+    const Workspace &w = c.w;
+    const P32 q = make_p32(c.p, c.nfilt);
     // Long star lists take the star-lane pass (pre32s_kernels.hpp: lane = star, the models' rows
     // broadcast from LDS); short ones -- the re-run over a handful of stars, lists with other
     // sweep counts than the opening pass's two -- the tile pass.
     // (development / test switches, read per call: the tests flip them inside one process)
     const int use_mfma = env_int("BRUTUS_PRE32_MFMA", 0);     // (measured, not the default: pre32m_kernels.hpp)
     const int min_stars = env_int("BRUTUS_PRE32_STAR_LANES_MIN", 32);
-    bool lanes_are_stars = brutus_i_pre32s_bands(NB) && mode != 2 && nrun >= min_stars &&
-                           env_int("BRUTUS_PRE32_STAR_LANES", 1) != 0;
-    // (two translation units, one definition of the shared layout: pre32_types.hpp)
-    if (brutus_i_pre32_layout(0) != (int)sizeof(Star32) || brutus_i_pre32_layout(1) != (int)sizeof(P32) ||
-        brutus_i_pre32_layout(2) != F2_T || brutus_i_pre32_layout(3) != TILE || brutus_i_pre32_layout(4) != NV32)
-        return fail(BRUTUS_EINVAL, "float32 pass: the library's translation units disagree on the Star32 / "
-                                   "tile layout (built with different flags?)");
-    if (lanes_are_stars && !RVF)
-        for (int k = 0; k < nrun && lanes_are_stars; ++k) lanes_are_stars = kfix[ids[k]] == 2;
+    const bool lanes_are_stars = brutus_i_pre32s_bands(NB) && two_sweeps && nrun >= min_stars &&
+                                 env_int("BRUTUS_PRE32_STAR_LANES", 1) != 0;
+    c.tm.begin("k_pre32");
     if (lanes_are_stars) {
-        tm.begin("k_pre32");
-        if (brutus_i_pre32s_launch(NB, use_mfma, RVF ? 1 : 0, grid, nmodel, nmodel_pad, nstar, nrun, list, w.s32, &q,
-                                   w.lnlp32, w.lnpr32, w.part32, st))
+        if (brutus_i_pre32s_launch(NB, use_mfma, RVF ? 1 : 0, c.grid, c.nmodel, c.nmodel_pad, c.nstar, nrun, list,
+                                   w.s32, &q, w.lnlp32, w.lnpr32, w.part32, c.st))
             return fail(BRUTUS_EHIP, "star-lane float32 pass: launch failed");
-        tm.end();
     } else {
-    tm.begin("k_pre32");
-    hipLaunchKernelGGL((k_pre32<NB, RVF, G>), dim3(8 * ((nblkx + 7) / 8) * ((nrun + G - 1) / G)),
-                       dim3(TILE), 0, st, grid,
-                       nmodel, nmodel_pad, nstar, nrun, list, w.s32, q, w.kfix, ntile, w.lnlp32,
-                       w.lnpr32, w.part32, nrun_dev);
-    tm.end();
+        hipLaunchKernelGGL((k_pre32<NB, RVF, G>), dim3(8 * ((c.nblkx + 7) / 8) * ((nrun + G - 1) / G)),
+                           dim3(TILE), 0, c.st, c.grid, c.nmodel, c.nmodel_pad, c.nstar, nrun, list, w.s32, q,
+                           w.kfix, c.ntile, w.lnlp32, w.lnpr32, w.part32, nrun_dev);
     }
-    hipLaunchKernelGGL(k_pre_decide, dim3(nrun), dim3(256), 0, st, nblkx, nstar, list, w.part32,
-                       w.s32, (float)p.ln_init, RVF ? 1 : 0, w.kfix, accept, w.st32, w.k1, w.status,
-                       w.nomA, mode == 1 ? w.ctr : (int32_t *)nullptr, w.ids2, w.ids, nrun_dev);
+    c.tm.end();
+    hipLaunchKernelGGL(k_pre_decide, dim3(nrun), dim3(256), 0, c.st, c.nblkx, c.nstar, list, w.part32,
+                       w.s32, (float)c.p.ln_init, RVF ? 1 : 0, w.kfix, accept, w.st32, w.k1, w.status,
+                       w.nomA, ctr, w.ids2, w.ids, nrun_dev);
     HIP_TRY(hipGetLastError());
     return 0;
 }
 
-// h_counts[0] = selected models of the batch (= d_rec_off[nstar]), [1] = candidates of the
-// cull (the record slots the flux phase owns), [2] = record slots needed in all.
+// device-driven opening pass over all stars (w.ids_all; kfix = 2 for every star, set by k_prep32)
 template <int NB, bool RVF>
-int run_fit(const float *grid, int64_t nmodel, int nfilt, int nstar, const DevParams &p,
-            int max_iter, Workspace &w, int64_t capacity, int32_t *d_rec_idx, int32_t *d_rec_slot,
-            double *d_rec_vals, int64_t *d_rec_off, int32_t *h_k1, int32_t *h_k2, int64_t *h_counts,
-            hipStream_t st, Timer &tm, bool device_driven) {
-    const int64_t nmodel_pad = pad_models(nmodel);
-    const int ntile = (int)(nmodel_pad / TILE);
-    const int nblkx = (ntile + F2_T - 1) / F2_T;
-    const dim3 blk(TILE);
-    const RecPlanes rec{d_rec_vals, capacity};
+int pre32_all_stars(FitCall &c) { return launch_pre32<NB, RVF>(c, c.w.ids_all, c.nstar, nullptr, 0, c.w.ctr, true); }
+// device-driven re-run over the redo list as it stands on the device (w.ids, length w.ctr[1])
+template <int NB, bool RVF>
+int pre32_redo_on_device(FitCall &c) { return launch_pre32<NB, RVF>(c, c.w.ids, c.nstar, c.w.ctr + 1, 1, nullptr, false); }
+// host-driven: `ids` and `kfix` (sweeps of every star) come from the host; k_pre_decide leaves k1 / status for it
+template <int NB, bool RVF>
+int pre32_host_list(FitCall &c, const std::vector<int32_t> &ids, const std::vector<int32_t> &kfix, int accept) {
+    const int nrun = (int)ids.size();
+    HIP_TRY(hipMemcpyAsync(c.w.ids, ids.data(), sizeof(int32_t) * nrun, hipMemcpyHostToDevice, c.st));
+    HIP_TRY(hipMemcpyAsync(c.w.kfix, kfix.data(), sizeof(int32_t) * c.nstar, hipMemcpyHostToDevice, c.st));
+    bool two_sweeps = true;
+    if (!RVF)
+        for (int k = 0; k < nrun && two_sweeps; ++k) two_sweeps = kfix[ids[k]] == 2;
+    return launch_pre32<NB, RVF>(c, c.w.ids, nrun, nullptr, accept, nullptr, two_sweeps);
+}
+
+// Exact K1 of listed stars by probing KS = 8 sweeps in float64 (k1 = 0: more needed).
+constexpr int KS = 8;
+template <int NB, bool RVF>
+int k1probe_host_list(FitCall &c, const std::vector<int32_t> &ids) {
+    const Workspace &w = c.w;
+    const int nblkx = (c.ntile + FS_TILES_PER_BLOCK - 1) / FS_TILES_PER_BLOCK;
+    const int nrun = (int)ids.size();
+    HIP_TRY(hipMemcpyAsync(w.ids, ids.data(), sizeof(int32_t) * nrun, hipMemcpyHostToDevice, c.st));
+    c.tm.begin("k_k1probe");
+    hipLaunchKernelGGL((k_k1probe<NB, KS, RVF>), dim3(nblkx, nrun), dim3(TILE), 0, c.st, c.grid, c.nmodel, c.nmodel_pad,
+                       c.nstar, nrun, w.ids, w.stars, c.p, FS_TILES_PER_BLOCK, c.ntile, w.part, (const int32_t *)nullptr);
+    c.tm.end();
+    int32_t *const none = nullptr;       // (no device lists to append to)
+    hipLaunchKernelGGL(k_k1_decide, dim3(nrun), dim3(256), 0, c.st, nblkx, c.nstar, w.ids, KS, w.part, c.p.ln_init,
+                       w.k1, (const int32_t *)nullptr, none, none, none, RVF ? 1 : 0, c.max_iter);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// The probe list (w.ids2, length w.ctr[0]) was put together on the device by k_pre_decide;
+// k_k1_decide then appends to the redo list (w.ids, length w.ctr[1]) itself.
+template <int NB, bool RVF>
+int k1probe_device_list(FitCall &c) {
+    const Workspace &w = c.w;
+    const int nblkx = (c.ntile + FS_TILES_PER_BLOCK - 1) / FS_TILES_PER_BLOCK;
+    c.tm.begin("k_k1probe");
+    hipLaunchKernelGGL((k_k1probe<NB, KS, RVF>), dim3(nblkx, c.nstar < 8 ? c.nstar : 8), dim3(TILE), 0, c.st,
+                       c.grid, c.nmodel, c.nmodel_pad, c.nstar, 0, w.ids2, w.stars, c.p, FS_TILES_PER_BLOCK,
+                       c.ntile, w.part, w.ctr + 0);
+    c.tm.end();
+    hipLaunchKernelGGL(k_k1_decide, dim3(c.nstar), dim3(256), 0, c.st, nblkx, c.nstar, w.ids2, KS, w.part,
+                       c.p.ln_init, w.k1, w.ctr + 0, w.kfix, w.ctr, w.ids, RVF ? 1 : 0, c.max_iter);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// The three launches of k_fflux: the opening one over all stars, and continuations over the stars
+// still iterating, listed in w.ids (device) by the host or by k_fflux_decide.
+template <int NB, bool RVF, bool OPENING>
+void launch_fflux(const FitCall &c, int nblocks, const int32_t *ids, int nact, const int32_t *nact_dev) {
+    const Workspace &w = c.w;
+    hipLaunchKernelGGL((k_fflux<NB, RVF, OPENING>), dim3(nblocks), dim3(TILE), 0, c.st, c.grid, c.nmodel,
+                       c.nmodel_pad, c.nstar, w.stars, c.p, w.k1, w.k2, w.surv_idx, w.surv_off, w.wbase_surv,
+                       w.items_surv, c.rec, w.step_st, w.lnprob_st, w.part, w.lnpr32, w.thr_cull, ids, nact, nact_dev);
+}
+template <int NB, bool RVF>
+void fflux_open(const FitCall &c) { launch_fflux<NB, RVF, true>(c, PERSIST_BLOCKS, nullptr, 0, nullptr); }
+template <int NB, bool RVF>
+void fflux_continue_host(const FitCall &c, int nact) {
+    launch_fflux<NB, RVF, false>(c, NCHUNK * nact * CONT_P, c.w.ids, nact, nullptr);
+}
+// (a launch of fixed size: a per cent of the stars reach the first round, fewer every round after it)
+template <int NB, bool RVF>
+void fflux_continue_device(const FitCall &c, int round, const int32_t *nact_dev) {
+    launch_fflux<NB, RVF, false>(c, round == 1 ? CONT_BLOCKS : CONT_BLOCKS / 8, c.w.ids, 0, nact_dev);
+}
+
+// ---- the stages.  k_prep32 also starts the call's small device state: w.ids_all = 0, 1, ...,
+// kfix = k2 = 2, n_unconv and ctr zero -- they lie side by side in the result block.
+int start_call(FitCall &c) {
+    const Workspace &w = c.w;
+    if (c.aud) HIP_TRY(hipMemsetAsync(w.aud, 0, sizeof(float) * c.nstar * 4, c.st));
+    c.h_counts[0] = c.h_counts[1] = c.h_counts[2] = 0;
+    hipLaunchKernelGGL(k_prep32, dim3(c.nstar), dim3(64), 0, c.st, c.nstar, w.stars,
+                       (float)env_double("BRUTUS_EPS_SCALE", 1.0), c.p.dim_prior, w.s32,
+                       CallInit{w.ids_all, w.kfix, w.k2, w.n_unconv, ResBlock::ZEROED});
+    return 0;
+}
+
+// float32 pass over the whole grid; K1 where float32 can decide it, the exact probe where not,
+// the float32 planes redone at the state after K1 sweeps -- all three over lists kept on the device
+template <int NB, bool RVF>
+int classify_on_device(FitCall &c) {
+    if (int rc = pre32_all_stars<NB, RVF>(c)) return rc;
+    if (int rc = k1probe_device_list<NB, RVF>(c)) return rc;
+    if (!RVF)       // (pinned Rv: the planes never depend on the sweep count)
+        if (int rc = pre32_redo_on_device<NB, RVF>(c)) return rc;
+    return 0;
+}
+
+// the same, the lists drawn up by the host: a round trip after the float32 pass, another after the probe
+template <int NB, bool RVF>
+int classify_on_host(FitCall &c) {
+    Workspace &w = c.w;
+    const int nstar = c.nstar;
     std::vector<int32_t> ids(nstar), kfix(nstar, 2), k1(nstar, 0), status(nstar, 0);
     for (int s = 0; s < nstar; ++s) ids[s] = s;
-    // the run-time audit of the float32 bound: every call with BRUTUS_AUDIT=1 (recorded for the
-    // caller to read: tests, tools/fuzz_fit.py), and ENFORCED on the calls dispatch_fit picks
-    // (the first of the process and every BRUTUS_AUDIT_EVERY-th after it, audit_verdict below)
-    const int audit_on = env_int("BRUTUS_AUDIT", 0) != 0 || t_audit_call;
-    float *aud = audit_on ? w.aud : nullptr;
-    if (aud) HIP_TRY(hipMemsetAsync(w.aud, 0, sizeof(float) * nstar * 4, st));
-    h_counts[0] = h_counts[1] = h_counts[2] = 0;
-
-    // ---- float32 pass over the whole grid; K1 where float32 can decide it ----------
-    // (k_prep32 also starts the call's small device state: w.ids_all = 0, 1, ..., kfix = k2 = 2,
-    // n_unconv and ctr zero -- they lie side by side in the result block)
-    hipLaunchKernelGGL(k_prep32, dim3(nstar), dim3(64), 0, st, nstar, w.stars,
-                       (float)env_double("BRUTUS_EPS_SCALE", 1.0), p.dim_prior, w.s32,
-                       CallInit{w.ids_all, w.kfix, w.k2, w.n_unconv, 12});
-    // Two drivers for the same kernels.  DEVICE-DRIVEN (default): which stars need the exact K1
-    // probe, which need their float32 planes redone and which iterate on in the flux phase is
-    // decided and listed ON THE DEVICE (k_pre_decide, k_k1_decide, k_fflux_decide), the
-    // follow-up launches are issued unconditionally with a size that fits any list (their
-    // surplus workgroups leave at once), and the host sees the call once, at its end.  What
-    // that cannot express -- a star that needs more than the eight probed sweeps, a flux phase
-    // longer than FLUX_ROUNDS continuations -- raises a flag, and the batch is done again by
-    // the HOST-DRIVEN driver below (round 3's: a host decision after the float32 pass and after
-    // every flux launch; each one idles the stream for a round trip).
-    const int FLUX_ROUNDS = env_int("BRUTUS_FLUX_ROUNDS", 4);       // (development switch)
-    if (device_driven) {
-        if (int rc = launch_pre32<NB, RVF>(grid, nmodel, nfilt, nstar, ids, kfix, p, w, 0, st, tm, 1)) return rc;
-        if (int rc = launch_k1probe<NB, RVF>(grid, nmodel, nstar, nullptr, p, max_iter, w, st, tm)) return rc;
-        if (!RVF)       // (pinned Rv: the planes never depend on the sweep count)
-            if (int rc = launch_pre32<NB, RVF>(grid, nmodel, nfilt, nstar, ids, kfix, p, w, 1, st, tm, 2)) return rc;
-    } else {
-    if (int rc = launch_pre32<NB, RVF>(grid, nmodel, nfilt, nstar, ids, kfix, p, w, 0, st, tm)) return rc;
-    HIP_TRY(hipMemcpyAsync(k1.data(), w.k1, sizeof(int32_t) * nstar, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(status.data(), w.status, sizeof(int32_t) * nstar, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    if (int rc = pre32_host_list<NB, RVF>(c, ids, kfix, 0)) return rc;
+    HIP_TRY(hipMemcpyAsync(k1.data(), w.k1, sizeof(int32_t) * nstar, hipMemcpyDeviceToHost, c.st));
+    HIP_TRY(hipMemcpyAsync(status.data(), w.status, sizeof(int32_t) * nstar, hipMemcpyDeviceToHost, c.st));
+    HIP_TRY(hipStreamSynchronize(c.st));
     std::vector<int32_t> probe, redo;
     for (int s = 0; s < nstar; ++s) {
         if (status[s] == 1) redo.push_back(s);
         if (status[s] == 2) probe.push_back(s);
     }
     if (!probe.empty()) {   // float32 could not decide: exact probe (float64, up to 8 sweeps, then deeper)
-        if (int rc = launch_k1probe<NB, RVF>(grid, nmodel, nstar, &probe, p, max_iter, w, st, tm)) return rc;
-        HIP_TRY(hipMemcpyAsync(k1.data(), w.k1, sizeof(int32_t) * nstar, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
+        if (int rc = k1probe_host_list<NB, RVF>(c, probe)) return rc;
+        HIP_TRY(hipMemcpyAsync(k1.data(), w.k1, sizeof(int32_t) * nstar, hipMemcpyDeviceToHost, c.st));
+        HIP_TRY(hipStreamSynchronize(c.st));
         for (int s : probe) {
             if (k1[s] == 0)
-                if (int rc = probe_k1_deep<NB>(grid, nmodel, s, p, max_iter, w, &k1[s], st)) return rc;
-            if (k1[s] > max_iter)
+                if (int rc = probe_k1_deep<NB>(c.grid, c.nmodel, s, c.p, c.max_iter, w, &k1[s], c.st)) return rc;
+            if (k1[s] > c.max_iter)
                 return fail(BRUTUS_ENOCONV, "magnitude phase of star %d needs %d sweeps (max_iter %d)", s,
-                            k1[s], max_iter);
+                            k1[s], c.max_iter);
             kfix[s] = k1[s];
             if (!RVF && k1[s] != 2) redo.push_back(s);
         }
     }
     for (int s : redo) kfix[s] = k1[s];
     if (!redo.empty())      // float32 statistics at the state after K1 sweeps
-        if (int rc = launch_pre32<NB, RVF>(grid, nmodel, nfilt, nstar, redo, kfix, p, w, 1, st, tm)) return rc;
-    }
+        if (int rc = pre32_host_list<NB, RVF>(c, redo, kfix, 1)) return rc;
+    return 0;
+}
 
-    // ---- exact cull threshold ---------------------------------------------------------
-    // (k_hot_list + k_top1: the hot (block, star) pairs as a list)
-    constexpr int TOP_BLOCKS = 1024;
-    tm.begin("k_top");
-    hipLaunchKernelGGL(k_hot_list, dim3(nstar), dim3(256), 0, st, nblkx, nstar, 0, w.part32, w.nomA,
+// exact cull threshold (k_hot_list + k_top1: the hot (block, star) pairs as a list), then the
+// candidates (lnl_p~ >= thr_cull - eps) as ordered lists
+template <int NB, bool RVF>
+void cull_candidates(FitCall &c) {
+    const Workspace &w = c.w;
+    const int nstar = c.nstar;
+    const dim3 blk(TILE);
+    c.tm.begin("k_top");
+    hipLaunchKernelGGL(k_hot_list, dim3(nstar), dim3(256), 0, c.st, c.nblkx, nstar, 0, w.part32, w.nomA,
                        (const double *)nullptr, w.s32, (double *)nullptr, w.part, w.hot, w.ctr + 4);
-    hipLaunchKernelGGL((k_top1<NB, RVF>), dim3(TOP_BLOCKS), blk, 0, st, grid, nmodel, nmodel_pad, nstar,
-                       w.stars, p, w.k1, ntile, 0, w.lnlp32, w.nomA, w.hot, w.ctr + 4, w.part, aud);
-    tm.end();
-    hipLaunchKernelGGL(k_top_decide, dim3(nstar), dim3(256), 0, st, nblkx, nstar, w.ids_all, 0, w.part,
-                       w.s32, p.ln_init, (const double *)nullptr, w.thr_cull, w.candS);
-
-    // ---- candidates (lnl_p~ >= thr_cull - eps) as ordered lists --------------------------
-    tm.begin("k_surv_compact");
-    hipLaunchKernelGGL(k_cmp_count32, dim3(NCHUNK, nstar), blk, 0, st, nmodel, ntile, w.lnlp32, w.candS,
+    hipLaunchKernelGGL((k_top1<NB, RVF>), dim3(TOP_BLOCKS), blk, 0, c.st, c.grid, c.nmodel, c.nmodel_pad, nstar,
+                       w.stars, c.p, w.k1, c.ntile, 0, w.lnlp32, w.nomA, w.hot, w.ctr + 4, w.part, c.aud);
+    c.tm.end();
+    hipLaunchKernelGGL(k_top_decide, dim3(nstar), dim3(256), 0, c.st, c.nblkx, nstar, w.ids_all, 0, w.part,
+                       w.s32, c.p.ln_init, (const double *)nullptr, w.thr_cull, w.candS);
+    c.tm.begin("k_surv_compact");
+    hipLaunchKernelGGL(k_cmp_count32, dim3(NCHUNK, nstar), blk, 0, c.st, c.nmodel, c.ntile, w.lnlp32, w.candS,
                        w.counts, w.smask);
-    {
-        const OffsetsJob job{w.counts, w.coffsets, w.surv_off, w.wbase_surv, w.res + 2};
-        hipLaunchKernelGGL(k_offsets, dim3(2), dim3(OFF_T), 0, st, nstar, job, job);
-    }
-    hipLaunchKernelGGL(k_items, dim3((NCHUNK * nstar + 255) / 256), dim3(256), 0, st, nstar, w.wbase_surv,
+    const OffsetsJob job{w.counts, w.coffsets, w.surv_off, w.wbase_surv, w.res + ResBlock::CANDIDATES};
+    hipLaunchKernelGGL(k_offsets, dim3(2), dim3(OFF_T), 0, c.st, nstar, job, job);
+    hipLaunchKernelGGL(k_items, dim3((NCHUNK * nstar + 255) / 256), dim3(256), 0, c.st, nstar, w.wbase_surv,
                        w.coffsets, w.surv_off, w.items_surv);
-    hipLaunchKernelGGL(k_cmp_scatter, dim3(NCHUNK, nstar), blk, 0, st, nmodel, ntile, w.smask,
-                       w.coffsets, (int64_t)nstar * nmodel, w.surv_idx);
-    tm.end();
-    int64_t h_ncand = 0;
-    if (!device_driven)
-        HIP_TRY(hipMemcpyAsync(&h_ncand, w.surv_off + nstar, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    hipLaunchKernelGGL(k_cmp_scatter, dim3(NCHUNK, nstar), blk, 0, c.st, c.nmodel, c.ntile, w.smask,
+                       w.coffsets, (int64_t)nstar * c.nmodel, w.surv_idx);
+    c.tm.end();
+}
 
-    // ---- exact cull test + flux phase on the candidates; results into the record planes ------
+// Does the record buffer hold the call?  ENOMEM and, in h_counts[1] / [2], the candidate slots and
+// the slots a repeat of the call needs in all, if not.
+enum class Asked { HostAfterFirstFlux, DeviceCandidates, WholeCall };
+int capacity_verdict(const FitCall &c, Asked when, int64_t ncand, int64_t nder) {
+    int64_t *n = c.h_counts;
+    if (when != Asked::WholeCall) {
+        // the flux phase keeps its results in the record planes: without room for the candidates there
+        // is nothing to go on with (every write was bounded by the capacity)
+        if (ncand <= c.capacity) return 0;
+        n[1] = ncand;
+        n[2] = when == Asked::HostAfterFirstFlux
+                   ? 2 * ncand                                 // stopped before anything is derived: a guess
+                   : ncand + (nder > 0 ? nder : ncand);        // ran to its end: knows nder
+        return fail(BRUTUS_ENOMEM, "record buffer too small: %lld candidate slots, capacity %lld",
+                    (long long)ncand, (long long)c.capacity);
+    }
+    n[1] = ncand;
+    n[2] = ncand + nder;
+    if (n[2] > c.capacity)
+        return fail(BRUTUS_ENOMEM, "record buffer too small: %lld slots needed, capacity %lld",
+                    (long long)n[2], (long long)c.capacity);
+    return 0;
+}
+
+// exact cull test + flux phase on the candidates; results into the record planes.  Opening launch +
+// flux_rounds continuations; round r's decision counts and lists the stars that iterate on in
+// w.n_unconv[r & 1] / w.ids, the next launch reads them there (both counters start at zero, k_prep32; round
+// r's decision zeroes the one round r + 1 adds to).  Still iterating at the end: w.n_unconv[flux_rounds & 1].
+template <int NB, bool RVF>
+void flux_on_device(FitCall &c) {
+    const Workspace &w = c.w;
+    for (int r = 0; r <= c.flux_rounds; ++r) {
+        c.tm.begin(r == 0 ? "k_fflux" : "k_fflux_cont");
+        if (r == 0) fflux_open<NB, RVF>(c);
+        else fflux_continue_device<NB, RVF>(c, r, w.n_unconv + ((r - 1) & 1));
+        c.tm.end();
+        hipLaunchKernelGGL(k_fflux_decide, dim3(c.nstar), dim3(256), 0, c.st, c.nstar, w.wbase_surv, w.part,
+                           c.p.ln_sub, w.k2, w.maxsurv, w.n_unconv + (r & 1), w.ids, w.n_unconv + ((r + 1) & 1));
+    }
+}
+
+// the same, one round trip per launch: the host reads K2 and lists the stars still iterating.
+// *ncand = candidates of the batch, known after the first round.
+template <int NB, bool RVF>
+int flux_on_host(FitCall &c, int64_t *ncand) {
+    const Workspace &w = c.w;
+    const int nstar = c.nstar;
+    HIP_TRY(hipMemcpyAsync(ncand, w.surv_off + nstar, sizeof(int64_t), hipMemcpyDeviceToHost, c.st));
     int32_t h_unconv = 0;
     int iter = 2;
     std::vector<int32_t> k2s(nstar), act;
-    if (device_driven) {
-        // opening launch + FLUX_ROUNDS continuations; round r's decision counts and lists the
-        // stars that iterate on in w.n_unconv[r & 1] / w.ids, the next launch reads them there
-        // (both counters start at zero, k_prep32; round r's decision zeroes the one round r + 1 adds to)
-        for (int r = 0; r <= FLUX_ROUNDS; ++r) {
-            tm.begin(r == 0 ? "k_fflux" : "k_fflux_cont");
-            launch_fflux<NB, RVF>(st, r == 0 ? 0 : -r, grid, nmodel, nmodel_pad, nstar, p, w, rec,
-                                  w.n_unconv + ((r - 1) & 1));
-            tm.end();
-            hipLaunchKernelGGL(k_fflux_decide, dim3(nstar), dim3(256), 0, st, nstar, w.wbase_surv, w.part,
-                               p.ln_sub, w.k2, w.maxsurv, w.n_unconv + (r & 1), w.ids,
-                               w.n_unconv + ((r + 1) & 1));
-        }
-        // (stars still iterating at the end: w.n_unconv[FLUX_ROUNDS & 1], read with the result block)
-    } else
     for (int first = 1;; first = 0) {
-        HIP_TRY(hipMemsetAsync(w.n_unconv, 0, sizeof(int32_t), st));
-        tm.begin(first ? "k_fflux" : "k_fflux_cont");
-        launch_fflux<NB, RVF>(st, (int)act.size(), grid, nmodel, nmodel_pad, nstar, p, w, rec);
-        tm.end();
-        hipLaunchKernelGGL(k_fflux_decide, dim3(nstar), dim3(256), 0, st, nstar, w.wbase_surv, w.part,
-                           p.ln_sub, w.k2, w.maxsurv, w.n_unconv, (int32_t *)nullptr, (int32_t *)nullptr);
-        HIP_TRY(hipMemcpyAsync(&h_unconv, w.n_unconv, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(k2s.data(), w.k2, sizeof(int32_t) * nstar, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        if (first && h_ncand > capacity) {
-            // the flux phase keeps its results in the record planes: nothing to go on with
-            h_counts[1] = h_ncand;
-            h_counts[2] = 2 * h_ncand;       // (the derived records come on top; a guess)
-            return fail(BRUTUS_ENOMEM, "record buffer too small: %lld candidate slots, capacity %lld",
-                        (long long)h_ncand, (long long)capacity);
-        }
-        if (h_unconv == 0) break;
-        if (iter >= max_iter)
+        HIP_TRY(hipMemsetAsync(w.n_unconv, 0, sizeof(int32_t), c.st));
+        c.tm.begin(first ? "k_fflux" : "k_fflux_cont");
+        if (first) fflux_open<NB, RVF>(c);
+        else fflux_continue_host<NB, RVF>(c, (int)act.size());
+        c.tm.end();
+        hipLaunchKernelGGL(k_fflux_decide, dim3(nstar), dim3(256), 0, c.st, nstar, w.wbase_surv, w.part,
+                           c.p.ln_sub, w.k2, w.maxsurv, w.n_unconv, (int32_t *)nullptr, (int32_t *)nullptr);
+        HIP_TRY(hipMemcpyAsync(&h_unconv, w.n_unconv, sizeof(int32_t), hipMemcpyDeviceToHost, c.st));
+        HIP_TRY(hipMemcpyAsync(k2s.data(), w.k2, sizeof(int32_t) * nstar, hipMemcpyDeviceToHost, c.st));
+        HIP_TRY(hipStreamSynchronize(c.st));
+        if (first)
+            if (int rc = capacity_verdict(c, Asked::HostAfterFirstFlux, *ncand, 0)) return rc;
+        if (h_unconv == 0) return 0;
+        if (iter >= c.max_iter)
             return fail(BRUTUS_ENOCONV, "flux phase not converged after %d iterations for %d star(s)",
                         iter, h_unconv);
         ++iter;
         act.clear();                 // the stars still iterating: the next launch walks their segments only
         for (int s = 0; s < nstar; ++s)
             if (k2s[s] >= 0) act.push_back(s);
-        HIP_TRY(hipMemcpyAsync(w.ids, act.data(), sizeof(int32_t) * act.size(), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(w.ids, act.data(), sizeof(int32_t) * act.size(), hipMemcpyHostToDevice, c.st));
     }
+}
 
-    // ---- exact first-cut threshold, selection masks ---------------------------------------
-    tm.begin("k_top");
-    hipLaunchKernelGGL(k_hot_list, dim3(nstar), dim3(256), 0, st, nblkx, nstar, 1, w.part32,
+// exact first-cut threshold, selection masks; record index (model, slot) in np.where order;
+// values of the derived records
+template <int NB, bool RVF>
+void select_and_derive(FitCall &c) {
+    const Workspace &w = c.w;
+    const int nstar = c.nstar;
+    const dim3 blk(TILE);
+    c.tm.begin("k_top");
+    hipLaunchKernelGGL(k_hot_list, dim3(nstar), dim3(256), 0, c.st, c.nblkx, nstar, 1, w.part32,
                        (const double *)nullptr, w.maxsurv, w.s32, w.nomB, w.part, w.hot, w.ctr + 5);
-    hipLaunchKernelGGL((k_top1<NB, RVF>), dim3(TOP_BLOCKS), blk, 0, st, grid, nmodel, nmodel_pad, nstar,
-                       w.stars, p, w.k1, ntile, 1, w.lnpr32, w.nomB, w.hot, w.ctr + 5, w.part,
-                       aud ? aud + nstar : nullptr);
-    tm.end();
-    hipLaunchKernelGGL(k_top_decide, dim3(nstar), dim3(256), 0, st, nblkx, nstar, w.ids_all, 1, w.part,
-                       w.s32, p.ln_wt, w.maxsurv, w.thr_sel, (double *)nullptr);
-    tm.begin("k_sel_classify");
-    hipLaunchKernelGGL(k_sel_classify, dim3(NCHUNK, nstar), blk, 0, st, nmodel, ntile, w.s32,
-                       w.lnpr32, w.lnprob_st, w.surv_off, w.thr_sel, w.counts, w.mask, w.dcounts,
-                       w.dmask, w.surv_idx, w.bandn);
-    tm.end();
-    tm.begin("k_sel_band");      // (the candidate lists in surv_idx are no longer needed)
-    hipLaunchKernelGGL((k_sel_band<NB, RVF>), dim3(NCHUNK / SB_C, nstar, SB_Z), blk, 0, st, grid, nmodel, nmodel_pad,
-                       ntile, w.stars, p, w.k1, w.lnpr32, w.thr_sel, w.surv_idx, w.bandn, w.counts,
-                       w.mask, w.dcounts, w.dmask, aud ? aud + 2 * nstar : nullptr);
-    tm.end();
-
-    // ---- record index (model, slot) in np.where order; values of the derived records -------
-    tm.begin("k_select");
-    {
-        const OffsetsJob sel{w.counts, w.offsets, d_rec_off, nullptr, w.res + 0};
-        const OffsetsJob der{w.dcounts, w.doffsets, w.der_off, w.wbase_der, w.res + 1};
-        hipLaunchKernelGGL(k_offsets, dim3(4), dim3(OFF_T), 0, st, nstar, sel, der);
-    }
-    hipLaunchKernelGGL(k_items, dim3((NCHUNK * nstar + 255) / 256), dim3(256), 0, st, nstar, w.wbase_der,
+    hipLaunchKernelGGL((k_top1<NB, RVF>), dim3(TOP_BLOCKS), blk, 0, c.st, c.grid, c.nmodel, c.nmodel_pad, nstar,
+                       w.stars, c.p, w.k1, c.ntile, 1, w.lnpr32, w.nomB, w.hot, w.ctr + 5, w.part,
+                       c.aud ? c.aud + nstar : nullptr);
+    c.tm.end();
+    hipLaunchKernelGGL(k_top_decide, dim3(nstar), dim3(256), 0, c.st, c.nblkx, nstar, w.ids_all, 1, w.part,
+                       w.s32, c.p.ln_wt, w.maxsurv, w.thr_sel, (double *)nullptr);
+    c.tm.begin("k_sel_classify");
+    hipLaunchKernelGGL(k_sel_classify, dim3(NCHUNK, nstar), blk, 0, c.st, c.nmodel, c.ntile, w.s32, w.lnpr32, w.lnprob_st,
+                       w.surv_off, w.thr_sel, w.counts, w.mask, w.dcounts, w.dmask, w.surv_idx, w.bandn);
+    c.tm.end();
+    c.tm.begin("k_sel_band");      // (the candidate lists in surv_idx are no longer needed)
+    hipLaunchKernelGGL((k_sel_band<NB, RVF>), dim3(NCHUNK / SB_C, nstar, SB_Z), blk, 0, c.st, c.grid, c.nmodel,
+                       c.nmodel_pad, c.ntile, w.stars, c.p, w.k1, w.lnpr32, w.thr_sel, w.surv_idx, w.bandn,
+                       w.counts, w.mask, w.dcounts, w.dmask, c.aud ? c.aud + 2 * nstar : nullptr);
+    c.tm.end();
+    c.tm.begin("k_select");
+    const OffsetsJob sel{w.counts, w.offsets, c.d_rec_off, nullptr, w.res + ResBlock::SELECTED};
+    const OffsetsJob der{w.dcounts, w.doffsets, w.der_off, w.wbase_der, w.res + ResBlock::DERIVED};
+    hipLaunchKernelGGL(k_offsets, dim3(4), dim3(OFF_T), 0, c.st, nstar, sel, der);
+    hipLaunchKernelGGL(k_items, dim3((NCHUNK * nstar + 255) / 256), dim3(256), 0, c.st, nstar, w.wbase_der,
                        w.doffsets, w.der_off, w.items_der);
     // (the band queues in surv_idx are no longer needed either: it now takes the derived lists)
-    hipLaunchKernelGGL(k_rec_index, dim3(NCHUNK, nstar), blk, 0, st, nmodel, ntile, nstar, w.mask, w.dmask,
-                       w.smask, w.offsets, w.doffsets, w.coffsets, w.surv_off, capacity, d_rec_idx,
-                       d_rec_slot, w.surv_idx);
-    tm.end();
-    tm.begin("k_derive");
-    hipLaunchKernelGGL((k_derive<NB, RVF>), dim3(PERSIST_BLOCKS), blk, 0, st, grid, nmodel_pad, nstar,
-                       w.stars, p, w.k1, w.surv_idx, w.wbase_der, w.items_der, w.surv_off, rec);
-    tm.end();
-    // everything the host wants to know, in one copy: totals, K1, K2, the counters
-    int64_t h_nder = 0;
-    int32_t h_ctr[8] = {0, 0, 0, 0, 0, 0, 0, 0}, h_left = 0;
-    std::vector<int64_t> h_res(4 + (2 * (size_t)nstar + 12 + 1) / 2);
-    HIP_TRY(hipMemcpyAsync(h_res.data(), w.res, sizeof(int64_t) * 4 + sizeof(int32_t) * (2 * (size_t)nstar + 12),
-                           hipMemcpyDeviceToHost, st));
+    hipLaunchKernelGGL(k_rec_index, dim3(NCHUNK, nstar), blk, 0, c.st, c.nmodel, c.ntile, nstar, w.mask, w.dmask,
+                       w.smask, w.offsets, w.doffsets, w.coffsets, w.surv_off, c.capacity, c.d_rec_idx,
+                       c.d_rec_slot, w.surv_idx);
+    c.tm.end();
+    c.tm.begin("k_derive");
+    hipLaunchKernelGGL((k_derive<NB, RVF>), dim3(PERSIST_BLOCKS), blk, 0, c.st, c.grid, c.nmodel_pad, nstar,
+                       w.stars, c.p, w.k1, w.surv_idx, w.wbase_der, w.items_der, w.surv_off, c.rec);
+    c.tm.end();
+}
+
+// everything the host wants to know, in one copy: totals, K1, K2, the counters
+int read_results(FitCall &c, std::vector<int64_t> &h_res) {
+    h_res.resize((ResBlock::bytes(c.nstar) + sizeof(int64_t) - 1) / sizeof(int64_t));
+    HIP_TRY(hipMemcpyAsync(h_res.data(), c.w.res, ResBlock::bytes(c.nstar), hipMemcpyDeviceToHost, c.st));
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(st));
-    {
-        const int32_t *r32 = reinterpret_cast<const int32_t *>(h_res.data() + 4);
-        h_counts[0] = h_res[0];
-        h_nder = h_res[1];
-        if (device_driven) h_ncand = h_res[2];
-        if (h_k1) memcpy(h_k1, r32, sizeof(int32_t) * nstar);
-        if (h_k2) memcpy(h_k2, r32 + nstar, sizeof(int32_t) * nstar);
-        if (device_driven) {
-            memcpy(h_ctr, r32 + 2 * nstar + 4, sizeof(h_ctr));
-            h_left = r32[2 * nstar + (FLUX_ROUNDS & 1)];
-        }
-    }
-    if (device_driven && h_ncand > capacity) {      // (every write was bounded by the capacity)
-        h_counts[1] = h_ncand;
-        h_counts[2] = h_ncand + (h_nder > 0 ? h_nder : h_ncand);
-        return fail(BRUTUS_ENOMEM, "record buffer too small: %lld candidate slots, capacity %lld",
-                    (long long)h_ncand, (long long)capacity);
-    }
-    if (device_driven && (h_ctr[3] != 0 || h_left != 0)) return BRUTUS_RETRY_HOSTDRIVEN;
-    h_counts[1] = h_ncand;
-    h_counts[2] = h_ncand + h_nder;
-    if (h_counts[2] > capacity)
-        return fail(BRUTUS_ENOMEM, "record buffer too small: %lld slots needed, capacity %lld",
-                    (long long)h_counts[2], (long long)capacity);
+    HIP_TRY(hipStreamSynchronize(c.st));
+    const ResBlock res(h_res.data(), c.nstar);
+    c.h_counts[0] = res.totals[ResBlock::SELECTED];
+    if (c.h_k1) memcpy(c.h_k1, res.k1, sizeof(int32_t) * c.nstar);
+    if (c.h_k2) memcpy(c.h_k2, res.k2, sizeof(int32_t) * c.nstar);
     return 0;
 }
 
-// Rv pinned by its limits at the value every fit starts from: the (offset, Av)
-// specialisation computes the same thing (SURVEY 8d, config 2)
-inline bool rv_pinned(const DevParams &p) { return p.rvmin == p.rvmax && p.rv_mean == p.rvmin; }
+template <int NB, bool RVF>
+int run_fit(FitCall &c, bool device_driven) {
+    int64_t ncand = 0;
+    std::vector<int64_t> h_res;
+    if (int rc = start_call(c)) return rc;
+    if (int rc = device_driven ? classify_on_device<NB, RVF>(c) : classify_on_host<NB, RVF>(c)) return rc;
+    cull_candidates<NB, RVF>(c);
+    if (device_driven)
+        flux_on_device<NB, RVF>(c);
+    else if (int rc = flux_on_host<NB, RVF>(c, &ncand))
+        return rc;
+    select_and_derive<NB, RVF>(c);
+    if (int rc = read_results(c, h_res)) return rc;
+    const ResBlock res(h_res.data(), c.nstar);
+    const int64_t nder = res.totals[ResBlock::DERIVED];
+    if (device_driven) {
+        ncand = res.totals[ResBlock::CANDIDATES];
+        if (int rc = capacity_verdict(c, Asked::DeviceCandidates, ncand, nder)) return rc;
+        // what the device could not express: a star beyond the probed sweeps, stars still iterating
+        if (res.ctr[3] != 0 || res.n_unconv[c.flux_rounds & 1] != 0) return BRUTUS_RETRY_HOSTDRIVEN;
+    }
+    return capacity_verdict(c, Asked::WholeCall, ncand, nder);
+}
 
 // The float32 pass only classifies, and what it "proves" below a threshold never reaches the
 // output: Star32::eps has to bound |float32 - float64| for that to be sound.  Every pair the call
@@ -725,55 +752,38 @@ int audit_verdict(const Workspace &w, int nstar, hipStream_t st) {
     return 0;
 }
 
-int dispatch_fit(int nb, int nfilt, const float *grid, int64_t nmodel, int nstar,
-                 const DevParams &p, int max_iter, Workspace &w, int64_t capacity,
-                 int32_t *d_rec_idx, int32_t *d_rec_slot, double *d_rec_vals, int64_t *d_rec_off,
-                 int32_t *h_k1, int32_t *h_k2, int64_t *h_counts, hipStream_t st, Timer &tm) {
-    const bool rvf = rv_pinned(p);
-    // BRUTUS_FIT_HOSTDRIVEN=1: round 3's driver for every batch (A/B timing, and the tests
-    // that compare the two drivers record for record)
+int dispatch_fit(int nb, FitCall &c) {
+    const bool rvf = rv_pinned(c.p);
+    // BRUTUS_FIT_HOSTDRIVEN=1: the host-driven driver for every batch (A/B timing; tests comparing the two drivers)
     const bool hostdriven = env_int("BRUTUS_FIT_HOSTDRIVEN", 0) != 0;
-    {
-        const long long call_no = g_fit_calls.fetch_add(1);
-        const int every = env_int("BRUTUS_AUDIT_EVERY", 64);
-        t_audit_call = every > 0 && call_no % every == 0;
-    }
-#define BRUTUS_CASE(N)                                                                             \
-    case N: {                                                                                      \
-        int rc = hostdriven ? BRUTUS_RETRY_HOSTDRIVEN : 0;                                         \
-        if (!hostdriven)                                                                           \
-            rc = rvf ? run_fit<N, true>(grid, nmodel, nfilt, nstar, p, max_iter, w, capacity,      \
-                                        d_rec_idx, d_rec_slot, d_rec_vals, d_rec_off, h_k1, h_k2,  \
-                                        h_counts, st, tm, true)                                    \
-                     : run_fit<N, false>(grid, nmodel, nfilt, nstar, p, max_iter, w, capacity,     \
-                                         d_rec_idx, d_rec_slot, d_rec_vals, d_rec_off, h_k1, h_k2, \
-                                         h_counts, st, tm, true);                                  \
-        if (rc == BRUTUS_RETRY_HOSTDRIVEN) {                                                       \
-            if (!hostdriven) g_fit_retries.fetch_add(1);                                           \
-            rc = rvf ? run_fit<N, true>(grid, nmodel, nfilt, nstar, p, max_iter, w, capacity,      \
-                                        d_rec_idx, d_rec_slot, d_rec_vals, d_rec_off, h_k1, h_k2,  \
-                                        h_counts, st, tm, false)                                   \
-                     : run_fit<N, false>(grid, nmodel, nfilt, nstar, p, max_iter, w, capacity,     \
-                                         d_rec_idx, d_rec_slot, d_rec_vals, d_rec_off, h_k1, h_k2, \
-                                         h_counts, st, tm, false);                                 \
-        }                                                                                          \
-        if (rc == 0 && t_audit_call) rc = audit_verdict(w, nstar, st);                             \
-        t_audit_call = 0;                                                                          \
-        return rc;                                                                                 \
-    }
-    switch (nb) {
-        BRUTUS_CASE(12)
-#ifndef BRUTUS_DEV_NB12_ONLY
-        BRUTUS_CASE(8)
-        BRUTUS_CASE(16)
-        BRUTUS_CASE(24)
-        BRUTUS_CASE(32)
-#endif
-    }
-#undef BRUTUS_CASE
+    // the audit of the float32 bound is enforced on the process's first call and every BRUTUS_AUDIT_EVERY-th after
+    const long long call_no = g_fit_calls.fetch_add(1);
+    const int every = env_int("BRUTUS_AUDIT_EVERY", 64);
+    c.audited = every > 0 && call_no % every == 0;
+    c.aud = env_int("BRUTUS_AUDIT", 0) != 0 || c.audited ? c.w.aud : nullptr;
+    c.flux_rounds = env_int("BRUTUS_FLUX_ROUNDS", 4);
+    // (two translation units, one definition of the shared layout: pre32_types.hpp)
+    if (brutus_i_pre32_layout(0) != (int)sizeof(Star32) || brutus_i_pre32_layout(1) != (int)sizeof(P32) ||
+        brutus_i_pre32_layout(2) != F2_T || brutus_i_pre32_layout(3) != TILE || brutus_i_pre32_layout(4) != NV32)
+        return fail(BRUTUS_EINVAL, "float32 pass: the library's translation units disagree on the Star32 / "
+                                   "tile layout (built with different flags?)");
+    int rc = 0;
+    const bool built = with_nb(nb, FitBands{}, [&](auto NB) {
+        constexpr int N = decltype(NB)::value;
+        auto run = [&](bool device_driven) {
+            return rvf ? run_fit<N, true>(c, device_driven) : run_fit<N, false>(c, device_driven);
+        };
+        rc = hostdriven ? BRUTUS_RETRY_HOSTDRIVEN : run(true);
+        if (rc == BRUTUS_RETRY_HOSTDRIVEN) {
+            if (!hostdriven) g_fit_retries.fetch_add(1);
+            rc = run(false);
+        }
+        if (rc == 0 && c.audited) rc = audit_verdict(c.w, c.nstar, c.st);
+    });
+    if (built) return rc;
     if (nb > BRUTUS_MAX_FILT_FIT)
         return fail(BRUTUS_EINVAL, "brutus_fit_batch fits at most %d bands at once (%d given): take the full-grid "
-                                   "outputs of brutus_loglike_batch and cut on them", BRUTUS_MAX_FILT_FIT, nfilt);
+                                   "outputs of brutus_loglike_batch and cut on them", BRUTUS_MAX_FILT_FIT, c.nfilt);
     return fail(BRUTUS_EINVAL, "unsupported band count %d", nb);
 }
 
@@ -894,18 +904,19 @@ int brutus_fit_batch(const float *d_grid_soa, int64_t nmodel, int nfilt, int nst
         return fail(BRUTUS_ENOMEM, "workspace too small: need %zu bytes, got %zu", w.bytes,
                     workspace_bytes);
     hipStream_t st = (hipStream_t)stream;
-    Timer tm(st);
+    const int64_t nmodel_pad = pad_models(nmodel);
+    const int ntile = (int)(nmodel_pad / TILE);
+    FitCall c{d_grid_soa, nmodel, nmodel_pad, ntile, (ntile + F2_T - 1) / F2_T, nfilt, nstar, p,
+              params->max_iter > 0 ? params->max_iter : 65536, w, RecPlanes{d_rec_vals, capacity}, capacity,
+              d_rec_idx, d_rec_slot, d_rec_off, h_k1, h_k2, h_counts, st, Timer(st)};
     if (int rc = launch_prep(nstar, nfilt, d_flux, d_err, d_mask, d_parallax, d_parallax_err,
-                             has_parallax, w, d_ndim, st))
+                             has_parallax, c.w, d_ndim, st))
         return rc;
-    const int max_iter = params->max_iter > 0 ? params->max_iter : 65536;
-    int rc = dispatch_fit(padded_nb(nfilt), nfilt, d_grid_soa, nmodel, nstar, p, max_iter, w,
-                          capacity, d_rec_idx, d_rec_slot, d_rec_vals, d_rec_off, h_k1, h_k2,
-                          h_counts, st, tm);
+    int rc = dispatch_fit(padded_nb(nfilt), c);
     (void)hipStreamSynchronize(st);
     if (rc) return rc;
     fix_k2(h_k2, nstar);
-    tm.collect();
+    c.tm.collect();
     return 0;
 }
 
@@ -926,20 +937,15 @@ struct CutWs {
 
 CutWs carve_cut(char *base, int64_t nmodel, int nstar) {
     CutWs w;
-    size_t off = 0;
-    auto take = [&](size_t n) {
-        char *q = base ? base + off : nullptr;
-        off += align_up(n);
-        return q;
-    };
+    Carver cv(base);
     w.stride = nmodel + (nmodel & 1);
-    w.lnprob = (double *)take(sizeof(double) * (size_t)nstar * (size_t)w.stride);
-    w.part = (double *)take(sizeof(double) * nstar * CUT_NCH);
-    w.thr = (double *)take(sizeof(double) * nstar);
-    w.counts = (int32_t *)take(sizeof(int32_t) * nstar * CUT_NCH);
-    w.offsets = (int64_t *)take(sizeof(int64_t) * nstar * CUT_NCH);
-    w.total = (int64_t *)take(sizeof(int64_t));
-    w.bytes = off + 256;      // (room to align a base that is not)
+    w.lnprob = (double *)cv.take(sizeof(double) * (size_t)nstar * (size_t)w.stride);
+    w.part = (double *)cv.take(sizeof(double) * nstar * CUT_NCH);
+    w.thr = (double *)cv.take(sizeof(double) * nstar);
+    w.counts = (int32_t *)cv.take(sizeof(int32_t) * nstar * CUT_NCH);
+    w.offsets = (int64_t *)cv.take(sizeof(int64_t) * nstar * CUT_NCH);
+    w.total = (int64_t *)cv.take(sizeof(int64_t));
+    w.bytes = cv.off + 256;      // (room to align a base that is not)
     return w;
 }
 
@@ -1084,15 +1090,8 @@ int brutus_debug_pre32_time(void *d_workspace, size_t workspace_bytes, const flo
     if (w.bytes > workspace_bytes) return fail(BRUTUS_ENOMEM, "workspace too small");
     const int nb = brutus_padded_filters(nfilt);
     if (!brutus_i_pre32s_bands(nb)) return fail(BRUTUS_EINVAL, "no star-lane pass for %d bands", nb);
-    const bool rvf = p.rvmin == p.rvmax && p.rvmin == p.rv_mean;
-    P32 q;
-    q.avmin = (float)p.avmin; q.avmax = (float)p.avmax; q.rvmin = (float)p.rvmin; q.rvmax = (float)p.rvmax;
-    q.av_mean = (float)p.av_mean; q.av_ivar = (float)p.av_ivar; q.rv_mean = (float)p.rv_mean;
-    q.rv_ivar = (float)p.rv_ivar;
-    q.mtol_hi = (float)(p.mtol * 1.002 + 1e-4);
-    q.mtol_lo = (float)(p.mtol * 0.998 - 1e-4);
-    q.dim_prior = p.dim_prior;
-    q.nfilt = nfilt;
+    const bool rvf = rv_pinned(p);
+    const P32 q = make_p32(p, nfilt);
     hipStream_t st = (hipStream_t)stream;
     hipEvent_t a, b;
     HIP_TRY(hipEventCreate(&a));

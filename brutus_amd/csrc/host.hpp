@@ -11,6 +11,7 @@
 #include <stdlib.h>
 
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -52,6 +53,41 @@ inline int64_t pad_models(int64_t n) { return (n + TILE - 1) / TILE * TILE; }
 // through starts on a page boundary of its own)
 inline size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
 inline size_t align_big(size_t x) { return (x + ((size_t)2 << 20) - 1) & ~(((size_t)2 << 20) - 1); }
+
+// The one bump allocator of the workspaces: lays arrays out over `base` (null: sizing only, every
+// pointer it hands out is then null); `off` is what has been taken so far.
+struct Carver {
+    char *base;
+    size_t off = 0;
+    explicit Carver(char *b) : base(b) {}
+    char *take(size_t n) {               // 256-byte steps
+        char *p = base ? base + off : nullptr;
+        off += align_up(n);
+        return p;
+    }
+    char *take_big(size_t n) {           // plane-sized arrays: absolute 2 MiB alignment
+        off = align_big((size_t)base + off) - (size_t)base;
+        char *p = base ? base + off : nullptr;
+        off += n;
+        return p;
+    }
+};
+
+// A run-time band count onto a compile-time one: with_nb(nb, FitBands{}, [&](auto NB) { ... })
+// calls the lambda with std::integral_constant<int, nb> when `nb` is in the list (and says so).
+template <int... NBS>
+struct BandCounts {};
+#ifdef BRUTUS_DEV_NB12_ONLY      // (tools/ab/build.sh: kernel A/B builds in seconds; never set for the product)
+using FitBands = BandCounts<12>;
+using GridBands = BandCounts<12>;
+#else
+using FitBands = BandCounts<12, 8, 16, 24, 32>;              // hot path, cluster likelihood
+using GridBands = BandCounts<12, 8, 16, 24, 32, 48, 64>;     // full-grid pipeline
+#endif
+template <int... NBS, class F>
+bool with_nb(int nb, BandCounts<NBS...>, F &&f) {
+    return ((nb == NBS && (f(std::integral_constant<int, NBS>{}), true)) || ...);
+}
 
 inline int env_int(const char *name, int dflt) {
     const char *v = getenv(name);

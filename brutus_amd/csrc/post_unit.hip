@@ -178,36 +178,31 @@ int mt_walk_parallel(int nstream, const std::vector<int32_t> &seg, uint32_t *d_s
     // one walk: pass 1 also writes the accepted candidates' normals (16 bytes per slot)
     const bool mapped = d_zloc && (size_t)Ttot <= zloc_pairs;
     // ---- carve ---------------------------------------------------------------------
-    size_t off = 0;
-    auto take = [&](size_t n) {
-        char *q = scratch + off;
-        off += (n + 255) & ~(size_t)255;
-        return q;
-    };
-    uint32_t *d_win = (uint32_t *)take((size_t)Ktot * MT_N * 4);
-    unsigned long long *d_bits = (unsigned long long *)take((size_t)Ttot / 8);
+    Carver cv(scratch);
+    uint32_t *d_win = (uint32_t *)cv.take((size_t)Ktot * MT_N * 4);
+    unsigned long long *d_bits = (unsigned long long *)cv.take((size_t)Ttot / 8);
     const int64_t nsb = Ttot / MT_SB;
-    uint32_t *d_cnt = (uint32_t *)take((size_t)nsb * 4);
-    int64_t *d_pre = (int64_t *)take((size_t)(nsb + nstream + 1) * 8);
+    uint32_t *d_cnt = (uint32_t *)cv.take((size_t)nsb * 4);
+    int64_t *d_pre = (int64_t *)cv.take((size_t)(nsb + nstream + 1) * 8);
     // read back together after k_mt_resolve: [fail | end slots]
-    int32_t *d_fail = (int32_t *)take(256);
-    int64_t *d_endslot = (int64_t *)take(8 * (size_t)nstream);
-    int32_t *d_endhasg = (int32_t *)take(4 * (size_t)nstream);
-    int32_t *d_endnew = (int32_t *)take(4 * (size_t)nstream);
-    double *d_endgauss = (double *)take(8 * (size_t)nstream);
+    int32_t *d_fail = (int32_t *)cv.take(256);
+    int64_t *d_endslot = (int64_t *)cv.take(8 * (size_t)nstream);
+    int32_t *d_endhasg = (int32_t *)cv.take(4 * (size_t)nstream);
+    int32_t *d_endnew = (int32_t *)cv.take(4 * (size_t)nstream);
+    double *d_endgauss = (double *)cv.take(8 * (size_t)nstream);
     // uploaded together before k_mt_advance: [window index | skip | skipc]
     const size_t adv_stride = (8 * (size_t)nstream + 255) & ~(size_t)255;
-    int64_t *d_widx = (int64_t *)take(8 * (size_t)nstream);
-    int64_t *d_skip = (int64_t *)take(8 * (size_t)nstream);
-    int64_t *d_skipc = (int64_t *)take(8 * (size_t)nstream);
-    MtObj *d_objs = (MtObj *)take((size_t)nobj_total * sizeof(MtObj));
-    int64_t *d_segp0 = (int64_t *)take(8 * ((size_t)Ktot + nobj_total));
-    int64_t *d_sega = (int64_t *)take(8 * ((size_t)Ktot + nobj_total));
-    int64_t *d_seglo = (int64_t *)take(8 * (size_t)nobj_total);
-    int32_t *d_nseg = (int32_t *)take(4 * (size_t)nobj_total);
-    double *d_cached = (double *)take(8 * (size_t)nobj_total);
-    int32_t *d_cflag = (int32_t *)take(4 * (size_t)nobj_total);
-    double *d_gauss0 = (double *)take(8 * (size_t)nstream);
+    int64_t *d_widx = (int64_t *)cv.take(8 * (size_t)nstream);
+    int64_t *d_skip = (int64_t *)cv.take(8 * (size_t)nstream);
+    int64_t *d_skipc = (int64_t *)cv.take(8 * (size_t)nstream);
+    MtObj *d_objs = (MtObj *)cv.take((size_t)nobj_total * sizeof(MtObj));
+    int64_t *d_segp0 = (int64_t *)cv.take(8 * ((size_t)Ktot + nobj_total));
+    int64_t *d_sega = (int64_t *)cv.take(8 * ((size_t)Ktot + nobj_total));
+    int64_t *d_seglo = (int64_t *)cv.take(8 * (size_t)nobj_total);
+    int32_t *d_nseg = (int32_t *)cv.take(4 * (size_t)nobj_total);
+    double *d_cached = (double *)cv.take(8 * (size_t)nobj_total);
+    int32_t *d_cflag = (int32_t *)cv.take(4 * (size_t)nobj_total);
+    double *d_gauss0 = (double *)cv.take(8 * (size_t)nstream);
     // chains
     std::vector<int64_t> c2s, c2d;
     std::vector<int32_t> c2n;
@@ -262,19 +257,19 @@ int mt_walk_parallel(int nstream, const std::vector<int32_t> &seg, uint32_t *d_s
     size_t n1tot = 0;
     for (int r = 0; r < 16; ++r) n1tot += r1s[r].size();
     // ---- the plan block: one contiguous device region, one page-locked mirror, one copy --------
-    const size_t plan0 = off;
-    uint32_t *d_polys = (uint32_t *)take(polys.size() * 4);
-    MtSub *d_subs = (MtSub *)take((size_t)Ktot * sizeof(MtSub));
-    int64_t *d_base = (int64_t *)take(8 * ((size_t)nstream + 1));
-    int64_t *d_bitbase = (int64_t *)take(8 * (size_t)nstream);
-    int64_t *d_sblo = (int64_t *)take(8 * ((size_t)nstream + 1));
-    int64_t *d_tslots = (int64_t *)take(8 * (size_t)nstream);
-    int64_t *d_c1s = (int64_t *)take(8 * (n1tot + 1)), *d_c1d = (int64_t *)take(8 * (n1tot + 1));
-    int32_t *d_c1n = (int32_t *)take(4 * (n1tot + 1));
-    int64_t *d_c2s = (int64_t *)take(8 * (n2 + 1)), *d_c2d = (int64_t *)take(8 * (n2 + 1));
-    int32_t *d_c2n = (int32_t *)take(4 * (n2 + 1));
-    const size_t plan_bytes = off - plan0;
-    if (off > scratch_bytes) return 1;
+    const size_t plan0 = cv.off;
+    uint32_t *d_polys = (uint32_t *)cv.take(polys.size() * 4);
+    MtSub *d_subs = (MtSub *)cv.take((size_t)Ktot * sizeof(MtSub));
+    int64_t *d_base = (int64_t *)cv.take(8 * ((size_t)nstream + 1));
+    int64_t *d_bitbase = (int64_t *)cv.take(8 * (size_t)nstream);
+    int64_t *d_sblo = (int64_t *)cv.take(8 * ((size_t)nstream + 1));
+    int64_t *d_tslots = (int64_t *)cv.take(8 * (size_t)nstream);
+    int64_t *d_c1s = (int64_t *)cv.take(8 * (n1tot + 1)), *d_c1d = (int64_t *)cv.take(8 * (n1tot + 1));
+    int32_t *d_c1n = (int32_t *)cv.take(4 * (n1tot + 1));
+    int64_t *d_c2s = (int64_t *)cv.take(8 * (n2 + 1)), *d_c2d = (int64_t *)cv.take(8 * (n2 + 1));
+    int32_t *d_c2n = (int32_t *)cv.take(4 * (n2 + 1));
+    const size_t plan_bytes = cv.off - plan0;
+    if (cv.off > scratch_bytes) return 1;
     char *hp = g_plan_pin.get(plan_bytes);
     if (!hp) return fail(BRUTUS_ENOMEM, "page-locked staging for the stream plan (%zu bytes)", plan_bytes);
     auto at = [&](const void *d) { return hp + ((const char *)d - (scratch + plan0)); };
@@ -459,45 +454,40 @@ constexpr int MC_SLOTS = 1024;     // persistent workgroups (= staging slots) of
 
 static PostWs carve_post(char *base, int nstar, int64_t cap, int nmc, int ndraws = 0) {
     PostWs w{};
-    size_t off = 0;
-    auto take = [&](size_t n) {
-        char *p = base ? base + off : nullptr;
-        off += align_up(n);
-        return p;
-    };
+    Carver cv(base);
     const size_t c = (size_t)cap;
-    w.lnp1 = (double *)take(8 * c);
-    w.mask = (unsigned long long *)take(8 * (c / 64 + 8 * (size_t)nstar + 16));
-    w.counts = (int64_t *)take(8 * (size_t)nstar * PCH);
-    w.offsets = (int64_t *)take(8 * (size_t)nstar * PCH);
-    w.part = (double *)take(8 * (size_t)nstar * PCH);
-    w.part_w = (double *)take(8 * (size_t)nstar * PCH);
-    w.part_max = (double *)take(8 * (size_t)nstar * PCH);
-    w.part_chi2 = (double *)take(8 * (size_t)nstar * PCH);
-    w.off2 = (int64_t *)take(8 * ((size_t)nstar + 1));
-    w.nbase = (uint64_t *)take(8 * ((size_t)nstar + 1));
-    w.flags = (int32_t *)take(4 * (size_t)nstar);
-    w.nsel = (int64_t *)take(8 * (size_t)nstar);
-    w.geom = (StarGeom *)take(sizeof(StarGeom) * (size_t)nstar);
-    w.star_out = (double *)take(8 * 4 * (size_t)nstar);
-    w.rp.src = (int32_t *)take(4 * c);
-    w.rp.lnp = (double *)take(8 * c);
-    w.rp.chol = (double *)take(8 * 6 * c);
-    w.cdf = (double *)take(8 * c);
-    w.sort_keys = (double *)take(8 * c);
-    w.sort_in = (int32_t *)take(4 * c);
-    w.sort_perm = (int32_t *)take(4 * c);
+    w.lnp1 = (double *)cv.take(8 * c);
+    w.mask = (unsigned long long *)cv.take(8 * (c / 64 + 8 * (size_t)nstar + 16));
+    w.counts = (int64_t *)cv.take(8 * (size_t)nstar * PCH);
+    w.offsets = (int64_t *)cv.take(8 * (size_t)nstar * PCH);
+    w.part = (double *)cv.take(8 * (size_t)nstar * PCH);
+    w.part_w = (double *)cv.take(8 * (size_t)nstar * PCH);
+    w.part_max = (double *)cv.take(8 * (size_t)nstar * PCH);
+    w.part_chi2 = (double *)cv.take(8 * (size_t)nstar * PCH);
+    w.off2 = (int64_t *)cv.take(8 * ((size_t)nstar + 1));
+    w.nbase = (uint64_t *)cv.take(8 * ((size_t)nstar + 1));
+    w.flags = (int32_t *)cv.take(4 * (size_t)nstar);
+    w.nsel = (int64_t *)cv.take(8 * (size_t)nstar);
+    w.geom = (StarGeom *)cv.take(sizeof(StarGeom) * (size_t)nstar);
+    w.star_out = (double *)cv.take(8 * 4 * (size_t)nstar);
+    w.rp.src = (int32_t *)cv.take(4 * c);
+    w.rp.lnp = (double *)cv.take(8 * c);
+    w.rp.chol = (double *)cv.take(8 * 6 * c);
+    w.cdf = (double *)cv.take(8 * c);
+    w.sort_keys = (double *)cv.take(8 * c);
+    w.sort_in = (int32_t *)cv.take(4 * c);
+    w.sort_perm = (int32_t *)cv.take(4 * c);
     w.sort_tmp_bytes = 16 * c + (8u << 20);
-    w.sort_tmp = take(w.sort_tmp_bytes);
-    w.mc_counter = (unsigned int *)take(256);
-    w.mc_order = (int32_t *)take(4 * (size_t)BRUTUS_MAX_BATCH);
-    w.mc_stage = (double2 *)take(sizeof(double2) * (size_t)MC_SLOTS * mc_npair_max(nmc) * TILE);
-    w.mt_states = (uint32_t *)take(sizeof(uint32_t) * (size_t)nstar * MT_STATE_WORDS);
-    w.mt_nnorm = (int64_t *)take(8 * (size_t)nstar);
-    w.mt_zoff = (int64_t *)take(8 * (size_t)nstar);
-    w.mt_seg = (int32_t *)take(4 * ((size_t)nstar + 1));
-    w.mt_uni = (double *)take(8 * (size_t)nstar * 2 * (size_t)(ndraws > 0 ? ndraws : 1));
-    w.bytes = off;
+    w.sort_tmp = cv.take(w.sort_tmp_bytes);
+    w.mc_counter = (unsigned int *)cv.take(256);
+    w.mc_order = (int32_t *)cv.take(4 * (size_t)BRUTUS_MAX_BATCH);
+    w.mc_stage = (double2 *)cv.take(sizeof(double2) * (size_t)MC_SLOTS * mc_npair_max(nmc) * TILE);
+    w.mt_states = (uint32_t *)cv.take(sizeof(uint32_t) * (size_t)nstar * MT_STATE_WORDS);
+    w.mt_nnorm = (int64_t *)cv.take(8 * (size_t)nstar);
+    w.mt_zoff = (int64_t *)cv.take(8 * (size_t)nstar);
+    w.mt_seg = (int32_t *)cv.take(4 * ((size_t)nstar + 1));
+    w.mt_uni = (double *)cv.take(8 * (size_t)nstar * 2 * (size_t)(ndraws > 0 ? ndraws : 1));
+    w.bytes = cv.off;
     return w;
 }
 

@@ -442,6 +442,58 @@ def test_device_driven_call_equals_host_driven_call(kw):
             assert np.array_equal(a[k], b[k]), (s, k)
 
 
+def _last_timing_names():
+    import ctypes as C
+    from brutus_amd import _lib
+    n, names, ms = C.c_int(0), (C.c_char_p * 32)(), (C.c_float * 32)()
+    _lib.lib().brutus_last_timing(C.byref(n), names, ms, 32)
+    return [names[i].decode() for i in range(n.value)]
+
+
+def test_device_driven_launch_sequence_does_not_depend_on_the_data(capfd):
+    """What the device-driven driver exists for: it issues the same timed sections whatever the
+    data say -- the lists live on the device and every follow-up launch is issued unconditionally.
+    The expected sequence is read off the driver (csrc/brutus_kernels.hip, run_fit): float32 pass,
+    K1 probe, float32 re-run (general Rv only: with Rv pinned the planes never depend on the sweep
+    count), exact cull threshold, candidate lists, opening flux launch and BRUTUS_FLUX_ROUNDS = 4
+    continuations, exact first-cut threshold, the selection kernels, the derived records.
+    `brutus_last_timing` reports each section's name once (with its summed time), so it pins the SET
+    of sections; how often each one ran is counted from the lines the library's timer writes to
+    stderr under BRUTUS_TRACE_KERNELS=1 (one "[brutus] <section> ..." per section begun).
+    4 099 models x 12 bands x 5 stars: the smallest shape of the suite that spans several tiles and
+    chunks, once with default parameters and once with Rv pinned; neither call is handed back to
+    the host-driven driver (asserted)."""
+    import collections
+    import re
+    from brutus_amd import _lib, fitting, synth
+    models, _, _ = synth.make_grid(4099, 12, seed=4099)
+    st = synth.make_stars(models, 5, seed=4100)
+    eng = fitting._Engine(fitting.DeviceGrid(models), max_batch=5)
+    up = eng._upload(st["flux"], st["err"], st["mask"], st["parallax"], st["parallax_err"])
+    L = _lib.lib()
+    for kw in (dict(), dict(rvlim=(3.32, 3.32))):
+        want = (["k_pre32", "k_k1probe"] + ([] if "rvlim" in kw else ["k_pre32"]) +
+                ["k_top", "k_surv_compact", "k_fflux"] + 4 * ["k_fflux_cont"] +
+                ["k_top", "k_sel_classify", "k_sel_band", "k_select", "k_derive"])
+        c0, r0 = _fit_stats()
+        capfd.readouterr()
+        L.brutus_enable_timing(1)
+        try:
+            with _Env(BRUTUS_TRACE_KERNELS=1):
+                eng.fit_batch_device(*up, _params(kw), grow=False)
+            names = _last_timing_names()
+        finally:
+            L.brutus_enable_timing(0)
+        begun = re.findall(r"^\[brutus\] (\w+) \.\.\.$", capfd.readouterr().err, flags=re.M)
+        c1, r1 = _fit_stats()
+        assert (c1 - c0, r1 - r0) == (1, 0), (c1 - c0, r1 - r0)      # one call, not repeated
+        counts = collections.Counter(begun)
+        assert counts == collections.Counter(want), counts
+        assert counts["k_pre32"] == (1 if "rvlim" in kw else 2) and counts["k_fflux_cont"] == 4
+        assert begun == want, begun
+        assert sorted(names) == sorted(set(want)), names
+
+
 def test_record_buffer_growth():
     """Record buffers too small for a batch -- below the candidate slots, then below
     candidates + derived records: `fit_batch_device` reports BRUTUS_ENOMEM with the sizes it
