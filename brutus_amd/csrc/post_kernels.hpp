@@ -186,6 +186,10 @@ struct StarGeom {      // per object: sightline unit vector and parallax
     int dust_on, nd;
     const double *los;
     double d_off, d_scale, d_smooth, d_scat2;
+    // tabulated distance prior (pdf.DistancePriorTable): dist[dt_nd], lnp[dt_nd] of this object;
+    // dt_on 0: none, 1: multiplies the Galactic prior, 2: replaces it
+    int dt_on, dt_nd;
+    const double *dtab;
     // constants of the Monte Carlo integrand for this object (k_post_geom, McC): read by
     // scalar loads inside the sample loop (mc_sample_c)
     double mc[32];
@@ -244,6 +248,29 @@ __device__ __forceinline__ double dust_lnp(const StarGeom &g, double dist, doubl
     const double e2 = er * er + g.d_scat2;
     const double dv = av - mean;
     return -0.5 * (dv * dv / e2 + log(2. * M_PI * e2));
+}
+
+struct DistCtx {       // host side of brutus_post_set_dist_table
+    const double *d_tab;     // (nstar, 2, nd): dist, lnp
+    int nd, replace;
+};
+// modes of the distance table: a compile-time property of the Monte Carlo kernels (DT_RT: the
+// object's own flag, read at run time -- the resampling kernel)
+constexpr int DT_OFF = 0, DT_MUL = 1, DT_REP = 2, DT_RT = 3;
+
+// ln prior of distance `dist` [kpc] from the table tab = (x[nd], f[nd]), interpolated like
+// numpy.interp (end values outside the table; NaN for a NaN distance): dust_lnp's bracketing
+// rule and interpolation form.  `tab` may point to global memory or to an LDS copy.
+__device__ __forceinline__ double dtab_lnp(const double *__restrict__ tab, int nd, double dist) {
+    const double *xp = tab, *fp = tab + nd;
+    if (!(dist > xp[0])) return dist == dist ? fp[0] : dist;
+    if (dist >= xp[nd - 1]) return fp[nd - 1];
+    int lo = 0, hi = nd - 1;                 // xp[lo] <= dist < xp[hi]
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (xp[mid] <= dist) lo = mid; else hi = mid;
+    }
+    return (fp[lo + 1] - fp[lo]) / (xp[lo + 1] - xp[lo]) * (dist - xp[lo]) + fp[lo];
 }
 
 __device__ __forceinline__ double lse3(double a, double b, double c) {
@@ -415,7 +442,9 @@ k_post_lnp1(PostParams pp, int64_t cap, const int32_t *__restrict__ sel_idx, con
             label_terms(pp, pp.has_feh ? feh[i] : 0., pp.has_loga ? loga[i] : 0., Fc, Ac, s_tbl);
             const double scale = sel_vals[2 * cap + vs];
             const double dist = 1. / sqrt(scale);
-            double v = sel_vals[vs] + lnprior[i] + gal_lnprior_dev(pp, g, dist, Fc, Ac, s_tbl);
+            double v = sel_vals[vs] + lnprior[i];
+            if (g.dt_on != DT_REP) v += gal_lnprior_dev(pp, g, dist, Fc, Ac, s_tbl);
+            if (g.dt_on) v += dtab_lnp(g.dtab, g.dt_nd, dist);
             if (g.dust_on) v += dust_lnp(g, dist, sel_vals[3 * cap + vs]);      // fitting.py:1009-1010
             lnp1[r] = v;
             if (v > m) m = v;
@@ -635,22 +664,28 @@ struct NormalReader {
 // nbase + (3 n + k) nmc + t, k = 0, 1, 2 (utils.py:897).  Returns (dist, av, rv),
 // whether it is inside the fit bounds, and its prior in split form:
 //   lnp_mc = lnK + ln(lin) + epar - par_lnorm / 2,   epar = -(par - par_obs)^2 ivar / 2 <= 0
+// DT: the tabulated distance prior joins epar (DT_MUL), and lin = 1 where it replaces the
+// Galactic prior (DT_REP; lnK = 0 then, fill_post_params); `lt`: the object's table in LDS.
+template <int DT = DT_OFF>
 __device__ __forceinline__ void mc_sample_lin(const PostParams &pp, const StarGeom &g, double z0,
                                               double z1, double z2, double s0, double a0, double r0,
                                               const double (&L)[6], const double (&Fc)[3],
                                               const double (&Ac)[3], const double *__restrict__ tbl,
                                               double &dist, double &a_mc, double &r_mc, bool &inb,
                                               double &lin, double &epar,
-                                              const double *__restrict__ ht = nullptr) {
+                                              const double *__restrict__ ht = nullptr,
+                                              const double *__restrict__ lt = nullptr) {
     const double s_mc = s0 + L[0] * z0;
     a_mc = a0 + (L[1] * z0 + L[2] * z1);
     r_mc = r0 + (L[3] * z0 + L[4] * z1 + L[5] * z2);
     double par;
     fast_sqrt_rsqrt(s_mc, par, dist);                           // parallax and distance (~1 ulp)
-    lin = gal_prior_lin(pp, g, dist, Fc, Ac, tbl, ht);
+    const int dt = DT == DT_RT ? g.dt_on : DT;
+    lin = dt == DT_REP ? 1. : gal_prior_lin(pp, g, dist, Fc, Ac, tbl, ht);
     const double dp = par - g.par;                              // pdf.py:166-173
     epar = g.has_par ? -0.5 * (dp * dp * g.par_ivar) : 0.;
     if (g.dust_on) epar += dust_lnp(g, dist, a_mc);             // fitting.py:1084-1085
+    if (dt) epar += lt ? dtab_lnp(lt, g.dt_nd, dist) : dtab_lnp(g.dtab, g.dt_nd, dist);
     inb = s_mc >= 1e-20 && a_mc >= pp.avlim[0] && a_mc <= pp.avlim[1] &&
           r_mc >= pp.rvlim[0] && r_mc <= pp.rvlim[1];
 }
@@ -905,6 +940,13 @@ __device__ __forceinline__ void mc_sample_c(CPtr cb, const PostParams &pp, const
           r_mc <= cb[MC_RV1];
 }
 
+// distance of the sample mc_sample_c integrates (the same operations: the same double)
+__device__ __forceinline__ double mc_dist(double s0, const double (&L)[6], double z0) {
+    double par, d;
+    fast_sqrt_rsqrt_pos(s0 + L[0] * z0, par, d);
+    return d;
+}
+
 // the same as one log value (-BIG outside the bounds, fitting.py:1086-1090),
 // drawing the normals on the fly
 __device__ __forceinline__ double mc_sample(const PostParams &pp, NormalReader (&rd)[3],
@@ -917,9 +959,9 @@ __device__ __forceinline__ double mc_sample(const PostParams &pp, NormalReader (
     const double z1 = rd[1].at(j0 + (uint64_t)pp.nmc);
     const double z2 = rd[2].at(j0 + 2ull * (uint64_t)pp.nmc);
     double lin, epar;
-    mc_sample_lin(pp, g, z0, z1, z2, s0, a0, r0, L, Fc, Ac, tbl, dist, a_mc, r_mc, inb, lin, epar);
+    mc_sample_lin<DT_RT>(pp, g, z0, z1, z2, s0, a0, r0, L, Fc, Ac, tbl, dist, a_mc, r_mc, inb, lin, epar);
     double v = pp.lnK + fast_log_r(lin);
-    if (g.has_par || g.dust_on) v += epar - (g.has_par ? 0.5 * g.par_lnorm : 0.);
+    if (g.has_par || g.dust_on || g.dt_on) v += epar - (g.has_par ? 0.5 * g.par_lnorm : 0.);
     if (!inb) v = -BIG;
     return v;
 }
@@ -963,7 +1005,13 @@ __global__ void k_post_order(int s0, int s1, const int64_t *__restrict__ nsel, i
     ord[rank] = s;
 }
 
-template <bool HT>
+// DT (distance table): DT_OFF is the kernel as it stands without the feature; DT_MUL adds the
+// table's term, read from global memory like the dust profile, to every sample; DT_REP (HT =
+// false: no Galactic prior is evaluated) takes lin = 1 and stages the object's table, once per
+// work item, in the LDS the sightline table would occupy -- DT_LDS_ND nodes fit; a longer table
+// is read from global memory.
+constexpr int DT_LDS_ND = (SL_NI + 1) * (SL_ROW / 2) / 2;
+template <bool HT, int DT = DT_OFF>
 __global__ void __launch_bounds__(TILE, 3)
 k_post_mc(PostParams pp, int64_t cap, int item_base, int nitem, unsigned int *__restrict__ counter,
           const double *__restrict__ zarr, const int64_t *__restrict__ zoff,
@@ -980,8 +1028,9 @@ k_post_mc(PostParams pp, int64_t cap, int item_base, int nitem, unsigned int *__
     __shared__ double2 s_zp[ZIG_N];
     __shared__ unsigned short s_pend[MC_PEND][TILE];
     __shared__ double s_halo[HALO_TBL];
-    __shared__ double2 s_sl[HT && SL_ON ? (SL_NI + 1) * (SL_ROW / 2) : 1];
+    __shared__ double2 s_sl[(HT && SL_ON) || DT == DT_REP ? (SL_NI + 1) * (SL_ROW / 2) : 1];
     __shared__ SlCtl s_ctl;
+    static_assert(DT == DT_OFF || DT == DT_MUL || (DT == DT_REP && !HT), "distance-table modes");
     stage_exp_table(s_tbl);
     stage_zig_pairs(s_zp);
     if constexpr (HT) stage_halo_table(pp, s_halo);
@@ -1011,6 +1060,16 @@ k_post_mc(PostParams pp, int64_t cap, int item_base, int nitem, unsigned int *__
         if constexpr (HT && SL_ON)
             sl = sl_item(cb0, one_rs, s_tbl, ht, SL_NI, s_sl, &s_ctl, a, b, !flags[s], rec_slot, sel_off[s], rp,
                          sel_vals, cap);
+        bool dt_lds = false;
+        if constexpr (DT == DT_REP) {
+            // (the previous item's readers are past the barriers at the top of the loop)
+            dt_lds = g.dt_nd <= DT_LDS_ND;
+            if (dt_lds) {
+                double *const dst = reinterpret_cast<double *>(s_sl);
+                for (int k = threadIdx.x; k < 2 * g.dt_nd; k += blockDim.x) dst[k] = g.dtab[k];
+            }
+            __syncthreads();
+        }
         if (!flags[s]) {
             for (int64_t o0 = a; o0 < b; o0 += TILE) {
                 const int64_t o = o0 + threadIdx.x;
@@ -1113,11 +1172,15 @@ k_post_mc(PostParams pp, int64_t cap, int item_base, int nitem, unsigned int *__
                         if constexpr (HT)
                             mc_sample_c<SL_ON>(mc_refresh(cb0), pp, g, g.has_par, g.dust_on, one_rs, z0, z1, z2,
                                               s0, a0, r0, L, Fc, Ac, s_tbl, ht, inb, lin, epar, sl);
+                        else if (DT == DT_REP && dt_lds)
+                            mc_sample_lin<DT>(pp, g, z0, z1, z2, s0, a0, r0, L, Fc, Ac, s_tbl, d_, a_, r_, inb, lin,
+                                              epar, nullptr, reinterpret_cast<const double *>(s_sl));
                         else
-                            mc_sample_lin(pp, g, z0, z1, z2, s0, a0, r0, L, Fc, Ac, s_tbl, d_, a_, r_, inb, lin,
-                                          epar);
+                            mc_sample_lin<DT>(pp, g, z0, z1, z2, s0, a0, r0, L, Fc, Ac, s_tbl, d_, a_, r_, inb, lin,
+                                              epar);
+                        if constexpr (HT && DT == DT_MUL) epar += dtab_lnp(g.dtab, g.dt_nd, mc_dist(s0, L, z0));
                         ninb += inb ? 1 : 0;
-                        if (g.has_par || g.dust_on) {
+                        if (DT != DT_OFF || g.has_par || g.dust_on) {
                             const double dM = epar - M;
                             const double ex = fast_exp_bf(-fabs(dM), s_tbl);
                             const bool up = inb && dM > 0.;
@@ -1131,7 +1194,7 @@ k_post_mc(PostParams pp, int64_t cap, int item_base, int nitem, unsigned int *__
                     // logsumexp(lnp_mc) - ln(#in bounds), fitting.py:1094-1102; with no
                     // sample in bounds the reference yields +inf -> not finite -> -BIG
                     double lse = pp.lnK + fast_log_r(acc);
-                    if (g.has_par || g.dust_on) lse += M - (g.has_par ? 0.5 * g.par_lnorm : 0.);
+                    if (DT != DT_OFF || g.has_par || g.dust_on) lse += M - (g.has_par ? 0.5 * g.par_lnorm : 0.);
                     double lnp = ninb > 0 ? rp.lnp[o] + (lse - fast_log_r((double)ninb)) : nan("");
                     if (!isfinite(lnp)) lnp = -BIG;                       // fitting.py:1103-1105
                     rp.lnp[o] = lnp;
@@ -1165,7 +1228,9 @@ k_post_mc(PostParams pp, int64_t cap, int item_base, int nitem, unsigned int *__
 constexpr int MCA_R = 8, MCA_G = 8, MCA_NMC = 64;
 constexpr int MCA_U = 8;          // loads of the tile copy a lane keeps in flight
 
-template <bool HT>
+// (DT as in k_post_mc; the table is read from global memory in every mode: the LDS of this
+// kernel is the tiles of normals)
+template <bool HT, int DT = DT_OFF>
 __global__ void __launch_bounds__(TILE, 3)
 k_post_mc_arr(PostParams pp, int64_t cap, int item_base, int nitem, unsigned int *__restrict__ counter,
               const double *__restrict__ zarr, const int64_t *__restrict__ zoff,
@@ -1284,10 +1349,12 @@ k_post_mc_arr(PostParams pp, int64_t cap, int item_base, int nitem, unsigned int
                                             zr[pp.nmc + t], zr[2 * pp.nmc + t], s0, a0, r0, L, Fc, Ac, s_tbl,
                                             ht, inb, lin, epar);
                             else
-                                mc_sample_lin(pp, g, zr[t], zr[pp.nmc + t], zr[2 * pp.nmc + t], s0, a0, r0, L,
-                                              Fc, Ac, s_tbl, d_, a_, r_, inb, lin, epar);
+                                mc_sample_lin<DT>(pp, g, zr[t], zr[pp.nmc + t], zr[2 * pp.nmc + t], s0, a0, r0, L,
+                                                  Fc, Ac, s_tbl, d_, a_, r_, inb, lin, epar);
+                            if constexpr (HT && DT == DT_MUL)
+                                epar += dtab_lnp(g.dtab, g.dt_nd, mc_dist(s0, L, zr[t]));
                             ninb += inb ? 1 : 0;
-                            if (g.has_par || g.dust_on) {
+                            if (DT != DT_OFF || g.has_par || g.dust_on) {
                                 const double dM = epar - M;
                                 const double ex = fast_exp_bf(-fabs(dM), s_tbl);
                                 const bool up = inb && dM > 0.;
@@ -1304,7 +1371,7 @@ k_post_mc_arr(PostParams pp, int64_t cap, int item_base, int nitem, unsigned int
                     for (int off = 1; off < MCA_G; off <<= 1) {
                         const double Mo = __shfl_xor(M, off, 64), acco = __shfl_xor(acc, off, 64);
                         ninb += __shfl_xor(ninb, off, 64);
-                        if (g.has_par || g.dust_on) {
+                        if (DT != DT_OFF || g.has_par || g.dust_on) {
                             if (Mo > -INFINITY) {
                                 if (M > -INFINITY) {
                                     const double ex = fast_exp_bf(-fabs(Mo - M), s_tbl);
@@ -1323,7 +1390,7 @@ k_post_mc_arr(PostParams pp, int64_t cap, int item_base, int nitem, unsigned int
                         // logsumexp(lnp_mc) - ln(#in bounds), fitting.py:1094-1102; with no
                         // sample in bounds the reference yields +inf -> not finite -> -BIG
                         double lse = pp.lnK + fast_log_r(acc);
-                        if (g.has_par || g.dust_on) lse += M - (g.has_par ? 0.5 * g.par_lnorm : 0.);
+                        if (DT != DT_OFF || g.has_par || g.dust_on) lse += M - (g.has_par ? 0.5 * g.par_lnorm : 0.);
                         double lnp = ninb > 0 ? rp.lnp[o] + (lse - fast_log_r((double)ninb)) : nan("");
                         if (!isfinite(lnp)) lnp = -BIG;                       // fitting.py:1103-1105
                         rp.lnp[o] = lnp;
@@ -1598,7 +1665,7 @@ __device__ __forceinline__ void sightline(const PostParams &pp, double l, double
 // per-object geometry / parallax constants
 __global__ void k_post_geom(PostParams pp, int nstar, const double *__restrict__ coords,
                             const double *__restrict__ par, const double *__restrict__ perr,
-                            DustCtx dc, StarGeom *__restrict__ geom) {
+                            DustCtx dc, DistCtx tc, StarGeom *__restrict__ geom) {
     const int s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= nstar) return;
     const double l = coords[2 * s] * (M_PI / 180.), b = coords[2 * s + 1] * (M_PI / 180.);
@@ -1616,6 +1683,9 @@ __global__ void k_post_geom(PostParams pp, int nstar, const double *__restrict__
     g.d_scale = dc.scale;
     g.d_smooth = dc.smooth;
     g.d_scat2 = dc.scatter * dc.scatter;
+    g.dt_on = tc.d_tab ? (tc.replace ? DT_REP : DT_MUL) : DT_OFF;
+    g.dt_nd = tc.nd;
+    g.dtab = tc.d_tab ? tc.d_tab + (int64_t)s * 2 * tc.nd : nullptr;
     const double o0 = pp.frame_off[0], o1 = pp.frame_off[1];
     for (int k = 0; k < 32; ++k) g.mc[k] = 0.;
     g.mc[MC_A2] = g.ux * g.ux + g.uy * g.uy;
@@ -1664,9 +1734,17 @@ __global__ void k_debug_galprior(PostParams pp, int n, const double *__restrict_
     sightline(pp, l, b, g);
     g.has_par = 0;
     g.dust_on = 0;
+    g.dt_on = DT_OFF;
     double Fc[3], Ac[3];
     label_terms(pp, feh[i], loga[i], Fc, Ac);
     out[i] = gal_lnprior_dev(pp, g, dist[i], Fc, Ac, kExp2Tbl);
+}
+
+// the device lookup of a distance table (dtab_lnp) on n distances
+__global__ void k_debug_dist_table(int nd, const double *__restrict__ tab, int64_t n,
+                                   const double *__restrict__ dist, double *__restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = dtab_lnp(tab, nd, dist[i]);
 }
 
 // the same ln prior as the sample loop of k_post_mc / k_post_mc_arr evaluates it: the object's

@@ -492,6 +492,20 @@ static PostWs carve_post(char *base, int nstar, int64_t cap, int nmc, int ndraws
 }
 
 thread_local DustCtx g_dust{};
+thread_local DistCtx g_dtab{};
+
+// the Monte Carlo kernels by halo form and distance-table mode (replace mode evaluates no
+// Galactic prior: one instantiation, the plain form with lin = 1)
+static auto pick_post_mc(bool ht, int dt) -> decltype(&k_post_mc<true, DT_OFF>) {
+    if (dt == DT_REP) return k_post_mc<false, DT_REP>;
+    if (dt == DT_MUL) return ht ? k_post_mc<true, DT_MUL> : k_post_mc<false, DT_MUL>;
+    return ht ? k_post_mc<true, DT_OFF> : k_post_mc<false, DT_OFF>;
+}
+static auto pick_post_mc_arr(bool ht, int dt) -> decltype(&k_post_mc_arr<true, DT_OFF>) {
+    if (dt == DT_REP) return k_post_mc_arr<false, DT_REP>;
+    if (dt == DT_MUL) return ht ? k_post_mc_arr<true, DT_MUL> : k_post_mc_arr<false, DT_MUL>;
+    return ht ? k_post_mc_arr<true, DT_OFF> : k_post_mc_arr<false, DT_OFF>;
+}
 
 struct MtArgs {            // numpy-stream mode of post_batch_impl
     int nstream;           // 1: one stream serves all objects in order; nstar: one per object
@@ -537,8 +551,10 @@ static int clip_to_nsel_max(PostWs &w, int64_t cap, int64_t a, int64_t n, int64_
     return 0;
 }
 
-static void fill_post_params(PostParams &pp, const brutus_post_params *params) {
+// `replace_gal`: a distance table stands in for the Galactic prior (brutus_post_set_dist_table)
+static void fill_post_params(PostParams &pp, const brutus_post_params *params, bool replace_gal = false) {
     memcpy(&pp, params, sizeof(brutus_post_params));
+    if (replace_gal) pp.has_feh = pp.has_loga = 0;      // no label terms without the Galactic prior
     pp.ln_f_thick = log(pp.f_thick);
     pp.ln_f_halo = log(pp.f_halo);
     const double rq2 = pp.r_q_halo * pp.r_q_halo, Rs2 = pp.R_solar * pp.R_solar, Zs = pp.Z_solar;
@@ -588,6 +604,7 @@ static void fill_post_params(PostParams &pp, const brutus_post_params *params) {
                     // (mc_sample_c takes its square roots without the x == 0 select)
                     pp.Rs_thin2 >= ldexp(1., -HALO_E0) && pp.Rs_thick2 >= ldexp(1., -HALO_E0);
     pp.halo_tbl = ok ? 1. : 0.;
+    if (replace_gal) pp.lnK = 0.;       // ln prior = ln(lin) + epar with lin = 1
 }
 
 }  // namespace
@@ -612,6 +629,11 @@ int post_batch_impl(int nstar, int64_t capacity, const int32_t *d_sel_idx, const
                       int32_t *h_flags, uint64_t *h_nbase, void *stream, const MtArgs *mt) {
     static_assert(sizeof(PostParams) == sizeof(brutus_post_params) + POST_DERIVED * sizeof(double),
                   "post params layout");
+    // one-shot: set by brutus_post_set_dist_table on this thread; every phase reads it (the
+    // table decides which Monte Carlo kernel phase 2 launches), a rejected call consumes it too)
+    const DistCtx tc = g_dtab;
+    g_dtab = DistCtx{};
+    const int dt = tc.d_tab ? (tc.replace ? DT_REP : DT_MUL) : DT_OFF;
     if (nstar < 1 || nstar > BRUTUS_MAX_BATCH || capacity < 1)
         return fail(BRUTUS_EINVAL, "bad post dimensions");
     if (!d_sel_idx || !d_rec_slot || !d_sel_vals || !d_sel_off || !d_lnprior || !d_coords || !params ||
@@ -627,7 +649,7 @@ int post_batch_impl(int nstar, int64_t capacity, const int32_t *d_sel_idx, const
         return fail(BRUTUS_ENOMEM, "post workspace too small: need %zu bytes, got %zu", w.bytes,
                     workspace_bytes);
     PostParams pp;
-    fill_post_params(pp, params);
+    fill_post_params(pp, params, dt == DT_REP);
     hipStream_t st = (hipStream_t)stream;
     Timer tm(st);
     const dim3 g2(PCH, nstar), blk(TILE);
@@ -637,7 +659,7 @@ int post_batch_impl(int nstar, int64_t capacity, const int32_t *d_sel_idx, const
     g_dust = DustCtx{};
     if (dc.d_los && (dc.nd < 2 || dc.nd > 4096)) return fail(BRUTUS_EINVAL, "bad dust table");
     hipLaunchKernelGGL(k_post_geom, dim3((nstar + 63) / 64), dim3(64), 0, st, pp, nstar, d_coords,
-                       d_parallax, d_parallax_err, dc, w.geom);
+                       d_parallax, d_parallax_err, dc, tc, w.geom);
     tm.begin("k_post_lnp1");
     hipLaunchKernelGGL(k_post_lnp1, g2, blk, 0, st, pp, capacity, d_sel_idx, d_rec_slot, d_sel_vals, d_sel_off,
                        w.geom, d_lnprior, d_feh, d_loga, w.lnp1, w.part);
@@ -675,7 +697,7 @@ int post_batch_impl(int nstar, int64_t capacity, const int32_t *d_sel_idx, const
             const int nitem = PCH * nstar;
             HIP_TRY(hipMemsetAsync(w.mc_counter, 0, 4, st));
             hipLaunchKernelGGL(k_post_order, dim3(1), dim3(BRUTUS_MAX_BATCH), 0, st, 0, nstar, w.nsel, w.mc_order);
-            hipLaunchKernelGGL(pp.halo_tbl != 0. ? k_post_mc<true> : k_post_mc<false>,
+            hipLaunchKernelGGL(pick_post_mc(pp.halo_tbl != 0., dt),
                                dim3(nitem < MC_SLOTS ? nitem : MC_SLOTS), blk, 0, st, pp,
                                capacity, 0, nitem, w.mc_counter, (const double *)nullptr,
                                (const int64_t *)nullptr, w.mc_stage, d_sel_idx, d_rec_slot, d_sel_vals, d_sel_off,
@@ -842,7 +864,7 @@ int post_batch_impl(int nstar, int64_t capacity, const int32_t *d_sel_idx, const
                 static const int use_arr = env_int("BRUTUS_POST_MC_ARR", 1);
                 static const int arr_persistent = env_int("BRUTUS_POST_MC_ARR_PERSISTENT", 0);
                 if (use_arr && pp.nmc <= MCA_NMC)
-                    hipLaunchKernelGGL(pp.halo_tbl != 0. ? k_post_mc_arr<true> : k_post_mc_arr<false>,
+                    hipLaunchKernelGGL(pick_post_mc_arr(pp.halo_tbl != 0., dt),
                                        dim3(arr_persistent ? (nitem < MC_SLOTS ? nitem : MC_SLOTS) : nitem), blk,
                                        sizeof(double) * (TILE / 64) * MCA_R * 3 * pp.nmc,
                                        st, pp, capacity, PCH * s0, PCH * s1,
@@ -851,7 +873,7 @@ int post_batch_impl(int nstar, int64_t capacity, const int32_t *d_sel_idx, const
                                        d_sel_vals, d_sel_off, w.off2, w.nsel, w.flags, w.geom, d_feh,
                                        d_loga, w.rp, w.part_max, w.part_chi2, el.zm, (const int32_t *)w.mc_order);
                 else
-                    hipLaunchKernelGGL(pp.halo_tbl != 0. ? k_post_mc<true> : k_post_mc<false>,
+                    hipLaunchKernelGGL(pick_post_mc(pp.halo_tbl != 0., dt),
                                        dim3(nitem < MC_SLOTS ? nitem : MC_SLOTS), blk, 0, st,
                                        pp, capacity, PCH * s0, PCH * s1, w.mc_counter,
                                        (const double *)zbase, (const int64_t *)w.mt_zoff, w.mc_stage,
@@ -954,6 +976,15 @@ int brutus_post_set_after_jump(void (*fn)(void *), void *arg) {
 int brutus_post_set_dust(const double *d_los, const int32_t *d_ok, int nd, double offset,
                          double scale, double smooth, double scatter) {
     g_dust = DustCtx{d_los, d_ok, nd, offset, scale, smooth, scatter};
+    return 0;
+}
+
+int brutus_post_set_dist_table(const double *d_tab, int nd, int replace_gal) {
+    if (d_tab && (nd < 2 || nd > 4096)) {
+        g_dtab = DistCtx{};
+        return fail(BRUTUS_EINVAL, "bad distance table");
+    }
+    g_dtab = d_tab ? DistCtx{d_tab, nd, replace_gal ? 1 : 0} : DistCtx{};
     return 0;
 }
 
@@ -1062,6 +1093,16 @@ int brutus_debug_galprior(const brutus_post_params *params, int n, const double 
     return 0;
 }
 
+int brutus_debug_dist_table(int nd, const double *d_tab, int64_t n, const double *d_dist, double *d_out,
+                            void *stream) {
+    if (nd < 2 || nd > 4096) return fail(BRUTUS_EINVAL, "bad distance table");
+    if (!d_tab || !d_dist || !d_out || n <= 0) return fail(BRUTUS_EINVAL, "bad arguments");
+    hipLaunchKernelGGL(k_debug_dist_table, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       nd, d_tab, n, d_dist, d_out);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 int brutus_debug_galprior_mc(const brutus_post_params *params, int n, const double *d_dist,
                              const double *d_coord, const double *d_feh, const double *d_loga,
                              double *d_out, void *stream) {
@@ -1074,7 +1115,7 @@ int brutus_debug_galprior_mc(const brutus_post_params *params, int n, const doub
     HIP_TRY(hipMalloc(&geom, sizeof(StarGeom)));
     DustCtx dc{};
     hipLaunchKernelGGL(k_post_geom, dim3(1), dim3(64), 0, st, pp, 1, d_coord, (const double *)nullptr,
-                       (const double *)nullptr, dc, geom);
+                       (const double *)nullptr, dc, DistCtx{}, geom);
     hipLaunchKernelGGL(pp.halo_tbl != 0. ? k_debug_galprior_mc<true> : k_debug_galprior_mc<false>,
                        dim3((n + 255) / 256), dim3(256), 0, st, pp, n, d_dist, geom, d_feh, d_loga, d_out);
     hipError_t e = hipGetLastError();
@@ -1098,7 +1139,7 @@ int brutus_debug_galprior_sl(const brutus_post_params *params, int n, const doub
     HIP_TRY(hipMalloc(&geom, sizeof(StarGeom)));
     DustCtx dc{};
     hipLaunchKernelGGL(k_post_geom, dim3(1), dim3(64), 0, st, pp, 1, d_coord, (const double *)nullptr,
-                       (const double *)nullptr, dc, geom);
+                       (const double *)nullptr, dc, DistCtx{}, geom);
     hipLaunchKernelGGL(k_debug_galprior_sl, dim3((n + TILE - 1) / TILE), dim3(TILE), 0, st, pp, n, d_dist, geom,
                        d_feh, d_loga, d_out, d_used);
     hipError_t e = hipGetLastError();

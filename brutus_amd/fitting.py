@@ -494,7 +494,8 @@ class _Engine(object):
         return rec, rec.off.cpu().numpy(), ndim.cpu().numpy(), k1, k2
 
     def post_batch_device(self, rec, nstar, statics,
-                          coords, parallax, parallax_err, pp, np_states=None, dust=None):
+                          coords, parallax, parallax_err, pp, np_states=None, dust=None,
+                          dtab=None):
         """`brutus_post_batch` on device-resident `Records`.  `statics` =
         (lnprior, feh, loga) device tensors (feh / loga may be None).
         `np_states` (uint32 (nstream, 628), advanced in place): draw from numpy's own
@@ -533,6 +534,7 @@ class _Engine(object):
                     zb = slot0["zbuf"] = torch.empty(int(gb * 2 ** 30) // 8, dtype=torch.float64,
                                                      device=g.device)
                 self._set_dust(dust)          # one-shot context: before EVERY (re)try
+                self._set_dist_table(dtab)
                 rc = L.brutus_post_batch_numpy(
                     nstar, cap, sel_idx.data_ptr(), rec_slot.data_ptr(), sel_vals.data_ptr(),
                     sel_off.data_ptr(),
@@ -554,6 +556,7 @@ class _Engine(object):
                 break
             return (out_idx.cpu().numpy(), out_vals.cpu().numpy(), star_out, flags, nbase)
         self._set_dust(dust)
+        self._set_dist_table(dtab)
         _lib.check(L.brutus_post_batch(
             nstar, cap, sel_idx.data_ptr(), rec_slot.data_ptr(), sel_vals.data_ptr(),
             sel_off.data_ptr(),
@@ -576,8 +579,18 @@ class _Engine(object):
             _lib.check(self.L.brutus_post_set_dust(t_los.data_ptr(), t_ok.data_ptr(),
                                                    int(t_los.shape[2]), 0., 1., 1., 0.2))
 
+    def _set_dist_table(self, dtab):
+        """Tabulated distance prior of the NEXT post call of this thread
+        (`brutus_post_set_dist_table`, one-shot like the dust context; a phase-2 call reads it
+        too).  `dtab` = (t_tab (nstar, 2, nd) device tensor, replace flag) or None."""
+        if dtab is not None:
+            t_tab, replace = dtab
+            _lib.check(self.L.brutus_post_set_dist_table(t_tab.data_ptr(), int(t_tab.shape[2]),
+                                                         1 if replace else 0))
+
     def post_numpy_begin(self, slot, rec, nstar, statics, coords,
-                         parallax, parallax_err, pp, np_states, dust=None, after_jump=None):
+                         parallax, parallax_err, pp, np_states, dust=None, after_jump=None,
+                         dtab=None):
         """Phase 1 of `brutus_post_batch_numpy_phase` in pipeline slot `slot` (own
         workspace, normal buffer and outputs): cuts, covariances, stream walk; `np_states`
         is advanced.  False if the objects do not fit the slot's buffer as one group
@@ -603,10 +616,10 @@ class _Engine(object):
             ctx["zbuf"] = torch.empty(int(gb * 2 ** 30) // 8, dtype=torch.float64, device=g.device)
         dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(g.device)
         lnprior, feh, loga = statics
-        # everything phase 2 reads stays referenced until `post_numpy_end` (the dust tables
-        # too: phase 2 evaluates the line-of-sight prior inside the Monte Carlo integral)
+        # everything phase 2 reads stays referenced until `post_numpy_end` (the dust and distance
+        # tables too: phase 2 evaluates them inside the Monte Carlo integral)
         ctx["keep"] = (rec.idx, rec.vals, rec.off, dev(coords), dev(parallax), dev(parallax_err),
-                       rec.slot, dust)
+                       rec.slot, dust, dtab)
         ctx["out"] = (torch.empty((nstar, pp.ndraws), dtype=torch.int32, device=g.device),
                       torch.empty((nstar, pp.ndraws, 17), dtype=torch.float64, device=g.device),
                       np.zeros((nstar, 4)), np.zeros(nstar, dtype=np.int32))
@@ -616,6 +629,7 @@ class _Engine(object):
             k, o = ctx["keep"], ctx["out"]
             if phase == 1:
                 self._set_dust(k[7])
+            self._set_dist_table(k[8])      # (both phases: phase 2 picks its kernel by it)
             return L.brutus_post_batch_numpy_phase(
                 nstar, cap, k[0].data_ptr(), k[6].data_ptr(), k[1].data_ptr(), k[2].data_ptr(),
                 lnprior.data_ptr(), feh.data_ptr() if feh is not None else None,
@@ -1495,6 +1509,10 @@ class BruteForce(object):
         statics = (up(lnprior),
                    up(dlabels['feh']) if 'feh' in names else None,
                    up(dlabels['loga']) if 'loga' in names else None)
+        # a tabulated distance prior (pdf.DistancePriorTable): the parameters are its base
+        # hook's (the defaults when it replaces the Galactic prior), the table goes up per batch
+        from . import pdf as _pdf
+        dist_prior = lngalprior if isinstance(lngalprior, _pdf.DistancePriorTable) else None
         gp = lngalprior.device_params()
         K = Ndraws * (2 if return_distreds else 1)
         Ndata = data.shape[0]
@@ -1689,6 +1707,10 @@ class BruteForce(object):
                         los, ok = dust_tables(a, b)  # them to every post call and retry and keeps
                         dust = (torch.from_numpy(np.ascontiguousarray(los)).to(dev),     # them alive
                                 torch.from_numpy(np.ascontiguousarray(ok)).to(dev))
+                    dtab = None
+                    if dist_prior is not None:       # kept alive like the dust tables
+                        dtab = (torch.from_numpy(_pdf.dist_tables(
+                                    dist_prior, data_coords[a:b])).to(dev), dist_prior.base is None)
                     if pipelined:
                         # Phase 2 of the previous batch is held back until the jump-ahead of
                         # THIS batch's walk is through (its kernels need whole compute units
@@ -1716,7 +1738,7 @@ class BruteForce(object):
                             began = eng.post_numpy_begin(
                                 kb % 2, rec, S, statics, data_coords[a:b],
                                 parallax[a:b], parallax_err[a:b], pp, np_states, dust=dust,
-                                after_jump=submit_prev)
+                                after_jump=submit_prev, dtab=dtab)
                         if sub:
                             pending = sub[0]
                         if began:
@@ -1735,7 +1757,8 @@ class BruteForce(object):
                                 yield row
                     out_idx, out_vals, star_out, flags, nbase = eng.post_batch_device(
                         rec, S, statics, data_coords[a:b],
-                        parallax[a:b], parallax_err[a:b], pp, np_states=np_states, dust=dust)
+                        parallax[a:b], parallax_err[a:b], pp, np_states=np_states, dust=dust,
+                        dtab=dtab)
                     ubase0 = pp.uniform_base
                     if np_mode == "shared":      # the caller's generator continues from here
                         rstate.set_state(words_to_state(np_states[0]))

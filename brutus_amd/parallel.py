@@ -300,7 +300,13 @@ def fit_sharded(bf, data, data_err, data_mask, data_labels, save_file,
         try:
             while True:
                 item = None
-                if not done and failure["local"] is None:
+                # The failure state is read ONCE per round, before the queue: a block taken
+                # from the queue is handed over in this round even if the fit raises while it
+                # is on its way (the fitting thread runs on as soon as the queue has room), and
+                # the failure goes into the next round's header.  Read after the `get`, the flag
+                # could drop rows that were fitted before anything went wrong.
+                failed = failure["local"] is not None
+                if not done and not failed:
                     try:
                         item = q.get(timeout=0.02)
                     except queue.Empty:
@@ -313,8 +319,9 @@ def fit_sharded(bf, data, data_err, data_mask, data_labels, save_file,
                         done = True
                     else:
                         failure["local"] = failure["local"] or RuntimeError(item[1])
-                hdr = torch.tensor([n, start, 1 if done else 0,
-                                    0 if failure["local"] is None else 1], dtype=torch.int64)
+                        failed = True
+                hdr = torch.tensor([n, start, 1 if done else 0, 1 if failed else 0],
+                                   dtype=torch.int64)
                 if world > 1:
                     hdrs = [torch.empty(4, dtype=torch.int64) for _ in range(world)]
                     dist.all_gather(hdrs, hdr, group=side)

@@ -23,7 +23,7 @@ __all__ = ["imf_lnprior", "ps1_MrLF_lnprior", "parallax_lnprior",
            "logp_feh", "logp_age_from_feh",
            "gal_lnprior", "dust_lnprior",
            "bin_pdfs_distred",
-           "LOSTable"]
+           "LOSTable", "DistancePriorTable", "dist_tables"]
 
 
 def _kroupa_segment(m, alpha_low, alpha_high, mass_break):
@@ -197,6 +197,121 @@ def los_tables(dustfile, coords):
     rows = [r if r.shape[1] == nd else np.concatenate(
         [r, np.repeat(r[:, -1:], nd - r.shape[1], axis=1)], axis=1) for r in rows]
     return np.stack(rows), np.asarray(ok, dtype=np.int32)
+
+
+# ---------------------------------------------------------------------------
+# tabulated distance priors
+# ---------------------------------------------------------------------------
+def _nearest_sightline(l, b, coord):
+    """Index of the tabulated sightline nearest to `coord` (great-circle, as `LOSTable.query`)."""
+    l0, b0 = np.deg2rad(coord[0]), np.deg2rad(coord[1])
+    l, b = np.deg2rad(l), np.deg2rad(b)
+    cosd = np.sin(b0) * np.sin(b) + np.cos(b0) * np.cos(b) * np.cos(l - l0)
+    return int(np.argmax(cosd))
+
+
+class DistancePriorTable(object):
+    """A distance prior given as a table, usable as the `lngalprior` hook of `fit()` / `lnpost()`
+    and as `lndistprior` of `bin_pdfs_distred`: a cluster or association distance, a
+    Bailer-Jones style prior, a field where the Milky-Way model does not apply.  Unlike an
+    opaque callable it has a device form, so `fit()` keeps the device `lnpost` stage.
+
+    `DistancePriorTable(dist, lnp, l=None, b=None, base=None)`: `dist` (nd,) kpc, strictly
+    increasing, 2 <= nd <= 4096; `lnp` (nd,) ln prior at those distances, shared by all objects,
+    or (Ntab, nd) with `l, b` (Ntab,) Galactic degrees of the sightlines the rows belong to (an
+    object takes the row of the nearest one).  Between the nodes the table is interpolated
+    linearly, outside it the end values hold (`numpy.interp`).
+
+    `base=None`: the table REPLACES the Galactic prior (no density, no d^2 volume factor, no
+    label terms).  `base=` another `lngalprior` hook: the table MULTIPLIES it; with a hook the
+    device implements (`gal_lnprior`, `gal_lnprior_simple`, a wrapper that has `device_params`)
+    the product runs on the device too, with any other callable on the host.
+
+    To tabulate a prior p(d): `d = np.geomspace(dmin, dmax, 256)`, then
+    `DistancePriorTable(d, np.log(p(d)))` -- include the volume factor d^2 in p if it is a space
+    density and the table replaces the Galactic prior; floor -inf at a finite value (-1e300 does).
+    """
+
+    def __init__(self, dist, lnp, l=None, b=None, base=None):
+        self.dist = np.ascontiguousarray(dist, dtype=np.float64)
+        lnp = np.asarray(lnp, dtype=np.float64)
+        if self.dist.ndim != 1 or not 2 <= self.dist.size <= 4096:
+            raise ValueError("DistancePriorTable: dist must be (nd,) with 2 <= nd <= 4096")
+        if not np.all(np.isfinite(self.dist)) or not np.all(np.diff(self.dist) > 0):
+            raise ValueError("DistancePriorTable: dist must be finite and strictly increasing")
+        if lnp.ndim == 1:
+            if l is not None or b is not None:
+                raise ValueError("DistancePriorTable: l, b go with a 2-d lnp (Ntab, nd)")
+            self.l = self.b = None
+        elif lnp.ndim == 2:
+            if l is None or b is None:
+                raise ValueError("DistancePriorTable: a 2-d lnp (Ntab, nd) needs l, b (Ntab,)")
+            self.l = np.atleast_1d(np.asarray(l, dtype=np.float64))
+            self.b = np.atleast_1d(np.asarray(b, dtype=np.float64))
+            if self.l.shape != (lnp.shape[0],) or self.b.shape != self.l.shape:
+                raise ValueError("DistancePriorTable: l, b must be (Ntab,)")
+            if lnp.shape[0] < 1 or not np.all(np.isfinite(self.l) & np.isfinite(self.b)):
+                raise ValueError("DistancePriorTable: l, b must be finite")
+        else:
+            raise ValueError("DistancePriorTable: lnp must be (nd,) or (Ntab, nd)")
+        if lnp.shape[-1] != self.dist.size:
+            raise ValueError("DistancePriorTable: lnp must have one value per node of dist")
+        if not np.all(np.isfinite(lnp)):
+            raise ValueError("DistancePriorTable: lnp must be finite (floor -inf at e.g. -1e300)")
+        if base is not None and not callable(base):
+            raise ValueError("DistancePriorTable: base must be a lngalprior hook or None")
+        self.lnp = np.ascontiguousarray(np.atleast_2d(lnp))
+        self.base = base
+        #: `lnpost` may pass the (Nsel,) label table for (Nmc, Nsel) distances
+        self.broadcasts_labels = base is None or bool(getattr(base, "broadcasts_labels", False))
+
+    @classmethod
+    def load(cls, path, base=None):
+        """From an `.npz` file with arrays `dist, lnp` and, for a 2-d `lnp`, `l, b`."""
+        z = np.load(path)
+        return cls(z["dist"], z["lnp"], z["l"] if "l" in z else None, z["b"] if "b" in z else None,
+                   base=base)
+
+    def _row(self, coord):
+        return 0 if self.l is None else _nearest_sightline(self.l, self.b, coord)
+
+    def query(self, coord):
+        """`(dist, lnp)` of the sightline nearest to `coord`."""
+        return self.dist, self.lnp[self._row(coord)]
+
+    def __call__(self, dists, coord, labels=None):
+        x, f = self.query(coord)
+        out = np.interp(np.asarray(dists, dtype=np.float64), x, f)
+        if self.base is not None:
+            out = out + self.base(dists, coord, labels=labels)
+        return out
+
+    @property
+    def replaces_gal(self):
+        return self.base is None
+
+    @property
+    def device_params(self):
+        """Like `gal_lnprior.device_params`: a callable returning the parameters of the Galactic
+        prior the device stage multiplies the table with (the defaults when the table replaces
+        it: they are not evaluated then), or None if `base` has no device form -- `fit()` then
+        runs the host stage, as for any callable."""
+        if self.base is None:
+            from .galprior import device_params
+            return device_params
+        return getattr(self.base, "device_params", None)
+
+
+def dist_tables(prior, coords):
+    """The distance tables of a batch of objects as one array for the device stage:
+    `tab (N, 2, nd) float64` = (dist, lnp) of the sightline nearest to each of `coords`.  Built
+    per batch like `los_tables`; all rows of a `DistancePriorTable` share one `dist` array, so
+    nothing is padded."""
+    coords = np.asarray(coords, dtype=np.float64).reshape(-1, 2)
+    tab = np.empty((coords.shape[0], 2, prior.dist.size), dtype=np.float64)
+    for k, c in enumerate(coords):
+        tab[k, 0], tab[k, 1] = prior.query(c)
+    return tab
 
 
 def dust_lnprior(dists, coord, avs, dustfile=None, offset=0., scale=1., smooth=1.,

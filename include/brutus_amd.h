@@ -311,6 +311,19 @@ int brutus_post_set_after_jump(void (*fn)(void *), void *arg);
 int brutus_post_set_dust(const double *d_los, const int32_t *d_ok, int nd,
                          double offset, double scale, double smooth, double scatter);
 
+/* Tabulated distance prior for the NEXT brutus_post_batch / brutus_post_batch_numpy /
+ * brutus_post_batch_numpy_phase call of the calling thread (one-shot, like
+ * brutus_post_set_dust: set it before every call and every retry; a phase-2 call reads it too,
+ * so set the same table before phase 1 and before phase 2):
+ *   d_tab (nstar, 2, nd) f64: dist [kpc] (strictly increasing), ln prior at those distances,
+ *   one table per object; interpolated like numpy.interp, end values outside the table.
+ *   replace_gal == 0: the table multiplies the Galactic prior of brutus_post_params;
+ *   replace_gal != 0: it replaces it (no density, no d^2 volume factor, no label terms).
+ * Applied at the MLE point and to every Monte Carlo sample.  d_tab == NULL clears a pending
+ * table.  BRUTUS_EINVAL "bad distance table" unless 2 <= nd <= 4096 (checked before any HIP
+ * call).  An additive entry point: BRUTUS_ABI_VERSION stays. */
+int brutus_post_set_dist_table(const double *d_tab, int nd, int replace_gal);
+
 /* Jump-ahead polynomials of MT19937 (brutus_amd/mt_jump.npz, made and checked against
  * numpy by tools/gen_mt_jump.py): h_polys = uint32 (npoly, 624), x^(stride - 1) mod phi
  * for stride0 = 2 096 640 words and 128 * stride0 * 2^r, r = 0 .. npoly - 2.  With them

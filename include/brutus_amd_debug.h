@@ -50,6 +50,12 @@ int brutus_debug_galprior_sl(const brutus_post_params *params, int n,
                              const double *d_feh, const double *d_loga, double *d_out,
                              int32_t *d_used, void *stream);
 
+/* The device lookup of a tabulated distance prior (brutus_post_set_dist_table): d_tab (2, nd)
+ * f64 = dist [kpc], lnp; d_out[i] = the table interpolated at d_dist[i] like numpy.interp (end
+ * values outside the table).  BRUTUS_EINVAL "bad distance table" for nd < 2 or nd > 4096. */
+int brutus_debug_dist_table(int nd, const double *d_tab, int64_t n, const double *d_dist,
+                            double *d_out, void *stream);
+
 /* Measurement aid: brutus_fit_batch calls of this process so far and how many of them had to
  * be repeated by the host-driven driver (a star with more than eight magnitude sweeps, a flux
  * phase longer than the device-driven call's continuation rounds).  Needs no GPU. */
