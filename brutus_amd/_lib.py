@@ -7,7 +7,7 @@ no GPU is visible, every compute entry point raises.
 import ctypes as C
 import os
 
-__all__ = ["lib", "Params", "PostParams", "check", "LIB_PATH", "BrutusError", "NVALS",
+__all__ = ["lib", "Params", "PostParams", "BinpdfParams", "check", "LIB_PATH", "BrutusError", "NVALS",
            "MAX_BATCH", "MAX_FILT", "MAX_FILT_FIT"]
 
 # BRUTUS_AMD_LIB: another build of the same library (A/B kernel timing)
@@ -62,9 +62,18 @@ class PostParams(C.Structure):
                 ("frame_mat", C.c_double * 9), ("frame_off", C.c_double * 3)]
 
 
+class BinpdfParams(C.Structure):
+    """struct brutus_binpdf_params (include/brutus_amd.h)."""
+    _fields_ = [("nx", C.c_int32), ("ny", C.c_int32), ("dist_type", C.c_int32),
+                ("ebv", C.c_int32), ("cdf", C.c_int32), ("nr", C.c_int32),
+                ("prior_mode", C.c_int32), ("max_attempts", C.c_int32),
+                ("avlim", C.c_double * 2), ("rvlim", C.c_double * 2),
+                ("ysigma_bins", C.c_double), ("seed", C.c_uint64), ("object0", C.c_int64)]
+
+
 # name -> (restype, argtypes); mirrors include/brutus_amd.h (product ABI) and
 # include/brutus_amd_debug.h (test hooks / measurement aids, see DEBUG_NAMES) one to one
-DEBUG_NAMES = ("brutus_calibrate_traffic", "brutus_calibrate_copy16", "brutus_calibrate_issue", "brutus_debug_exp10", "brutus_debug_math", "brutus_debug_mt_stream", "brutus_debug_rng", "brutus_debug_galprior", "brutus_debug_galprior_mc", "brutus_debug_galprior_sl", "brutus_debug_dist_table", "brutus_debug_zig_table", "brutus_debug_copy", "brutus_debug_sizeof_star32", "brutus_debug_fit_stats", "brutus_debug_pre32_time")
+DEBUG_NAMES = ("brutus_calibrate_traffic", "brutus_calibrate_copy16", "brutus_calibrate_issue", "brutus_debug_exp10", "brutus_debug_math", "brutus_debug_mt_stream", "brutus_debug_rng", "brutus_debug_galprior", "brutus_debug_galprior_mc", "brutus_debug_galprior_sl", "brutus_debug_dist_table", "brutus_debug_zig_table", "brutus_debug_copy", "brutus_debug_sizeof_star32", "brutus_debug_fit_stats", "brutus_debug_pre32_time", "brutus_debug_binpdf_draws")
 SIGNATURES = {
     "brutus_abi_version": (C.c_int, []),
     "brutus_last_error": (C.c_char_p, []),
@@ -107,6 +116,13 @@ SIGNATURES = {
     "brutus_post_set_dist_table": (C.c_int, [_vp, _i32, _i32]),
     "brutus_post_set_after_jump": (C.c_int, [_vp, _vp]),
     "brutus_debug_dist_table": (C.c_int, [_i32, _vp, _i64, _vp, _vp, _vp]),
+    "brutus_binpdf_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32, _i32]),
+    "brutus_binpdf_saved": (C.c_int, [_i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
+                                      C.POINTER(BinpdfParams), _vp, _vp, _sz, _vp]),
+    "brutus_binpdf_regen": (C.c_int, [_i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                      C.POINTER(PostParams), _vp, _i32, _vp, _vp, _vp,
+                                      C.POINTER(BinpdfParams), _vp, _vp, _vp, _sz, _vp]),
+    "brutus_debug_binpdf_draws": (C.c_int, [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "brutus_debug_rng": (C.c_int, [_u64, _u64, _i64, _vp, _vp, _vp]),
     "brutus_debug_zig_table": (C.c_int, [_vp, _vp, _i32]),
     "brutus_debug_fit_stats": (C.c_int, [_vp, _vp]),

@@ -1,6 +1,7 @@
 // post_unit.hip -- translation unit of libbrutus_amd.so: lnpost on the device (brutus_post_*:
 // second cut, Monte Carlo prior integral, resampling; post_kernels.hpp) with numpy's MT19937
-// stream walked by many workgroups (mt_kernels.hpp), and their test hooks.
+// stream walked by many workgroups (mt_kernels.hpp), the binned (distance, reddening) posteriors
+// made from its draws (brutus_binpdf_*; binpdf_kernels.hpp), and their test hooks.
 
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_radix_sort.hpp>
@@ -21,6 +22,7 @@
 #include "fastmath.hpp"
 #include "mt_kernels.hpp"
 #include "post_kernels.hpp"
+#include "binpdf_kernels.hpp"
 
 namespace {
 
@@ -1147,6 +1149,184 @@ int brutus_debug_galprior_sl(const brutus_post_params *params, int n, const doub
     hipFree(geom);
     HIP_TRY(e);
     HIP_TRY(e2);
+    return 0;
+}
+
+}  // extern "C"
+
+// ---- binned (distance, reddening) posteriors (binpdf_kernels.hpp) ------------------------
+namespace {
+
+struct BinWs {
+    double *ds, *da, *dr, *lnp;       // (nobj, nsamps, nr): realisations, ln prior -> weight
+    StarGeom *geom;                   // (nobj,)
+    unsigned long long *acc;          // (nobj, nx, ny) integer planes
+    float *tmp;                       // (nobj, nx, ny) between the two smoothing passes
+    size_t bytes;
+};
+
+// (the realisations come first: brutus_debug_binpdf_draws finds them from nobj, nsamps, nr alone)
+BinWs carve_binpdf(char *base, int nobj, int nx, int ny, int nsamps, int nr) {
+    BinWs w{};
+    Carver cv(base);
+    const size_t per = (size_t)nobj * (size_t)nsamps * (size_t)nr;
+    w.ds = (double *)cv.take(8 * per);
+    w.da = (double *)cv.take(8 * per);
+    w.dr = (double *)cv.take(8 * per);
+    w.lnp = (double *)cv.take(8 * per);
+    w.geom = (StarGeom *)cv.take(sizeof(StarGeom) * (size_t)(nr ? nobj : 0));
+    const size_t plane = (size_t)nobj * (size_t)nx * (size_t)ny;
+    w.acc = (unsigned long long *)cv.take(8 * plane);
+    w.tmp = (float *)cv.take(4 * plane);
+    w.bytes = cv.off;
+    return w;
+}
+
+bool binpdf_sizes_ok(int nobj, int nx, int ny, int nsamps, int nr) {
+    return nobj >= 1 && nobj <= 65535 && nx >= 1 && nx <= 65536 && ny >= 1 && ny <= 65536 &&
+           (int64_t)nx * ny <= ((int64_t)1 << 28) && nsamps >= 1 && nsamps <= 4096 && nr >= 0 &&
+           nr <= 65536 && (int64_t)nsamps * nr <= ((int64_t)1 << 24);
+}
+
+// what both forms check before any HIP call
+int binpdf_check(int nobj, int nsamps, int nr, const brutus_binpdf_params *p, const void *xe,
+                 const void *ye, const void *xs, const void *out, const void *ws) {
+    if (!p) return fail(BRUTUS_EINVAL, "NULL pointer (binpdf params)");
+    if (!binpdf_sizes_ok(nobj, p->nx, p->ny, nsamps, nr))
+        return fail(BRUTUS_EINVAL, "bad binpdf dimensions (nobj=%d, nsamps=%d, nr=%d, nx=%d, ny=%d)", nobj,
+                    nsamps, nr, p->nx, p->ny);
+    if (p->dist_type < 0 || p->dist_type > 3) return fail(BRUTUS_EINVAL, "bad binpdf dist_type %d", p->dist_type);
+    if (!(p->ysigma_bins >= 0.) || !(4. * p->ysigma_bins + 0.5 < (double)(BP_MAXR + 1)))
+        return fail(BRUTUS_EINVAL, "binpdf smoothing width along y must be >= 0 with a radius of at most %d bins",
+                    BP_MAXR);
+    if (!xe || !ye || !xs || !out || !ws) return fail(BRUTUS_EINVAL, "NULL pointer");
+    return 0;
+}
+
+// integer planes -> d_out: H / nsamps, the two smoothing passes, the cumulative sum
+int binpdf_finish(int nobj, int nsamps, const brutus_binpdf_params *p, double unit, const double *d_xsig,
+                  BinWs &w, float *d_out, hipStream_t st, Timer &tm) {
+    const int64_t plane = (int64_t)p->nx * p->ny;
+    const dim3 gp((unsigned)((plane + BP_NT - 1) / BP_NT), (unsigned)nobj), blk(BP_NT);
+    tm.begin("k_binpdf_convert");
+    hipLaunchKernelGGL(k_binpdf_convert, dim3((unsigned)((plane * nobj + BP_NT - 1) / BP_NT)), blk, 0, st,
+                       plane * nobj, w.acc, unit, (double)nsamps, d_out);
+    tm.end();
+    tm.begin("k_binpdf_smooth_x");
+    hipLaunchKernelGGL(k_binpdf_smooth<0>, gp, blk, 0, st, p->nx, p->ny, d_xsig, 0., (const float *)d_out, w.tmp);
+    tm.end();
+    tm.begin("k_binpdf_smooth_y");
+    hipLaunchKernelGGL(k_binpdf_smooth<1>, gp, blk, 0, st, p->nx, p->ny, (const double *)nullptr,
+                       p->ysigma_bins, (const float *)w.tmp, d_out);
+    tm.end();
+    if (p->cdf) {
+        tm.begin("k_binpdf_cdf");
+        hipLaunchKernelGGL(k_binpdf_cdf, dim3((unsigned)(((int64_t)nobj * p->ny + BP_NT - 1) / BP_NT)), blk, 0,
+                           st, nobj, p->nx, p->ny, d_out);
+        tm.end();
+    }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t brutus_binpdf_workspace_bytes(int nobj, int nx, int ny, int nsamps, int nr) {
+    if (!binpdf_sizes_ok(nobj, nx, ny, nsamps, nr)) return 0;
+    return carve_binpdf(nullptr, nobj, nx, ny, nsamps, nr).bytes;
+}
+
+int brutus_binpdf_saved(int nobj, int nsamps, const double *d_dist, const double *d_red,
+                        const double *d_dred, const double *d_xedges, const double *d_yedges,
+                        const double *d_xsigma_bins, const brutus_binpdf_params *params,
+                        float *d_out, void *d_workspace, size_t workspace_bytes, void *stream) {
+    if (int rc = binpdf_check(nobj, nsamps, 0, params, d_xedges, d_yedges, d_xsigma_bins, d_out, d_workspace))
+        return rc;
+    if (!d_dist || !d_red || (params->ebv && !d_dred)) return fail(BRUTUS_EINVAL, "NULL pointer");
+    BinWs w = carve_binpdf((char *)d_workspace, nobj, params->nx, params->ny, nsamps, 0);
+    if (w.bytes > workspace_bytes)
+        return fail(BRUTUS_ENOMEM, "binpdf workspace too small: need %zu bytes, got %zu", w.bytes, workspace_bytes);
+    hipStream_t st = (hipStream_t)stream;
+    Timer tm(st);
+    const BinGrid bg{d_xedges, d_yedges, params->nx, params->ny, params->dist_type, params->ebv ? 1 : 0};
+    const int64_t plane = (int64_t)params->nx * params->ny;
+    tm.begin("k_binpdf_hist");
+    HIP_TRY(hipMemsetAsync(w.acc, 0, 8 * (size_t)plane * nobj, st));
+    hipLaunchKernelGGL(k_binpdf_hist, dim3((unsigned)(((int64_t)nobj * nsamps + BP_NT - 1) / BP_NT)), dim3(BP_NT),
+                       0, st, nobj, nsamps, d_dist, d_red, d_dred, bg, w.acc);
+    tm.end();
+    if (int rc = binpdf_finish(nobj, nsamps, params, 1., d_xsigma_bins, w, d_out, st, tm)) return rc;
+    tm.collect();
+    return 0;
+}
+
+int brutus_binpdf_regen(int nobj, int nsamps, const double *d_scale, const double *d_av,
+                        const double *d_rv, const double *d_cov, const double *d_par,
+                        const double *d_parerr, const double *d_coord,
+                        const brutus_post_params *gal, const double *d_dtab, int nd,
+                        const double *d_xedges, const double *d_yedges,
+                        const double *d_xsigma_bins, const brutus_binpdf_params *params,
+                        int32_t *d_status, float *d_out, void *d_workspace,
+                        size_t workspace_bytes, void *stream) {
+    if (int rc = binpdf_check(nobj, nsamps, params ? params->nr : 0, params, d_xedges, d_yedges,
+                              d_xsigma_bins, d_out, d_workspace))
+        return rc;
+    if (params->nr < 1) return fail(BRUTUS_EINVAL, "bad binpdf dimensions (nr=%d)", params->nr);
+    if (params->prior_mode < 0 || params->prior_mode > 2 || params->max_attempts < 1 ||
+        params->max_attempts > 65536)
+        return fail(BRUTUS_EINVAL, "bad binpdf prior_mode / max_attempts");
+    if (!d_scale || !d_av || !d_rv || !d_cov || !d_coord || !gal || !d_status)
+        return fail(BRUTUS_EINVAL, "NULL pointer");
+    if (params->prior_mode != 0 && (!d_dtab || nd < 2 || nd > 4096))
+        return fail(BRUTUS_EINVAL, "bad distance table");
+    BinWs w = carve_binpdf((char *)d_workspace, nobj, params->nx, params->ny, nsamps, params->nr);
+    if (w.bytes > workspace_bytes)
+        return fail(BRUTUS_ENOMEM, "binpdf workspace too small: need %zu bytes, got %zu", w.bytes, workspace_bytes);
+    hipStream_t st = (hipStream_t)stream;
+    Timer tm(st);
+    const bool replace = params->prior_mode == 1;
+    PostParams pp;
+    fill_post_params(pp, gal, replace);
+    pp.has_feh = pp.has_loga = 0;           // the hook is called without labels
+    const DistCtx tc = params->prior_mode ? DistCtx{d_dtab, nd, replace ? 1 : 0} : DistCtx{};
+    const BinGrid bg{d_xedges, d_yedges, params->nx, params->ny, params->dist_type, params->ebv ? 1 : 0};
+    const BinRegen br{nsamps, params->nr, params->prior_mode, params->max_attempts, params->avlim[0],
+                      params->avlim[1], params->rvlim[0], params->rvlim[1], params->seed, params->object0};
+    const int64_t plane = (int64_t)params->nx * params->ny;
+    const int per = nsamps * params->nr;
+    HIP_TRY(hipMemsetAsync(d_status, 0, 12 * (size_t)nobj, st));
+    hipLaunchKernelGGL(k_post_geom, dim3((nobj + 63) / 64), dim3(64), 0, st, pp, nobj, d_coord, d_par,
+                       d_parerr, DustCtx{}, tc, w.geom);
+    tm.begin("k_binpdf_regen");
+    hipLaunchKernelGGL(k_binpdf_regen, dim3((unsigned)((per + BP_NT - 1) / BP_NT), (unsigned)nobj), dim3(BP_NT), 0,
+                       st, pp, (const StarGeom *)w.geom, br, d_scale, d_av, d_rv, d_cov, w.ds, w.da, w.dr,
+                       w.lnp, d_status);
+    tm.end();
+    tm.begin("k_binpdf_wbin");
+    HIP_TRY(hipMemsetAsync(w.acc, 0, 8 * (size_t)plane * nobj, st));
+    hipLaunchKernelGGL(k_binpdf_wbin, dim3((unsigned)((nsamps + BP_NT / 64 - 1) / (BP_NT / 64)), (unsigned)nobj),
+                       dim3(BP_NT), 0, st, br, bg, (const double *)w.ds, (const double *)w.da,
+                       (const double *)w.dr, w.lnp, w.acc);
+    tm.end();
+    if (int rc = binpdf_finish(nobj, nsamps, params, 1. / BP_FIX, d_xsigma_bins, w, d_out, st, tm)) return rc;
+    tm.collect();
+    return 0;
+}
+
+int brutus_debug_binpdf_draws(int nobj, int nsamps, int nr, const void *d_workspace, double *d_scale,
+                              double *d_av, double *d_rv, double *d_weight, void *stream) {
+    if (!binpdf_sizes_ok(nobj, 1, 1, nsamps, nr) || nr < 1) return fail(BRUTUS_EINVAL, "bad binpdf dimensions");
+    if (!d_workspace || !d_scale || !d_av || !d_rv || !d_weight) return fail(BRUTUS_EINVAL, "NULL pointer");
+    const BinWs w = carve_binpdf((char *)const_cast<void *>(d_workspace), nobj, 1, 1, nsamps, nr);
+    hipStream_t st = (hipStream_t)stream;
+    const size_t n = 8 * (size_t)nobj * nsamps * nr;
+    HIP_TRY(hipMemcpyAsync(d_scale, w.ds, n, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_av, w.da, n, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_rv, w.dr, n, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_weight, w.lnp, n, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));
     return 0;
 }
 

@@ -344,11 +344,11 @@ def bin_pdfs_distred(data, cdf=False, ebv=False, dist_type='distance_modulus',
                      lndistprior=None, coord=None, avlim=(0., 6.), rvlim=(1., 8.),
                      parallaxes=None, parallax_errors=None, Nr=100,
                      bins=(750, 300), span=None, smooth=0.01, rstate=None,
-                     verbose=False):
+                     verbose=False, device=None, device_out=False, object0=0):
     """Binned 2-D (distance, reddening) posteriors of a set of fitted objects, the input of
     the line-of-sight fits and of `plotting.dist_vs_red`; same arguments and return values as
-    reference `pdf.bin_pdfs_distred` (pdf.py:843-1113).  Host numpy: it acts on the few
-    hundred draws per object that `fit()` wrote.
+    reference `pdf.bin_pdfs_distred` (pdf.py:843-1113).  Host numpy by default: a loop over
+    the objects; `device=` runs the whole computation on a GPU (below).
 
     `data` is `(dists, reds, dreds)` as saved by `fit(save_dar_draws=True)`, each
     `(Nobj, Nsamps)`, or `(scales, avs, rvs, covs_sar)`, from which `Nr` realisations per draw
@@ -357,6 +357,20 @@ def bin_pdfs_distred(data, cdf=False, ebv=False, dist_type='distance_modulus',
     Returns `(binned_vals (Nobj, Nxbin, Nybin) float32, xedges, yedges)`; every object's
     histogram is divided by `Nsamps` and smoothed with a Gaussian whose width along the
     distance axis is capped by the object's parallax error.
+
+    `device=` (a torch device or "cuda"): binning, smoothing, the CDF and, for 4-tuple `data`,
+    the regeneration and re-weighting run on that GPU (`brutus_binpdf_saved` /
+    `brutus_binpdf_regen`), in chunks of objects whose workspace stays under about 1 GiB.
+    `device_out=True` leaves the result there, a float32 torch tensor `(Nobj, Nxbin, Nybin)`:
+    the copy to the host is 0.9 MB per object at the default bins.  The distance priors with a
+    device form are the Galactic prior (`lndistprior=None`, or a hook with `device_params`), a
+    `DistancePriorTable` replacing it, and one multiplying a base with `device_params`; any
+    other callable needs the host path.  With 4-tuple `data` `rstate` must be a
+    `rng.PhiloxRandomState`: only its `.seed` is read (its positions do not advance), object
+    `i` draws from the indexed stream of `utils.draw_sar_indexed` with the key
+    `(seed + object0 + i) mod 2**64`, so a batch may be binned in pieces (`object0` = index of
+    the piece's first object).  A covariance that is not positive definite raises ValueError;
+    realisations dropped for a non-finite ln prior or an exhausted rejection loop are warned of.
     """
     import sys
     from scipy.ndimage import gaussian_filter
@@ -404,6 +418,10 @@ def bin_pdfs_distred(data, cdf=False, ebv=False, dist_type='distance_modulus',
     xsmooth = sx * xspan if sx < 1 else sx * dx
     ysmooth = sy * yspan if sy < 1 else sy * dy
 
+    if device is not None:
+        return _bin_pdfs_device(data, regenerate, cdf, ebv, dist_type, lndistprior, coord, avlim,
+                                rvlim, parallaxes, parallax_errors, Nr, xbins, ybins, xsmooth,
+                                ysmooth, rstate, device, device_out, object0)
     binned = np.zeros((nobjs, xbin, ybin), dtype='float32')
     xedges, yedges = xbins, ybins
     for i in range(nobjs):
@@ -445,3 +463,171 @@ def bin_pdfs_distred(data, cdf=False, ebv=False, dist_type='distance_modulus',
         for i in range(nobjs):
             binned[i] = binned[i].cumsum(axis=0)
     return binned, xedges, yedges
+
+
+#: largest smoothing radius, in bins, of the device path (BP_MAXR of binpdf_kernels.hpp)
+_BINPDF_MAX_RADIUS = 2047
+#: bytes of workspace a chunk of objects may take on the device
+_BINPDF_WS_LIMIT = 1 << 30
+#: test hook: a list here receives `(scales, avs, rvs, weights)`, each (n, Nsamps, Nr), of every
+#: chunk of a regenerating device call (brutus_debug_binpdf_draws)
+_BINPDF_KEEP_DRAWS = None
+
+
+def _xsigma_bins(dist_type, parallaxes, parallax_errors, xsmooth, dx):
+    """Width of the Gaussian along the distance axis per object, in bins: `xsmooth` capped by
+    the parallax error -- the loop body of `bin_pdfs_distred`, vectorised with its NaN rules
+    (Python's `max(a, 1e-10)` keeps a NaN `a`; a cap that is not finite does not apply)."""
+    with warnings.catch_warnings(), np.errstate(all="ignore"):
+        warnings.simplefilter("ignore")
+        lo = parallaxes - parallax_errors
+        p1 = np.stack([parallaxes + parallax_errors, np.where(1e-10 > lo, 1e-10, lo)])
+        q = {'scale': p1 ** 2, 'parallax': p1, 'distance': 1. / p1,
+             'distance_modulus': 5. * np.log10(1. / p1)}[dist_type]
+        cap = np.abs(q[1] - q[0]) / 2.
+        xs = np.where(np.isfinite(cap), np.minimum(cap, xsmooth), xsmooth)
+    return xs / dx
+
+
+def _device_prior(lndistprior):
+    """`(prior_mode, table or None, parameters of the Galactic prior)` of a distance prior with
+    a device form; ValueError for any other callable."""
+    from .galprior import device_params
+    if isinstance(lndistprior, DistancePriorTable):
+        dp = lndistprior.device_params
+        if dp is not None:
+            return (1 if lndistprior.base is None else 2), lndistprior, dp()
+    elif getattr(lndistprior, "device_params", None) is not None:
+        return 0, None, lndistprior.device_params()
+    raise ValueError("bin_pdfs_distred: this `lndistprior` has no device form (the Galactic prior, "
+                     "a DistancePriorTable, or a table over a base with `device_params` do); "
+                     "the host path (device=None) handles any callable")
+
+
+def _bin_pdfs_device(data, regenerate, cdf, ebv, dist_type, lndistprior, coord, avlim, rvlim,
+                     parallaxes, parallax_errors, Nr, xbins, ybins, xsmooth, ysmooth, rstate,
+                     device, device_out, object0):
+    """The device form of `bin_pdfs_distred` (its arguments after the host's preparation of
+    edges and smoothing widths)."""
+    import ctypes as C
+    from .rng import PhiloxRandomState
+    nobjs, nsamps = np.shape(data[0])[:2]
+    nx, ny = len(xbins) - 1, len(ybins) - 1
+    mode, table, gp = 0, None, None
+    if regenerate:
+        if not isinstance(rstate, PhiloxRandomState):
+            raise ValueError("bin_pdfs_distred(device=) regenerates draws from the indexed Philox "
+                             "stream: `rstate` must be a rng.PhiloxRandomState (its seed keys the "
+                             "objects); the host path (device=None) takes any rstate")
+        mode, table, gp = _device_prior(lndistprior)
+        if mode != 1 and coord is None:
+            raise ValueError("`coord` must be passed if the default distance "
+                             "prior was used.")
+        if table is not None and table.l is not None and coord is None:
+            raise ValueError("`coord` must be passed to pick the sightlines of the distance table")
+    dx, dy = xbins[1] - xbins[0], ybins[1] - ybins[0]
+    xsig = np.ascontiguousarray(_xsigma_bins(dist_type, parallaxes, parallax_errors, xsmooth, dx),
+                                dtype=np.float64)
+    ysig = float(ysmooth / dy)
+    if not (ysig >= 0. and 4. * ysig + 0.5 < _BINPDF_MAX_RADIUS + 1) or \
+            not np.all((xsig >= 0.) & (4. * xsig + 0.5 < _BINPDF_MAX_RADIUS + 1)):
+        raise ValueError("bin_pdfs_distred(device=): smoothing widths must be >= 0 with a radius of "
+                         "at most %d bins; the host path (device=None) has no such limit"
+                         % _BINPDF_MAX_RADIUS)
+    if nsamps > 4096:
+        raise ValueError("bin_pdfs_distred(device=): at most 4096 draws per object")
+
+    import torch
+    from . import _lib
+    L = _lib.lib()
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise ValueError("bin_pdfs_distred: `device` must be a GPU")
+    bp = _lib.BinpdfParams()
+    bp.nx, bp.ny = nx, ny
+    bp.dist_type = ('scale', 'parallax', 'distance', 'distance_modulus').index(dist_type)
+    bp.ebv, bp.cdf = (1 if ebv else 0), (1 if cdf else 0)
+    bp.nr = int(Nr) if regenerate else 0
+    bp.prior_mode, bp.max_attempts = mode, 256
+    bp.avlim[:] = [float(avlim[0]), float(avlim[1])]
+    bp.rvlim[:] = [float(rvlim[0]), float(rvlim[1])]
+    bp.ysigma_bins = ysig
+    bp.seed = rstate.seed if regenerate else 0
+    pp = None
+    if regenerate:
+        pp = _lib.PostParams()
+        for k, val in gp.items():
+            if isinstance(val, tuple):
+                getattr(pp, k)[:] = list(val)
+            else:
+                setattr(pp, k, val)
+        crd = (np.zeros((nobjs, 2)) if coord is None
+               else np.ascontiguousarray(coord, dtype=np.float64).reshape(nobjs, 2))
+
+    # objects per call: the workspace of a chunk stays under about 1 GiB
+    nr_ws = bp.nr
+    one = L.brutus_binpdf_workspace_bytes(1, nx, ny, nsamps, nr_ws)
+    if one == 0:
+        raise ValueError("bin_pdfs_distred(device=): sizes outside the device path's limits "
+                         "(nx, ny <= 65536, nx ny <= 2**28, Nsamps Nr <= 2**24)")
+    chunk = int(max(1, min(nobjs, 65535, _BINPDF_WS_LIMIT // one)))
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream().cuda_stream
+
+        def up(a):
+            return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
+
+        ws_bytes = L.brutus_binpdf_workspace_bytes(chunk, nx, ny, nsamps, nr_ws)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        t_xe, t_ye = up(xbins), up(ybins)
+        if device_out:
+            out = torch.empty((nobjs, nx, ny), dtype=torch.float32, device=dev)
+        else:
+            out = np.empty((nobjs, nx, ny), dtype=np.float32)
+            t_out = torch.empty((chunk, nx, ny), dtype=torch.float32, device=dev)
+        status = np.zeros((nobjs, 3), dtype=np.int32)
+        for a in range(0, nobjs, chunk):
+            b = min(nobjs, a + chunk)
+            dst = out[a:b] if device_out else t_out[:b - a]
+            t_xs = up(xsig[a:b])
+            if not regenerate:
+                t = [up(np.asarray(data[q])[a:b]) for q in range(3 if ebv else 2)]
+                _lib.check(L.brutus_binpdf_saved(
+                    b - a, nsamps, t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr() if ebv else None,
+                    t_xe.data_ptr(), t_ye.data_ptr(), t_xs.data_ptr(), C.byref(bp), dst.data_ptr(),
+                    ws.data_ptr(), ws_bytes, stream))
+            else:
+                t = [up(np.asarray(data[q])[a:b]) for q in range(4)]
+                if tuple(t[3].shape) != (b - a, nsamps, 3, 3):
+                    raise ValueError("covs_sar must be (Nobj, Nsamps, 3, 3)")
+                t_par, t_perr, t_crd = up(parallaxes[a:b]), up(parallax_errors[a:b]), up(crd[a:b])
+                t_tab = up(dist_tables(table, crd[a:b])) if table is not None else None
+                t_st = torch.empty((b - a, 3), dtype=torch.int32, device=dev)
+                bp.object0 = int(object0) + a
+                _lib.check(L.brutus_binpdf_regen(
+                    b - a, nsamps, t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr(), t[3].data_ptr(),
+                    t_par.data_ptr(), t_perr.data_ptr(), t_crd.data_ptr(), C.byref(pp),
+                    t_tab.data_ptr() if table is not None else None,
+                    table.dist.size if table is not None else 0, t_xe.data_ptr(), t_ye.data_ptr(),
+                    t_xs.data_ptr(), C.byref(bp), t_st.data_ptr(), dst.data_ptr(), ws.data_ptr(),
+                    ws_bytes, stream))
+                status[a:b] = t_st.cpu().numpy()
+                if _BINPDF_KEEP_DRAWS is not None:
+                    kept = [torch.empty((b - a, nsamps, bp.nr), dtype=torch.float64, device=dev)
+                            for _ in range(4)]
+                    _lib.check(L.brutus_debug_binpdf_draws(b - a, nsamps, bp.nr, ws.data_ptr(),
+                                                           *[k.data_ptr() for k in kept], stream))
+                    _BINPDF_KEEP_DRAWS.append(tuple(k.cpu().numpy() for k in kept))
+            if not device_out:
+                out[a:b] = dst.cpu().numpy()
+        if device_out:
+            torch.cuda.current_stream().synchronize()
+    bad = np.nonzero(status[:, 0])[0]
+    if bad.size:
+        raise ValueError("bin_pdfs_distred: the covariance of a draw is not positive definite for "
+                         "object(s) %s" % ", ".join(str(int(i)) for i in bad))
+    if status[:, 1:].any():
+        warnings.warn("bin_pdfs_distred: %d realisation(s) with a ln prior that is not finite and %d "
+                      "that found no draw inside the bounds carry no weight"
+                      % (int(status[:, 2].sum()), int(status[:, 1].sum())), RuntimeWarning)
+    return out, xbins, ybins

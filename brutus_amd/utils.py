@@ -13,7 +13,7 @@ import numpy as np
 __all__ = ["_function_wrapper", "_adjoint3", "_inverse_transpose3", "_inverse3", "_dot3",
            "_isPSD", "_chisquare_logpdf", "_truncnorm_pdf", "_truncnorm_logpdf", "_get_seds",
            "fetch_isos", "fetch_tracks", "fetch_dustmaps", "fetch_grids", "fetch_offsets",
-           "fetch_nns", "load_models", "load_offsets", "quantile", "draw_sar",
+           "fetch_nns", "load_models", "load_offsets", "quantile", "draw_sar", "draw_sar_indexed",
            "sample_multivariate_normal", "magnitude", "inv_magnitude", "luptitude",
            "inv_luptitude", "add_mag", "get_seds", "phot_loglike", "photometric_offsets"]
 
@@ -226,6 +226,48 @@ def draw_sar(scales, avs, rvs, covs_sar, ndraws=500, avlim=(0., 6.),
             have += int(ok.sum())
         out[:, i, :] = np.concatenate(kept, axis=1)[:, :ndraws]
     return out[0], out[1], out[2]
+
+
+def draw_sar_indexed(scales, avs, rvs, covs_sar, ndraws=500, avlim=(0., 6.),
+                     rvlim=(1., 8.), seed=0, max_attempts=256):
+    """`draw_sar` with a stream a device can walk in parallel: the specification of the
+    regenerating form of `pdf.bin_pdfs_distred(device=)` (kernel `k_binpdf_regen`), which
+    equals this function deviate for deviate.
+
+    `draw_sar` consumes its `rstate` sequentially (batches of `ndraws`, redrawn until enough
+    fall inside the bounds), so the position of a deviate depends on every rejection before
+    it.  Here slot (draw `k`, realisation `r`) of the `Nsamps = len(scales)` draws owns its
+    attempts: the three normals of attempt `t` are
+
+        z_c = rng.philox_normal(seed, 3 * ((t * Nsamps + k) * ndraws + r) + c),  c = 0, 1, 2
+
+    the candidate is `mean_k + L_k z` with `L_k = cholesky(covs_sar[k])` (lower), and the slot
+    takes its first attempt inside `scale >= 0, avlim, rvlim`.  Per-slot rejection gives the
+    same i.i.d. truncated normal as the batch rejection of `draw_sar`.  `seed` is the key of
+    ONE object (`bin_pdfs_distred` uses `(rstate.seed + object0 + i) mod 2**64` for object
+    `i`).  A slot none of whose `max_attempts` attempts falls inside holds NaN.
+
+    Returns `(sdraws, adraws, rdraws, nexhausted)`, the arrays `(Nsamps, ndraws)`.
+    """
+    from .rng import philox_normal
+    mean = np.stack([np.asarray(scales, dtype=np.float64), np.asarray(avs, dtype=np.float64),
+                     np.asarray(rvs, dtype=np.float64)], axis=1)
+    n, nr = mean.shape[0], int(ndraws)
+    L = np.linalg.cholesky(np.asarray(covs_sar, dtype=np.float64).reshape(n, 3, 3))
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    out = np.full((3, n, nr), np.nan)
+    kk, rr = (a.ravel() for a in np.meshgrid(np.arange(n), np.arange(nr), indexing="ij"))
+    for t in range(int(max_attempts)):
+        if kk.size == 0:
+            break
+        j = np.uint64(3) * ((np.uint64(t) * np.uint64(n) + kk.astype(np.uint64)) * np.uint64(nr)
+                            + rr.astype(np.uint64))
+        z = philox_normal(seed, j[:, None] + np.arange(3, dtype=np.uint64))
+        s, a, r = (mean[kk] + np.matmul(L[kk], z[:, :, None])[:, :, 0]).T
+        ok = (s >= 0.) & (a >= avlim[0]) & (a <= avlim[1]) & (r >= rvlim[0]) & (r <= rvlim[1])
+        out[0, kk[ok], rr[ok]], out[1, kk[ok], rr[ok]], out[2, kk[ok], rr[ok]] = s[ok], a[ok], r[ok]
+        kk, rr = kk[~ok], rr[~ok]
+    return out[0], out[1], out[2], int(kk.size)
 
 
 def phot_loglike(data, data_err, data_mask, models, dim_prior=True):

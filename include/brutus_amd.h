@@ -438,6 +438,69 @@ int brutus_offsets_bootstrap(int band, int nobj, int nsamps, int nfilt, int n, i
                              void *d_workspace, size_t workspace_bytes, double *d_meds,
                              void *stream);
 
+/* ---- binned (distance, reddening) posteriors: pdf.bin_pdfs_distred on the device ----------
+ * One call bins, smooths and (cdf) accumulates the posteriors of nobj objects into
+ * d_out (nobj, nx, ny) f32, row-major, y fastest.  Additive entry points: BRUTUS_ABI_VERSION
+ * stays.
+ *   nx, ny         bins along the distance axis / the reddening axis
+ *   dist_type      what the distance axis holds: 0 scale 1/d^2, 1 parallax 1/d, 2 distance d,
+ *                  3 distance modulus 5 log10(d) + 10
+ *   ebv            != 0: the reddening axis holds Av / Rv
+ *   cdf            != 0: cumulative sum along the distance axis (float32, sequential)
+ *   nr, prior_mode, max_attempts, avlim, rvlim, seed, object0: the regenerating form only.
+ *                  prior_mode 0: Galactic prior, 1: the distance table replaces it, 2: the
+ *                  table multiplies it.  1 <= max_attempts <= 65536 bounds the rejection loop.
+ *   ysigma_bins    width of the Gaussian along the reddening axis, in bins (>= 0, finite)
+ * Binning is numpy.histogram2d's with explicit edges (d_xedges (nx + 1), d_yedges (ny + 1) f64,
+ * increasing; the last bin is closed on the right; values outside and NaN are dropped),
+ * divided by nsamps and rounded once to float32; smoothing is scipy.ndimage.gaussian_filter's
+ * (radius int(4 sigma + 0.5), boundary `reflect`, float64 accumulation, float32 between the
+ * axes, an axis with sigma <= 1e-15 skipped) with the per-object width d_xsigma_bins (nobj) f64
+ * along the distance axis.  A radius above 2047 bins is refused (y) / clamped (x: the caller
+ * checks the array it computed).  Sums are integers (counts; weights in 2^-50 fixed point), so
+ * the result does not depend on the order the device meets the draws in.
+ * Limits: 1 <= nobj <= 65535, 1 <= nx, ny <= 65536, nx ny <= 2^28, 1 <= nsamps <= 4096,
+ * 1 <= nr <= 65536, nsamps nr <= 2^24; checked, like every pointer, before any HIP call. */
+typedef struct brutus_binpdf_params {
+    int32_t nx, ny, dist_type, ebv, cdf, nr, prior_mode, max_attempts;
+    double avlim[2], rvlim[2];
+    double ysigma_bins;
+    uint64_t seed;
+    int64_t object0;
+} brutus_binpdf_params;
+
+/* Bytes of d_workspace for a call of either form (nr = 0: the saved-draws form); 0 = bad sizes. */
+size_t brutus_binpdf_workspace_bytes(int nobj, int nx, int ny, int nsamps, int nr);
+
+/* Saved draws: d_dist, d_red, d_dred (nobj, nsamps) f64 = distance [kpc], Av, Rv of every draw
+ * (d_dred may be NULL unless params->ebv). */
+int brutus_binpdf_saved(int nobj, int nsamps, const double *d_dist, const double *d_red,
+                        const double *d_dred, const double *d_xedges, const double *d_yedges,
+                        const double *d_xsigma_bins, const brutus_binpdf_params *params,
+                        float *d_out, void *d_workspace, size_t workspace_bytes, void *stream);
+
+/* Regenerated draws: around every draw (d_scale, d_av, d_rv (nobj, nsamps) f64 with covariance
+ * d_cov (nobj, nsamps, 9) f64, row-major 3x3) params->nr realisations are drawn from the
+ * truncated normal (scale >= 0, avlim, rvlim) with the indexed stream of
+ * brutus_amd/utils.py `draw_sar_indexed` (key seed + object0 + object; normals
+ * 3 ((t nsamps + k) nr + r) + c of draw k, realisation r, attempt t), weighted by the
+ * distance prior at d = 1 / sqrt(scale) and the parallax likelihood (d_par, d_parerr (nobj),
+ * NaN = none; either may be NULL), normalised per draw, and binned with those weights.
+ *   d_coord (nobj, 2) f64 Galactic l, b [deg]; gal: the Galactic prior's constants (label
+ *   terms are not evaluated; required in every mode); d_dtab (nobj, 2, nd) f64 the distance
+ *   tables as for brutus_post_set_dist_table, NULL with prior_mode 0.
+ *   d_status (nobj, 3) i32 out: [0] != 0: a covariance of the object is not positive definite
+ *   (its plane is not meaningful); [1] slots that exhausted max_attempts; [2] realisations
+ *   whose ln prior was not finite.  Slots of [1] and [2] carry weight 0. */
+int brutus_binpdf_regen(int nobj, int nsamps, const double *d_scale, const double *d_av,
+                        const double *d_rv, const double *d_cov, const double *d_par,
+                        const double *d_parerr, const double *d_coord,
+                        const brutus_post_params *gal, const double *d_dtab, int nd,
+                        const double *d_xedges, const double *d_yedges,
+                        const double *d_xsigma_bins, const brutus_binpdf_params *params,
+                        int32_t *d_status, float *d_out, void *d_workspace,
+                        size_t workspace_bytes, void *stream);
+
 
 /* Name and average duration (HIP events on `stream`) of the kernels launched
  * by the last *_batch call; used by bench.py for the roofline line. */

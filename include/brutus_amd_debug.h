@@ -108,6 +108,13 @@ int brutus_debug_pre32_time(void *d_workspace, size_t workspace_bytes, const flo
                             int64_t nmodel, int nfilt, int nstar, const brutus_params *params,
                             int form, int reps, float *h_ms, void *stream);
 
+/* Test hook: the realisations the last brutus_binpdf_regen call with these sizes left in its
+ * workspace: d_scale, d_av, d_rv, d_weight (nobj, nsamps, nr) f64 = the draws (NaN in a slot
+ * that exhausted its attempts) and their weights, normalised per draw.  Compared with
+ * brutus_amd/utils.py `draw_sar_indexed` by tests/test_gpu_binpdf.py.  Synchronises the stream. */
+int brutus_debug_binpdf_draws(int nobj, int nsamps, int nr, const void *d_workspace,
+                              double *d_scale, double *d_av, double *d_rv, double *d_weight,
+                              void *stream);
 
 #ifdef __cplusplus
 }

@@ -549,6 +549,41 @@ def gen_bin_pdfs():
     print("wrote bin_pdfs.npz")
 
 
+def bin_pdfs_edge_cases():
+    """Keywords of the saved-draw calls of `bin_pdfs_edge.npz`; tests/test_gpu_binpdf.py repeats
+    them (`EDGE_CASES`) and checks its names against the fixture's."""
+    return [
+        ("dm_small", dict(bins=(8, 5), smooth=(3., 2.))),
+        ("par_ebv", dict(dist_type="parallax", ebv=True, bins=(8, 5), smooth=(3., 2.))),
+        ("scale_cdf", dict(dist_type="scale", cdf=True, bins=(9, 7), smooth=(0.2, 1.))),
+        ("dist_span", dict(dist_type="distance", span=((0., 6.), (0.5, 3.)), bins=(10, 6), smooth=1.5)),
+    ]
+
+
+def gen_bin_pdfs_edge():
+    """Saved-draw calls of `pdf.bin_pdfs_distred` at shapes where a device implementation can go
+    wrong: 70 draws (no multiple of a wave), fewer bins than the smoothing radius (the
+    reflection repeats), one parallax-capped object beside two uncapped, Av clipped onto both
+    limits, draws outside the span, one draw exactly on an interior x edge and one on the last."""
+    rng = np.random.RandomState(2024)
+    nobj, ns = 3, 70
+    dists = 10. ** rng.normal(0.2, 0.25, size=(nobj, ns))
+    reds = np.clip(rng.normal(2.5, 2.5, size=(nobj, ns)), 0., 6.)
+    dreds = rng.normal(3.3, 0.2, size=(nobj, ns))
+    dists[0, 3], dists[1, 5] = 1.25, 3.           # edges of linspace(0.5, 3., 11)
+    dists[2, 0], dists[2, 1] = 0.3, 4.5           # outside that span
+    par, perr = np.array([1., np.nan, .5]), np.array([.01, .1, np.nan])
+    res = dict(dists=dists, reds=reds, dreds=dreds, parallaxes=par, parallax_errors=perr,
+               names=np.array([c[0] for c in bin_pdfs_edge_cases()]))
+    assert (reds == 0.).sum() >= 3 and (reds == 6.).sum() >= 3
+    for name, kw in bin_pdfs_edge_cases():
+        b, xe, ye = P.bin_pdfs_distred((dists.copy(), reds.copy(), dreds.copy()), parallaxes=par,
+                                       parallax_errors=perr, **kw)
+        res["saved_%s" % name], res["saved_%s_x" % name], res["saved_%s_y" % name] = b, xe, ye
+    np.savez_compressed(os.path.join(OUT, "bin_pdfs_edge.npz"), **res)
+    print("wrote bin_pdfs_edge.npz")
+
+
 def gen_utils_misc():
     """The small helpers of `brutus.utils.__all__` (utils.py:43-127, 179-347, 718-762, 978-1086)."""
     rng = np.random.RandomState(12)
@@ -687,6 +722,8 @@ if __name__ == "__main__":
                              "cluster"]
     if "binpdfs" in which:
         gen_bin_pdfs()
+    if "binpdfsedge" in which:
+        gen_bin_pdfs_edge()
     if "utilsmisc" in which:
         gen_utils_misc()
     if "init" in which:
