@@ -20,15 +20,17 @@ ever sees the models that survived the device-side cut.
 
 There is no CPU fallback: without the HIP library or a GPU these functions raise.
 """
+import collections
+import os
 import sys
 import time
 import warnings
 
-import os
-
 import numpy as np
 
 from . import _lib
+from . import pdf as _pdf
+from .rng import PhiloxRandomState, numpy_stream, state_to_words, words_to_state
 from .pdf import (imf_lnprior, parallax_lnprior, parallax_to_scale, ps1_MrLF_lnprior,
                   scale_parallax_lnprior)
 from .utils import _inverse3, magnitude, sample_multivariate_normal
@@ -218,6 +220,21 @@ class _RowBlock(object):
         self.start, self.n, self.arrays = start, n, arrays
 
 
+#: one device `lnpost` call: `PostParams`, the numpy generator states it advances (uint32
+#: (nstream, 628); None: Philox stream), the batch's dust tables and distance tables or None
+_PostCall = collections.namedtuple("_PostCall", "pp np_states dust dtab")
+#: what a post call reads of a batch: its `Records` and per-object device tensors
+_PostInputs = collections.namedtuple("_PostInputs", "rec coords parallax parallax_err")
+#: what a post call returns (include/brutus_amd.h: `brutus_post_batch`; `nbase`: Philox form)
+_PostResult = collections.namedtuple("_PostResult", "out_idx out_vals star_out flags nbase")
+
+
+class _PostSlot(object):
+    """Buffers of one pipeline slot of the device `lnpost` calls and, between the two phases
+    of `brutus_post_batch_numpy_phase`, the batch phase 1 left in it."""
+    ws = zbuf = inputs = out = run = hook = None
+
+
 class _Engine(object):
     """Owns the device workspace and drives the *_batch entry points."""
 
@@ -241,6 +258,11 @@ class _Engine(object):
         self._ws = None
         self._ws_batch = 0
         self.regrown = 0       # record-buffer growths (each repeats a batch)
+        self._rec_bufs = None  # (idx, slot, vals) record buffers kept between calls
+        self._fg_planes = None # full-grid route: the eleven float64 planes of a chunk
+        self._cut_ws = None    # ... and the workspace of `brutus_cut_batch`
+        self._post_slots = {}  # pipeline slot -> `_PostSlot` of the device `lnpost` calls
+        self._zbuf_gb = None   # size the pipeline's first normal buffer was given
 
     def _workspace(self, nstar):
         torch = self.torch
@@ -334,7 +356,7 @@ class _Engine(object):
             return self._fit_batch_device_full_grid(f, e, m, p, pe, has_par, params, ext=ext)
         ws = self._workspace(S)
         if buffers is None:
-            buffers = getattr(self, "_rec_bufs", None)
+            buffers = self._rec_bufs
         if buffers is None:
             buffers = self._record_buffers(max(1 << 20, (S * g.nmodel) // 8))
         off = torch.empty(S + 1, dtype=torch.int64, device=g.device)
@@ -355,14 +377,14 @@ class _Engine(object):
             if rc == -2 and grow and b"record buffer too small" in L.brutus_last_error():
                 # the flux phase keeps its results in the record planes themselves, so a
                 # batch that does not fit is redone as a whole
-                self.regrown = getattr(self, "regrown", 0) + 1
+                self.regrown += 1
                 buffers = idx = slot = vals = None
                 self._rec_bufs = None
                 buffers = self._record_buffers(int(counts[2] * 1.25) + 4096)
                 continue
             _lib.check(rc)
             break
-        if buffers is not None and (getattr(self, "_rec_bufs", None) is None
+        if buffers is not None and (self._rec_bufs is None
                                     or self._rec_bufs[0].numel() <= capacity):
             self._rec_bufs = buffers
         rv_const = (float(params.rv_gauss[0])
@@ -403,7 +425,7 @@ class _Engine(object):
             n_ext = int(labels_t.shape[0])
             if ext_par.shape != (n_ext, S, 3) or labels_t.shape[1] != g.nmodel:
                 raise ValueError("`ext` does not match the batch or the grid")
-        buffers = getattr(self, "_rec_bufs", None)
+        buffers = self._rec_bufs
         if buffers is None:
             buffers = self._record_buffers(max(1 << 20, (S * g.nmodel) // 8))
         base = 0
@@ -424,13 +446,13 @@ class _Engine(object):
             return new
 
         with torch.cuda.device(dev):
-            fg = getattr(self, "_fg_planes", None)
+            fg = self._fg_planes
             if fg is None or fg.shape[1] < chunk:
                 self._fg_planes = fg = None
                 self._fg_planes = fg = torch.empty((_lib.NVALS, chunk, g.nmodel),
                                                    dtype=torch.float64, device=dev)
             nbytes = L.brutus_cut_workspace_bytes(g.nmodel, chunk)
-            cws = getattr(self, "_cut_ws", None)
+            cws = self._cut_ws
             if cws is None or cws.numel() < nbytes:
                 self._cut_ws = cws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
             for a in range(0, S, chunk):
@@ -482,7 +504,7 @@ class _Engine(object):
                     _lib.check(rc)
                     break
                 base = int(counts[1])
-        if getattr(self, "_rec_bufs", None) is None or self._rec_bufs[0].numel() <= capacity:
+        if self._rec_bufs is None or self._rec_bufs[0].numel() <= capacity:
             self._rec_bufs = buffers
         return (Records(idx, slot, vals, off, None, np.array([base, base, base], dtype=np.int64)),
                 ndim, k1, k2)
@@ -493,152 +515,135 @@ class _Engine(object):
         rec, ndim, k1, k2 = self.fit_batch_device(f, e, m, p, pe, has_par, params, ext=ext)
         return rec, rec.off.cpu().numpy(), ndim.cpu().numpy(), k1, k2
 
+    def _post_slot(self, slot, nbytes, zbuf_frac=None, alike=False):
+        """Pipeline slot `slot` with a workspace of at least `nbytes` and (`zbuf_frac` given) a
+        normal buffer; a new one takes that fraction of the free device memory, or what
+        BRUTUS_AMD_ZBUF_GB says.  `alike`: both slots of the pipeline get the size the first
+        one was given."""
+        torch, dev = self.torch, self.grid.device
+        ctx = self._post_slots.setdefault(slot, _PostSlot())
+        if ctx.ws is None or ctx.ws.numel() < nbytes:
+            ctx.ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        if zbuf_frac is not None and ctx.zbuf is None:
+            gb = self._zbuf_gb if alike else None
+            if gb is None:
+                # normals of one group of objects; a 128-object batch of the bench workload
+                # (1.4e5 kept models x 150 normals each) needs ~22 GB as a flat array, ~29 GB
+                # as the pairs of one stream walk (16 B per generated slot), + 1/8 scratch
+                free = torch.cuda.mem_get_info(dev)[0] / 2 ** 30
+                gb = float(os.environ.get("BRUTUS_AMD_ZBUF_GB", min(64., max(1., zbuf_frac * free))))
+                if alike:
+                    self._zbuf_gb = gb
+            ctx.zbuf = torch.empty(int(gb * 2 ** 30) // 8, dtype=torch.float64, device=dev)
+        return ctx
+
+    def _post_inputs(self, rec, coords, parallax, parallax_err):
+        """What a post call reads of one batch, on the device (`_PostInputs`)."""
+        torch, dev = self.torch, self.grid.device
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
+        return _PostInputs(rec, up(coords), up(parallax), up(parallax_err))
+
+    def _post_outputs(self, nstar, ndraws, nbase=None):
+        """Fresh outputs of one post call: draws on the device, per-object values on the host."""
+        torch, dev = self.torch, self.grid.device
+        return _PostResult(torch.empty((nstar, ndraws), dtype=torch.int32, device=dev),
+                           torch.empty((nstar, ndraws, 17), dtype=torch.float64, device=dev),
+                           np.zeros((nstar, 4)), np.zeros(nstar, dtype=np.int32), nbase)
+
+    @staticmethod
+    def _post_leading_args(nstar, inp, statics, pp, ws, out):
+        """The 19 arguments the three `brutus_post_batch*` entry points begin with."""
+        lnprior, feh, loga = statics
+        rec = inp.rec
+        return (nstar, rec.capacity, rec.idx.data_ptr(), rec.slot.data_ptr(), rec.vals.data_ptr(),
+                rec.off.data_ptr(), lnprior.data_ptr(),
+                feh.data_ptr() if feh is not None else None,
+                loga.data_ptr() if loga is not None else None, inp.coords.data_ptr(),
+                inp.parallax.data_ptr(), inp.parallax_err.data_ptr(), pp, ws.data_ptr(),
+                ws.numel(), out.out_idx.data_ptr(), out.out_vals.data_ptr(),
+                out.star_out.ctypes.data, out.flags.ctypes.data)
+
     def post_batch_device(self, rec, nstar, statics,
                           coords, parallax, parallax_err, pp, np_states=None, dust=None,
                           dtab=None):
         """`brutus_post_batch` on device-resident `Records`.  `statics` =
         (lnprior, feh, loga) device tensors (feh / loga may be None).
         `np_states` (uint32 (nstream, 628), advanced in place): draw from numpy's own
-        legacy stream(s) instead (`brutus_post_batch_numpy`)."""
-        torch, L, g = self.torch, self.L, self.grid
+        legacy stream(s) instead (`brutus_post_batch_numpy`).  Returns a `_PostResult`."""
+        torch, L = self.torch, self.L
         rec.fill_rv()
-        sel_idx, rec_slot, sel_vals, sel_off = rec.idx, rec.slot, rec.vals, rec.off
-        cap = rec.capacity
-        nbytes = L.brutus_post_workspace_bytes(nstar, cap, pp.nmc)
-        slot0 = self.__dict__.setdefault("_post_slots", {}).setdefault(0, {})
         # (one set of buffers with pipeline slot 0: the two forms never run at the same time)
-        if slot0.get("ws") is None or slot0["ws"].numel() < nbytes:
-            slot0["ws"] = torch.empty(nbytes, dtype=torch.uint8, device=g.device)
-        self._post_ws = slot0["ws"]
-        dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(g.device)
-        t_coords, t_par, t_perr = dev(coords), dev(parallax), dev(parallax_err)
-        out_idx = torch.empty((nstar, pp.ndraws), dtype=torch.int32, device=g.device)
-        out_vals = torch.empty((nstar, pp.ndraws, 17), dtype=torch.float64,
-                               device=g.device)
-        star_out = np.zeros((nstar, 4))
-        flags = np.zeros(nstar, dtype=np.int32)
-        nbase = np.zeros(nstar + 1, dtype=np.uint64)
-        lnprior, feh, loga = statics
-        if np_states is not None:
-            assert np_states.dtype == np.uint32 and np_states.flags.c_contiguous
-            while True:
-                zb = slot0.get("zbuf")
-                if zb is None:
-                    import os
-                    # normals of one group of objects; a 128-object batch of the bench
-                    # workload (1.4e5 kept models x 150 normals each) needs ~22 GB as a flat
-                    # array, ~29 GB as the pairs of one stream walk (16 B per generated
-                    # slot), + 1/8 scratch
-                    free = torch.cuda.mem_get_info(g.device)[0] / 2 ** 30
-                    gb = float(os.environ.get("BRUTUS_AMD_ZBUF_GB", min(64., max(1., 0.25 * free))))
-                    zb = slot0["zbuf"] = torch.empty(int(gb * 2 ** 30) // 8, dtype=torch.float64,
-                                                     device=g.device)
-                self._set_dust(dust)          # one-shot context: before EVERY (re)try
-                self._set_dist_table(dtab)
-                rc = L.brutus_post_batch_numpy(
-                    nstar, cap, sel_idx.data_ptr(), rec_slot.data_ptr(), sel_vals.data_ptr(),
-                    sel_off.data_ptr(),
-                    lnprior.data_ptr(), feh.data_ptr() if feh is not None else None,
-                    loga.data_ptr() if loga is not None else None, t_coords.data_ptr(),
-                    t_par.data_ptr(), t_perr.data_ptr(), pp, self._post_ws.data_ptr(),
-                    self._post_ws.numel(), out_idx.data_ptr(), out_vals.data_ptr(),
-                    star_out.ctypes.data, flags.ctypes.data, int(np_states.shape[0]),
-                    np_states.ctypes.data, zb.data_ptr(), zb.numel(), _stream_ptr(torch))
+        ctx = self._post_slot(0, L.brutus_post_workspace_bytes(nstar, rec.capacity, pp.nmc),
+                              None if np_states is None else 0.25)
+        inp = self._post_inputs(rec, coords, parallax, parallax_err)
+        out = self._post_outputs(nstar, pp.ndraws, np.zeros(nstar + 1, dtype=np.uint64))
+        lead = self._post_leading_args(nstar, inp, statics, pp, ctx.ws, out)
+        assert np_states is None or (np_states.dtype == np.uint32 and np_states.flags.c_contiguous)
+        while True:
+            self._set_tables(dust, dtab)          # one-shot context: before EVERY (re)try
+            if np_states is None:
+                rc = L.brutus_post_batch(*lead + (out.nbase.ctypes.data, _stream_ptr(torch)))
+            else:
+                zb = ctx.zbuf
+                rc = L.brutus_post_batch_numpy(*lead + (
+                    int(np_states.shape[0]), np_states.ctypes.data, zb.data_ptr(), zb.numel(),
+                    _stream_ptr(torch)))
                 if rc == -2 and b"normal buffer too small" in L.brutus_last_error() \
                         and zb.numel() * 8 < 96 * 2 ** 30:
                     # one object alone exceeds the buffer (the states were not touched): grow
                     n = zb.numel() * 2
-                    slot0["zbuf"] = zb = None
+                    ctx.zbuf = zb = None
                     torch.cuda.empty_cache()
-                    slot0["zbuf"] = torch.empty(n, dtype=torch.float64, device=g.device)
+                    ctx.zbuf = torch.empty(n, dtype=torch.float64, device=self.grid.device)
                     continue
-                _lib.check(rc)
-                break
-            return (out_idx.cpu().numpy(), out_vals.cpu().numpy(), star_out, flags, nbase)
-        self._set_dust(dust)
-        self._set_dist_table(dtab)
-        _lib.check(L.brutus_post_batch(
-            nstar, cap, sel_idx.data_ptr(), rec_slot.data_ptr(), sel_vals.data_ptr(),
-            sel_off.data_ptr(),
-            lnprior.data_ptr(), feh.data_ptr() if feh is not None else None,
-            loga.data_ptr() if loga is not None else None, t_coords.data_ptr(),
-            t_par.data_ptr(), t_perr.data_ptr(), pp, self._post_ws.data_ptr(),
-            self._post_ws.numel(), out_idx.data_ptr(), out_vals.data_ptr(),
-            star_out.ctypes.data, flags.ctypes.data, nbase.ctypes.data,
-            _stream_ptr(torch)))
-        return (out_idx.cpu().numpy(), out_vals.cpu().numpy(), star_out, flags,
-                nbase)
+            _lib.check(rc)
+            break
+        return out._replace(out_idx=out.out_idx.cpu().numpy(), out_vals=out.out_vals.cpu().numpy())
 
-    # ---- brutus_post_batch_numpy in two halves (pipelined across batches) --------------
-    def _set_dust(self, dust):
-        """Line-of-sight dust context of the NEXT post call of this thread
-        (`brutus_post_set_dust` is one-shot: it has to precede every call and every retry).
-        `dust` = (t_los, t_ok) device tensors or None."""
+    def _set_tables(self, dust, dtab):
+        """Line-of-sight dust context and tabulated distance prior of the NEXT post call of this
+        thread (`brutus_post_set_dust`, `brutus_post_set_dist_table` are one-shot: they have to
+        precede every call and every retry; a phase-2 call reads the distance table too).
+        `dust` = (t_los, t_ok) device tensors, `dtab` = (t_tab (nstar, 2, nd) device tensor,
+        replace flag), or None."""
         if dust is not None:
             t_los, t_ok = dust
             _lib.check(self.L.brutus_post_set_dust(t_los.data_ptr(), t_ok.data_ptr(),
                                                    int(t_los.shape[2]), 0., 1., 1., 0.2))
-
-    def _set_dist_table(self, dtab):
-        """Tabulated distance prior of the NEXT post call of this thread
-        (`brutus_post_set_dist_table`, one-shot like the dust context; a phase-2 call reads it
-        too).  `dtab` = (t_tab (nstar, 2, nd) device tensor, replace flag) or None."""
         if dtab is not None:
             t_tab, replace = dtab
             _lib.check(self.L.brutus_post_set_dist_table(t_tab.data_ptr(), int(t_tab.shape[2]),
                                                          1 if replace else 0))
 
-    def post_numpy_begin(self, slot, rec, nstar, statics, coords,
-                         parallax, parallax_err, pp, np_states, dust=None, after_jump=None,
-                         dtab=None):
+    # ---- brutus_post_batch_numpy in two halves (pipelined across batches) --------------
+    def post_numpy_begin(self, slot, rec, nstar, statics, coords, parallax, parallax_err, call,
+                         after_jump=None):
         """Phase 1 of `brutus_post_batch_numpy_phase` in pipeline slot `slot` (own
-        workspace, normal buffer and outputs): cuts, covariances, stream walk; `np_states`
-        is advanced.  False if the objects do not fit the slot's buffer as one group
-        (nothing consumed: use `post_batch_device`).  `after_jump()` is called exactly once
-        from inside the call, when the walk's jump-ahead windows are complete
-        (`brutus_post_set_after_jump`) -- or before this method returns, whatever happens."""
-        import os
-        torch, L, g = self.torch, self.L, self.grid
-        ctxs = self.__dict__.setdefault("_post_slots", {})
-        ctx = ctxs.setdefault(slot, {})
+        workspace, normal buffer and outputs) for the `_PostCall` `call`: cuts, covariances,
+        stream walk; `call.np_states` is advanced.  False if the objects do not fit the slot's
+        buffer as one group (nothing consumed: use `post_batch_device`).  `after_jump()` is
+        called exactly once from inside the call, when the walk's jump-ahead windows are
+        complete (`brutus_post_set_after_jump`) -- or before this method returns, whatever
+        happens."""
+        torch, L = self.torch, self.L
+        pp, np_states = call.pp, call.np_states
         rec.fill_rv()
-        cap = rec.capacity
-        nbytes = L.brutus_post_workspace_bytes(nstar, cap, pp.nmc)
-        if ctx.get("ws") is None or ctx["ws"].numel() < nbytes:
-            ctx["ws"] = torch.empty(nbytes, dtype=torch.uint8, device=g.device)
-        if ctx.get("zbuf") is None:
-            # (both slots of the pipeline get the size the first one was given)
-            gb = self.__dict__.get("_zbuf_gb")
-            if gb is None:
-                free = torch.cuda.mem_get_info(g.device)[0] / 2 ** 30
-                gb = self._zbuf_gb = float(os.environ.get("BRUTUS_AMD_ZBUF_GB",
-                                                          min(64., max(1., 0.22 * free))))
-            ctx["zbuf"] = torch.empty(int(gb * 2 ** 30) // 8, dtype=torch.float64, device=g.device)
-        dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(g.device)
-        lnprior, feh, loga = statics
+        ctx = self._post_slot(slot, L.brutus_post_workspace_bytes(nstar, rec.capacity, pp.nmc),
+                              0.22, alike=True)
         # everything phase 2 reads stays referenced until `post_numpy_end` (the dust and distance
-        # tables too: phase 2 evaluates them inside the Monte Carlo integral)
-        ctx["keep"] = (rec.idx, rec.vals, rec.off, dev(coords), dev(parallax), dev(parallax_err),
-                       rec.slot, dust, dtab)
-        ctx["out"] = (torch.empty((nstar, pp.ndraws), dtype=torch.int32, device=g.device),
-                      torch.empty((nstar, pp.ndraws, 17), dtype=torch.float64, device=g.device),
-                      np.zeros((nstar, 4)), np.zeros(nstar, dtype=np.int32))
+        # tables too, by `run`: phase 2 evaluates them inside the Monte Carlo integral)
+        ctx.inputs = self._post_inputs(rec, coords, parallax, parallax_err)
+        ctx.out = self._post_outputs(nstar, pp.ndraws)
         assert np_states.dtype == np.uint32 and np_states.flags.c_contiguous
+        lead = self._post_leading_args(nstar, ctx.inputs, statics, pp, ctx.ws, ctx.out)
+        tail = (int(np_states.shape[0]), np_states.ctypes.data, ctx.zbuf.data_ptr(),
+                ctx.zbuf.numel())
 
-        def call(phase):
-            k, o = ctx["keep"], ctx["out"]
-            if phase == 1:
-                self._set_dust(k[7])
-            self._set_dist_table(k[8])      # (both phases: phase 2 picks its kernel by it)
-            return L.brutus_post_batch_numpy_phase(
-                nstar, cap, k[0].data_ptr(), k[6].data_ptr(), k[1].data_ptr(), k[2].data_ptr(),
-                lnprior.data_ptr(), feh.data_ptr() if feh is not None else None,
-                loga.data_ptr() if loga is not None else None, k[3].data_ptr(), k[4].data_ptr(),
-                k[5].data_ptr(), pp, ctx["ws"].data_ptr(), ctx["ws"].numel(), o[0].data_ptr(),
-                o[1].data_ptr(), o[2].ctypes.data, o[3].ctypes.data, int(np_states.shape[0]),
-                np_states.ctypes.data, ctx["zbuf"].data_ptr(), ctx["zbuf"].numel(), phase,
-                _stream_ptr(torch))
-        ctx["call"] = call
+        def run(phase):
+            # (the distance table in both phases: phase 2 picks its kernel by it)
+            self._set_tables(call.dust if phase == 1 else None, call.dtab)
+            return L.brutus_post_batch_numpy_phase(*lead + tail + (phase, _stream_ptr(torch)))
+        ctx.run = run
         fired = [after_jump is None]
         if after_jump is not None:
             import ctypes as C
@@ -647,10 +652,10 @@ class _Engine(object):
                 if not fired[0]:
                     fired[0] = True
                     after_jump()
-            cb = ctx["hook"] = C.CFUNCTYPE(None, C.c_void_p)(hook)      # (kept alive by the slot)
+            cb = ctx.hook = C.CFUNCTYPE(None, C.c_void_p)(hook)      # (kept alive by the slot)
             L.brutus_post_set_after_jump(C.cast(cb, C.c_void_p), None)
         try:
-            rc = call(1)
+            rc = run(1)
         finally:
             if after_jump is not None:
                 L.brutus_post_set_after_jump(None, None)
@@ -665,21 +670,23 @@ class _Engine(object):
     def post_numpy_end(self, slot):
         """Phase 2 for the batch `post_numpy_begin` left in `slot` (any thread / stream)."""
         ctx = self._post_slots[slot]
-        _lib.check(ctx["call"](2))
-        o = ctx["out"]
-        res = (o[0].cpu().numpy(), o[1].cpu().numpy(), o[2], o[3],
-               np.zeros(o[3].size + 1, dtype=np.uint64))
-        ctx["keep"] = ctx["call"] = None
-        return res
+        _lib.check(ctx.run(2))
+        out = ctx.out
+        ctx.inputs = ctx.run = None
+        return out._replace(out_idx=out.out_idx.cpu().numpy(), out_vals=out.out_vals.cpu().numpy())
+
+    @staticmethod
+    def _record_dict(idx, vals, ndim, k1, k2):
+        return dict(sel=idx, lnlike=vals[0], chi2=vals[1],
+                    scale=vals[2], av=vals[3], rv=vals[4],
+                    icov=_icov_from6(vals[5:11]), Ndim=int(ndim), K1=int(k1),
+                    K2=int(k2))
 
     @staticmethod
     def record_of(rec, off, s, ndim, k1=0, k2=0):
         """One object's first-cut records as the host-stage dict."""
         idx, vals = rec.host(int(off[s]), int(off[s + 1]))
-        return dict(sel=idx, lnlike=vals[0], chi2=vals[1],
-                    scale=vals[2], av=vals[3], rv=vals[4],
-                    icov=_icov_from6(vals[5:11]), Ndim=int(ndim), K1=int(k1),
-                    K2=int(k2))
+        return _Engine._record_dict(idx, vals, ndim, k1, k2)
 
     def fit_batch(self, flux, err, mask, parallax, parallax_err, params):
         """Host numpy in -> list of per-star compact record dicts."""
@@ -690,15 +697,8 @@ class _Engine(object):
                                                    parallax_err)
             rec, off, ndim, k1, k2 = self.records_device(f, e, m, p, pe, has_par, params)
             idx, vals = rec.host(0, int(off[-1]))
-        out = []
-        for s in range(S):
-            a, b = int(off[s]), int(off[s + 1])
-            out.append(dict(sel=idx[a:b], lnlike=vals[0, a:b],
-                            chi2=vals[1, a:b], scale=vals[2, a:b],
-                            av=vals[3, a:b], rv=vals[4, a:b],
-                            icov=_icov_from6(vals[5:11, a:b]),
-                            Ndim=int(ndim[s]), K1=int(k1[s]), K2=int(k2[s])))
-        return out
+        return [self._record_dict(idx[off[s]:off[s + 1]], vals[:, off[s]:off[s + 1]],
+                                  ndim[s], k1[s], k2[s]) for s in range(S)]
 
 
 def _icov_from6(icov6):
@@ -823,13 +823,22 @@ def _psd_repair(cov, icov, scale):
     return cov
 
 
-def _lnpost_selected(sel, lnlike, scales, avs, rvs, icovs, lnprior, parallax,
-                     parallax_err, coord, Nmc_prior, wt_thresh, cdf_thresh,
-                     lngalprior, lndustprior, dustfile, dlabels, avlim, rvlim,
-                     rstate, apply_av_prior, mem_lim, lnprob_first):
+#: the per-call constants of the `lnpost` stage (`lnpost`'s own keywords; `Ndraws` and
+#: `return_distreds` are `_fit`'s): built once per call, shipped whole to the host workers
+_PostOptions = collections.namedtuple("_PostOptions", (
+    "Nmc_prior", "lnprior", "wt_thresh", "cdf_thresh", "lngalprior", "lndustprior", "dustfile",
+    "dlabels", "avlim", "rvlim", "mem_lim", "apply_av_prior", "Ndraws", "return_distreds"))
+
+
+def _lnpost_selected(first, lnprob_first, parallax, parallax_err, coord, rstate, opts):
     """Everything in reference `lnpost` after the first cut
-    (fitting.py:1000-1107).  All array arguments are aligned with `sel`
-    (the first-cut model indices, ascending)."""
+    (fitting.py:1000-1107).  `first` = (sel, lnlike, scales, avs, rvs, icovs) and
+    `lnprob_first` are aligned with `sel` (the first-cut model indices, ascending)."""
+    sel, lnlike, scales, avs, rvs, icovs = first
+    o = opts
+    Nmc_prior, lnprior, wt_thresh, cdf_thresh = o.Nmc_prior, o.lnprior, o.wt_thresh, o.cdf_thresh
+    lngalprior, lndustprior, dustfile, dlabels = o.lngalprior, o.lndustprior, o.dustfile, o.dlabels
+    avlim, rvlim, mem_lim, apply_av_prior = o.avlim, o.rvlim, o.mem_lim, o.apply_av_prior
     mvn = sample_multivariate_normal
     Nsel_max = int(mem_lim / Nmc_prior / 4.0e-4) if Nmc_prior > 0 else None
     with warnings.catch_warnings(), np.errstate(all="ignore"):
@@ -956,11 +965,10 @@ def lnpost(results, parallax=None, parallax_err=None, coord=None,
             order = np.argsort(lnprob)
             prob = np.exp(lnprob - logsumexp(lnprob))
             sel = order[np.cumsum(prob[order]) <= (1. - cdf_thresh)]
-    return _lnpost_selected(sel, lnlike[sel], scales[sel], avs[sel], rvs[sel],
-                            icovs_sar[sel], lnprior, parallax, parallax_err,
-                            coord, Nmc_prior, wt_thresh, cdf_thresh, lngalprior,
-                            lndustprior, dustfile, dlabels, avlim, rvlim, rstate,
-                            apply_av_prior, mem_lim, lnprob[sel])
+    opts = _PostOptions(Nmc_prior, lnprior, wt_thresh, cdf_thresh, lngalprior, lndustprior,
+                        dustfile, dlabels, avlim, rvlim, mem_lim, apply_av_prior, None, None)
+    return _lnpost_selected((sel, lnlike[sel], scales[sel], avs[sel], rvs[sel], icovs_sar[sel]),
+                            lnprob[sel], parallax, parallax_err, coord, rstate, opts)
 
 
 # ---------------------------------------------------------------------------
@@ -969,33 +977,28 @@ def lnpost(results, parallax=None, parallax_err=None, coord=None,
 _POOL_CTX = {}
 
 
-def _pool_init(ctx):
-    _POOL_CTX.update(ctx)
+def _pool_init(rng_kind, opts):
+    _POOL_CTX.update(rng_kind=rng_kind, opts=opts)
 
 
 def _pool_task(args):
     rec, parallax, parallax_err, coord, seed = args
-    c = _POOL_CTX
-    if c.get("rng_kind", "numpy") == "philox":      # same stream as the in-process stage
-        from .rng import PhiloxRandomState
+    if _POOL_CTX["rng_kind"] == "philox":      # same stream as the in-process stage
         rstate = PhiloxRandomState(seed)
     else:
         rstate = np.random.RandomState(seed)
-    return BruteForce._finish_star(
-        rec, parallax, parallax_err, coord, c["Nmc_prior"], c["lnprior"],
-        c["wt_thresh"], c["cdf_thresh"], c["lngalprior"], c["lndustprior"],
-        c["dustfile"], c["dlabels"], c["avlim"], c["rvlim"], c["mem_lim"],
-        rstate, c["apply_av_prior"], c["Ndraws"], c["return_distreds"])
+    return BruteForce._finish_star(rec, parallax, parallax_err, coord, rstate, _POOL_CTX["opts"])
 
 
 class _HostPool(object):
-    """`spawn`ed worker processes (they never touch the GPU) running
-    `_finish_star`; prior hooks must be picklable (module-level functions)."""
+    """`spawn`ed worker processes (they never touch the GPU) running `_finish_star` with the
+    call's `_PostOptions` on `rng_kind` ("philox" / "numpy") streams; prior hooks must be
+    picklable (module-level functions)."""
 
-    def __init__(self, nproc, ctx):
+    def __init__(self, nproc, rng_kind, opts):
         import multiprocessing as mp
         self.pool = mp.get_context("spawn").Pool(nproc, initializer=_pool_init,
-                                                 initargs=(ctx,))
+                                                 initargs=(rng_kind, opts))
 
     def submit(self, rec, parallax, parallax_err, coord, seed):
         return self.pool.apply_async(_pool_task, ((rec, parallax, parallax_err,
@@ -1004,6 +1007,207 @@ class _HostPool(object):
     def close(self):
         self.pool.terminate()
         self.pool.join()
+
+
+# ---------------------------------------------------------------------------
+# device `lnpost` stage of `BruteForce._fit`: stream, rows, schedule
+# ---------------------------------------------------------------------------
+#: the per-object inputs of one `_fit` call, (Ndata, ...) host arrays
+_Stars = collections.namedtuple("_Stars", "data data_err data_mask parallax parallax_err coords")
+_Scanned = collections.namedtuple("_Scanned", "rec off ndim k1 k2")     # `_Engine.records_device`
+
+
+class _DeviceStream(object):
+    """The random stream of one device-`lnpost` call: numpy's legacy MT19937 (`numpy`) or the
+    counter-based Philox one; either shared by the objects in order (`rstate`, the caller's
+    generator, which moves on as the batches go) or one per object (`seed0`: object i draws
+    from the generator seeded `seed0 + i`, the caller's is not touched)."""
+
+    def __init__(self, numpy, rstate=None, seed0=None):
+        self.numpy, self.rstate, self.seed0 = numpy, rstate, seed0
+
+    def begin(self, pp, a, b):
+        """Write the stream position of objects a:b into `pp`; returns the numpy generator
+        states the call advances (uint32 (nstream, 628)), None for a Philox stream."""
+        pp.per_object = pp.object0 = pp.seed = pp.normal_base = pp.uniform_base = 0
+        if self.numpy and self.seed0 is None:
+            return state_to_words(self.rstate.get_state()).reshape(1, -1).copy()
+        if self.numpy:
+            return np.stack([state_to_words(np.random.RandomState(self.seed0 + i).get_state())
+                             for i in range(a, b)])
+        if self.seed0 is not None:
+            pp.per_object, pp.object0, pp.seed = 1, a, int(self.seed0) & (2 ** 64 - 1)
+        else:
+            pp.seed = self.rstate.seed
+            pp.normal_base, pp.uniform_base = self.rstate.n_normal, self.rstate.n_uniform
+        return None
+
+    def advance(self, np_states, nbase=None, nuniform=0):
+        """The batch's stream positions are final: the caller's generator continues from
+        there.  Philox: `nbase[-1]` = the normal-stream position after the batch, which also
+        took `nuniform` uniforms."""
+        if self.seed0 is not None:
+            return
+        if self.numpy:
+            self.rstate.set_state(words_to_state(np_states[0]))
+        else:
+            self.rstate.n_normal = int(nbase[-1])
+            self.rstate.n_uniform += nuniform
+
+
+def _post_params(opts, statics, galactic):
+    """The part of `PostParams` that is the same for every batch of a call; `galactic` =
+    `device_params()` of the Galactic prior."""
+    pp = _lib.PostParams()
+    pp.nmc, pp.ndraws = int(opts.Nmc_prior), int(opts.Ndraws)
+    pp.return_distreds = 1 if opts.return_distreds else 0
+    pp.has_feh = 1 if statics[1] is not None else 0
+    pp.has_loga = 1 if statics[2] is not None else 0
+    pp.wt_thresh = float(opts.wt_thresh)
+    pp.avlim[:] = [float(opts.avlim[0]), float(opts.avlim[1])]
+    pp.rvlim[:] = [float(opts.rvlim[0]), float(opts.rvlim[1])]
+    pp.nsel_max = int(opts.mem_lim / opts.Nmc_prior / 4.0e-4)
+    for k, val in galactic.items():
+        if isinstance(val, tuple):
+            getattr(pp, k)[:] = list(val)
+        else:
+            setattr(pp, k, val)
+    return pp
+
+
+def _post_rows(a, S, stars, ndim, res, return_distreds, as_block):
+    """The tuples `_fit` yields for objects a:a + S from the `_PostResult` of their batch -- or,
+    for `fit()` (which only wants the rows in the file: `as_block`), the whole batch as ONE
+    `_RowBlock` of arrays in the file's layout: 128 tuples of 13 slices per batch are 1.2 ms of
+    Python, a third of `fit()`'s time where the posteriors are sharp."""
+    out_idx, out_vals, star_out, flags = res[:4]
+    parallax, parallax_err = stars.parallax, stars.parallax_err
+    if flags.any():     # (the library never asks for a host redo at present: include/brutus_amd.h)
+        raise _lib.BrutusError("object %d: the device `lnpost` stage flagged it for the host "
+                               "stage, which no longer exists" % (a + int(np.flatnonzero(flags)[0])))
+    if as_block and np.all(star_out[:S, 3] >= 1):
+        v = out_vals[:S]
+        fin = np.isfinite(parallax[a:a + S]) & np.isfinite(parallax_err[a:a + S])
+        f4 = np.float32
+        with np.errstate(over="ignore"):   # -1e300 (out-of-bounds draw) -> -inf in f32, as h5py does
+            # one contiguous pass to the file's float32; the per-dataset planes are VIEWS of it
+            # (stride 13 or 17): the results writer's thread gathers them when it writes
+            v4 = v.astype(f4)
+            arr = {"model_idx": out_idx[:S].astype(np.int32),
+                   "ml_scale": v4[:, :, 0], "ml_av": v4[:, :, 1], "ml_rv": v4[:, :, 2],
+                   "ml_cov_sar": v4[:, :, 3:12].reshape(S, v4.shape[1], 3, 3),
+                   "obj_Nbands": (np.asarray(ndim[:S]).astype(np.int64) + fin).astype(np.int16),
+                   "obj_log_post": v4[:, :, 12],
+                   "obj_log_evid": star_out[:S, 0].astype(f4),
+                   "obj_chi2min": star_out[:S, 1].astype(f4)}
+            if return_distreds:
+                for q, name in enumerate(("samps_dist", "samps_red", "samps_dred", "samps_logp")):
+                    arr[name] = v4[:, :, 13 + q]
+        yield _RowBlock(a, S, arr)
+        return
+    for s in range(S):
+        i = a + s
+        if star_out[s, 3] < 1:
+            raise ValueError("object %d: no model survives the prior "
+                             "cuts (the reference fails in np.min on an "
+                             "empty selection, fitting.py:2034)" % i)
+        v = out_vals[s]
+        nd = int(ndim[s]) + (1 if np.isfinite(parallax[i])
+                             and np.isfinite(parallax_err[i]) else 0)
+        row = (out_idx[s].astype(np.int64), v[:, 0], v[:, 1], v[:, 2],
+               v[:, 3:12].reshape(-1, 3, 3), nd, v[:, 12],
+               float(star_out[s, 0]), float(star_out[s, 1]))
+        if return_distreds:
+            row += (v[:, 13], v[:, 14], v[:, 15], v[:, 16])
+        yield row
+
+
+#: the stages of batch k, as `_post_schedule` calls them:
+#:   scan(k) -> scanned                    first cut, on engine k % nE
+#:   args(k) -> call                       host-side arguments of the post call
+#:   begin(k, slot, scanned, call, after_jump) -> bool    phase 1 in pipeline slot `slot`; False:
+#:                                         declined, nothing consumed.  Calls `after_jump()`
+#:                                         exactly once before it returns or raises
+#:   end(slot) -> result                   phase 2 of the batch phase 1 left in `slot`
+#:   whole(k, scanned, call) -> result     both phases as one call
+#:   rows(k, scanned, result) -> iterable  what the caller gets
+_PostStages = collections.namedtuple("_PostStages", "scan args begin end whole rows")
+
+
+def _post_schedule(nbatch, stages, ahead, pipelined):
+    """Generator of the rows of batches 0 .. nbatch - 1, in order: who runs which stage when.
+    It knows threads and hand-overs, nothing of the device (the stages bring their own stream
+    and device contexts), so that the order can be tested with stand-in stages.
+
+    `ahead`: scan k + 1 runs in a helper thread while this one runs `lnpost` of batch k and
+    the caller consumes the rows (the random-stream positions only chain the `lnpost` calls,
+    which stay in order here).  `pipelined` (numpy streams; needs `ahead`): phase 2 of batch
+    k - 1 runs in a second helper thread beside phase 1 of batch k, in the other of two slots.
+    It is held back until the jump-ahead of batch k's walk is through (`after_jump`: those
+    kernels need whole compute units and would starve behind the Monte Carlo integral).  A
+    batch phase 1 declines is served by the whole call, in order.
+
+    Per batch k: (1) take scan k; (2) submit scan k + 1; (3) build the arguments; (4) wait for
+    phase 2 of k - 2, which holds slot k % 2; (5) phase 1 of k; (6) hand out the rows of
+    k - 2, while the device is busy again.  (4) comes after (2): a scan submitted behind the
+    wait lands on the next batch's jump-ahead kernels and delays the phase 2 behind them
+    (-11 % with per-object streams) -- hence four scan engines, scan k + 1 must not reuse the
+    one whose records phase 2 of k - 2 still reads.  (4) comes after (3): the host
+    preparations (128 generator states with per-object streams) overlap that phase 2's tail."""
+    import concurrent.futures
+    scanner = concurrent.futures.ThreadPoolExecutor(max_workers=1) if ahead else None
+    finisher = concurrent.futures.ThreadPoolExecutor(max_workers=1) if pipelined else None
+    pending = None        # (future of phase 2, k, scanned): submitted, rows not handed out yet
+    unsub = [None]        # (slot, k, scanned): phase 1 done, phase 2 not submitted yet
+
+    def finished(entry):
+        fut, k, scanned = entry
+        return stages.rows(k, scanned, fut.result())
+
+    def submit_unsub():
+        if unsub[0] is not None:
+            (slot, k, scanned), unsub[0] = unsub[0], None
+            return finisher.submit(stages.end, slot), k, scanned
+    try:
+        fut = scanner.submit(stages.scan, 0) if ahead else None
+        for k in range(nbatch):
+            if ahead:
+                scanned = fut.result()
+                fut = scanner.submit(stages.scan, k + 1) if k + 1 < nbatch else None
+            else:
+                scanned = stages.scan(k)
+            call = stages.args(k)
+            if pipelined:
+                ready = None
+                if pending is not None:
+                    (prev, kp, sp), pending = pending, None
+                    ready = (kp, sp, prev.result())
+                sub = []
+                began = stages.begin(k, k % 2, scanned, call, lambda: sub.append(submit_unsub()))
+                pending = sub[0]
+                if began:
+                    unsub[0] = (k % 2, k, scanned)
+                if ready is not None:
+                    yield from stages.rows(*ready)
+                if began:
+                    continue
+                if pending is not None:      # whole-call form for this batch, in order
+                    entry, pending = pending, None
+                    yield from finished(entry)
+            yield from stages.rows(k, scanned, stages.whole(k, scanned, call))
+        if pending is not None:
+            yield from finished(pending)
+        last = submit_unsub()
+        if last is not None:
+            yield from finished(last)
+    finally:
+        # also when the caller abandons the generator: the scan that runs ahead still
+        # writes its engine's workspace and record buffers, a running phase 2 still reads
+        # them, and the next `_fit` on this object starts on the same engines
+        if scanner is not None:
+            scanner.shutdown(wait=True)
+        if finisher is not None:
+            finisher.shutdown(wait=True)
 
 
 # ---------------------------------------------------------------------------
@@ -1044,6 +1248,9 @@ class BruteForce(object):
         self.post_pipeline = os.environ.get("BRUTUS_POST_PIPELINE", "1") != "0"
         # `lnpost` on the device also for numpy's own random stream (RandomState / None)
         self.device_numpy_rng = True
+        self._engine_extra = None       # the further scan engines of the device `lnpost` stage
+        self._yield_row_blocks = False  # `fit()`: the device stage hands over whole batches
+        self._test_phase2_delay = 0.    # test hook: seconds by which phase 2 starts late
 
     # -- device state -------------------------------------------------------
     def _engine(self, bands=None):
@@ -1209,7 +1416,6 @@ class BruteForce(object):
                                rstate=rstate)
         Ndata, Nfilt = data.shape
 
-        import os
         todo = None
         if resume and os.path.exists("{0}.h5".format(save_file)):
             out = h5io.ResultsFile.resume("{0}.h5".format(save_file), Ndata,
@@ -1357,25 +1563,24 @@ class BruteForce(object):
                               wt_thresh=wt_thresh)
         step = (eng.batch if lnprior_ext is None and not cdf_mode
                 else max(1, min(eng.batch, 8)))
-        step_device = eng.batch
-        from .rng import PhiloxRandomState
         philox_per_object = (seed0 is not None and isinstance(rstate_per_object, str)
                              and rstate_per_object == "philox")
         if philox_per_object:
             rstate_per_object = lambda i: PhiloxRandomState(seed0 + i)
-        # random stream the device `lnpost` can reproduce: the counter-based Philox stream,
-        # or numpy's own legacy MT19937 stream -- one shared `RandomState` / the global
-        # `numpy.random` (the reference's semantics), or `RandomState(seed0 + i)` per object
-        from .rng import numpy_stream
-        np_mode = None
-        if rstate_per_object is None:
-            if seed0 is not None:
-                np_mode = "per_object"
-            elif numpy_stream(rstate) is not None:
-                np_mode = "shared"
+        # The random stream, decided once.  One the device `lnpost` can reproduce: the
+        # counter-based Philox stream, or numpy's own legacy MT19937 stream -- one shared
+        # `RandomState` / the global `numpy.random` (the reference's semantics), or
+        # `RandomState(seed0 + i)` per object.  Or None: any other stream keeps the host stage.
+        stream = None
+        if philox_per_object:
+            stream = _DeviceStream(False, seed0=seed0)
+        elif rstate_per_object is None and isinstance(rstate, PhiloxRandomState):
+            stream = _DeviceStream(False, rstate=rstate)
+        elif (rstate_per_object is None and self.device_numpy_rng
+              and (seed0 is not None or numpy_stream(rstate) is not None)):
+            stream = _DeviceStream(True, rstate=rstate, seed0=seed0)
         # the built-in line-of-sight dust prior (pdf.dust_lnprior with a caller-supplied
         # table) is evaluated on the device too; any other dust hook keeps the host stage
-        from . import pdf as _pdf
         dust_tables = None
         if apply_av_prior and lndustprior is _pdf.dust_lnprior:
             # built per batch (bounded memory, no catalogue-long Python loop up front).  The
@@ -1392,15 +1597,14 @@ class BruteForce(object):
                 dust_tables = lambda a, b: (first if (a, b) == (0, b0) else
                                             _pdf.los_tables(dustfile, data_coords[a:b]))
         dust_ok = (not apply_av_prior and lndustprior is None) or dust_tables is not None
+        stars = _Stars(data, data_err, data_mask, parallax, parallax_err, data_coords)
+        opts = _PostOptions(Nmc_prior, lnprior, wt_thresh, cdf_thresh, lngalprior, lndustprior,
+                            dustfile, dlabels, avlim, rvlim, mem_lim, apply_av_prior, Ndraws,
+                            return_distreds)
         if (self.device_lnpost and dust_ok
                 and wt_thresh is not None and wt_thresh > 0
                 and getattr(lngalprior, "device_params", None) is not None
-                and Ndraws <= 4096
-                and (philox_per_object
-                     or (isinstance(rstate, PhiloxRandomState)
-                         and rstate_per_object is None)
-                     or (np_mode is not None and self.device_numpy_rng))):
-            philox = philox_per_object or isinstance(rstate, PhiloxRandomState)
+                and Ndraws <= 4096 and stream is not None):
             ext = None
             if lnprior_ext is not None:
                 # external per-object constraints on labels (fitting.py:1995-2009): the label
@@ -1412,14 +1616,8 @@ class BruteForce(object):
                        ).to(eng.grid.device),
                        np.stack([np.asarray(lnprior_ext[k], dtype=np.float64).reshape(-1, 2)
                                  for k in keys]))
-            for out in self._fit_device_post(
-                    eng, params, step_device, data, data_err, data_mask, parallax,
-                    parallax_err, data_coords, lnprior, lngalprior, dlabels,
-                    Nmc_prior, wt_thresh, cdf_thresh, Ndraws, avlim, rvlim,
-                    mem_lim, return_distreds, rstate,
-                    seed0 if (philox_per_object or (not philox and np_mode == "per_object")) else None,
-                    np_mode=None if philox else np_mode, dust_tables=dust_tables, ext=ext):
-                yield out
+            yield from self._fit_device_post(eng, params, eng.batch, stars, opts, stream,
+                                             dust_tables=dust_tables, ext=ext)
             return
         pool = None
         # worker processes rebuild the per-object stream from (kind, seed0 + i): only the
@@ -1431,376 +1629,181 @@ class BruteForce(object):
             rstate_per_object._numpy_default = True
         if (seed0 is not None and self.host_workers and self.host_workers > 1
                 and poolable):
-            pool = _HostPool(self.host_workers, dict(
-                rng_kind="philox" if philox_per_object else "numpy",
-                Nmc_prior=Nmc_prior, lnprior=lnprior, wt_thresh=wt_thresh,
-                cdf_thresh=cdf_thresh, lngalprior=lngalprior,
-                lndustprior=lndustprior, dustfile=dustfile, dlabels=dlabels,
-                avlim=avlim, rvlim=rvlim, mem_lim=mem_lim,
-                apply_av_prior=apply_av_prior, Ndraws=Ndraws,
-                return_distreds=return_distreds))
+            pool = _HostPool(self.host_workers, "philox" if philox_per_object else "numpy", opts)
+        rstate_of = (lambda i: rstate) if rstate_per_object is None else rstate_per_object
         try:
-            for out in self._fit_loop(eng, params, step, Ndata, data, data_err,
-                                      data_mask, parallax, parallax_err,
-                                      data_coords, lnprior_ext,
-                                      (wt_thresh, cdf_thresh, cdf_mode), pool,
-                                      seed0, rstate, rstate_per_object,
-                                      (Nmc_prior, lnprior, wt_thresh, cdf_thresh,
-                                       lngalprior, lndustprior, dustfile, dlabels,
-                                       avlim, rvlim, mem_lim),
-                                      (apply_av_prior, Ndraws, return_distreds)):
-                yield out
+            yield from self._fit_loop(eng, params, step, stars, lnprior_ext, cdf_mode, pool,
+                                      seed0, rstate_of, opts)
         finally:
             if pool is not None:
                 pool.close()
 
-    def _fit_loop(self, eng, params, step, Ndata, data, data_err, data_mask,
-                  parallax, parallax_err, data_coords, lnprior_ext, cut,
-                  pool, seed0, rstate, rstate_per_object, post_args, tail_args):
-        (Nmc_prior, lnprior, wt_thresh, cdf_thresh, lngalprior, lndustprior,
-         dustfile, dlabels, avlim, rvlim, mem_lim) = post_args
-        apply_av_prior, Ndraws, return_distreds = tail_args
-        cdf_mode = cut[2]
+    def _fit_loop(self, eng, params, step, stars, lnprior_ext, cdf_mode, pool, seed0,
+                  rstate_of, opts):
+        """The host `lnpost` stage behind the device's first cut: in this process on the
+        stream `rstate_of(i)` of object i, or (`pool`) in worker processes on `seed0 + i`."""
+        Ndata = stars.data.shape[0]
         pending = []      # in-flight host-pool results, in object order
         for a in range(0, Ndata, step):
             b = min(Ndata, a + step)
             if lnprior_ext is None and not cdf_mode:
-                recs = eng.fit_batch(data[a:b], data_err[a:b], data_mask[a:b],
-                                     parallax[a:b], parallax_err[a:b], params)
+                recs = eng.fit_batch(stars.data[a:b], stars.data_err[a:b], stars.data_mask[a:b],
+                                     stars.parallax[a:b], stars.parallax_err[a:b], params)
             else:
-                recs = self._first_cut_with_ext(eng, data[a:b], data_err[a:b],
-                                                data_mask[a:b], parallax[a:b],
-                                                parallax_err[a:b], params,
-                                                lnprior_ext, a, wt_thresh, cdf_thresh)
+                recs = self._first_cut_with_ext(eng, stars, a, b, params, lnprior_ext,
+                                                opts.wt_thresh, opts.cdf_thresh)
             if pool is not None:
                 # keep the device busy: hand this batch to the pool, yield what
                 # is finished from earlier batches (always in object order)
                 for i, rec in zip(range(a, b), recs):
-                    pending.append(pool.submit(rec, parallax[i], parallax_err[i],
-                                               data_coords[i], seed0 + i))
+                    pending.append(pool.submit(rec, stars.parallax[i], stars.parallax_err[i],
+                                               stars.coords[i], seed0 + i))
                 while len(pending) > 2 * step:
                     yield pending.pop(0).get()
                 continue
             for i, rec in zip(range(a, b), recs):
-                rs = rstate if rstate_per_object is None else rstate_per_object(i)
-                yield self._finish_star(rec, parallax[i], parallax_err[i],
-                                        data_coords[i], Nmc_prior, lnprior,
-                                        wt_thresh, cdf_thresh, lngalprior,
-                                        lndustprior, dustfile, dlabels, avlim,
-                                        rvlim, mem_lim, rs, apply_av_prior,
-                                        Ndraws, return_distreds)
+                yield self._finish_star(rec, stars.parallax[i], stars.parallax_err[i],
+                                        stars.coords[i], rstate_of(i), opts)
         while pending:
             yield pending.pop(0).get()
 
-    def _fit_device_post(self, eng, params, step, data, data_err, data_mask,
-                         parallax, parallax_err, data_coords, lnprior, lngalprior,
-                         dlabels, Nmc_prior, wt_thresh, cdf_thresh, Ndraws, avlim,
-                         rvlim, mem_lim, return_distreds, rstate, seed0, np_mode=None,
-                         dust_tables=None, ext=None):
-        """`_fit` with `lnpost` and the resampling on the device
-        (`brutus_post_batch`): built-in priors, Philox random stream.  Yields
-        exactly what the host stage yields for the same `rstate` -- one shared
-        sequential `PhiloxRandomState`, or (`seed0`) one stream per object."""
-        from .rng import PhiloxRandomState, state_to_words, words_to_state
+    def _scan_engines(self, eng, nE):
+        """`nE` engines over `eng`'s grid (`eng` first; the others are kept between calls) with a
+        stream each, for the scans that run ahead."""
         torch = eng.torch
-        dev = eng.grid.device
+        extra = self._engine_extra
+        if (extra is None or len(extra) < nE - 1 or extra[0].batch != eng.batch
+                or extra[0].grid is not eng.grid):
+            extra = self._engine_extra = [_Engine(eng.grid, max_batch=eng.batch)
+                                          for _ in range(nE - 1)]
+        return ((eng,) + tuple(extra[:nE - 1]),
+                tuple(torch.cuda.Stream(device=eng.grid.device) for _ in range(nE)))
+
+    def _fit_device_post(self, eng, params, step, stars, opts, stream, dust_tables=None,
+                         ext=None):
+        """`_fit` with `lnpost` and the resampling on the device (`brutus_post_batch`):
+        built-in priors, a random stream the device reproduces (`stream`, a `_DeviceStream`).
+        Yields exactly what the host stage yields for the same stream.  Here: what is fixed
+        for the call, and the stages of a batch for `_post_schedule`."""
+        torch, dev = eng.torch, eng.grid.device
+        lngalprior, dlabels = opts.lngalprior, opts.dlabels
         names = dlabels.dtype.names if dlabels is not None else ()
         up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
-        statics = (up(lnprior),
+        statics = (up(opts.lnprior),
                    up(dlabels['feh']) if 'feh' in names else None,
                    up(dlabels['loga']) if 'loga' in names else None)
         # a tabulated distance prior (pdf.DistancePriorTable): the parameters are its base
         # hook's (the defaults when it replaces the Galactic prior), the table goes up per batch
-        from . import pdf as _pdf
         dist_prior = lngalprior if isinstance(lngalprior, _pdf.DistancePriorTable) else None
-        gp = lngalprior.device_params()
-        K = Ndraws * (2 if return_distreds else 1)
-        Ndata = data.shape[0]
-        starts = list(range(0, Ndata, step))
-        # The grid scan of batch k+1 runs ahead on its own stream / engine
-        # (workspace + record buffers) in a helper thread while this thread runs
-        # `lnpost` of batch k and the caller consumes the rows: the two stages
-        # share nothing but the read-only grid, and the random-stream positions
-        # only chain the `lnpost` calls, which stay in order here.
-        ahead = len(starts) > 1 and self.scan_ahead
+        pp0 = _post_params(opts, statics, lngalprior.device_params())
+        K = opts.Ndraws * (2 if opts.return_distreds else 1)
+        Ndata = stars.data.shape[0]
+        bounds = [(a, min(Ndata, a + step)) for a in range(0, Ndata, step)]
+        # (the scan of batch k+1 runs ahead on its own stream / engine -- workspace + record
+        # buffers: it shares nothing with `lnpost` of batch k but the read-only grid)
+        ahead = len(bounds) > 1 and self.scan_ahead
         # numpy streams: the generator state is final after the stream walk, so the Monte
         # Carlo integral / evidence / draws of batch k (a second helper thread and stream)
         # run beside the cuts + stream walk of batch k + 1 (this thread): the first is bound
-        # by float64 issue, the second by LDS and HBM.  Needs FOUR scan engines: the records
-        # of batch k are read until phase 2 of batch k has been waited for, at the top of
-        # iteration k + 2 -- after the scan of batch k + 3 has been submitted there (it has to
-        # go first: submitted behind the wait it lands on the next batch's jump-ahead kernels
-        # and delays the phase 2 behind them, -11 % with per-object streams).  With three
-        # engines that scan overwrote the records under the tail of a long phase 2.
-        pipelined = ahead and np_mode is not None and getattr(self, "post_pipeline", True)
+        # by float64 issue, the second by LDS and HBM.  Needs FOUR scan engines, see
+        # `_post_schedule`: with three the scan of batch k + 3 overwrote the records of batch k
+        # under the tail of a long phase 2.
+        pipelined = ahead and stream.numpy and self.post_pipeline
         if pipelined:
             # the pipeline holds two more scan workspaces and a second post workspace + normal
             # buffer: only where that clearly fits (a quarter of the device free per slot)
-            have = (len(getattr(self, "_engine_extra", None) or ()) >= 3
-                    and len(getattr(eng, "_post_slots", None) or ()) >= 2)
+            have = len(self._engine_extra or ()) >= 3 and len(eng._post_slots) >= 2
             free = torch.cuda.mem_get_info(dev)[0]
             per_engine = eng.L.brutus_workspace_bytes(eng.grid.nmodel, eng.grid.nfilt,
                                                       eng.batch) + eng.batch * 600000 * 92
             pipelined = have or free > 5 * per_engine + (16 << 30)
         nE = 4 if pipelined else 2
-        finisher = None
-        if ahead:
-            import concurrent.futures
-            extra = getattr(self, "_engine_extra", None)
-            if (extra is None or len(extra) < nE - 1 or extra[0].batch != eng.batch
-                    or extra[0].grid is not eng.grid):
-                extra = self._engine_extra = [_Engine(eng.grid, max_batch=eng.batch)
-                                              for _ in range(nE - 1)]
-            engines = (eng,) + tuple(extra[:nE - 1])
-            streams = tuple(torch.cuda.Stream(device=dev) for _ in range(nE))
-            pool = concurrent.futures.ThreadPoolExecutor(max_workers=1)
-            if pipelined:
-                finisher = concurrent.futures.ThreadPoolExecutor(max_workers=1)
-                fin_stream = torch.cuda.Stream(device=dev)
-                # (default priority: the walk's pass 1 is a long kernel, and a high-priority
-                # stream with thousands of workgroups queued starves phase 2 of the previous
-                # batch until it is through -- the two then run one after the other)
-                walk_stream = torch.cuda.Stream(device=dev)
-        else:
-            engines, streams, pool = (eng, eng), (None, None), None
+        engines, streams = self._scan_engines(eng, nE) if ahead else ((eng, eng), (None, None))
+        if pipelined:
+            fin_stream = torch.cuda.Stream(device=dev)
+            # (default priority: the walk's pass 1 is a long kernel, and a high-priority
+            # stream with thousands of workgroups queued starves phase 2 of the previous
+            # batch until it is through -- the two then run one after the other)
+            walk_stream = torch.cuda.Stream(device=dev)
 
         def scan(k):
-            a = starts[k]
-            b = min(Ndata, a + step)
-            en = engines[k % nE]
-            with torch.cuda.device(dev):
+            a, b = bounds[k]
+            en, st = engines[k % nE], streams[k % nE]
+            # (`st` None -- no scan ahead -- leaves the current stream in place)
+            with torch.cuda.device(dev), torch.cuda.stream(st):
                 # (external label constraints of the batch's objects: the full-grid route)
                 ext_b = None if ext is None else (ext[0], ext_constraint_params(ext[1][:, a:b]))
-                if streams[k % nE] is None:
-                    f, e, m, p, pe, hp = en._upload(data[a:b], data_err[a:b], data_mask[a:b],
-                                                    parallax[a:b], parallax_err[a:b])
-                    out = en.records_device(f, e, m, p, pe, hp, params, ext=ext_b)
-                    out[0].fill_rv()
-                    return out
-                with torch.cuda.stream(streams[k % nE]):
-                    f, e, m, p, pe, hp = en._upload(data[a:b], data_err[a:b], data_mask[a:b],
-                                                    parallax[a:b], parallax_err[a:b])
-                    out = en.records_device(f, e, m, p, pe, hp, params, ext=ext_b)
-                    out[0].fill_rv()
-                    streams[k % nE].synchronize()
-                    return out
+                f, e, m, p, pe, hp = en._upload(stars.data[a:b], stars.data_err[a:b],
+                                                stars.data_mask[a:b], stars.parallax[a:b],
+                                                stars.parallax_err[a:b])
+                out = en.records_device(f, e, m, p, pe, hp, params, ext=ext_b)
+                out[0].fill_rv()
+                if st is not None:
+                    st.synchronize()
+                return _Scanned(*out)
 
-        def finish(slot):
-            delay = getattr(self, "_test_phase2_delay", 0.)     # (test hook: a late phase 2)
-            if delay:
-                time.sleep(delay)
+        def call_args(k):
+            a, b = bounds[k]
+            pp = _lib.PostParams.from_buffer_copy(pp0)
+            np_states = stream.begin(pp, a, b)
+            dust = dtab = None
+            if dust_tables is not None:      # this batch's sightlines; the engine hands
+                los, ok = dust_tables(a, b)  # them to every post call and retry and keeps
+                dust = (torch.from_numpy(np.ascontiguousarray(los)).to(dev),     # them alive
+                        torch.from_numpy(np.ascontiguousarray(ok)).to(dev))
+            if dist_prior is not None:       # kept alive like the dust tables
+                dtab = (torch.from_numpy(_pdf.dist_tables(
+                            dist_prior, stars.coords[a:b])).to(dev), dist_prior.base is None)
+            return _PostCall(pp, np_states, dust, dtab)
+
+        def inputs(k, scanned):      # the leading arguments of both forms of the post call
+            a, b = bounds[k]
+            return (scanned.rec, b - a, statics, stars.coords[a:b], stars.parallax[a:b],
+                    stars.parallax_err[a:b])
+
+        def begin(k, slot, scanned, call, after_jump):
+            with torch.cuda.device(dev), torch.cuda.stream(walk_stream):
+                began = eng.post_numpy_begin(slot, *inputs(k, scanned), call,
+                                             after_jump=after_jump)
+            if began:       # final already: the walk is done
+                stream.advance(call.np_states)
+            return began
+
+        def end(slot):
+            if self._test_phase2_delay:      # (test hook: a late phase 2)
+                time.sleep(self._test_phase2_delay)
             with torch.cuda.device(dev), torch.cuda.stream(fin_stream):
                 return eng.post_numpy_end(slot)
 
-        def flagged_records(a, S, rec, off, ndim, k1, k2, out_idx, out_vals, star_out, flags,
-                            nbase, ubase0, pre=None):
-            """Host copies of the records of the (rare) objects `rows` hands to the host stage,
-            taken while the engine's record buffers still hold this batch."""
-            return {s: eng.record_of(rec, off, s, ndim[s], k1[s], k2[s])
-                    for s in range(S) if flags[s]}
+        def whole(k, scanned, call):
+            with torch.cuda.device(dev):
+                res = eng.post_batch_device(*inputs(k, scanned), call.pp, np_states=call.np_states,
+                                            dust=call.dust, dtab=call.dtab)
+            stream.advance(call.np_states, res.nbase, len(res.flags) * K)
+            return res
 
-        def rows(a, S, rec, off, ndim, k1, k2, out_idx, out_vals, star_out, flags,
-                 nbase, ubase0, pre=None):
-            """The tuples `_fit` yields for the objects of one batch -- or, for `fit()` (which only
-            wants the rows in the file: `self._yield_row_blocks`), the whole batch as ONE `_RowBlock`
-            of arrays in the file's layout: 128 tuples of 13 slices per batch are 1.2 ms of Python,
-            a third of `fit()`'s time where the posteriors are sharp."""
-            if (getattr(self, "_yield_row_blocks", False) and not np.any(flags[:S])
-                    and np.all(star_out[:S, 3] >= 1)):
-                v = out_vals[:S]
-                fin = np.isfinite(parallax[a:a + S]) & np.isfinite(parallax_err[a:a + S])
-                f4 = np.float32
-                with np.errstate(over="ignore"):   # -1e300 (out-of-bounds draw) -> -inf in f32, as h5py does
-                    # one contiguous pass to the file's float32; the per-dataset planes are VIEWS of it
-                    # (stride 13 or 17): the results writer's thread gathers them when it writes
-                    v4 = v.astype(f4)
-                    arr = {"model_idx": out_idx[:S].astype(np.int32),
-                           "ml_scale": v4[:, :, 0], "ml_av": v4[:, :, 1], "ml_rv": v4[:, :, 2],
-                           "ml_cov_sar": v4[:, :, 3:12].reshape(S, v4.shape[1], 3, 3),
-                           "obj_Nbands": (np.asarray(ndim[:S]).astype(np.int64) + fin).astype(np.int16),
-                           "obj_log_post": v4[:, :, 12],
-                           "obj_log_evid": star_out[:S, 0].astype(f4),
-                           "obj_chi2min": star_out[:S, 1].astype(f4)}
-                    if return_distreds:
-                        for q, name in enumerate(("samps_dist", "samps_red", "samps_dred", "samps_logp")):
-                            arr[name] = v4[:, :, 13 + q]
-                yield _RowBlock(a, S, arr)
-                return
-            for s in range(S):
-                i = a + s
-                if flags[s]:
-                    # more than Nsel_max models survive the second cut: the
-                    # reference re-sorts them (fitting.py:1029-1036); rare,
-                    # done by the host stage on the same stream positions
-                    rs = (PhiloxRandomState(seed0 + i) if seed0 is not None else
-                          PhiloxRandomState(rstate.seed, n_normal=int(nbase[s]),
-                                            n_uniform=int(ubase0) + s * K))
-                    rec1 = (pre[s] if pre is not None else
-                            eng.record_of(rec, off, s, ndim[s], k1[s], k2[s]))
-                    yield self._finish_star(rec1, parallax[i], parallax_err[i],
-                                            data_coords[i], Nmc_prior, lnprior,
-                                            wt_thresh, cdf_thresh, lngalprior, None,
-                                            None, dlabels, avlim, rvlim, mem_lim, rs,
-                                            False, Ndraws, return_distreds)
-                    continue
-                if star_out[s, 3] < 1:
-                    raise ValueError("object %d: no model survives the prior "
-                                     "cuts (the reference fails in np.min on an "
-                                     "empty selection, fitting.py:2034)" % i)
-                v = out_vals[s]
-                nd = int(ndim[s]) + (1 if np.isfinite(parallax[i])
-                                     and np.isfinite(parallax_err[i]) else 0)
-                res = (out_idx[s].astype(np.int64), v[:, 0], v[:, 1], v[:, 2],
-                       v[:, 3:12].reshape(-1, 3, 3), nd, v[:, 12],
-                       float(star_out[s, 0]), float(star_out[s, 1]))
-                if return_distreds:
-                    res += (v[:, 13], v[:, 14], v[:, 15], v[:, 16])
-                yield res
+        def rows(k, scanned, res):
+            a, b = bounds[k]
+            return _post_rows(a, b - a, stars, scanned.ndim, res, opts.return_distreds,
+                              self._yield_row_blocks)
 
-        pending = None        # (future of phase 2, row arguments) of an earlier batch
-        unsub = [None]        # (slot, row arguments) of the batch whose phase 2 is not submitted yet
-        try:
-            fut = pool.submit(scan, 0) if ahead else None
-            for kb, a in enumerate(starts):
-                b = min(Ndata, a + step)
-                S = b - a
-                with torch.cuda.device(dev):
-                    ready = None
-                    if ahead:
-                        (rec, off, ndim, k1, k2) = fut.result()
-                        # (engine (kb + 1) % nE: with four engines its last batch was kb - 3,
-                        # whose phase 2 was waited for an iteration ago)
-                        fut = pool.submit(scan, kb + 1) if kb + 1 < len(starts) else None
-                    else:
-                        (rec, off, ndim, k1, k2) = scan(kb)
-                    pp = _lib.PostParams()
-                    pp.nmc, pp.ndraws = int(Nmc_prior), int(Ndraws)
-                    pp.return_distreds = 1 if return_distreds else 0
-                    pp.has_feh = 1 if statics[1] is not None else 0
-                    pp.has_loga = 1 if statics[2] is not None else 0
-                    pp.wt_thresh = float(wt_thresh)
-                    pp.avlim[:] = [float(avlim[0]), float(avlim[1])]
-                    pp.rvlim[:] = [float(rvlim[0]), float(rvlim[1])]
-                    pp.nsel_max = int(mem_lim / Nmc_prior / 4.0e-4)
-                    np_states = None
-                    if np_mode == "shared":
-                        np_states = state_to_words(rstate.get_state()).reshape(1, -1).copy()
-                    elif np_mode == "per_object":
-                        np_states = np.stack([state_to_words(
-                            np.random.RandomState(seed0 + i).get_state()) for i in range(a, b)])
-                    if np_mode is not None:
-                        pp.per_object, pp.object0, pp.seed = 0, 0, 0
-                        pp.normal_base = pp.uniform_base = 0
-                    elif seed0 is not None:
-                        pp.per_object, pp.object0, pp.seed = 1, a, int(seed0) & (2 ** 64 - 1)
-                        pp.normal_base = pp.uniform_base = 0
-                    else:
-                        pp.per_object, pp.object0, pp.seed = 0, 0, rstate.seed
-                        pp.normal_base, pp.uniform_base = rstate.n_normal, rstate.n_uniform
-                    for k, val in gp.items():
-                        if isinstance(val, tuple):
-                            getattr(pp, k)[:] = list(val)
-                        else:
-                            setattr(pp, k, val)
-                    dust = None
-                    if dust_tables is not None:      # this batch's sightlines; the engine hands
-                        los, ok = dust_tables(a, b)  # them to every post call and retry and keeps
-                        dust = (torch.from_numpy(np.ascontiguousarray(los)).to(dev),     # them alive
-                                torch.from_numpy(np.ascontiguousarray(ok)).to(dev))
-                    dtab = None
-                    if dist_prior is not None:       # kept alive like the dust tables
-                        dtab = (torch.from_numpy(_pdf.dist_tables(
-                                    dist_prior, data_coords[a:b])).to(dev), dist_prior.base is None)
-                    if pipelined:
-                        # Phase 2 of the previous batch is held back until the jump-ahead of
-                        # THIS batch's walk is through (its kernels need whole compute units
-                        # and would starve behind the Monte Carlo integral), then runs beside
-                        # the walk itself.  `pending`: phase 2 submitted; `unsub`: phase 1 done.
-                        if pending is not None:
-                            # Phase 2 of batch kb - 2 holds the post slot this batch takes:
-                            # wait for it here -- behind this batch's host preparations (128
-                            # generator states with per-object streams), which so overlap its
-                            # tail -- and hand out its rows later, while the device is busy
-                            # again (the records of the objects that go to the host stage are
-                            # copied out now).
-                            prev, pargs = pending
-                            pending = None
-                            ready = pargs + prev.result() + (0,)
-                            ready = ready + (flagged_records(*ready),)
-                        sub = []
+        return _post_schedule(len(bounds), _PostStages(scan, call_args, begin, end, whole, rows),
+                              ahead, pipelined)
 
-                        def submit_prev():
-                            if unsub[0] is not None:
-                                slot_, args_ = unsub[0]
-                                unsub[0] = None
-                                sub.append((finisher.submit(finish, slot_), args_))
-                        with torch.cuda.stream(walk_stream):
-                            began = eng.post_numpy_begin(
-                                kb % 2, rec, S, statics, data_coords[a:b],
-                                parallax[a:b], parallax_err[a:b], pp, np_states, dust=dust,
-                                after_jump=submit_prev, dtab=dtab)
-                        if sub:
-                            pending = sub[0]
-                        if began:
-                            if np_mode == "shared":   # final already: the walk is done
-                                rstate.set_state(words_to_state(np_states[0]))
-                            unsub[0] = (kb % 2, (a, S, rec, off, ndim, k1, k2))
-                        if ready is not None:
-                            for row in rows(*ready):
-                                yield row
-                        if began:
-                            continue
-                        if pending is not None:      # whole-call form for this batch, in order
-                            prev, pargs = pending
-                            pending = None
-                            for row in rows(*(pargs + prev.result() + (0,))):
-                                yield row
-                    out_idx, out_vals, star_out, flags, nbase = eng.post_batch_device(
-                        rec, S, statics, data_coords[a:b],
-                        parallax[a:b], parallax_err[a:b], pp, np_states=np_states, dust=dust,
-                        dtab=dtab)
-                    ubase0 = pp.uniform_base
-                    if np_mode == "shared":      # the caller's generator continues from here
-                        rstate.set_state(words_to_state(np_states[0]))
-                    elif np_mode is None and seed0 is None:
-                        # what the batch consumed from the shared stream
-                        rstate.n_normal = int(nbase[S])
-                        rstate.n_uniform = int(ubase0) + S * K
-                    for row in rows(a, S, rec, off, ndim, k1, k2, out_idx, out_vals,
-                                    star_out, flags, nbase, ubase0):
-                        yield row
-            if pending is not None:
-                prev, pargs = pending
-                pending = None
-                for row in rows(*(pargs + prev.result() + (0,))):
-                    yield row
-            if unsub[0] is not None:
-                slot_, pargs = unsub[0]
-                unsub[0] = None
-                for row in rows(*(pargs + finisher.submit(finish, slot_).result() + (0,))):
-                    yield row
-        finally:
-            # also when the caller abandons the generator: the scan that runs ahead still
-            # writes its engine's workspace and record buffers (it ends with a stream
-            # synchronize), and the next `_fit` on this object starts on the same engines
-            if pool is not None:
-                pool.shutdown(wait=True)
-            if finisher is not None:
-                finisher.shutdown(wait=True)     # a running phase 2 still reads the buffers
-
-    def _first_cut_with_ext(self, eng, data, err, mask, par, perr, params,
-                            lnprior_ext, offset, wt_thresh, cdf_thresh=None):
-        """First cut on the host from the full-grid device outputs, for the two rare
-        options the device cut does not cover: external per-object Gaussian label
+    def _first_cut_with_ext(self, eng, stars, a, b, params, lnprior_ext, wt_thresh,
+                            cdf_thresh=None):
+        """First cut of objects a:b on the host from the full-grid device outputs, for the two
+        rare options the device cut does not cover: external per-object Gaussian label
         constraints, which modify lnlike over the whole grid before the cut
         (fitting.py:1995-2009), and CDF thresholding (`wt_thresh=None`, fitting.py:992-998),
         whose selection comes in ascending-lnprob order."""
+        data, err, mask, par, perr = (x[a:b] for x in stars[:5])
         res = eng.loglike_batch(data, err, mask, par, perr, params)
         recs = []
         for s in range(data.shape[0]):
             lnl = res["lnl"][s].copy()
             for k in (lnprior_ext.keys() if lnprior_ext is not None else ()):
-                mean, std = lnprior_ext[k][offset + s]
+                mean, std = lnprior_ext[k][a + s]
                 if np.isfinite(mean) and std > 0:
                     chi2e = (self.models_labels[k] - mean) ** 2 / std ** 2
                     lnl += -0.5 * (chi2e + np.log(2. * np.pi * std ** 2))
@@ -1824,12 +1827,10 @@ class BruteForce(object):
         return recs
 
     @staticmethod
-    def _finish_star(rec, parallax, parallax_err, coord, Nmc_prior, lnprior,
-                     wt_thresh, cdf_thresh, lngalprior, lndustprior, dustfile,
-                     dlabels, avlim, rvlim, mem_lim, rstate, apply_av_prior,
-                     Ndraws, return_distreds):
+    def _finish_star(rec, parallax, parallax_err, coord, rstate, opts):
         """lnpost's host stage + evidence + resampling for one object
         (reference fitting.py:2012-2065)."""
+        Nmc_prior, Ndraws, return_distreds = opts.Nmc_prior, opts.Ndraws, opts.return_distreds
         sel0 = rec["sel"]
         Ndim = rec["Ndim"]
         with warnings.catch_warnings(), np.errstate(all="ignore"):
@@ -1837,11 +1838,8 @@ class BruteForce(object):
             # lnprob of the first cut is only consumed by the Nmc_prior=0 branch
             (sel, cov_sar, lnprob, dists, reds, dreds,
              logwts) = _lnpost_selected(
-                sel0, rec["lnlike"], rec["scale"], rec["av"], rec["rv"],
-                rec["icov"], lnprior, parallax, parallax_err, coord, Nmc_prior,
-                wt_thresh, cdf_thresh, lngalprior, lndustprior, dustfile,
-                dlabels, avlim, rvlim, rstate, apply_av_prior, mem_lim,
-                rec["lnlike"])
+                (sel0, rec["lnlike"], rec["scale"], rec["av"], rec["rv"], rec["icov"]),
+                rec["lnlike"], parallax, parallax_err, coord, rstate, opts)
             Nsel = len(sel)
             # position of the final selection inside the first-cut records (which are in
             # ascending model order, except after CDF thresholding)
