@@ -73,7 +73,7 @@ class BinpdfParams(C.Structure):
 
 # name -> (restype, argtypes); mirrors include/brutus_amd.h (product ABI) and
 # include/brutus_amd_debug.h (test hooks / measurement aids, see DEBUG_NAMES) one to one
-DEBUG_NAMES = ("brutus_calibrate_traffic", "brutus_calibrate_copy16", "brutus_calibrate_issue", "brutus_debug_exp10", "brutus_debug_math", "brutus_debug_mt_stream", "brutus_debug_rng", "brutus_debug_galprior", "brutus_debug_galprior_mc", "brutus_debug_galprior_sl", "brutus_debug_dist_table", "brutus_debug_zig_table", "brutus_debug_copy", "brutus_debug_sizeof_star32", "brutus_debug_fit_stats", "brutus_debug_pre32_time", "brutus_debug_binpdf_draws")
+DEBUG_NAMES = ("brutus_calibrate_traffic", "brutus_calibrate_copy16", "brutus_calibrate_issue", "brutus_debug_exp10", "brutus_debug_math", "brutus_debug_mt_stream", "brutus_debug_plan_streams", "brutus_debug_rng","brutus_debug_galprior", "brutus_debug_galprior_mc", "brutus_debug_galprior_sl", "brutus_debug_dist_table", "brutus_debug_zig_table", "brutus_debug_copy", "brutus_debug_sizeof_star32", "brutus_debug_fit_stats", "brutus_debug_pre32_time", "brutus_debug_binpdf_draws")
 SIGNATURES = {
     "brutus_abi_version": (C.c_int, []),
     "brutus_last_error": (C.c_char_p, []),
@@ -111,6 +111,7 @@ SIGNATURES = {
                                                 _vp, _vp, C.POINTER(PostParams), _vp, _sz, _vp,
                                                 _vp, _vp, _vp, _i32, _vp, _vp, _sz, _i32, _vp]),
     "brutus_debug_mt_stream": (C.c_int, [_i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp]),
+    "brutus_debug_plan_streams": (C.c_int, [_i32, _vp, _vp, _vp, _i32, _vp, _vp, _i64, _vp, _i64]),
     "brutus_set_mt_jump": (C.c_int, [_vp, _i32, _i64, _i64]),
     "brutus_post_set_dust": (C.c_int, [_vp, _vp, _i32, _dbl, _dbl, _dbl, _dbl]),
     "brutus_post_set_dist_table": (C.c_int, [_vp, _i32, _i32]),

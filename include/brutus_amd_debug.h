@@ -19,6 +19,21 @@ int brutus_debug_mt_stream(int nobj, int nstream, uint32_t *h_states,
                            const int64_t *h_nnorm, int nuni, double *d_z, double *d_u,
                            void *stream);
 
+/* Test hook: the host plan of the many-workgroup walk of nstream streams (needs no GPU, only the
+ * jump polynomials of brutus_set_mt_jump).  Stream g serves objects [h_seg[g], h_seg[g + 1]),
+ * which need h_nnorm[o] normals and nuni uniforms each, and stands at word h_pos0[g] of its block.
+ *   h_totals[8]   sub-streams of all streams, slots of all streams, first-level chain entries,
+ *                 second-level chain entries, MT_J, MT_L1, MT_SB, 0
+ *   h_subs        (sub-streams, 4): q0, q1, skip, stream -- stream by stream, in stream order
+ *   h_chains      (entries, 4) in launch order: level (1, 2); round of the first level / windows
+ *                 made in a row by the second; source window; (first) destination window
+ * BRUTUS_EINVAL if a stream is longer than the polynomials reach, BRUTUS_ENOMEM (h_totals filled)
+ * if the plan has more than max_subs sub-streams or max_chains chain entries. */
+int brutus_debug_plan_streams(int nstream, const int32_t *h_seg, const int32_t *h_pos0,
+                              const int64_t *h_nnorm, int nuni, int64_t *h_totals,
+                              int64_t *h_subs, int64_t max_subs, int64_t *h_chains,
+                              int64_t max_chains);
+
 /* Test hooks for the two building blocks above. */
 int brutus_debug_rng(uint64_t seed, uint64_t start, int64_t n, double *d_normals,
                      double *d_uniforms, void *stream);

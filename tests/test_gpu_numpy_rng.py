@@ -414,3 +414,113 @@ def test_pipeline_with_a_late_phase_two_equals_the_sequential_form():
             assert np.array_equal(a[0], b[0]), (delay, i)
             for x, y in zip(a[1:], b[1:]):
                 assert np.array_equal(np.asarray(x), np.asarray(y)), (delay, i)
+
+
+_P = ["k_post_lnp1", "k_post_cut2"]
+_T = ["k_post_mc", "k_post_cdf", "k_post_draw"]
+# case -> (grid seed, objects, objects per batch, generator, environment, mem_lim)
+_SECTION_CASES = {
+    "philox": (31, 4, 4, "philox", {}, None),
+    "philox, Nsel_max clip": (51, 4, 4, "philox", {}, 20 * 4e-4 * 300),           # Nsel_max = 300
+    "numpy, two phases": (31, 8, 4, "numpy", {}, None),
+    "numpy, two phases, one workgroup per stream": (31, 8, 4, "numpy", {"BRUTUS_MT_PARALLEL": "0"}, None),
+    "numpy, small buffer": (57, 9, 5, "numpy", {"BRUTUS_AMD_ZBUF_GB": "0.003"}, None),
+}
+
+
+@pytest.mark.parametrize("case", sorted(_SECTION_CASES))
+def test_post_call_sections(case, capfd, monkeypatch):
+    """The timed sections the lnpost of ONE batch issues, in order, for each driver of
+    csrc/post_unit.hip (post_philox, post_numpy_whole, post_numpy_phase1 + post_numpy_phase2),
+    read off the drivers: P = second cut, T = Monte Carlo integral, cdf, draws.  Kernel timing
+    is on -- phase 2 then keeps its parked k_mt_emit on the one stream, inside a section of its
+    own -- and the sections are the "[brutus] <section> ..." lines the library's timer writes to
+    stderr under BRUTUS_TRACE_KERNELS=1.  The suite's small shape (6 000 x 8, Nmc_prior=20,
+    Ndraws=60); every result is held against the oracle like the neighbouring tests'.
+    `_fit` takes the two-phase form only when there is a next batch to overlap with, so the
+    numpy cases run two batches under a stand-in for `fitting._post_schedule` that issues the
+    same stage calls one after the other on this thread (phase 1, then phase 2 -- or, where
+    phase 1 declines, the whole call) and traces the first batch alone: no two lnpost calls
+    trace at once.  With the small buffer phase 1 runs the second cut and declines ("normal
+    buffer too small"); the whole call starts over and serves the objects in groups through the
+    sequential walker."""
+    import contextlib
+    import re
+    from brutus_amd import _lib, fitting
+    from brutus_amd.galprior import gal_lnprior
+    from brutus_amd.rng import PhiloxRandomState
+    from oracle import brutus_oracle as O
+    seed, n, batch, gen, env, mem_lim = _SECTION_CASES[case]
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    L = _lib.lib()
+
+    @contextlib.contextmanager
+    def traced(on=True):
+        if on:
+            os.environ["BRUTUS_TRACE_KERNELS"] = "1"
+            L.brutus_enable_timing(1)
+        try:
+            yield
+        finally:
+            if on:
+                L.brutus_enable_timing(0)
+                del os.environ["BRUTUS_TRACE_KERNELS"]
+
+    taken = []
+
+    def one_after_the_other(nbatch, stages, ahead, pipelined):
+        assert nbatch == 2 and pipelined
+        for k in range(nbatch):
+            scanned, call = stages.scan(k), stages.args(k)
+            with traced(k == 0):
+                taken.append(stages.begin(k, k % 2, scanned, call, lambda: None))
+                res = stages.end(k % 2) if taken[-1] else stages.whole(k, scanned, call)
+            yield from stages.rows(k, scanned, res)
+
+    BF, models, labels, st, lnprior = _bf(seed=seed)
+    BF.batch_size = batch
+    new = (lambda: PhiloxRandomState(9)) if gen == "philox" else (lambda: np.random.RandomState(2024))
+    rs, ro = new(), new()
+    kw = dict(Nmc_prior=20, Ndraws=60, **({} if mem_lim is None else {"mem_lim": mem_lim}))
+    if gen == "numpy":
+        monkeypatch.setattr(fitting, "_post_schedule", one_after_the_other)
+    capfd.readouterr()
+    with traced(gen == "philox"):
+        dev = list(BF._fit(st["flux"][:n], st["err"][:n], st["mask"][:n], parallax=st["parallax"][:n],
+                           parallax_err=st["parallax_err"][:n], lnprior=lnprior, lngalprior=gal_lnprior,
+                           data_coords=st["coords"][:n], rstate=rs, **kw))
+    begun = re.findall(r"^\[brutus\] (k_(?:post|mt)_\w+) \.\.\.$", capfd.readouterr().err, flags=re.M)
+    print(case, taken, begun)
+    if case == "philox":
+        assert begun == _P + _T, begun
+    elif case == "philox, Nsel_max clip":
+        nclip = begun.count("k_post_clip")
+        assert nclip >= 1 and begun == _P + nclip * ["k_post_clip"] + _T, begun
+    elif case == "numpy, two phases":
+        assert taken == [True, True]
+        assert begun == _P + ["k_mt_jump", "k_mt_bits", "k_mt_resolve", "k_mt_emit"] + _T, begun
+    elif case == "numpy, two phases, one workgroup per stream":
+        assert taken == [True, True]
+        assert begun == _P + ["k_mt_stream"] + _T, begun
+    else:
+        assert taken[0] is False
+        group = ["k_mt_stream"] + _T
+        ngroup = (len(begun) - 2 * len(_P)) // len(group)
+        assert ngroup >= 2 and begun == _P + _P + ngroup * group, begun
+    assert len(dev) == n
+    for i in range(n):
+        ref = O.fit_star(st["flux"][i], st["err"][i], st["mask"][i], models, lnprior, labels,
+                         st["coords"][i], st["parallax"][i], st["parallax_err"][i], ro, gal_lnprior, **kw)
+        assert np.array_equal(dev[i][0], ref[0]), (case, i)
+        for name, a, b in zip(NAMES[1:], ref[1:], dev[i][1:]):
+            if gen == "philox" and name in ("reds", "dreds"):
+                # (a drawn Av / Rv may land near zero: measured against the array's largest
+                # value, as tests/test_gpu_lnpost.py does for its Philox runs)
+                a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+                err = float(np.max(np.abs(a - b)) / np.max(np.abs(a))) if a.size else 0.
+            else:
+                err = relerr(a, b)
+            assert err < 1e-8, (case, i, name, err)
+    if gen == "numpy":
+        assert np.array_equal(rs.random_sample(5), ro.random_sample(5))

@@ -1,6 +1,7 @@
 """CPU: the counter-based random state (brutus_amd/rng.py), the specification
 the device stream is checked against on the GPU."""
 import numpy as np
+import pytest
 
 from brutus_amd.rng import (PhiloxRandomState, philox4x32, philox_normal,
                             philox_uniform)
@@ -104,3 +105,76 @@ def test_choice_semantics_match_numpy_legacy():
     assert rs.n_uniform == 1001
     counts = np.bincount(idx, minlength=5) / 1000.
     assert np.max(np.abs(counts - p)) < 0.06
+
+
+def _plan_streams(seg, pos0, nnorm, nuni, cap=4096):
+    """brutus_debug_plan_streams -> (totals dict, subs (K, 4), chains (n, 4))"""
+    from brutus_amd import _lib
+    seg, pos0 = np.asarray(seg, np.int32), np.asarray(pos0, np.int32)
+    nnorm = np.asarray(nnorm, np.int64)
+    tot, subs, chains = np.zeros(8, np.int64), np.zeros((cap, 4), np.int64), np.zeros((cap, 4), np.int64)
+    _lib.check(_lib.lib().brutus_debug_plan_streams(len(pos0), seg.ctypes.data, pos0.ctypes.data,
+                                                    nnorm.ctypes.data, nuni, tot.ctypes.data,
+                                                    subs.ctypes.data, cap, chains.ctypes.data, cap))
+    t = dict(zip("Ktot Ttot n1 n2 J L1 SB".split(), (int(v) for v in tot)))
+    return t, subs[:t["Ktot"]], chains[:t["n1"] + t["n2"]]
+
+
+PLAN_SHAPES = {
+    "one object, block start": ([0, 1], [0], [5550], 120),
+    "one object, last word of the block": ([0, 1], [623], [5550], 120),
+    "one object, block used up": ([0, 1], [624], [5550], 120),
+    "one stream, five objects": ([0, 5], [17], [30000, 0, 151, 24975, 3000000], 500),
+    "five streams, one object each": ([0, 1, 2, 3, 4, 5], [0, 623, 624, 311, 5],
+                                      [150 * 200, 0, 1, 9000001, 75 * 333], 20),
+    "two first-level rounds and more": ([0, 2], [101], [21000000, 7], 500),
+}
+
+
+@pytest.mark.parametrize("shape", sorted(PLAN_SHAPES))
+def test_stream_plan_invariants(shape):
+    """What the kernels of the many-workgroup stream walk take for granted about the host plan
+    (csrc/post_unit.hip, plan_streams; the hook needs no GPU): within a stream the sub-streams'
+    slot ranges tile [0, T) in order, every interior boundary is a multiple of 64 (k_mt_bits
+    writes whole bitmap words), T is a multiple of the superblock MT_SB, `skip` is the word of
+    the sub-stream's window at which slot q0 begins, the windows reach past the stream's last
+    slot, and every window but a stream's first is made by exactly one jump from a window that
+    is complete in an earlier round (first level: doubling rounds, launched in order; second
+    level: one launch after them, each chain sequential inside its workgroup)."""
+    seg, pos0, nnorm, nuni = PLAN_SHAPES[shape]
+    t, subs, chains = _plan_streams(seg, pos0, nnorm, nuni)
+    J, L1, SB = t["J"], t["L1"], t["SB"]
+    assert (J, L1, SB) == (624 * 3360, 4, 4096)
+    nstream = len(pos0)
+    assert sorted(set(subs[:, 3])) == list(range(nstream)) and np.all(np.diff(subs[:, 3]) >= 0)
+    first, Tsum = [], 0
+    for g in range(nstream):
+        rows = np.where(subs[:, 3] == g)[0]
+        q0, q1, skip = subs[rows, 0], subs[rows, 1], subs[rows, 2]
+        K, T = len(rows), int(q1[-1])
+        first.append(int(rows[0]))
+        assert q0[0] == 0 and np.array_equal(q1[:-1], q0[1:]) and np.all(q0 <= q1), (g, q0, q1)
+        assert np.all(q0[1:] % 64 == 0), (g, q0)
+        assert T > 0 and T % SB == 0, (g, T)
+        assert np.array_equal(skip, pos0[g] + 4 * q0 - np.arange(K) * J), (g, skip)
+        assert np.all(skip >= 0) and np.all(skip[1:] < 4 * 64 + 4), (g, skip)
+        assert (K - 1) * J < pos0[g] + 4 * T <= K * J or K == 1, (g, K, T)
+        # (room for what the objects draw: a slot per pair of normals and per two uniforms)
+        objs = range(seg[g], seg[g + 1])
+        assert T >= sum((nnorm[o] + 1) // 2 for o in objs) + len(objs) * nuni // 2
+        Tsum += T
+    assert Tsum == t["Ttot"] and len(subs) == t["Ktot"]
+    made = {w: -1 for w in first}                      # window -> round in which it is complete
+    for level, r, src, dst in chains[:t["n1"]]:
+        assert level == 1 and dst not in made and made.get(src, r) < r, (level, r, src, dst)
+        assert (dst - src) % L1 == 0
+        made[int(dst)] = int(r)
+    assert np.all(np.diff(chains[:t["n1"], 1]) >= 0)   # (launched round by round)
+    for level, n, src, dst in chains[t["n1"]:]:
+        assert level == 2 and 1 <= n < L1 and src in made and made[src] < 16 and dst == src + 1
+        for w in range(dst, dst + n):
+            assert w not in made, w
+            made[int(w)] = 16
+    assert sorted(made) == list(range(t["Ktot"]))
+    if shape.startswith("two first-level"):
+        assert len(set(chains[:t["n1"], 1])) >= 2, chains[:t["n1"]]
