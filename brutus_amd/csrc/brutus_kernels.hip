@@ -365,6 +365,7 @@ struct FitCall {
     Timer tm;
     // set by dispatch_fit
     int flux_rounds = 4;    // BRUTUS_FLUX_ROUNDS (development switch): continuations of the device-driven flux phase
+    bool list_fast = true;  // BRUTUS_LIST_FAST (development switch): the plane passes that skip dead blocks
     bool audited = false;   // this call's float32 bound is audited and ENFORCED (audit_verdict)
     float *aud = nullptr;   // w.aud on an audited call and with BRUTUS_AUDIT=1 (recorded for the caller to read)
 };
@@ -564,8 +565,15 @@ void cull_candidates(FitCall &c) {
     hipLaunchKernelGGL(k_top_decide, dim3(nstar), dim3(256), 0, c.st, c.nblkx, nstar, w.ids_all, 0, w.part,
                        w.s32, c.p.ln_init, (const double *)nullptr, w.thr_cull, w.candS);
     c.tm.begin("k_surv_compact");
-    hipLaunchKernelGGL(k_cmp_count32, dim3(NCHUNK, nstar), blk, 0, c.st, c.nmodel, c.ntile, w.lnlp32, w.candS,
-                       w.counts, w.smask);
+    if (!c.list_fast)
+        hipLaunchKernelGGL(k_cmp_count32, dim3(NCHUNK, nstar), blk, 0, c.st, c.nmodel, c.ntile, w.lnlp32, w.candS,
+                           w.counts, w.smask);
+    else if (c.nmodel % 4 == 0)
+        hipLaunchKernelGGL(k_cmp_count32_live<true>, dim3(NCHUNK, nstar), blk, 0, c.st, c.nmodel, c.ntile, nstar,
+                           w.lnlp32, w.part32, w.candS, w.counts, w.smask);
+    else
+        hipLaunchKernelGGL(k_cmp_count32_live<false>, dim3(NCHUNK, nstar), blk, 0, c.st, c.nmodel, c.ntile, nstar,
+                           w.lnlp32, w.part32, w.candS, w.counts, w.smask);
     const OffsetsJob job{w.counts, w.coffsets, w.surv_off, w.wbase_surv, w.res + ResBlock::CANDIDATES};
     hipLaunchKernelGGL(k_offsets, dim3(2), dim3(OFF_T), 0, c.st, nstar, job, job);
     hipLaunchKernelGGL(k_items, dim3((NCHUNK * nstar + 255) / 256), dim3(256), 0, c.st, nstar, w.wbase_surv,
@@ -668,8 +676,13 @@ void select_and_derive(FitCall &c) {
     hipLaunchKernelGGL(k_top_decide, dim3(nstar), dim3(256), 0, c.st, c.nblkx, nstar, w.ids_all, 1, w.part,
                        w.s32, c.p.ln_wt, w.maxsurv, w.thr_sel, (double *)nullptr);
     c.tm.begin("k_sel_classify");
-    hipLaunchKernelGGL(k_sel_classify, dim3(NCHUNK, nstar), blk, 0, c.st, c.nmodel, c.ntile, w.s32, w.lnpr32, w.lnprob_st,
-                       w.surv_off, w.thr_sel, w.counts, w.mask, w.dcounts, w.dmask, w.surv_idx, w.bandn);
+    if (c.list_fast && c.nmodel % 4 == 0)
+        hipLaunchKernelGGL(k_sel_classify_live, dim3(NCHUNK, nstar), blk, 0, c.st, c.nmodel, c.ntile, nstar, w.s32,
+                           w.lnpr32, w.part32, w.candS, w.lnprob_st, w.surv_off, w.thr_sel, w.counts, w.mask, w.dcounts,
+                           w.dmask, w.surv_idx, w.bandn);
+    else        // (the dword form of the skipping pass measured no faster than this kernel)
+        hipLaunchKernelGGL(k_sel_classify, dim3(NCHUNK, nstar), blk, 0, c.st, c.nmodel, c.ntile, w.s32, w.lnpr32,
+                           w.lnprob_st, w.surv_off, w.thr_sel, w.counts, w.mask, w.dcounts, w.dmask, w.surv_idx, w.bandn);
     c.tm.end();
     c.tm.begin("k_sel_band");      // (the candidate lists in surv_idx are no longer needed)
     hipLaunchKernelGGL((k_sel_band<NB, RVF>), dim3(NCHUNK / SB_C, nstar, SB_Z), blk, 0, c.st, c.grid, c.nmodel,
@@ -762,6 +775,8 @@ int dispatch_fit(int nb, FitCall &c) {
     c.audited = every > 0 && call_no % every == 0;
     c.aud = env_int("BRUTUS_AUDIT", 0) != 0 || c.audited ? c.w.aud : nullptr;
     c.flux_rounds = env_int("BRUTUS_FLUX_ROUNDS", 4);
+    // BRUTUS_LIST_FAST=0: the plane passes of the cull and the first cut as they were, every block read (A/B, tests)
+    c.list_fast = env_int("BRUTUS_LIST_FAST", 1) != 0;
     // (two translation units, one definition of the shared layout: pre32_types.hpp)
     if (brutus_i_pre32_layout(0) != (int)sizeof(Star32) || brutus_i_pre32_layout(1) != (int)sizeof(P32) ||
         brutus_i_pre32_layout(2) != F2_T || brutus_i_pre32_layout(3) != TILE || brutus_i_pre32_layout(4) != NV32)
@@ -1070,6 +1085,8 @@ int brutus_debug_copy(void *d_workspace, size_t workspace_bytes, int64_t nmodel,
         case 7: src = w.thr_sel; have = 8 * (size_t)nstar; break;
         case 8: src = w.st32; have = 4 * (size_t)nstar * NV32; break;
         case 9: src = w.status; have = 4 * (size_t)nstar; break;
+        case 10: src = w.part32; have = 4 * (size_t)((pad_models(nmodel) / TILE + F2_T - 1) / F2_T) * nstar * NV32; break;
+        case 11: src = w.candS; have = 8 * (size_t)nstar; break;
         default: return fail(BRUTUS_EINVAL, "unknown array %d", which);
     }
     if (nbytes > have) return fail(BRUTUS_EINVAL, "array %d holds %zu bytes, %zu requested", which, have, nbytes);

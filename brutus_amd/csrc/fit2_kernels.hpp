@@ -829,6 +829,248 @@ k_sel_classify(int64_t nmodel, int ntile, const Star32 *__restrict__ s32,
     }
 }
 
+// ---------------------------------------------------------------------------
+// k_cmp_count32_live + k_sel_classify_live: the two plane passes, dead blocks skipped
+// ---------------------------------------------------------------------------
+// The float32 pass leaves, per (F2_T-tile block, star), the maxima of both statistics over the
+// block (part32 columns 6 and 7; NaN lanes are left out of them and flagged in column 9).  Once
+// the thresholds stand, a block whose maximum is below them provably holds no hit:
+//   dead for the cull:       (double)max lnl_p~ < candS[s], no NaN flag
+//                            (the lanes' own test is !((double)v < candS[s]))
+//   dead for the first cut:  dead for the cull -- so no survivor tag stands in the block, its
+//                            lnprob~ entries are as the float32 pass left them --, and
+//                            (double)max lnprob~ < thr_sel[s] - eps, no NaN flag
+//                            (neither selected, v >= thr + eps, nor in the band, !(v < thr - eps))
+// A dead block's plane entries are not read: its membership words are written as zeros, nothing
+// is counted or queued.  The maxima describe the planes as they stand: every float32 pass
+// (opening, re-run) writes a star's planes and its partials together, over all blocks.
+//
+// Geometry: a wave takes units of LIST_U tiles (aligned, so a unit lies in one block), the four
+// waves of a workgroup the units of the chunk in turn; the verdicts of 64 blocks are one ballot.
+// V4 (nmodel % 4 == 0: a star's plane row starts on 16 bytes): a lane loads four consecutive
+// models as one 16-byte access, a wave one tile per load.  Word w of the tile = the lanes'
+// 4-bit hit patterns of lanes 16 w .. 16 w + 15 side by side: the patterns, shifted to their
+// place in a dword, are ORed across each 8 lanes on the DPP path and leave as eight dwords.
+// !V4 (count pass only): four dword loads per tile (lane + 64 k), one ballot per word.
+constexpr int LIST_U = 4;                   // tiles per unit = 16-byte loads in flight per lane (8: no faster)
+static_assert(F2_T % LIST_U == 0, "a unit of the list passes must not straddle two blocks");
+
+// bit j = block b0 + j of star s is LIVE (blocks past `blast` read as live; they are never asked)
+__device__ __forceinline__ unsigned long long
+live_blocks(const float *__restrict__ part32, int nstar, int s, int b0, int blast, double cand,
+            bool first_cut, double thr_lo) {
+    const int b = b0 + (int)(threadIdx.x & 63);
+    bool live = true;
+    if (b <= blast) {
+        const float *pp = part32 + ((int64_t)b * nstar + s) * NV32;
+        const float m6 = pp[6], m7 = pp[7], f9 = pp[9];        // (one round trip, not three)
+        const bool dead = ((double)m6 < cand) & (f9 <= 0.f) & (!first_cut | ((double)m7 < thr_lo));
+        live = !dead;
+    }
+    return __ballot(live);
+}
+
+// the LIST_U x 4 plane entries of a lane's unit, all loads in flight at once (clamped
+// addresses, see k_cmp_count32); entries outside [ta, tz) x [0, nmodel) read as -inf.
+// Model of entry (u, k): V4  t * TILE + 4 * lane + k;   !V4  t * TILE + 64 * k + lane.
+template <bool V4>
+__device__ __forceinline__ int64_t unit_model(int t, int k, int lane) {
+    return (int64_t)t * TILE + (V4 ? 4 * lane + k : 64 * k + lane);
+}
+template <bool V4>
+__device__ __forceinline__ void unit_load(const float *__restrict__ row, int64_t nmodel, int q,
+                                          int ta, int tz, int lane, float (&v)[LIST_U][4]) {
+#pragma unroll
+    for (int u = 0; u < LIST_U; ++u) {
+        const int t = q * LIST_U + u;
+        const bool tin = t >= ta && t < tz;
+        if constexpr (V4) {
+            const int64_t i = unit_model<true>(t, 0, lane);
+            const bool in = tin && i < nmodel;       // (nmodel % 4 == 0: all four or none)
+            const float4 x = *reinterpret_cast<const float4 *>(row + (in ? i : nmodel - 4));
+            v[u][0] = in ? x.x : -INFINITY;
+            v[u][1] = in ? x.y : -INFINITY;
+            v[u][2] = in ? x.z : -INFINITY;
+            v[u][3] = in ? x.w : -INFINITY;
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int64_t i = unit_model<false>(t, k, lane);
+                const bool in = tin && i < nmodel;
+                const float x = row[in ? i : nmodel - 1];
+                v[u][k] = in ? x : -INFINITY;
+            }
+        }
+    }
+}
+
+// the four membership words of tile t of a star's row from the lanes' hits.  `tin`: the tile is
+// in the unit's range -- a store predicate, not a branch around the tile's work: with a branch
+// the compiler sinks the tile's load into it and waits there, one load at a time
+template <bool V4>
+__device__ __forceinline__ void tile_words(unsigned long long *__restrict__ mrow, int t, bool tin, int lane,
+                                           const bool (&hit)[4]) {
+    if constexpr (V4) {
+        int y = ((hit[0] ? 1 : 0) | (hit[1] ? 2 : 0) | (hit[2] ? 4 : 0) | (hit[3] ? 8 : 0)) << (4 * (lane & 7));
+        y |= dpp_i32<0xB1, 0xf>(y);         // quad_perm [1, 0, 3, 2]
+        y |= dpp_i32<0x4E, 0xf>(y);         // quad_perm [2, 3, 0, 1]
+        y |= dpp_i32<0x141, 0xf>(y);        // row_half_mirror: the other quad of the eight lanes
+        if (tin && (lane & 7) == 0) reinterpret_cast<int *>(mrow)[(int64_t)t * 8 + (lane >> 3)] = y;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const unsigned long long b = __ballot(hit[k]);
+            if (tin && lane == 0) mrow[(int64_t)t * 4 + k] = b;
+        }
+    }
+}
+// ... all zero, for the tiles [ta, tz) of a dead unit (at most LIST_U * 8 = 32 dwords)
+__device__ __forceinline__ void zero_words(unsigned long long *__restrict__ mrow, int ta, int tz, int lane) {
+    if (lane < (tz - ta) * 8) reinterpret_cast<int *>(mrow)[(int64_t)ta * 8 + lane] = 0;
+}
+
+// The walk both passes share: f(q, ta, tz, live) for this wave's units of chunk [t0, t1).
+template <class F>
+__device__ __forceinline__ void walk_units(int t0, int t1, const float *__restrict__ part32, int nstar,
+                                           int s, double cand, bool first_cut, double thr_lo, F f) {
+    if (t0 >= t1) return;
+    constexpr int QB = F2_T / LIST_U;       // units per block
+    const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int blast = (t1 - 1) / F2_T;
+    for (int bs = t0 / F2_T; bs <= blast; bs += 64) {
+        const unsigned long long live = live_blocks(part32, nstar, s, bs, blast, cand, first_cut, thr_lo);
+        const int qa = max(t0 / LIST_U, bs * QB);
+        const int qz = min((t1 + LIST_U - 1) / LIST_U, (bs + 64) * QB);
+        for (int q = qa + w; q < qz; q += TILE / 64)
+            f(q, max(q * LIST_U, t0), min(q * LIST_U + LIST_U, t1), ((live >> (q / QB - bs)) & 1ull) != 0ull);
+    }
+}
+
+template <bool V4>
+__global__ void __launch_bounds__(TILE)
+k_cmp_count32_live(int64_t nmodel, int ntile, int nstar, const float *__restrict__ plane,
+                   const float *__restrict__ part32, const double *__restrict__ thr,
+                   int64_t *__restrict__ counts, unsigned long long *__restrict__ mask) {
+    __shared__ int wsum[4];
+    const int s = blockIdx.y, c = blockIdx.x;
+    const int t0 = (int)((int64_t)ntile * c / NCHUNK), t1 = (int)((int64_t)ntile * (c + 1) / NCHUNK);
+    const double th = thr[s];
+    const int lane = threadIdx.x & 63;
+    const float *row = plane + (int64_t)s * nmodel;
+    unsigned long long *mrow = mask + (int64_t)s * (4 * ntile);
+    int n = 0;
+    walk_units(t0, t1, part32, nstar, s, th, false, 0., [&](int q, int ta, int tz, bool live) {
+        if (!live) {
+            zero_words(mrow, ta, tz, lane);
+            return;
+        }
+        float v[LIST_U][4];
+        unit_load<V4>(row, nmodel, q, ta, tz, lane, v);
+#pragma unroll
+        for (int u = 0; u < LIST_U; ++u) {
+            const int t = q * LIST_U + u;
+            const bool tin = t >= ta && t < tz;
+            bool hit[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                // (pad lanes of the last tile never count, whatever the threshold: -inf or NaN included)
+                hit[k] = tin & (unit_model<V4>(t, k, lane) < nmodel) & !((double)v[u][k] < th);
+                n += hit[k] ? 1 : 0;
+            }
+            tile_words<V4>(mrow, t, tin, lane, hit);
+        }
+    });
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) n += __shfl_xor(n, off, 64);
+    if (lane == 0) wsum[threadIdx.x >> 6] = n;
+    __syncthreads();
+    if (threadIdx.x == 0) counts[(int64_t)s * NCHUNK + c] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+}
+
+// (16-byte form only: with dword loads the skip buys this pass nothing -- 168 against 165 us for
+// k_sel_classify on the bench's grid --, so a model count that is no multiple of four keeps that kernel)
+__global__ void __launch_bounds__(TILE)
+k_sel_classify_live(int64_t nmodel, int ntile, int nstar, const Star32 *__restrict__ s32,
+                    const float *__restrict__ lnpr32, const float *__restrict__ part32,
+                    const double *__restrict__ candS,
+                    const double *__restrict__ lnprob_st, const int64_t *__restrict__ cand_off,
+                    const double *__restrict__ thr_sel,
+                    int64_t *__restrict__ counts, unsigned long long *__restrict__ mask,
+                    int64_t *__restrict__ dcounts, unsigned long long *__restrict__ dmask,
+                    int32_t *__restrict__ bandq, int32_t *__restrict__ bandn) {
+    __shared__ int qn;
+    __shared__ int wsum[4], dsum[4];
+    if (threadIdx.x == 0) qn = 0;
+    __syncthreads();
+    const int s = blockIdx.y, c = blockIdx.x;
+    const int t0 = (int)((int64_t)ntile * c / NCHUNK), t1 = (int)((int64_t)ntile * (c + 1) / NCHUNK);
+    const double th = thr_sel[s];
+    const double e = (double)s32[s].eps;
+    const int64_t cbase = cand_off[s];
+    const int lane = threadIdx.x & 63;
+    const float *row = lnpr32 + (int64_t)s * nmodel;
+    unsigned long long *mrow = mask + (int64_t)s * (4 * ntile), *drow = dmask + (int64_t)s * (4 * ntile);
+    int32_t *queue = bandq + (int64_t)s * nmodel + (int64_t)t0 * TILE;
+    int n = 0, nd = 0;
+    walk_units(t0, t1, part32, nstar, s, candS[s], true, th - e, [&](int q, int ta, int tz, bool live) {
+        if (!live) {
+            zero_words(mrow, ta, tz, lane);
+            zero_words(drow, ta, tz, lane);
+            return;
+        }
+        float v32[LIST_U][4];
+        unit_load<true>(row, nmodel, q, ta, tz, lane, v32);
+        // (the survivors' staged values: second round of loads, again all in flight)
+        double vst[LIST_U][4];
+#pragma unroll
+        for (int u = 0; u < LIST_U; ++u)
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                vst[u][k] = surv_is(v32[u][k]) ? lnprob_st[cbase + surv_slot(v32[u][k])] : 0.;
+#pragma unroll
+        for (int u = 0; u < LIST_U; ++u) {
+            const int t = q * LIST_U + u;
+            const bool tin = t >= ta && t < tz;
+            bool yes[4], der[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int64_t i = unit_model<true>(t, k, lane);
+                bool bd = false;
+                yes[k] = der[k] = false;
+                if (tin && i < nmodel) {
+                    if (surv_is(v32[u][k])) {
+                        yes[k] = vst[u][k] > th;
+                    } else {
+                        const double v = (double)v32[u][k];
+                        yes[k] = der[k] = v >= th + e;
+                        bd = !yes[k] && !(v < th - e);
+                    }
+                }
+                n += yes[k] ? 1 : 0;
+                nd += der[k] ? 1 : 0;
+                if (bd) queue[atomicAdd(&qn, 1)] = (int32_t)i;
+            }
+            tile_words<true>(mrow, t, tin, lane, yes);
+            tile_words<true>(drow, t, tin, lane, der);
+        }
+    });
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        n += __shfl_xor(n, off, 64);
+        nd += __shfl_xor(nd, off, 64);
+    }
+    if (lane == 0) {
+        wsum[threadIdx.x >> 6] = n;
+        dsum[threadIdx.x >> 6] = nd;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        counts[(int64_t)s * NCHUNK + c] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+        dcounts[(int64_t)s * NCHUNK + c] = dsum[0] + dsum[1] + dsum[2] + dsum[3];
+        bandn[s * NCHUNK + c] = qn;
+    }
+}
+
 // grid = (NCHUNK / SB_C, nstar, SB_Z): the queues of SB_C neighbouring chunks form one list
 // (a single chunk queues ~50 models on the Av-only bench: a quarter of the lanes, and 8 192
 // workgroups that each pay the full index -> row -> MLE latency chain); a list longer than a
