@@ -7,7 +7,7 @@ no GPU is visible, every compute entry point raises.
 import ctypes as C
 import os
 
-__all__ = ["lib", "Params", "PostParams", "BinpdfParams", "check", "LIB_PATH", "BrutusError", "NVALS",
+__all__ = ["lib", "Params", "PostParams", "BinpdfParams", "IsoParams", "check", "LIB_PATH", "BrutusError", "NVALS",
            "MAX_BATCH", "MAX_FILT", "MAX_FILT_FIT"]
 
 # BRUTUS_AMD_LIB: another build of the same library (A/B kernel timing)
@@ -60,6 +60,19 @@ class PostParams(C.Structure):
                 ("age_sigma", C.c_double * 3), ("age_lnnorm", C.c_double * 3),
                 ("min_age", C.c_double), ("max_age", C.c_double),
                 ("frame_mat", C.c_double * 9), ("frame_off", C.c_double * 3)]
+
+
+class IsoParams(C.Structure):
+    """struct brutus_iso_params (include/brutus_amd.h)."""
+    _fields_ = [(n, C.c_int32) for n in
+                ("nfeh", "nafe", "nloga", "neep_tab", "npred", "idx_mini", "idx_logl", "idx_logt",
+                 "idx_logg", "idx_feh_surf", "idx_afe_surf", "nfilt", "h1", "h2", "neep", "nsmf",
+                 "flags")] + \
+               [(n, C.c_double) for n in ("feh", "afe", "loga", "av", "rv", "dist", "mini_bound",
+                                          "eep_binary_max")] + [("corr", C.c_double * 4)]
+
+
+ISO_APPLY_CORR, ISO_EEP2_GIVEN, ISO_PRED_ONLY = 1, 2, 4
 
 
 class BinpdfParams(C.Structure):
@@ -152,6 +165,8 @@ SIGNATURES = {
                                                _vp, _vp, _vp, _i32, _vp, _sz, _i32, _i32, _vp]),
     "brutus_cluster_lnl_merge": (C.c_int, [_i32, _i32, _vp, _sz, _vp, _vp]),
     "brutus_cluster_mix": (C.c_int, [_i32, _vp, _vp, C.c_double, C.c_double, _vp, _vp, _vp]),
+    "brutus_iso_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "brutus_iso_seds_grid": (C.c_int, [C.POINTER(IsoParams)] + [_vp] * 14 + [_sz, _vp]),
 }
 
 

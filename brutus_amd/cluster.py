@@ -2,8 +2,9 @@
 
 Host-side mirror of reference `brutus/cluster.py:isochrone_loglike`
 (cluster.py:23-419).  The population model (`isochrone.get_seds`, the MIST/NN
-isochrone generator of reference `seds.py`) stays a host-side, duck-typed
-plug-in exactly as in the reference (cluster.py:339-344); the hot block -- the
+isochrone generator of reference `seds.py`) stays a duck-typed plug-in exactly as
+in the reference (cluster.py:339-344) -- a host-side one, or `seds.Isochrone`, which
+makes its magnitudes on the device --; the hot block -- the
 chi2 of every object against every isochrone point of every
 secondary-mass-fraction slice, the chi-square/normal log-pdf and the
 marginalisation over mass and mass fraction (cluster.py:379-407) -- runs in the
@@ -127,7 +128,10 @@ def _isochrone_loglike(theta, isochrone, phot, err, cluster_params, offsets, cor
     is asked for a GROUP of consecutive mass fractions at a time (`smf_grid` = that group, 3
     growing groups per call by default, BRUTUS_CLUSTER_PIPELINE) instead of once per mass fraction; with
     `out=` it fills the page-locked buffer the device copy starts from.  Either way the device
-    turns a group into fluxes and sums it while the plug-in works on the next one."""
+    turns a group into fluxes and sums it while the plug-in works on the next one.  A plug-in that
+    offers `get_seds_grid_device(smf_grid=, out=, ...same keywords...) -> mini (Neep,)`
+    (`seds.Isochrone`) is asked once instead, for all mass fractions, and fills the device tensor
+    `out (Nsmf, Neep, Nbands)` the sum reads: its magnitudes never visit the host."""
     from .fitting import _torch, _stream_ptr
     from scipy.stats import chi2 as chisquare
     if phot is None:
@@ -397,8 +401,9 @@ def _staging(nrow, nb, dev, torch):
 # Whole calls per second, same box: 1 group 1 235, 2 groups 1 380, 3 groups 1 400-1 420,
 # 4 groups 1 350 (equal halves before the growth: 1 300).  Marks of a call
 # (tools/dev/cluster_marks.py, 3 groups): plug-in 0.10 + 0.10 + 0.13 ms, host waiting for the
-# device at the end 0.19 ms.  A plug-in that takes milliseconds per slice (the MIST /
-# neural-net isochrones) hides the device entirely with any split; BRUTUS_CLUSTER_PIPELINE
+# device at the end 0.19 ms.  A HOST plug-in that takes milliseconds per slice (MIST / neural-net
+# isochrones in numpy) hides the device entirely with any split -- seds.Isochrone makes them on
+# the device instead and is asked once, `get_seds_grid_device` below; BRUTUS_CLUSTER_PIPELINE
 # sets the number of groups (1: one call to the plug-in and one sum, as before round 4).
 # (Tried: the group's copy on a stream of its own, beside the previous group's sum.  Through
 # torch the stream context and two events cost the host more than the 0.05 ms they free
@@ -453,7 +458,11 @@ def _point_table(isochrone, feh, loga, av, rv, dist, corr_coef, smf_grid, grad_s
               mini_bound=mini_bound, eep_binary_max=eep_binary_max, corr_params=corr_coef)
     nsmf, neep = len(smf_grid), len(eep_grid)
     nrow = nsmf * neep
-    bounds = _group_bounds(nsmf, int(os.environ.get("BRUTUS_CLUSTER_PIPELINE", _PIPELINE_GROUPS)))
+    # a plug-in that makes its magnitudes on the device (seds.Isochrone) is asked once, for all
+    # slices, straight into the staging tensor: there is no host work to hide behind groups
+    dev_hook = hasattr(isochrone, "get_seds_grid_device")
+    bounds = [0, nsmf] if dev_hook else \
+        _group_bounds(nsmf, int(os.environ.get("BRUTUS_CLUSTER_PIPELINE", _PIPELINE_GROUPS)))
     ngroup = len(bounds) - 1
     nchunk = L.brutus_cluster_chunks()
     cbounds = [0]                                   # partial-sum chunks in proportion, >= 1 each
@@ -497,7 +506,14 @@ def _point_table(isochrone, feh, loga, av, rv, dist, corr_coef, smf_grid, grad_s
         for g in range(ngroup):
             a, b = bounds[g], bounds[g + 1]
             c0, c1 = cbounds[g], cbounds[g + 1]
-            if grid_hook:
+            if dev_hook:
+                mini = np.asarray(isochrone.get_seds_grid_device(
+                    smf_grid=smf_grid[a:b], out=stage.d_mags.view(nsmf, neep, Nbands)[a:b], **kw),
+                    dtype=np.float64)
+                if mini.ndim != 1:
+                    raise RuntimeError("get_seds_grid_device must return the one (Neep,) mass "
+                                       "grid all slices share")
+            elif grid_hook:
                 if stage.hook_out[type(isochrone)]:             # straight into pinned memory
                     mags, mini = isochrone.get_seds_grid(smf_grid=smf_grid[a:b], out=h_mags[a:b],
                                                          **kw)
@@ -516,7 +532,9 @@ def _point_table(isochrone, feh, loga, av, rv, dist, corr_coef, smf_grid, grad_s
             _mark("plug-in %d" % g)
             # the group's host -> device copy starts now, from page-locked memory, and runs
             # under the host arithmetic below
-            stage.d_mags[a * neep:b * neep].copy_(stage.h_mags[a * neep:b * neep], non_blocking=True)
+            if not dev_hook:
+                stage.d_mags[a * neep:b * neep].copy_(stage.h_mags[a * neep:b * neep],
+                                                      non_blocking=True)
             if mini.ndim == 1:
                 # one mass grid for all slices: 2 000 logarithms per call, the (slice, EEP) table
                 # of weights is formed on the device and the kept rows are looked up, not rebuilt

@@ -402,6 +402,44 @@ int brutus_cluster_lnl_merge(int nobj, int nchunk, void *d_workspace, size_t wor
 int brutus_cluster_mix(int nobj, const double *d_lnl, const double *d_lnl_outlier, double ln_fin,
                        double ln_fout, double *d_lnl_mix, double *d_lnl_tot, void *stream);
 
+/* ---- seds.Isochrone (reference seds.py:1081-1502; FastNN evaluation seds.py:960-1078) ----
+ * MIST isochrones + one small network per filter, for the plug-in of the cluster likelihood:
+ * one call makes the magnitudes of every (mass-fraction slice, EEP, filter) on the device.
+ * Float64.  Table and axes as the reference holds them AFTER build_interpolator (holes
+ * filled, a single [alpha/Fe] padded to two nodes). */
+#define BRUTUS_ISO_APPLY_CORR 1  /* empirical Teff / radius corrections (seds.py:1327-1356)     */
+#define BRUTUS_ISO_EEP2_GIVEN 2  /* d_eep2 holds np.interp's secondaries' EEPs (before the cuts) */
+#define BRUTUS_ISO_PRED_ONLY 4   /* stop after the primaries' predictions (d_prim, d_mini)      */
+typedef struct {
+    int32_t nfeh, nafe, nloga, neep_tab, npred;   /* table (nfeh, nafe, nloga, neep_tab, npred)  */
+    int32_t idx_mini, idx_logl, idx_logt, idx_logg, idx_feh_surf, idx_afe_surf; /* its columns   */
+    int32_t nfilt, h1, h2;                        /* networks 6 -> h1 -> h2 -> 1, h1 <= 64       */
+    int32_t neep, nsmf, flags;                    /* the query; BRUTUS_ISO_* bits                */
+    double feh, afe, loga, av, rv, dist;          /* dist in pc                                  */
+    double mini_bound, eep_binary_max;
+    double corr[4];                               /* dtdm, drdm, msto_smooth, feh_scale          */
+} brutus_iso_params;
+size_t brutus_iso_workspace_bytes(int neep, int nsmf, int nfilt);   /* 0: bad dimensions */
+/*   d_table   (nfeh, nafe, nloga, neep_tab, npred)       d_axes  feh | afe | loga | eep nodes
+ *   d_weights per filter w1 (h1, 6) | b1 (h1) | w2 (h2, h1) | b2 (h2) | w3 (h2) | b3 (1)
+ *   d_xmin, d_xmax (6)  bounds of the networks' inputs [Teff, logg, feh_surf, afe_surf, av, rv]
+ *   d_eep (neep), d_smf (nsmf)
+ * writes d_mags (nsmf, neep, nfilt) apparent magnitudes, combined as seds.py:1467-1496 does
+ * (NaN rows where the reference has them); d_prim (neep, npred) and d_sec (nsmf, neep, npred),
+ * the predictions of the two components (d_sec NaN outside 0 < smf < 1); d_mini (neep);
+ * d_eep2 (nsmf, neep) the secondaries' EEPs after the cuts; d_status int32[2]: [0] = 1 if the
+ * finite initial masses are not strictly increasing with EEP -- the device's bisection is
+ * then not np.interp, and the caller repeats the call with np.interp's values in d_eep2 and
+ * BRUTUS_ISO_EEP2_GIVEN --, [1] the number of finite primaries.
+ * BRUTUS_EINVAL (before any HIP call): an axis with fewer than 2 nodes, npred outside
+ * [1, 16], a column index outside the table, neep / nsmf / nfilt < 1, h1 outside [1, 64] or
+ * more than 64 KiB of weights per filter, a NULL pointer.  BRUTUS_ENOMEM: workspace. */
+int brutus_iso_seds_grid(const brutus_iso_params *p, const double *d_table, const double *d_axes,
+                         const double *d_weights, const double *d_xmin, const double *d_xmax,
+                         const double *d_eep, const double *d_smf, double *d_mags, double *d_prim,
+                         double *d_sec, double *d_mini, double *d_eep2, int32_t *d_status,
+                         void *d_workspace, size_t workspace_bytes, void *stream);
+
 /* ---- utils.photometric_offsets (reference utils.py:1218-1400) ------------------------
  * The per-band bootstrap of model / data flux ratios over the resampled fits of many
  * objects.  The caller keeps numpy's random stream and the final median / std over the

@@ -1,0 +1,241 @@
+"""Shared by tools/gen_golden.py (`gen_iso`) and the isochrone tests: the synthetic MIST-like
+table and networks that tests/golden/iso_seds.npz was made from, the list of its cases, and a
+numpy restatement of `seds.Isochrone` (test infrastructure, not product; it is itself checked
+against the golden in tests/test_iso_host.py)."""
+import os
+
+import numpy as np
+
+GOLDEN_ISO = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "iso_seds.npz")
+PREDICTIONS = ["mini", "mass", "logl", "logt", "logr", "logg", "feh_surf", "afe_surf"]
+EEP_QUERY = np.linspace(202., 808., 250)
+SMF_ALL = (0., 0.2, 0.5, 0.95, 1.)
+
+
+def make_table(two_afe=False, dip=False):
+    """Axes and raw predictions `(4, 1 or 2, 5, 61, 8)`: smooth in every coordinate, `mini`
+    strictly increasing with EEP (>= 1.4 at EEP 480), the oldest age without its EEPs above
+    ~700, one interior hole of 3 EEPs.  `dip`: `mini` falls once along EEP (the non-monotonic
+    case of np.interp)."""
+    feh = np.array([-1., -0.5, 0., 0.5])
+    afe = np.array([0., 0.4]) if two_afe else np.array([0.])
+    loga = np.array([8.5, 9., 9.5, 10., 10.15])
+    eep = np.linspace(200., 810., 61)
+    F, A, G, E = np.meshgrid(feh, afe, loga, eep, indexing="ij")
+    x = (E - 200.) / 610.
+    mini = 0.1 + (3.4 + 0.2 * F - 0.3 * (G - 9.) + 0.1 * A) * x
+    if dip:
+        mini = mini - 0.25 * np.exp(-0.5 * ((E - 400.) / 12.) ** 2)
+    lm = np.log10(mini)
+    logt = 3.75 + 0.45 * lm - 0.04 * F + 0.02 * A - 0.3 * x ** 3
+    logl = 4. * lm + 0.6 * x ** 2 - 0.1 * F
+    logr = 0.5 * logl - 2. * (logt - 3.762)
+    logg = 4.438 + lm - 2. * logr
+    pred = np.stack([mini, 0.98 * mini, logl, logt, logr, logg, F + 0.02 * x, A + 0.01 * x],
+                    axis=-1)
+    pred[:, :, -1, eep > 700.] = np.nan
+    pred[1, 0, 2, 20:23] = np.nan
+    return feh, afe, loga, eep, pred
+
+
+def make_networks(nfilt, h1, h2, seed):
+    """Seeded normal weights of `nfilt` networks 6 -> h1 -> h2 -> 1 and the bounds of their
+    inputs [Teff, logg, feh_surf, afe_surf, av, rv]: part of the isochrone lies outside."""
+    rng = np.random.RandomState(seed)
+    w = dict(w1=rng.normal(size=(nfilt, h1, 6)), b1=rng.normal(size=(nfilt, h1, 1)),
+             w2=rng.normal(size=(nfilt, h2, h1)) / np.sqrt(h1), b2=rng.normal(size=(nfilt, h2, 1)),
+             w3=rng.normal(size=(nfilt, 1, h2)) / np.sqrt(h2), b3=rng.normal(size=(nfilt, 1, 1)))
+    xmin = np.array([2300., 0.5, -2.1, -0.2, 0., 1.])
+    xmax = np.array([6400., 5.6, 0.75, 0.6, 4., 8.])
+    filters = ["band%02d" % i for i in range(nfilt)]
+    return w, xmin, xmax, filters
+
+
+# name -> (table keywords, networks (nfilt, h1, h2, seed), get_seds keywords, mass fractions)
+_BASE = dict(feh=-0.2, afe=0., loga=9.3, av=0.3, rv=3.1, dist=900., mini_bound=0.3,
+             eep_binary_max=480., apply_corr=True, corr_params=None)
+CASES = {
+    "young": (dict(), (5, 10, 7, 11), dict(_BASE), SMF_ALL),
+    "old": (dict(), (5, 10, 7, 11), dict(_BASE, loga=10.1, corr_params=(0.1, -0.08, 25., 0.4)),
+            (0., 0.5, 1.)),
+    "afe2": (dict(two_afe=True), (12, 16, 16, 12), dict(_BASE, afe=0.15, feh=0.3), (0.95,)),
+    "nocorr": (dict(), (5, 10, 7, 11), dict(_BASE, apply_corr=False), (0.5,)),
+    "outside": (dict(), (5, 10, 7, 11), dict(_BASE, feh=0.9), (0.5,)),
+}
+MINI_BOUND_SMF02 = 0.08        # (the slice smf = 0.2 has no secondary above 0.3 solar masses)
+
+
+def case_kwargs(name, smf):
+    kw = dict(CASES[name][2])
+    if smf == 0.2:
+        kw["mini_bound"] = MINI_BOUND_SMF02
+    return kw
+
+
+def case_arrays(name):
+    """The arguments of `Isochrone.from_arrays` for a case."""
+    tab, net = CASES[name][:2]
+    feh, afe, loga, eep, pred = make_table(**tab)
+    w, xmin, xmax, filters = make_networks(*net)
+    return dict(feh=feh, afe=afe, loga=loga, eep=eep, pred_grid=pred, weights=w, xmin=xmin,
+                xmax=xmax, filters=filters)
+
+
+# The likelihood cases: 200 objects x 5 bands drawn from the isochrone itself.
+LNL_THETA = np.array([-0.2, 9.3, 0.3, 3.1, 900., 0.05])
+
+
+def make_lnl_data(get_seds):
+    """Photometry of 200 objects on the "young" isochrone (`get_seds`: the reference's, when
+    the golden is made; the data are stored there)."""
+    rng = np.random.RandomState(77)
+    feh, loga, av, rv, dist, _ = LNL_THETA
+    eep = rng.uniform(230., 700., 1000)
+    mag = get_seds(feh=feh, loga=loga, av=av, rv=rv, eep=eep, smf=0., dist=dist,
+                   mini_bound=0.08)[0]
+    mag = mag[np.all(np.isfinite(mag), axis=1)][:200]
+    assert mag.shape[0] == 200
+    flux = 10. ** (-0.4 * mag)
+    err = 0.04 * flux
+    phot = flux + rng.normal(size=flux.shape) * err
+    miss = rng.uniform(size=phot.shape) < 0.06
+    miss[:, 0] = False
+    phot[miss] = np.nan
+    par = 1e3 / dist + rng.normal(size=200) * 0.04
+    perr = np.full(200, 0.04)
+    par[rng.uniform(size=200) < 0.3] = np.nan
+    return phot, err, par, perr
+
+
+class HostIsochrone(object):
+    """`seds.Isochrone` restated in numpy, whole arrays at a time: what a user could run on the
+    host.  The secondaries' EEPs come from `np.interp`, as in the reference."""
+
+    def __init__(self, feh, afe, loga, eep, pred_grid, weights, xmin, xmax, filters,
+                 predictions=None):
+        self.filters, self.predictions = filters, list(predictions or PREDICTIONS)
+        grid = np.array(pred_grid, dtype=np.float64)
+        eep = np.unique(eep)
+        for track in grid.reshape(-1, grid.shape[-2], grid.shape[-1]):
+            sel = np.all(np.isfinite(track), axis=1)
+            if sel.any():
+                for p in range(track.shape[1]):
+                    track[:, p] = np.interp(eep, eep[sel], track[sel, p], left=np.nan, right=np.nan)
+        afe = np.unique(afe)
+        if len(afe) == 1:
+            afe, grid = np.array([afe[0] - 1e-5, afe[0] + 1e-5]), np.concatenate([grid, grid], axis=1)
+        self.xgrid, self.pred_grid = (np.unique(feh), afe, np.unique(loga), eep), grid
+        self.w = {k: np.asarray(v, float) for k, v in weights.items()}
+        self.xmin, self.xmax = np.asarray(xmin, float), np.asarray(xmax, float)
+        self.col = {n: i for i, n in enumerate(self.predictions)}
+
+    def get_predictions(self, feh=0., afe=0., loga=8.5, eep=None, apply_corr=True,
+                        corr_params=None):
+        eep = np.asarray(eep, float)
+        idx, wts, inside = [], [], np.ones(eep.shape, bool)
+        with np.errstate(all="ignore"):
+            for ax, q in zip(self.xgrid, (feh, afe, loga, eep)):
+                q = np.broadcast_to(np.asarray(q, float), eep.shape)
+                i = np.clip(np.searchsorted(ax, q, side="right") - 1, 0, len(ax) - 2)
+                idx.append(i)
+                wts.append((q - ax[i]) / (ax[i + 1] - ax[i]))
+                inside &= (q >= ax[0]) & (q <= ax[-1])
+            out = np.zeros(eep.shape + (self.pred_grid.shape[-1],))
+            for corner in range(16):
+                bits = [(corner >> (3 - d)) & 1 for d in range(4)]
+                w = np.ones(eep.shape)
+                for d in range(4):
+                    w = w * (wts[d] if bits[d] else 1. - wts[d])
+                out = out + self.pred_grid[idx[0] + bits[0], idx[1] + bits[1], idx[2] + bits[2],
+                                           idx[3] + bits[3]] * w[:, None]
+            out[~inside] = np.nan
+            if apply_corr:
+                dtdm, drdm, smooth, scale = (0.09, -0.09, 30., 0.5) if corr_params is None else corr_params
+                mini = out[:, self.col["mini"]]
+                damp = (1. - 1. / (1. + np.exp(-(eep - 454.) / smooth))) * np.exp(scale * feh)
+                dlogt = np.where(mini >= 1., 0., np.log10(1. + (mini - 1.) * dtdm) * damp)
+                dlogr = np.where(mini >= 1., 0., np.log10(1. + (mini - 1.) * drdm) * damp)
+                out[:, self.col["logt"]] += dlogt
+                out[:, self.col["logl"]] += 2. * dlogr
+                out[:, self.col["logg"]] -= 2. * dlogr
+        return out
+
+    def inputs(self, preds, av, rv):
+        """The networks' inputs of every row."""
+        c = self.col
+        n = preds.shape[0]
+        with np.errstate(all="ignore"):
+            return np.stack([10. ** preds[:, c["logt"]], preds[:, c["logg"]], preds[:, c["feh_surf"]],
+                             preds[:, c["afe_surf"]], np.full(n, av), np.full(n, rv)], axis=1)
+
+    def _mags(self, preds, av, rv, dist, mini_bound):
+        c, w = self.col, self.w
+        x = self.inputs(preds, av, rv)
+        with np.errstate(all="ignore"):
+            ok = (np.all(np.isfinite(x), axis=1) & np.all((x >= self.xmin) & (x <= self.xmax), axis=1)
+                  & (preds[:, c["mini"]] >= mini_bound))
+            sig = lambda a: 1. / (1. + np.exp(-a))
+            xe = ((np.where(ok[:, None], x, self.xmin) - self.xmin) / (self.xmax - self.xmin)).T
+            a1 = sig(np.matmul(w["w1"], xe) + w["b1"])                       # (Nfilt, H1, N)
+            a2 = sig(np.matmul(w["w2"], a1) + w["b2"])
+            bc = (np.matmul(w["w3"], a2) + w["b3"])[:, 0, :].T               # (N, Nfilt)
+            m = (-2.5 * preds[:, c["logl"]] + 4.74)[:, None] - bc + (5. * np.log10(dist) - 5.)
+        m[~ok] = np.nan
+        return m
+
+    def get_seds(self, feh=0., afe=0., loga=8.5, eep=None, av=0., rv=3.3, smf=0., dist=1000.,
+                 mini_bound=0.5, eep_binary_max=480., apply_corr=True, corr_params=None,
+                 return_dict=True, **kwargs):
+        eep = np.asarray(eep, float)
+        kw = dict(feh=feh, afe=afe, loga=loga, apply_corr=apply_corr, corr_params=corr_params)
+        p1 = self.get_predictions(eep=eep, **kw)
+        seds = self._mags(p1, av, rv, dist, mini_bound)
+        p2 = np.full_like(p1, np.nan)
+        if 0. < smf < 1.:
+            mini = p1[:, self.col["mini"]]
+            fin = np.isfinite(mini)
+            eep2 = np.full_like(eep, np.nan)
+            if fin.any():
+                eep2 = np.interp(mini * smf, mini[fin], eep[fin], left=np.nan, right=np.nan)
+            with np.errstate(all="ignore"):
+                eep2[(eep2 > eep_binary_max) | (eep > eep_binary_max)] = np.nan
+                p2 = self.get_predictions(eep=eep2, **kw)
+                seds2 = self._mags(p2, av, rv, dist, mini_bound)
+                seds = -2.5 * np.log10(10. ** (-0.4 * seds) + 10. ** (-0.4 * seds2))
+        elif smf == 1.:
+            seds[eep <= eep_binary_max] -= 2.5 * np.log10(2.)
+        if return_dict:
+            d1 = dict(zip(self.predictions, p1.T))
+            return seds, d1, (dict(d1) if smf == 1. else dict(zip(self.predictions, p2.T)))
+        return seds, p1, p2
+
+    def get_seds_grid(self, smf_grid=(0.,), **kw):
+        kw.pop("smf", None)
+        res = [self.get_seds(smf=s, **kw) for s in smf_grid]
+        return np.stack([r[0] for r in res]), res[0][1]["mini"]
+
+
+class SedsOnly(object):
+    """A plug-in that shows `isochrone_loglike` only the `get_seds` of another one."""
+
+    def __init__(self, iso):
+        self.get_seds = iso.get_seds
+
+
+def assert_matches(seds, p1, p2, golden, name, smf, kw):
+    """`get_seds(..., return_dict=False)` output against the golden of a case: identical NaN
+    pattern; finite values to 1e-9, absolute in magnitudes and relative in parameters."""
+    ref = (golden["%s_smf%g_seds" % (name, smf)], golden["%s_mb%g_params" % (name, kw["mini_bound"])],
+           golden["%s_smf%g_params2" % (name, smf)])
+    for what, got, want, rel in zip(("seds", "params", "params2"), (seds, p1, p2), ref,
+                                    (False, True, True)):
+        assert got.shape == want.shape, (what, got.shape, want.shape)
+        fin = np.isfinite(want)
+        assert np.array_equal(np.isnan(got), np.isnan(want)), (name, smf, what)
+        assert np.array_equal(np.isfinite(got), fin), (name, smf, what)
+        err = np.abs(got[fin] - want[fin])
+        if rel:
+            err = err / np.maximum(np.abs(want[fin]), 1e-300)
+        worst = float(err.max()) if err.size else 0.
+        print("%s smf=%g %s: worst %s error %.3g" % (name, smf, what, "relative" if rel else "absolute", worst))
+        assert worst < 1e-9, (name, smf, what, worst)

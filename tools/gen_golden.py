@@ -352,6 +352,93 @@ def gen_cluster():
     np.savez_compressed(os.path.join(OUT, "cluster.npz"), **res)
 
 
+def gen_iso():
+    """`seds.Isochrone.get_seds` (reference seds.py:1360-1502) and `cluster.isochrone_loglike`
+    with that isochrone, on the synthetic table and networks of tests/iso_helpers.py.  The
+    conditions of the golden (no comparison hinges on a rounding flip) are asserted here, on
+    the reference's own output."""
+    import importlib
+    import inspect
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import iso_helpers as H
+    S = importlib.import_module("brutus.seds")
+
+    def reference(name):
+        a = H.case_arrays(name)
+        iso = object.__new__(S.Isochrone)
+        iso.filters, iso.predictions, iso.pred_labels = a["filters"], H.PREDICTIONS, H.PREDICTIONS
+        iso.feh_grid, iso.afe_grid, iso.loga_grid, iso.eep_grid = a["feh"], a["afe"], a["loga"], a["eep"]
+        iso.pred_grid = a["pred_grid"].copy()
+        iso.build_interpolator()
+        nn = object.__new__(S.FastNNPredictor)
+        nn.filters, nn.NFILT = a["filters"], len(a["filters"])
+        for k, v in a["weights"].items():
+            setattr(nn, k, v)
+        nn.xmin, nn.xmax, nn.xspan = a["xmin"], a["xmax"], a["xmax"] - a["xmin"]
+        iso.FNNP = nn
+        return iso, H.HostIsochrone(**a)
+
+    def clear(v, bound, span=1.):
+        v = np.asarray(v, float)
+        v = v[np.isfinite(v)]
+        return v.size == 0 or np.min(np.abs(v - bound)) > 1e-6 * span
+
+    res = {}
+    for name, (_, _, _, smfs) in H.CASES.items():
+        iso, host = reference(name)
+        if name == "young":
+            res["pred_grid"] = iso.pred_grid
+            for k, ax in enumerate(iso.xgrid):
+                res["xgrid%d" % k] = ax
+        for smf in smfs:
+            kw = H.case_kwargs(name, smf)
+            seds, p1, p2 = iso.get_seds(eep=H.EEP_QUERY, smf=smf, return_dict=False, **kw)
+            tag = "%s_smf%g" % (name, smf)
+            res[tag + "_seds"], res[tag + "_params2"] = seds, p2
+            res["%s_mb%g_params" % (name, kw["mini_bound"])] = p1
+            fin, nan = np.all(np.isfinite(seds), axis=1), np.all(np.isnan(seds), axis=1)
+            print("iso", tag, "finite rows", fin.sum(), "all-NaN rows", nan.sum(), "of", len(fin))
+            if name == "outside":
+                assert nan.all()
+                continue
+            assert not nan.all() and not fin.all(), tag
+            if smf != 0.2:
+                assert fin.mean() >= 0.15 and nan.mean() >= 0.05, tag
+            # nothing sits on a threshold: the networks' bounds, the mass cuts, the binary cut
+            mini = p1[:, 0]
+            eep2 = np.full_like(mini, np.nan)
+            if 0. < smf < 1.:
+                ok = np.isfinite(mini)
+                eep2 = np.interp(mini * smf, mini[ok], H.EEP_QUERY[ok], left=np.nan, right=np.nan)
+            for p in (p1, p2):
+                x = host.inputs(p, kw["av"], kw["rv"])
+                for d in range(6):
+                    for b in (host.xmin[d], host.xmax[d]):
+                        assert clear(x[:, d], b, host.xmax[d] - host.xmin[d]), (tag, d)
+                assert clear(p[:, 0], kw["mini_bound"]) and clear(p[:, 0], 1.), tag
+            assert clear(H.EEP_QUERY, kw["eep_binary_max"]) and clear(eep2, kw["eep_binary_max"]), tag
+    for meth in ("__init__", "get_predictions", "get_corrections", "get_seds"):
+        res["sig_" + meth] = str(inspect.signature(getattr(S.Isochrone, meth)))
+
+    # the likelihood with the reference isochrone: 200 objects x 5 bands, 15 x 250 points
+    iso, _ = reference("young")
+    phot, err, par, perr = H.make_lnl_data(iso.get_seds)
+    res.update(lnl_phot=phot, lnl_err=err, lnl_par=par, lnl_perr=perr)
+    for dp in (True, False):
+        tot, mix = C.isochrone_loglike(H.LNL_THETA, iso, phot.copy(), err.copy(), parallax=par.copy(),
+                                       parallax_err=perr.copy(), eep_grid=H.EEP_QUERY,
+                                       dim_prior=dp, return_lnls=True)
+        res["lnl_dp%d_tot" % dp], res["lnl_dp%d_mix" % dp] = tot, mix
+        print("iso lnl dim_prior", dp, tot)
+    theta2 = np.concatenate([H.LNL_THETA, np.linspace(0.97, 1.03, 4), [0.1]])
+    tot, mix = C.isochrone_loglike(theta2, iso, phot.copy(), err.copy(), offsets=[1.0] + [None] * 4,
+                                   corr_params=[None, -0.08, 25., 0.4], eep_grid=H.EEP_QUERY,
+                                   return_lnls=True)
+    res["lnl_free_tot"], res["lnl_free_mix"] = tot, mix
+    print("iso lnl free offsets + corr_params", tot)
+    np.savez_compressed(os.path.join(OUT, "iso_seds.npz"), **res)
+
+
 def gen_orion():
     """`_fit` yields for 20 objects of the reference's real-data demo
     catalogue (demos/Orion_l204.7_b-19.2.h5: PS grizy + 2MASS JHKs magnitudes,
@@ -738,6 +825,8 @@ if __name__ == "__main__":
         gen_psd()
     if "cluster" in which:
         gen_cluster()
+    if "iso" in which:
+        gen_iso()
     if "orion" in which:
         gen_orion()
     if "philox" in which:
