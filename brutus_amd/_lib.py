@@ -7,7 +7,7 @@ no GPU is visible, every compute entry point raises.
 import ctypes as C
 import os
 
-__all__ = ["lib", "Params", "PostParams", "BinpdfParams", "IsoParams", "check", "LIB_PATH", "BrutusError", "NVALS",
+__all__ = ["lib", "Params", "PostParams", "BinpdfParams", "IsoParams", "SedParams", "check", "LIB_PATH", "BrutusError", "NVALS",
            "MAX_BATCH", "MAX_FILT", "MAX_FILT_FIT"]
 
 # BRUTUS_AMD_LIB: another build of the same library (A/B kernel timing)
@@ -73,6 +73,20 @@ class IsoParams(C.Structure):
 
 
 ISO_APPLY_CORR, ISO_EEP2_GIVEN, ISO_PRED_ONLY = 1, 2, 4
+
+
+class SedParams(C.Structure):
+    """struct brutus_sed_params (include/brutus_amd.h)."""
+    _fields_ = [(n, C.c_int32) for n in
+                ("nmini", "neep_tab", "nfeh", "nafe", "npred", "idx_loga", "idx_logl", "idx_logt",
+                 "idx_logg", "idx_feh_surf", "idx_afe_surf", "nfilt", "h1", "h2", "nmodel", "nav",
+                 "nrv", "flags")] + \
+               [(n, C.c_double) for n in ("av", "rv", "dist", "loga_max", "eep_binary_max",
+                                          "mini_min", "tol", "loga_target")] + \
+               [("corr", C.c_double * 4)]
+
+
+SED_APPLY_CORR, SED_EEP2_GIVEN, SED_PRED_ONLY, SED_FIT, SED_SCAN, SED_EEP_ONLY = 1, 2, 4, 8, 16, 32
 
 
 class BinpdfParams(C.Structure):
@@ -167,6 +181,8 @@ SIGNATURES = {
     "brutus_cluster_mix": (C.c_int, [_i32, _vp, _vp, C.c_double, C.c_double, _vp, _vp, _vp]),
     "brutus_iso_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "brutus_iso_seds_grid": (C.c_int, [C.POINTER(IsoParams)] + [_vp] * 14 + [_sz, _vp]),
+    "brutus_sed_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "brutus_sed_grid": (C.c_int, [C.POINTER(SedParams)] + [_vp] * 17 + [_sz, _vp]),
 }
 
 

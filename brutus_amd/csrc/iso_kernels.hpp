@@ -23,6 +23,8 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "interp_common.hpp"
+
 constexpr int ISO_T = 256;          // lanes per workgroup, all kernels
 constexpr int ISO_MAX_PRED = 16;    // predictions per table point
 constexpr int ISO_MAX_H1 = 64;      // units of the first hidden layer
@@ -42,61 +44,13 @@ struct IsoCall {
     int neep, nsmf, nfilt, h1, h2;
 };
 
-__device__ __forceinline__ double iso_nan() { return __longlong_as_double(0x7ff8000000000000LL); }
-
-// Cell of `x` on an ascending axis: ax[lo] <= x < ax[lo + 1], the last node in the last cell;
-// false for a coordinate outside the axis or NaN (no index is formed from it).
-__device__ __forceinline__ bool iso_cell(const double *ax, int n, double x, int &lo, double &t) {
-    lo = 0;
-    t = 0.;
-    if (!(x >= ax[0] && x <= ax[n - 1])) return false;
-    int hi = n - 1;
-#pragma unroll 1
-    for (int it = 0; it < 32 && hi - lo > 1; it++) {
-        const int mid = lo + ((hi - lo) >> 1);
-        if (ax[mid] <= x) lo = mid; else hi = mid;
-    }
-    t = (x - ax[lo]) / (ax[lo + 1] - ax[lo]);
-    return true;
-}
-
 // One row of predictions at (feh, afe, loga, eep) into out[0 .. npred): 4-D multilinear, every
 // corner enters (a NaN corner poisons the row even at weight 0), NaN outside the grid; then
 // the empirical corrections (seds.py:1327-1356) on logt, logl and logg.
 __device__ void iso_predict(const IsoTable &T, const IsoCall &c, double eep, double *out) {
     const double q[4] = {c.feh, c.afe, c.loga, eep};
-    int lo[4];
-    double t[4];
-    bool in = true;
-#pragma unroll
-    for (int d = 0; d < 4; d++) in = iso_cell(T.ax[d], T.n[d], q[d], lo[d], t[d]) && in;
-    if (!in) {
-        for (int p = 0; p < T.npred; p++) out[p] = iso_nan();
-        return;
-    }
-    double w[16];
-    size_t off[16];
-#pragma unroll
-    for (int k = 0; k < 16; k++) {      // corner k: bit 3 = feh ... bit 0 = eep, lower corner first
-        double wk = 1.;
-        size_t o = 0;
-#pragma unroll
-        for (int d = 0; d < 4; d++) {
-            const int up = (k >> (3 - d)) & 1;
-            wk = wk * (up ? t[d] : 1. - t[d]);
-            o = o * (size_t)T.n[d] + (size_t)(lo[d] + up);
-        }
-        w[k] = wk;
-        off[k] = o * (size_t)T.npred;
-    }
-    double mini = iso_nan();
-    for (int p = 0; p < T.npred; p++) {
-        double v = 0.;
-#pragma unroll
-        for (int k = 0; k < 16; k++) v = v + T.tab[off[k] + p] * w[k];
-        out[p] = v;
-        if (p == T.i_mini) mini = v;
-    }
+    if (!iso_interp4(T.tab, T.ax, T.n, T.npred, q, out)) return;
+    const double mini = out[T.i_mini];
     if (!c.apply_corr) return;
     double dlogt = log10(1. + (mini - 1.) * c.dtdm);
     double dlogr = log10(1. + (mini - 1.) * c.drdm);
@@ -167,21 +121,6 @@ k_iso_compact(int neep, const double *__restrict__ mini, const double *__restric
     }
 }
 
-// np.interp(x, xp, fp, left=nan, right=nan) for increasing xp as a bisection of at most 32 steps.
-__device__ __forceinline__ double iso_interp(double x, const double *xp, const double *fp, int n) {
-    if (n <= 0 || !(x >= xp[0] && x <= xp[n - 1])) return iso_nan();
-    if (x == xp[n - 1]) return fp[n - 1];
-    int lo = 0, hi = n - 1;
-#pragma unroll 1
-    for (int it = 0; it < 32 && hi - lo > 1; it++) {
-        const int mid = lo + ((hi - lo) >> 1);
-        if (xp[mid] <= x) lo = mid; else hi = mid;
-    }
-    if (xp[lo] == x) return fp[lo];
-    const double slope = (fp[lo + 1] - fp[lo]) / (xp[lo + 1] - xp[lo]);
-    return slope * (x - xp[lo]) + fp[lo];
-}
-
 __global__ void __launch_bounds__(ISO_T)
 k_iso_secondary(IsoTable T, IsoCall c, const double *__restrict__ eep,
                 const double *__restrict__ smf, const double *__restrict__ mini,
@@ -203,8 +142,6 @@ k_iso_secondary(IsoTable T, IsoCall c, const double *__restrict__ eep,
     eep2[r] = e2;
     iso_predict(T, c, e2, row);
 }
-
-__device__ __forceinline__ double iso_sigmoid(double a) { return 1. / (1. + exp(-a)); }
 
 // Apparent magnitude of one row in one filter (seds.py:1062-1076 under the mass cut of
 // seds.py:1456), the filter's weights in LDS: sw1 (HP, 6), sb1 (HP), sw2 (h2, HP), sb2 (h2),

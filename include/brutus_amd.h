@@ -440,6 +440,54 @@ int brutus_iso_seds_grid(const brutus_iso_params *p, const double *d_table, cons
                          double *d_sec, double *d_mini, double *d_eep2, int32_t *d_status,
                          void *d_workspace, size_t workspace_bytes, void *stream);
 
+/* ---- seds.MISTtracks / seds.SEDmaker (reference seds.py:49-857; FastNN seds.py:960-1078) ----
+ * EEP tracks + one small network per filter: predictions at labels (mini, eep, feh, afe),
+ * the SED of a single star or an unresolved binary (get_sed), and the model grid that
+ * BruteForce fits against (make_grid): per model and filter the magnitude at (av, rv) and the
+ * linear fits of the magnitudes in Av and Rv.  Float64.  Table and axes as the reference holds
+ * them AFTER build_interpolator (a single [alpha/Fe] padded to two nodes, holes NaN). */
+#define BRUTUS_SED_APPLY_CORR 1  /* empirical Teff / radius corrections at the label mass (seds.py:349-384) */
+#define BRUTUS_SED_EEP2_GIVEN 2  /* d_eep2_in holds the secondaries' EEPs; nothing is solved              */
+#define BRUTUS_SED_PRED_ONLY 4   /* stop after the primaries' predictions (d_out_param)                   */
+#define BRUTUS_SED_FIT 8         /* make_grid: (sed, seda, sedr) per filter; without it get_sed: one value */
+#define BRUTUS_SED_SCAN 16       /* loga does not rise along every track: the root nearest the primary's EEP */
+#define BRUTUS_SED_EEP_ONLY 32   /* get_eep: d_out_eep2 alone, for the age loga_target at the label's afe  */
+typedef struct {
+    int32_t nmini, neep_tab, nfeh, nafe, npred;   /* table (nmini, neep_tab, nfeh, nafe, npred)   */
+    int32_t idx_loga, idx_logl, idx_logt, idx_logg, idx_feh_surf, idx_afe_surf; /* its columns    */
+    int32_t nfilt, h1, h2;                        /* networks 6 -> h1 -> h2 -> 1, h1 <= 64        */
+    int32_t nmodel, nav, nrv, flags;              /* the query; BRUTUS_SED_* bits                 */
+    double av, rv, dist;                          /* the reference point; dist in pc              */
+    double loga_max, eep_binary_max, mini_min;    /* the cuts; mini_min binds the secondary alone */
+    double tol, loga_target;                      /* get_eep                                      */
+    double corr[4];                               /* dtdm, drdm, msto_smooth, feh_scale           */
+} brutus_sed_params;
+size_t brutus_sed_workspace_bytes(int nmodel, int nfilt, int nfit);   /* 0: bad dimensions */
+/*   d_table   (nmini, neep_tab, nfeh, nafe, npred)       d_axes  mini | eep | feh | afe nodes
+ *   d_weights, d_xmin, d_xmax as brutus_iso_seds_grid takes them
+ *   d_labels (nmodel, 5)   mini, eep, feh, afe, smf of every model
+ *   d_eep2_in (nmodel) or NULL   the secondaries' EEPs (BRUTUS_SED_EEP2_GIVEN)
+ *   d_fitcoef (2, nrv, nav)   seda = sum fitcoef[0] * mag, sedr = sum fitcoef[1] * mag over the fit
+ *                             points (av[a], rv[r]): the two weighted straight-line fits of
+ *                             seds.py:828-831 as linear functionals; d_av (nav), d_rv (nrv)
+ * writes d_out_sed (nmodel, nfilt, 3) = (mag at (av, rv), seda, sedr) with BRUTUS_SED_FIT, else
+ * (nmodel, nfilt) magnitudes; d_out_param, d_out_param2 (nmodel, npred) the predictions of the
+ * two components (param2 NaN without a secondary); d_out_eep2 (nmodel) the secondaries' EEPs,
+ * given or solved: loga along a track is piecewise linear in EEP, so the root is exact (a cell
+ * with a NaN node holds none; a target outside the range of the finite nodes takes the nearer
+ * finite end node if its squared residual is below tol); d_out_sel (nmodel) 1 where the magnitudes at (av, rv) and the
+ * primary's predictions hold no NaN -- with BRUTUS_SED_FIT the other rows of d_out_sed are NaN
+ * throughout.  d_status is reserved and may be NULL.
+ * BRUTUS_EINVAL (before any HIP call): an axis with fewer than 2 nodes, npred outside [1, 16],
+ * a column index outside the table, nmodel / nfilt < 1, nav * nrv outside [4, 256], h1 outside
+ * [1, 64] or more than 64 KiB of LDS per filter, a NULL pointer.  BRUTUS_ENOMEM: workspace. */
+int brutus_sed_grid(const brutus_sed_params *p, const double *d_table, const double *d_axes,
+                    const double *d_weights, const double *d_xmin, const double *d_xmax,
+                    const double *d_labels, const double *d_eep2_in, const double *d_fitcoef,
+                    const double *d_av, const double *d_rv, double *d_out_sed, double *d_out_param,
+                    double *d_out_param2, double *d_out_eep2, uint8_t *d_out_sel, int32_t *d_status,
+                    void *d_workspace, size_t workspace_bytes, void *stream);
+
 /* ---- utils.photometric_offsets (reference utils.py:1218-1400) ------------------------
  * The per-band bootstrap of model / data flux ratios over the resampled fits of many
  * objects.  The caller keeps numpy's random stream and the final median / std over the

@@ -439,6 +439,153 @@ def gen_iso():
     np.savez_compressed(os.path.join(OUT, "iso_seds.npz"), **res)
 
 
+def gen_sedmaker():
+    """`seds.MISTtracks` / `seds.SEDmaker` (reference seds.py:49-857): construction from a
+    library, `get_predictions`, `get_corrections`, `get_sed` and `make_grid` on the synthetic
+    tracks, networks and grids of tests/sed_helpers.py, with the `eep2` the reference's
+    `get_eep` found for every model.  The conditions of the golden are asserted here, on the
+    reference's own output."""
+    import importlib
+    import inspect
+    import warnings
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import sed_helpers as H
+    np.float = float                      # (the reference's make_grid uses the removed alias)
+    S = importlib.import_module("brutus.seds")
+    TOL = 1e-3
+
+    def reference(name):
+        a = H.case_arrays(name)
+        sm = object.__new__(S.SEDmaker)
+        sm.labels, sm.predictions = list(H.LABELS), list(H.PREDICTIONS)
+        sm.ndim, sm.npred = 4, len(sm.predictions)
+        sm.mini_idx, sm.eep_idx, sm.feh_idx = 0, 1, 2
+        for n in ("logt", "logl", "logg"):
+            setattr(sm, n + "_idx", sm.predictions.index(n))
+        sm.libparams = np.zeros(len(a["labels"]), dtype=[(n, float) for n in H.LABELS])
+        for k, n in enumerate(H.LABELS):
+            sm.libparams[n] = a["labels"][:, k]
+        sm.output = a["output"].copy()
+        sm.lib_as_grid()
+        sm._ageidx = sm.predictions.index("loga")
+        sm.add_age_weights(verbose=False)
+        sm.build_interpolator()
+        sm.filters = a["filters"]
+        nn = object.__new__(S.FastNNPredictor)
+        nn.filters, nn.NFILT = a["filters"], len(a["filters"])
+        for k, v in a["weights"].items():
+            setattr(nn, k, v)
+        nn.xmin, nn.xmax, nn.xspan = a["xmin"], a["xmax"], a["xmax"] - a["xmin"]
+        sm.FNNP = nn
+        solved, inner = {}, sm.get_eep
+
+        def get_eep(loga, mini=1., eep=350., feh=0., afe=0., smf=1., tol=1e-3):
+            with warnings.catch_warnings():
+                warnings.simplefilter("ignore")
+                e2 = inner(loga, mini=mini, eep=eep, feh=feh, afe=afe, smf=smf, tol=tol)
+                fun = (sm.get_predictions([mini * smf, e2, feh, afe])[sm._ageidx] - loga) ** 2
+            solved[(loga, mini, eep, feh, smf)] = (e2, fun)
+            return e2
+        sm.get_eep = get_eep
+        return sm, solved, H.HostSEDmaker(**a)
+
+    def clear(v, bound, span=1.):
+        v = np.asarray(v, float)
+        v = v[np.isfinite(v)]
+        return v.size == 0 or np.min(np.abs(v - bound)) > 1e-6 * span
+
+    res = {}
+    av_grid, _, rv_grid = H.default_grids()
+    for name in H.CASES:
+        sm, solved, host = reference(name)
+        kw = H.case_kwargs(name)
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            sm.make_grid(verbose=False, **kw)
+        lab = np.array([list(r) for r in sm.grid_label])
+        sed = np.array([[sm.grid_sed[f][i] for f in sm.filters] for i in range(len(lab))])
+        par = np.array([list(r) for r in sm.grid_param])
+        sel = sm.grid_sel.copy()
+        eep2 = np.array([solved.get((la, m, e, f, s), (np.nan, np.nan))
+                         for (m, e, f, a, s), la in zip(lab, par[:, 0])])
+        fun, eep2 = eep2[:, 1], eep2[:, 0]
+        print("sedmaker", name, "models", len(lab), "selected %.3f" % sel.mean(),
+              "finite secondaries %d of %d" % (np.isfinite(eep2).sum(), (lab[:, 4] > 0).sum()))
+        # the conditions: selected and unselected shares, secondaries, nothing on a threshold
+        assert sel.mean() >= 0.15 and (~sel).mean() >= 0.05, name
+        assert np.all(fun[np.isfinite(eep2)] < TOL / 10.), name
+        if name.startswith("A"):
+            assert np.isfinite(eep2).sum() >= 0.1 * (lab[:, 4] > 0).sum(), name
+        assert np.all(np.isnan(sed[~sel])) and np.all(np.isfinite(sed[sel])), name
+        ckw = {k: kw[k] for k in ("apply_corr", "corr_params") if k in kw}
+        p1 = host.get_predictions(lab[:, :4], **ckw)
+        p2 = host.get_predictions(np.c_[lab[:, 0] * lab[:, 4], eep2, lab[:, 2:4]], **ckw)
+        for p in (p1, p2):                # (Av and Rv are compared as given: nothing is computed)
+            x = host.inputs(p, 0., 3.3)
+            for d in range(4):
+                for b in (host.xmin[d], host.xmax[d]):
+                    assert clear(x[:, d], b, host.xmax[d] - host.xmin[d]), (name, d)
+        assert clear(p1[:, 0], 10.14) and clear(lab[:, 0] * lab[:, 4], 0.5), name
+        assert clear(lab[:, 0] * lab[:, 4], sm.mini_bound) and clear(lab[:, 0] * lab[:, 4], 1.), name
+        assert clear(lab[:, 1], 480.) and clear(lab[:, 1], 454.), name
+        res[name + "_sel"], res[name + "_eep2"] = sel, eep2
+        if name == "A_rvwt":              # (everything else is grid A's)
+            assert np.array_equal(sel, res["A_sel"])
+            assert not np.array_equal(sed[sel][..., 1:], res["A_sed"][sel][..., 1:])
+            res[name + "_sed"] = sed[..., 1:]
+            continue
+        res[name + "_sed"] = sed
+        if name in ("A12", "A64"):        # (the same table and grid: labels and parameters are A's)
+            assert np.array_equal(lab, res["A_label"])
+            assert np.array_equal(par, res["A_param"], equal_nan=True)
+        else:
+            res[name + "_label"], res[name + "_param"] = lab, par
+        if name in ("A", "B"):
+            tag = "two" if name == "A" else "one"
+            res[tag + "_ygrid"] = sm.ygrid
+            res[tag + "_mini_bound"] = sm.mini_bound
+            res[tag + "_grid_dims"] = sm.grid_dims
+            res[tag + "_predictions"] = np.array(sm.predictions)
+            for k, ax in enumerate(sm.xgrid):
+                res["%s_xgrid%d" % (tag, k)] = ax
+    # single calls on the two-[alpha/Fe] table: predictions, corrections, SEDs
+    sm, solved, host = reference("A")
+    pts = np.array([[1.23, 300., 0.2, 0.1], [0.8, 456.3, -0.7, 0.3], [0.62, 640., 0.45, 0.1],
+                    [0.8, 402., 0.2, 0.3], [2.3, 300., 0., 0.1], [1., 350., 0.7, 0.2],
+                    [0.45, 650., 0.2, 0.1], [0.9, 405., 0., 0.]])
+    res["pts"] = pts
+    res["pts_pred_corr"] = np.array([sm.get_predictions(p) for p in pts])
+    res["pts_pred_corrB"] = np.array([sm.get_predictions(p, corr_params=H.CORR_B) for p in pts])
+    res["pts_pred_nocorr"] = sm.get_predictions(pts, apply_corr=False)
+    res["pts_corr_1d"] = np.array([sm.get_corrections(p) for p in pts])
+    res["pts_corr_2d"] = sm.get_corrections(pts.T)
+    res["pts_corr_2dB"] = sm.get_corrections(pts.T, corr_params=H.CORR_B)
+    # (mini, eep, feh, afe, smf, av, rv, dist, eep2 given or NaN)
+    calls = np.array([[1.23, 300., 0.2, 0.1, 0., 0.4, 3.1, 900., np.nan],
+                      [1.23, 300., 0.2, 0.1, 0.6, 0.4, 3.1, 900., 281.7],
+                      [1.0, 452.5, -0.7, 0.3, 0.85, 0., 3.3, 1000., 333.3],
+                      [1.0, 483.7, 0.2, 0.3, 0.85, 0.2, 2.8, 1000., 333.3],
+                      [0.8, 402., 0.2, 0.3, 0.6, 0.2, 2.8, 1000., 300.],
+                      [2.3, 300., 0., 0.1, 0., 0., 3.3, 1000., np.nan],
+                      [0.45, 300., 0.2, 0.1, 0., 0., 3.3, 1000., np.nan],
+                      [1.0, 350., 0.2, 0.1, 0., 4.5, 3.3, 1000., np.nan],
+                      [1.0, 350., 0.2, 0.1, 0.85, 0.3, 3.3, 1000., 900.]])
+    out = []
+    for mini, eep, feh, afe, smf, av, rv, dist, e2 in calls:
+        r = sm.get_sed(mini=mini, eep=eep, feh=feh, afe=afe, smf=smf, av=av, rv=rv, dist=dist,
+                       eep2=None if np.isnan(e2) else e2, return_eep2=True, return_dict=False)
+        assert smf == 0. or r[3] is None or r[3] == e2
+        out.append(np.concatenate([r[0], r[1], r[2]]))
+    res["calls"], res["calls_out"] = calls, np.array(out)
+    for cls, meths in ((S.MISTtracks, ("__init__", "get_predictions", "get_corrections")),
+                       (S.SEDmaker, ("__init__", "get_sed", "get_eep", "make_grid"))):
+        for meth in meths:
+            res["sig_%s_%s" % (cls.__name__, meth)] = str(inspect.signature(getattr(cls, meth)))
+    path = os.path.join(OUT, "sedmaker.npz")
+    np.savez_compressed(path, **res)
+    print("sedmaker.npz: %d bytes" % os.path.getsize(path))
+
+
 def gen_orion():
     """`_fit` yields for 20 objects of the reference's real-data demo
     catalogue (demos/Orion_l204.7_b-19.2.h5: PS grizy + 2MASS JHKs magnitudes,
@@ -827,6 +974,8 @@ if __name__ == "__main__":
         gen_cluster()
     if "iso" in which:
         gen_iso()
+    if "sedmaker" in which:
+        gen_sedmaker()
     if "orion" in which:
         gen_orion()
     if "philox" in which:
