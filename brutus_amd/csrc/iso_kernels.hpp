@@ -23,19 +23,7 @@
 #include <math.h>
 #include <stdint.h>
 
-#include "interp_common.hpp"
-
-constexpr int ISO_T = 256;          // lanes per workgroup, all kernels
-constexpr int ISO_MAX_PRED = 16;    // predictions per table point
-constexpr int ISO_MAX_H1 = 64;      // units of the first hidden layer
-
-struct IsoTable {
-    const double *tab;              // (n[0], n[1], n[2], n[3], npred)
-    const double *ax[4];            // feh, afe, loga, eep axes, ascending
-    int n[4];
-    int npred;
-    int i_mini, i_logl, i_logt, i_logg, i_feh_surf, i_afe_surf;
-};
+#include "seds_common.hpp"
 
 struct IsoCall {
     double feh, afe, loga, av, rv, mu, mini_bound, eep_binary_max;
@@ -47,42 +35,36 @@ struct IsoCall {
 // One row of predictions at (feh, afe, loga, eep) into out[0 .. npred): 4-D multilinear, every
 // corner enters (a NaN corner poisons the row even at weight 0), NaN outside the grid; then
 // the empirical corrections (seds.py:1327-1356) on logt, logl and logg.
-__device__ void iso_predict(const IsoTable &T, const IsoCall &c, double eep, double *out) {
+__device__ void iso_predict(const SedsTable &T, const IsoCall &c, double eep, double *out) {
     const double q[4] = {c.feh, c.afe, c.loga, eep};
     if (!iso_interp4(T.tab, T.ax, T.n, T.npred, q, out)) return;
-    const double mini = out[T.i_mini];
     if (!c.apply_corr) return;
-    double dlogt = log10(1. + (mini - 1.) * c.dtdm);
-    double dlogr = log10(1. + (mini - 1.) * c.drdm);
-    const double ecorr = 1. - 1. / (1. + exp(-(eep - 454.) / c.msto_smooth));
-    const double fcorr = exp(c.feh_scale * c.feh);
-    dlogt *= ecorr * fcorr;
-    dlogr *= ecorr * fcorr;
-    if (mini >= 1.) dlogt = dlogr = 0.;
+    double dlogt, dlogr;
+    seds_corrections(out[T.i_first], eep, c.feh, c.dtdm, c.drdm, c.msto_smooth, c.feh_scale, dlogt, dlogr);
     out[T.i_logt] += dlogt;
     out[T.i_logl] += 2. * dlogr;
     out[T.i_logg] -= 2. * dlogr;
 }
 
-__global__ void __launch_bounds__(ISO_T)
-k_iso_primary(IsoTable T, IsoCall c, const double *__restrict__ eep, double *__restrict__ prim,
+__global__ void __launch_bounds__(SEDS_T)
+k_iso_primary(SedsTable T, IsoCall c, const double *__restrict__ eep, double *__restrict__ prim,
               double *__restrict__ mini) {
-    const int i = blockIdx.x * ISO_T + threadIdx.x;
+    const int i = blockIdx.x * SEDS_T + threadIdx.x;
     if (i >= c.neep) return;
     double *row = prim + (size_t)i * T.npred;
     iso_predict(T, c, eep[i], row);
-    mini[i] = row[T.i_mini];
+    mini[i] = row[T.i_first];
 }
 
 // The finite primaries, in order: xp = mini, fp = eep (seds.py:1470-1473).  status[0] = 1 if
 // a pair of neighbours is not increasing (np.interp is then not a bisection), status[1] = count.
-__global__ void __launch_bounds__(ISO_T)
+__global__ void __launch_bounds__(SEDS_T)
 k_iso_compact(int neep, const double *__restrict__ mini, const double *__restrict__ eep,
               double *__restrict__ xp, double *__restrict__ fp, int32_t *__restrict__ status) {
-    __shared__ int s_cnt[ISO_T];
+    __shared__ int s_cnt[SEDS_T];
     __shared__ int s_bad;
     const int tid = threadIdx.x;
-    const int per = (neep + ISO_T - 1) / ISO_T;
+    const int per = (neep + SEDS_T - 1) / SEDS_T;
     const int a = min(tid * per, neep), b = min(a + per, neep);
     int n = 0;
     for (int i = a; i < b; i++) n += isfinite(mini[i]) ? 1 : 0;
@@ -90,7 +72,7 @@ k_iso_compact(int neep, const double *__restrict__ mini, const double *__restric
     if (tid == 0) s_bad = 0;
     __syncthreads();
     int first = 0, total = 0;
-    for (int k = 0; k < ISO_T; k++) {
+    for (int k = 0; k < SEDS_T; k++) {
         first += k < tid ? s_cnt[k] : 0;
         total += s_cnt[k];
     }
@@ -121,13 +103,13 @@ k_iso_compact(int neep, const double *__restrict__ mini, const double *__restric
     }
 }
 
-__global__ void __launch_bounds__(ISO_T)
-k_iso_secondary(IsoTable T, IsoCall c, const double *__restrict__ eep,
+__global__ void __launch_bounds__(SEDS_T)
+k_iso_secondary(SedsTable T, IsoCall c, const double *__restrict__ eep,
                 const double *__restrict__ smf, const double *__restrict__ mini,
                 const double *__restrict__ xp, const double *__restrict__ fp,
                 const int32_t *__restrict__ status, double *__restrict__ eep2,
                 double *__restrict__ sec) {
-    const int r = blockIdx.x * ISO_T + threadIdx.x;
+    const int r = blockIdx.x * SEDS_T + threadIdx.x;
     if (r >= c.nsmf * c.neep) return;
     const int s = r / c.neep, i = r - s * c.neep;
     const double f = smf[s];
@@ -144,16 +126,18 @@ k_iso_secondary(IsoTable T, IsoCall c, const double *__restrict__ eep,
 }
 
 // Apparent magnitude of one row in one filter (seds.py:1062-1076 under the mass cut of
-// seds.py:1456), the filter's weights in LDS: sw1 (HP, 6), sb1 (HP), sw2 (h2, HP), sb2 (h2),
-// sw3 (h2), sb3 (1), rows / columns past h1 zero.
+// seds.py:1456), the filter's weights in LDS as nn_stage leaves them.
 template <int HP>
-__device__ __forceinline__ double iso_mag(const IsoTable &T, const IsoCall &c,
+__device__ __forceinline__ double iso_mag(const SedsTable &T, const IsoCall &c,
                                           const double *__restrict__ row,
                                           const double *__restrict__ xmin,
                                           const double *__restrict__ xmax, const double *sw) {
-    const double mini = row[T.i_mini], logl = row[T.i_logl];
+    const double mini = row[T.i_first], logl = row[T.i_logl];
     const double x[6] = {pow(10., row[T.i_logt]), row[T.i_logg], row[T.i_feh_surf],
                          row[T.i_afe_surf], c.av, c.rv};
+    // (all six inputs here, not nn_inputs for the first four: with it the kernels come out some 70
+    // instructions longer.  The first layer below sums its six products from zero and then adds
+    // the bias, k_sed_nn_fit starts from the bias: two roundings, see seds_common.hpp.)
     bool ok = mini >= c.mini_bound;
     double xe[6];
 #pragma unroll
@@ -172,44 +156,22 @@ __device__ __forceinline__ double iso_mag(const IsoTable &T, const IsoCall &c,
         for (int d = 0; d < 6; d++) a += sw1[k * 6 + d] * xe[d];
         a1[k] = iso_sigmoid(a + sb1[k]);
     }
-    double y = 0.;
-#pragma unroll 1
-    for (int j = 0; j < c.h2; j++) {
-        const double *wj = sw2 + j * HP;
-        double a = 0., b = 0.;                  // two chains: the FMA latency is not the limit
-#pragma unroll
-        for (int k = 0; k < HP; k += 2) {
-            a += wj[k] * a1[k];
-            b += wj[k + 1] * a1[k + 1];
-        }
-        y += sw3[j] * iso_sigmoid(a + b + sb2[j]);
-    }
-    const double bc = y + sb3[0];
+    const double bc = nn_tail<HP>(a1, c.h2, sw2, sb2, sw3) + sb3[0];
     return -2.5 * logl + 4.74 - bc + c.mu;
 }
 
 template <int HP, bool SECOND>
-__global__ void __launch_bounds__(ISO_T)
-k_iso_nn(IsoTable T, IsoCall c, const double *__restrict__ weights,
+__global__ void __launch_bounds__(SEDS_T)
+k_iso_nn(SedsTable T, IsoCall c, const double *__restrict__ weights,
          const double *__restrict__ xmin, const double *__restrict__ xmax,
          const double *__restrict__ eep, const double *__restrict__ smf,
          const double *__restrict__ rows, const double *__restrict__ mag_prim,
          double *__restrict__ out) {
     extern __shared__ double sw[];
-    const int f = blockIdx.y, h1 = c.h1, h2 = c.h2;
-    // packed per filter: w1 (h1, 6) | b1 (h1) | w2 (h2, h1) | b2 (h2) | w3 (h2) | b3 (1)
-    const double *g = weights + (size_t)f * ((size_t)h1 * 7 + (size_t)h2 * h1 + 2 * (size_t)h2 + 1);
-    const double *gb1 = g + h1 * 6, *gw2 = gb1 + h1, *gb2 = gw2 + h2 * h1;
-    double *sb1 = sw + HP * 6, *sw2 = sb1 + HP, *sb2 = sw2 + h2 * HP;
-    for (int k = threadIdx.x; k < HP * 6; k += ISO_T) sw[k] = k < h1 * 6 ? g[k] : 0.;
-    for (int k = threadIdx.x; k < HP; k += ISO_T) sb1[k] = k < h1 ? gb1[k] : 0.;
-    for (int k = threadIdx.x; k < h2 * HP; k += ISO_T) {
-        const int j = k / HP, i = k - j * HP;
-        sw2[k] = i < h1 ? gw2[j * h1 + i] : 0.;
-    }
-    for (int k = threadIdx.x; k < 2 * h2 + 1; k += ISO_T) sb2[k] = gb2[k];
+    const int f = blockIdx.y;
+    nn_stage<HP>(sw, weights, f, c.h1, c.h2);
     __syncthreads();
-    const int r = blockIdx.x * ISO_T + threadIdx.x;
+    const int r = blockIdx.x * SEDS_T + threadIdx.x;
     const int nrow = SECOND ? c.nsmf * c.neep : c.neep;
     if (r >= nrow) return;
     if (!SECOND) {

@@ -8,8 +8,8 @@
 
 #include "../../include/brutus_amd.h"
 
-#include "host.hpp"
 #include "common.hpp"
+#include "seds_host.hpp"
 #include "iso_kernels.hpp"
 
 namespace {
@@ -24,15 +24,6 @@ static void carve_iso(char *base, int neep, int nfilt, IsoWs &w) {
     w.fp = (double *)cv.take(sizeof(double) * (size_t)neep);
     w.mag_prim = (double *)cv.take(sizeof(double) * (size_t)neep * nfilt);
     w.bytes = cv.off;
-}
-// LDS of k_iso_nn: w1 (HP, 6) | b1 (HP) | w2 (h2, HP) | b2 (h2) | w3 (h2) | b3
-static size_t iso_lds_bytes(int hp, int h2) {
-    return sizeof(double) * ((size_t)hp * 7 + (size_t)h2 * hp + 2 * (size_t)h2 + 1);
-}
-static int iso_hp(int h1) {
-    for (int hp : {8, 16, 32, 64})
-        if (h1 <= hp) return hp;
-    return -1;
 }
 static bool iso_dims_ok(int neep, int nsmf, int nfilt) {
     return neep > 0 && nsmf > 0 && nfilt > 0 && (int64_t)neep * nsmf * (int64_t)nfilt < ((int64_t)1 << 31);
@@ -55,29 +46,15 @@ int brutus_iso_seds_grid(const brutus_iso_params *p, const double *d_table, cons
                          void *d_workspace, size_t workspace_bytes, void *stream) {
     if (!p) return fail(BRUTUS_EINVAL, "NULL isochrone parameters");
     const int nax[4] = {p->nfeh, p->nafe, p->nloga, p->neep_tab};
-    int64_t ntab = 1;
-    for (int d = 0; d < 4; d++) {
-        if (nax[d] < 2 || nax[d] > (1 << 20))
-            return fail(BRUTUS_EINVAL, "bad isochrone table (axes %d x %d x %d x %d, each needs 2 nodes or more)",
-                        nax[0], nax[1], nax[2], nax[3]);
-        ntab *= nax[d];
-    }
-    if (p->npred < 1 || p->npred > ISO_MAX_PRED || ntab * p->npred >= ((int64_t)1 << 40))
-        return fail(BRUTUS_EINVAL, "bad isochrone table (npred=%d, at most %d)", p->npred, ISO_MAX_PRED);
     const int idx[6] = {p->idx_mini, p->idx_logl, p->idx_logt, p->idx_logg, p->idx_feh_surf, p->idx_afe_surf};
-    for (int k = 0; k < 6; k++)
-        if (idx[k] < 0 || idx[k] >= p->npred)
-            return fail(BRUTUS_EINVAL, "bad isochrone prediction column %d (npred=%d)", idx[k], p->npred);
+    if (int e = seds_check_table("isochrone", nax, p->npred, idx)) return e;
     const bool pred_only = p->flags & BRUTUS_ISO_PRED_ONLY;      // predictions of the primaries alone
     const int nfilt = pred_only ? 1 : p->nfilt;
     if (!iso_dims_ok(p->neep, pred_only ? 1 : p->nsmf, nfilt))
         return fail(BRUTUS_EINVAL, "bad isochrone dimensions (neep=%d, nsmf=%d, nfilt=%d)", p->neep,
                     p->nsmf, p->nfilt);
-    const int hp = iso_hp(p->h1);
-    if (!pred_only &&
-        (p->h1 < 1 || hp < 0 || p->h2 < 1 || iso_lds_bytes(hp, p->h2) > 64 * 1024))
-        return fail(BRUTUS_EINVAL, "bad network (h1=%d, at most %d; h2=%d; at most 64 KiB of weights per filter)",
-                    p->h1, ISO_MAX_H1, p->h2);
+    if (!pred_only)
+        if (int e = nn_check(p->h1, p->h2, 0)) return e;
     if (!d_table || !d_axes || !d_eep || !d_prim || !d_mini)
         return fail(BRUTUS_EINVAL, "NULL device pointer");
     if (!pred_only && (!d_weights || !d_xmin || !d_xmax || !d_smf || !d_mags || !d_sec || !d_eep2 ||
@@ -86,21 +63,7 @@ int brutus_iso_seds_grid(const brutus_iso_params *p, const double *d_table, cons
     if (!pred_only && workspace_bytes < brutus_iso_workspace_bytes(p->neep, p->nsmf, nfilt))
         return fail(BRUTUS_ENOMEM, "isochrone workspace too small");
 
-    IsoTable T;
-    T.tab = d_table;
-    const double *ax = d_axes;
-    for (int d = 0; d < 4; d++) {
-        T.ax[d] = ax;
-        T.n[d] = nax[d];
-        ax += nax[d];
-    }
-    T.npred = p->npred;
-    T.i_mini = p->idx_mini;
-    T.i_logl = p->idx_logl;
-    T.i_logt = p->idx_logt;
-    T.i_logg = p->idx_logg;
-    T.i_feh_surf = p->idx_feh_surf;
-    T.i_afe_surf = p->idx_afe_surf;
+    const SedsTable T = seds_table(d_table, d_axes, nax, p->npred, idx);
     IsoCall c;
     c.feh = p->feh;
     c.afe = p->afe;
@@ -110,10 +73,7 @@ int brutus_iso_seds_grid(const brutus_iso_params *p, const double *d_table, cons
     c.mu = 5. * log10(p->dist) - 5.;
     c.mini_bound = p->mini_bound;
     c.eep_binary_max = p->eep_binary_max;
-    c.dtdm = p->corr[0];
-    c.drdm = p->corr[1];
-    c.msto_smooth = p->corr[2];
-    c.feh_scale = p->corr[3];
+    seds_corr(c, p->corr);
     c.apply_corr = p->flags & BRUTUS_ISO_APPLY_CORR ? 1 : 0;
     c.eep2_given = p->flags & BRUTUS_ISO_EEP2_GIVEN ? 1 : 0;
     c.neep = p->neep;
@@ -123,42 +83,43 @@ int brutus_iso_seds_grid(const brutus_iso_params *p, const double *d_table, cons
     c.h2 = p->h2;
 
     hipStream_t st = (hipStream_t)stream;
-    const dim3 gp((p->neep + ISO_T - 1) / ISO_T);
+    const dim3 gp((p->neep + SEDS_T - 1) / SEDS_T);
     Timer tm(st);
     tm.begin("k_iso_primary");
-    hipLaunchKernelGGL(k_iso_primary, gp, dim3(ISO_T), 0, st, T, c, d_eep, d_prim, d_mini);
+    hipLaunchKernelGGL(k_iso_primary, gp, dim3(SEDS_T), 0, st, T, c, d_eep, d_prim, d_mini);
     tm.end();
     if (pred_only) {
         HIP_TRY(hipGetLastError());
         tm.collect();
         return 0;
     }
-    const dim3 gs((p->neep * p->nsmf + ISO_T - 1) / ISO_T);
+    const dim3 gs((p->neep * p->nsmf + SEDS_T - 1) / SEDS_T);
     IsoWs w;
     carve_iso((char *)d_workspace, p->neep, nfilt, w);
     tm.begin("k_iso_compact");
-    hipLaunchKernelGGL(k_iso_compact, dim3(1), dim3(ISO_T), 0, st, p->neep, d_mini, d_eep, w.xp, w.fp,
+    hipLaunchKernelGGL(k_iso_compact, dim3(1), dim3(SEDS_T), 0, st, p->neep, d_mini, d_eep, w.xp, w.fp,
                        d_status);
     tm.end();
     tm.begin("k_iso_secondary");
-    hipLaunchKernelGGL(k_iso_secondary, gs, dim3(ISO_T), 0, st, T, c, d_eep, d_smf, d_mini, w.xp, w.fp,
+    hipLaunchKernelGGL(k_iso_secondary, gs, dim3(SEDS_T), 0, st, T, c, d_eep, d_smf, d_mini, w.xp, w.fp,
                        d_status, d_eep2, d_sec);
     tm.end();
-    const size_t lds = iso_lds_bytes(hp, p->h2);
+    const int hp = nn_hp(p->h1);
+    const size_t lds = nn_lds_bytes(hp, p->h2, 0);
     auto nn = [&](auto HP) {
         constexpr int H = decltype(HP)::value;
         tm.begin("k_iso_nn primaries");
-        hipLaunchKernelGGL((k_iso_nn<H, false>), dim3(gp.x, nfilt), dim3(ISO_T), lds, st, T, c, d_weights,
+        hipLaunchKernelGGL((k_iso_nn<H, false>), dim3(gp.x, nfilt), dim3(SEDS_T), lds, st, T, c, d_weights,
                            d_xmin, d_xmax, d_eep, d_smf, (const double *)d_prim,
                            (const double *)nullptr, w.mag_prim);
         tm.end();
         tm.begin("k_iso_nn secondaries");
-        hipLaunchKernelGGL((k_iso_nn<H, true>), dim3(gs.x, nfilt), dim3(ISO_T), lds, st, T, c, d_weights,
+        hipLaunchKernelGGL((k_iso_nn<H, true>), dim3(gs.x, nfilt), dim3(SEDS_T), lds, st, T, c, d_weights,
                            d_xmin, d_xmax, d_eep, d_smf, (const double *)d_sec,
                            (const double *)w.mag_prim, d_mags);
         tm.end();
     };
-    with_nb(hp, BandCounts<8, 16, 32, 64>{}, nn);
+    with_nb(hp, NetWidths{}, nn);
     HIP_TRY(hipGetLastError());
     tm.collect();
     return 0;

@@ -27,20 +27,9 @@
 #include <math.h>
 #include <stdint.h>
 
-#include "interp_common.hpp"
+#include "seds_common.hpp"
 
-constexpr int SED_T = 256;          // lanes per workgroup, all kernels
-constexpr int SED_MAX_PRED = 16;    // predictions per table point
-constexpr int SED_MAX_H1 = 64;      // units of the first hidden layer
 constexpr int SED_MAX_FIT = 256;    // (Rv, Av) points of the fit
-
-struct SedTable {
-    const double *tab;              // (n[0], n[1], n[2], n[3], npred)
-    const double *ax[4];            // mini, eep, feh, afe axes, ascending
-    int n[4];
-    int npred;
-    int i_loga, i_logl, i_logt, i_logg, i_feh_surf, i_afe_surf;
-};
 
 struct SedCall {
     double av, rv, mu, loga_max, eep_binary_max, mini_min, tol, loga_target;
@@ -51,18 +40,13 @@ struct SedCall {
 
 // Predictions at the labels (mini, eep, feh, afe) into out[0 .. npred) (seds.py:263-312); the
 // corrections take the label's mass and metallicity (seds.py:349-384).
-__device__ void sed_predict(const SedTable &T, const SedCall &c, double mini, double eep, double feh,
+__device__ void sed_predict(const SedsTable &T, const SedCall &c, double mini, double eep, double feh,
                             double afe, double *out) {
     const double q[4] = {mini, eep, feh, afe};
     if (!iso_interp4(T.tab, T.ax, T.n, T.npred, q, out)) return;
     if (!c.apply_corr) return;
-    double dlogt = log10(1. + (mini - 1.) * c.dtdm);
-    double dlogr = log10(1. + (mini - 1.) * c.drdm);
-    const double ecorr = 1. - 1. / (1. + exp(-(eep - 454.) / c.msto_smooth));
-    const double fcorr = exp(c.feh_scale * feh);
-    dlogt *= ecorr * fcorr;
-    dlogr *= ecorr * fcorr;
-    if (mini >= 1.) dlogt = dlogr = 0.;
+    double dlogt, dlogr;
+    seds_corrections(mini, eep, feh, c.dtdm, c.drdm, c.msto_smooth, c.feh_scale, dlogt, dlogr);
     out[T.i_logt] += dlogt;
     out[T.i_logl] += 2. * dlogr;
     out[T.i_logg] -= 2. * dlogr;
@@ -79,7 +63,7 @@ __device__ void sed_predict(const SedTable &T, const SedCall &c, double mini, do
 // bisection would need a compacted copy of the track per lane.  The pass is 8 loads and 8 FMAs
 // per node -- at the 800 nodes of a MIST track 6 400 loads per binary model, against the 4 x 10^6
 // FMAs the same model then spends in k_sed_nn_fit.
-__device__ double sed_solve_eep(const SedTable &T, const SedCall &c, double target, double mini,
+__device__ double sed_solve_eep(const SedsTable &T, const SedCall &c, double target, double mini,
                                 double eep0, double feh, double afe) {
     int lm, lf, la;
     double tm, tf, ta;
@@ -95,7 +79,7 @@ __device__ double sed_solve_eep(const SedTable &T, const SedCall &c, double targ
         const int um = (k >> 2) & 1, uf = (k >> 1) & 1, ua = k & 1;
         w[k] = (um ? tm : 1. - tm) * (uf ? tf : 1. - tf) * (ua ? ta : 1. - ta);
         off[k] = (((size_t)(lm + um) * T.n[1]) * T.n[2] + (size_t)(lf + uf)) * T.n[3] + (size_t)(la + ua);
-        off[k] = off[k] * T.npred + T.i_loga;
+        off[k] = off[k] * T.npred + T.i_first;
     }
     auto node = [&](int j) {
         double v = 0.;
@@ -149,33 +133,18 @@ __device__ double sed_solve_eep(const SedTable &T, const SedCall &c, double targ
     return r < c.tol ? (r_first <= r_last ? e_first : e_last) : iso_nan();
 }
 
-// The encoded inputs that do not move with (Av, Rv) -- [Teff, logg, feh_surf, afe_surf] -- of
-// one row of predictions; false where the bounds test of seds.py:1066-1068 fails on them.
-__device__ __forceinline__ bool sed_inputs(const SedTable &T, const double *__restrict__ row,
-                                           const double *__restrict__ xmin,
-                                           const double *__restrict__ xmax, double *xe) {
-    const double x[4] = {pow(10., row[T.i_logt]), row[T.i_logg], row[T.i_feh_surf], row[T.i_afe_surf]};
-    bool ok = true;
-#pragma unroll
-    for (int d = 0; d < 4; d++) {
-        ok = ok && isfinite(x[d]) && x[d] >= xmin[d] && x[d] <= xmax[d];
-        xe[d] = (x[d] - xmin[d]) / (xmax[d] - xmin[d]);
-    }
-    return ok;
-}
-
 // state of a model: 0 no SED (too old, an ineligible binary, a component outside the networks'
 // bounds), 1 the primary alone, 2 both.  The models of state 1 and of state 2 are also listed,
 // each kind in a list of its own (count[0], count[1] entries, in no particular order), so that
 // k_sed_nn_fit runs on dense lanes whatever share of the grid has no SED.
-__global__ void __launch_bounds__(SED_T)
-k_sed_tracks(SedTable T, SedCall c, const double *__restrict__ labels,
+__global__ void __launch_bounds__(SEDS_T)
+k_sed_tracks(SedsTable T, SedCall c, const double *__restrict__ labels,
              const double *__restrict__ eep2_in, const double *__restrict__ xmin,
              const double *__restrict__ xmax, double *__restrict__ param,
              double *__restrict__ param2, double *__restrict__ eep2_out,
              uint8_t *__restrict__ sel, int32_t *__restrict__ state, int32_t *__restrict__ list1,
              int32_t *__restrict__ list2, int32_t *__restrict__ count) {
-    const int i = blockIdx.x * SED_T + threadIdx.x;
+    const int i = blockIdx.x * SEDS_T + threadIdx.x;
     if (i >= c.nmodel) return;
     const double *lab = labels + (size_t)i * 5;
     const double mini = lab[0], eep = lab[1], feh = lab[2], afe = lab[3], smf = lab[4];
@@ -192,7 +161,7 @@ k_sed_tracks(SedTable T, SedCall c, const double *__restrict__ labels,
         whole = whole && !isnan(row[p]);
         row2[p] = iso_nan();
     }
-    const double loga = row[T.i_loga];
+    const double loga = row[T.i_first];
     double e2 = c.eep2_given ? eep2_in[i] : iso_nan();
     int st = 0;
     if (loga <= c.loga_max) {           // seds.py:558-590
@@ -209,8 +178,8 @@ k_sed_tracks(SedTable T, SedCall c, const double *__restrict__ labels,
         }
     }
     double xe[4];
-    if (st >= 1 && !sed_inputs(T, row, xmin, xmax, xe)) st = 0;      // (NaN at every point)
-    if (st == 2 && !sed_inputs(T, row2, xmin, xmax, xe)) st = 0;
+    if (st >= 1 && !nn_inputs(T, row, xmin, xmax, xe)) st = 0;      // (NaN at every point)
+    if (st == 2 && !nn_inputs(T, row2, xmin, xmax, xe)) st = 0;
     eep2_out[i] = e2;
     state[i] = st;
     sel[i] = st != 0 && whole ? 1 : 0;
@@ -218,32 +187,13 @@ k_sed_tracks(SedTable T, SedCall c, const double *__restrict__ labels,
     if (st == 2) list2[atomicAdd(&count[1], 1)] = i;
 }
 
-// Layers two and three on a first layer a1[0 .. HP) (columns past h1 are zero in sw2).
-template <int HP>
-__device__ __forceinline__ double sed_tail(const double *a1, int h2, const double *sw2,
-                                           const double *sb2, const double *sw3) {
-    double y = 0.;
-#pragma unroll 1
-    for (int j = 0; j < h2; j++) {
-        const double *wj = sw2 + j * HP;
-        double a = 0., b = 0.;
-#pragma unroll
-        for (int k = 0; k < HP; k += 2) {
-            a += wj[k] * a1[k];
-            b += wj[k + 1] * a1[k + 1];
-        }
-        y += sw3[j] * iso_sigmoid(a + b + sb2[j]);
-    }
-    return y;
-}
-
 // LDS: the filter's weights as k_iso_nn holds them -- w1 (HP, 6) | b1 (HP) | w2 (h2, HP) |
 // b2 (h2) | w3 (h2) | b3 (1) -- then five values per point (the reference point first, then
 // the nrv x nav fit points): av_e, rv_e, inside the networks' bounds (1 / 0), the point's
 // coefficient in seda and in sedr.
 template <int HP, bool BASE, bool SECOND>
-__global__ void __launch_bounds__(SED_T)
-k_sed_nn_fit(SedTable T, SedCall c, const double *__restrict__ weights,
+__global__ void __launch_bounds__(SEDS_T)
+k_sed_nn_fit(SedsTable T, SedCall c, const double *__restrict__ weights,
              const double *__restrict__ xmin, const double *__restrict__ xmax,
              const double *__restrict__ param, const double *__restrict__ param2,
              const int32_t *__restrict__ list, const int32_t *__restrict__ count,
@@ -253,21 +203,25 @@ k_sed_nn_fit(SedTable T, SedCall c, const double *__restrict__ weights,
     extern __shared__ double sw[];
     const int f = blockIdx.y, h1 = c.h1, h2 = c.h2;
     const int n = min(count[SECOND ? 1 : 0], c.nmodel);              // models of this kind
-    if (blockIdx.x * SED_T >= n) return;                             // (the whole workgroup)
+    if (blockIdx.x * SEDS_T >= n) return;                            // (the whole workgroup)
     const int nfit = c.fit ? c.nav * c.nrv : 0, npts = 1 + nfit;
+    // The staging of nn_stage (seds_common.hpp), written out: with the call in its place the
+    // compiler orders the loop-carried values of the point loop below differently in the
+    // BASE = false instantiations and two constant moves change places in their code.  The
+    // kernels were to stay as they were to the instruction, so the four loops stay here.
     const double *g = weights + (size_t)f * ((size_t)h1 * 7 + (size_t)h2 * h1 + 2 * (size_t)h2 + 1);
     const double *gb1 = g + h1 * 6, *gw2 = gb1 + h1, *gb2 = gw2 + h2 * h1;
     double *sb1 = sw + HP * 6, *sw2 = sb1 + HP, *sb2 = sw2 + h2 * HP, *sw3 = sb2 + h2, *sb3 = sw3 + h2;
     double *s_av = sb3 + 1, *s_rv = s_av + npts, *s_ok = s_rv + npts, *s_ca = s_ok + npts,
            *s_cr = s_ca + npts;
-    for (int k = threadIdx.x; k < HP * 6; k += SED_T) sw[k] = k < h1 * 6 ? g[k] : 0.;
-    for (int k = threadIdx.x; k < HP; k += SED_T) sb1[k] = k < h1 ? gb1[k] : 0.;
-    for (int k = threadIdx.x; k < h2 * HP; k += SED_T) {
+    for (int k = threadIdx.x; k < HP * 6; k += SEDS_T) sw[k] = k < h1 * 6 ? g[k] : 0.;
+    for (int k = threadIdx.x; k < HP; k += SEDS_T) sb1[k] = k < h1 ? gb1[k] : 0.;
+    for (int k = threadIdx.x; k < h2 * HP; k += SEDS_T) {
         const int j = k / HP, i = k - j * HP;
         sw2[k] = i < h1 ? gw2[j * h1 + i] : 0.;
     }
-    for (int k = threadIdx.x; k < 2 * h2 + 1; k += SED_T) sb2[k] = gb2[k];
-    for (int p = threadIdx.x; p < npts; p += SED_T) {
+    for (int k = threadIdx.x; k < 2 * h2 + 1; k += SEDS_T) sb2[k] = gb2[k];
+    for (int p = threadIdx.x; p < npts; p += SEDS_T) {
         const int q = p - 1;
         const double av = p ? av_grid[q % c.nav] : c.av, rv = p ? rv_grid[q / c.nav] : c.rv;
         s_ok[p] = isfinite(av) && isfinite(rv) && av >= xmin[4] && av <= xmax[4] && rv >= xmin[5] &&
@@ -280,7 +234,7 @@ k_sed_nn_fit(SedTable T, SedCall c, const double *__restrict__ weights,
         s_cr[p] = p ? fitcoef[nfit + q] : 0.;
     }
     __syncthreads();
-    const int lane = blockIdx.x * SED_T + threadIdx.x;
+    const int lane = blockIdx.x * SEDS_T + threadIdx.x;
     if (lane >= n) return;
     const int r = list[lane];
     if (r < 0 || r >= c.nmodel) return;
@@ -288,8 +242,8 @@ k_sed_nn_fit(SedTable T, SedCall c, const double *__restrict__ weights,
     double *o = out + ((size_t)r * c.nfilt + f) * nout;
     const double *row = param + (size_t)r * T.npred, *row2 = param2 + (size_t)r * T.npred;
     double xe[4], xe2[SECOND ? 4 : 1];
-    const bool ok1 = sed_inputs(T, row, xmin, xmax, xe);
-    const bool ok2 = SECOND && sed_inputs(T, row2, xmin, xmax, xe2);
+    const bool ok1 = nn_inputs(T, row, xmin, xmax, xe);
+    const bool ok2 = SECOND && nn_inputs(T, row2, xmin, xmax, xe2);
     const double lum1 = -2.5 * row[T.i_logl] + 4.74 + c.mu;
     const double lum2 = SECOND ? -2.5 * row2[T.i_logl] + 4.74 + c.mu : 0.;
     double base[BASE ? HP : 1];
@@ -322,7 +276,7 @@ k_sed_nn_fit(SedTable T, SedCall c, const double *__restrict__ weights,
                 }
                 a1[k] = iso_sigmoid(a + sw[k * 6 + 4] * ave + sw[k * 6 + 5] * rve);
             }
-            m = lum1 - (sed_tail<HP>(a1, h2, sw2, sb2, sw3) + sb3[0]);
+            m = lum1 - (nn_tail<HP>(a1, h2, sw2, sb2, sw3) + sb3[0]);
         }
         if (SECOND) {                   // seds.py:587: add_mag of the two components
             double m2 = iso_nan();
@@ -335,7 +289,7 @@ k_sed_nn_fit(SedTable T, SedCall c, const double *__restrict__ weights,
                     for (int d = 0; d < 4; d++) a += sw[k * 6 + d] * xe2[d];
                     a1[k] = iso_sigmoid(a + sw[k * 6 + 4] * ave + sw[k * 6 + 5] * rve);
                 }
-                m2 = lum2 - (sed_tail<HP>(a1, h2, sw2, sb2, sw3) + sb3[0]);
+                m2 = lum2 - (nn_tail<HP>(a1, h2, sw2, sb2, sw3) + sb3[0]);
             }
             m = -2.5 * log10(pow(10., -0.4 * m) + pow(10., -0.4 * m2));
         }
@@ -355,10 +309,10 @@ k_sed_nn_fit(SedTable T, SedCall c, const double *__restrict__ weights,
 }
 
 // NaN rows: the models without an SED and, for make_grid, the unselected ones.
-__global__ void __launch_bounds__(SED_T)
+__global__ void __launch_bounds__(SEDS_T)
 k_sed_finish(int nmodel, int nvals, int fit, const int32_t *__restrict__ state,
              const uint8_t *__restrict__ sel, double *__restrict__ out) {
-    const int i = blockIdx.x * SED_T + threadIdx.x;
+    const int i = blockIdx.x * SEDS_T + threadIdx.x;
     if (i >= nmodel || (state[i] != 0 && (!fit || sel[i]))) return;
     for (int k = 0; k < nvals; k++) out[(size_t)i * nvals + k] = iso_nan();
 }

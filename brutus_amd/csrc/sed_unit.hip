@@ -8,8 +8,8 @@
 
 #include "../../include/brutus_amd.h"
 
-#include "host.hpp"
 #include "common.hpp"
+#include "seds_host.hpp"
 #include "sed_kernels.hpp"
 
 namespace {
@@ -25,15 +25,6 @@ static void carve_sed(char *base, int nmodel, SedWs &w) {
     w.list2 = (int32_t *)cv.take(sizeof(int32_t) * (size_t)nmodel);
     w.count = (int32_t *)cv.take(sizeof(int32_t) * 2);
     w.bytes = cv.off;
-}
-// LDS of k_sed_nn_fit: the weights of a filter, then five values per point
-static size_t sed_lds_bytes(int hp, int h2, int nfit) {
-    return sizeof(double) * ((size_t)hp * 7 + (size_t)h2 * hp + 2 * (size_t)h2 + 1 + 5 * (size_t)(1 + nfit));
-}
-static int sed_hp(int h1) {
-    for (int hp : {8, 16, 32, 64})
-        if (h1 <= hp) return hp;
-    return -1;
 }
 static bool sed_dims_ok(int nmodel, int nfilt, int nfit) {
     return nmodel > 0 && nfilt > 0 && nfilt <= 65535 && nfit >= 0 && nfit <= SED_MAX_FIT &&
@@ -58,19 +49,8 @@ int brutus_sed_grid(const brutus_sed_params *p, const double *d_table, const dou
                     void *d_workspace, size_t workspace_bytes, void *stream) {
     if (!p) return fail(BRUTUS_EINVAL, "NULL track parameters");
     const int nax[4] = {p->nmini, p->neep_tab, p->nfeh, p->nafe};
-    int64_t ntab = 1;
-    for (int d = 0; d < 4; d++) {
-        if (nax[d] < 2 || nax[d] > (1 << 20))
-            return fail(BRUTUS_EINVAL, "bad track table (axes %d x %d x %d x %d, each needs 2 nodes or more)",
-                        nax[0], nax[1], nax[2], nax[3]);
-        ntab *= nax[d];
-    }
-    if (p->npred < 1 || p->npred > SED_MAX_PRED || ntab * p->npred >= ((int64_t)1 << 40))
-        return fail(BRUTUS_EINVAL, "bad track table (npred=%d, at most %d)", p->npred, SED_MAX_PRED);
     const int idx[6] = {p->idx_loga, p->idx_logl, p->idx_logt, p->idx_logg, p->idx_feh_surf, p->idx_afe_surf};
-    for (int k = 0; k < 6; k++)
-        if (idx[k] < 0 || idx[k] >= p->npred)
-            return fail(BRUTUS_EINVAL, "bad track prediction column %d (npred=%d)", idx[k], p->npred);
+    if (int e = seds_check_table("track", nax, p->npred, idx)) return e;
     const bool pred_only = p->flags & BRUTUS_SED_PRED_ONLY, eep_only = p->flags & BRUTUS_SED_EEP_ONLY;
     const bool tracks_only = pred_only || eep_only, fit = p->flags & BRUTUS_SED_FIT;
     const int nfit = fit ? p->nav * p->nrv : 0;
@@ -80,10 +60,9 @@ int brutus_sed_grid(const brutus_sed_params *p, const double *d_table, const dou
     const int nfilt = tracks_only ? 1 : p->nfilt;
     if (!sed_dims_ok(p->nmodel, nfilt, nfit))
         return fail(BRUTUS_EINVAL, "bad grid dimensions (nmodel=%d, nfilt=%d)", p->nmodel, p->nfilt);
-    const int hp = sed_hp(p->h1);
-    if (!tracks_only && (p->h1 < 1 || hp < 0 || p->h2 < 1 || sed_lds_bytes(hp, p->h2, nfit) > 64 * 1024))
-        return fail(BRUTUS_EINVAL, "bad network (h1=%d, at most %d; h2=%d; at most 64 KiB of weights per filter)",
-                    p->h1, SED_MAX_H1, p->h2);
+    const size_t npoint = 5 * (size_t)(1 + nfit);     // LDS of k_sed_nn_fit behind the weights: five values per point
+    if (!tracks_only)
+        if (int e = nn_check(p->h1, p->h2, npoint)) return e;
     if (!d_table || !d_axes || !d_labels) return fail(BRUTUS_EINVAL, "NULL device pointer");
     if (eep_only ? !d_out_eep2 : !d_out_param) return fail(BRUTUS_EINVAL, "NULL device pointer");
     if (!tracks_only && (!d_weights || !d_xmin || !d_xmax || !d_out_sed || !d_out_param2 || !d_out_eep2 ||
@@ -94,21 +73,7 @@ int brutus_sed_grid(const brutus_sed_params *p, const double *d_table, const dou
         return fail(BRUTUS_ENOMEM, "grid workspace too small");
     (void)d_status;
 
-    SedTable T;
-    T.tab = d_table;
-    const double *ax = d_axes;
-    for (int d = 0; d < 4; d++) {
-        T.ax[d] = ax;
-        T.n[d] = nax[d];
-        ax += nax[d];
-    }
-    T.npred = p->npred;
-    T.i_loga = p->idx_loga;
-    T.i_logl = p->idx_logl;
-    T.i_logt = p->idx_logt;
-    T.i_logg = p->idx_logg;
-    T.i_feh_surf = p->idx_feh_surf;
-    T.i_afe_surf = p->idx_afe_surf;
+    const SedsTable T = seds_table(d_table, d_axes, nax, p->npred, idx);
     SedCall c;
     c.av = p->av;
     c.rv = p->rv;
@@ -118,10 +83,7 @@ int brutus_sed_grid(const brutus_sed_params *p, const double *d_table, const dou
     c.mini_min = p->mini_min;
     c.tol = p->tol;
     c.loga_target = p->loga_target;
-    c.dtdm = p->corr[0];
-    c.drdm = p->corr[1];
-    c.msto_smooth = p->corr[2];
-    c.feh_scale = p->corr[3];
+    seds_corr(c, p->corr);
     c.apply_corr = p->flags & BRUTUS_SED_APPLY_CORR ? 1 : 0;
     c.eep2_given = p->flags & BRUTUS_SED_EEP2_GIVEN ? 1 : 0;
     c.scan = p->flags & BRUTUS_SED_SCAN ? 1 : 0;
@@ -135,13 +97,13 @@ int brutus_sed_grid(const brutus_sed_params *p, const double *d_table, const dou
     c.fit = fit ? 1 : 0;
 
     hipStream_t st = (hipStream_t)stream;
-    const dim3 gm((p->nmodel + SED_T - 1) / SED_T);
+    const dim3 gm((p->nmodel + SEDS_T - 1) / SEDS_T);
     SedWs w;
     carve_sed(tracks_only ? nullptr : (char *)d_workspace, p->nmodel, w);
     Timer tm(st);
     if (!tracks_only) HIP_TRY(hipMemsetAsync(w.count, 0, sizeof(int32_t) * 2, st));
     tm.begin("k_sed_tracks");
-    hipLaunchKernelGGL(k_sed_tracks, gm, dim3(SED_T), 0, st, T, c, d_labels, d_eep2_in, d_xmin, d_xmax,
+    hipLaunchKernelGGL(k_sed_tracks, gm, dim3(SEDS_T), 0, st, T, c, d_labels, d_eep2_in, d_xmin, d_xmax,
                        d_out_param, tracks_only ? (double *)nullptr : d_out_param2, d_out_eep2, d_out_sel,
                        w.state, w.list1, w.list2, w.count);
     tm.end();
@@ -150,7 +112,8 @@ int brutus_sed_grid(const brutus_sed_params *p, const double *d_table, const dou
         tm.collect();
         return 0;
     }
-    const size_t lds = sed_lds_bytes(hp, p->h2, nfit);
+    const int hp = nn_hp(p->h1);
+    const size_t lds = nn_lds_bytes(hp, p->h2, npoint);
     // (the first layer's base in registers or formed anew at every point: sed_kernels.hpp;
     // BRUTUS_SED_BASE = 0 / 1 overrides the choice, for A/B timing)
     const bool base = env_int("BRUTUS_SED_BASE", hp <= 16 ? 1 : 0) != 0;
@@ -158,7 +121,7 @@ int brutus_sed_grid(const brutus_sed_params *p, const double *d_table, const dou
         constexpr int H = decltype(HP)::value;
         auto launch = [&](const char *name, auto kernel, const int32_t *list) {
             tm.begin(name);
-            hipLaunchKernelGGL(kernel, dim3(gm.x, nfilt), dim3(SED_T), lds, st, T, c, d_weights, d_xmin, d_xmax,
+            hipLaunchKernelGGL(kernel, dim3(gm.x, nfilt), dim3(SEDS_T), lds, st, T, c, d_weights, d_xmin, d_xmax,
                                (const double *)d_out_param, (const double *)d_out_param2, list,
                                (const int32_t *)w.count, d_fitcoef, d_av, d_rv, d_out_sed, d_out_sel);
             tm.end();
@@ -167,9 +130,9 @@ int brutus_sed_grid(const brutus_sed_params *p, const double *d_table, const dou
         else launch("k_sed_nn_fit", k_sed_nn_fit<H, false, false>, w.list1);
         launch("k_sed_nn_fit binaries", k_sed_nn_fit<H, false, true>, w.list2);
     };
-    with_nb(hp, BandCounts<8, 16, 32, 64>{}, nn);
+    with_nb(hp, NetWidths{}, nn);
     tm.begin("k_sed_finish");
-    hipLaunchKernelGGL(k_sed_finish, gm, dim3(SED_T), 0, st, p->nmodel, nfilt * (fit ? 3 : 1), fit ? 1 : 0,
+    hipLaunchKernelGGL(k_sed_finish, gm, dim3(SEDS_T), 0, st, p->nmodel, nfilt * (fit ? 3 : 1), fit ? 1 : 0,
                        (const int32_t *)w.state, (const uint8_t *)d_out_sel, d_out_sed);
     tm.end();
     HIP_TRY(hipGetLastError());

@@ -11,13 +11,15 @@ it -- is numpy on the host; every evaluation runs in the HIP kernels of `csrc/se
 empirical corrections, the secondaries of unresolved binaries, one network per filter, the
 combination of the components and, for `SEDmaker.make_grid`, the fits in Av and Rv.
 """
+import ctypes as C
 import sys
 from copy import deepcopy
 
 import numpy as np
 
-from . import _lib
+from . import _lib, h5io
 from .filters import FILTERS
+from .fitting import _stream_ptr, _torch
 
 __all__ = ["MISTtracks", "SEDmaker", "Isochrone"]
 
@@ -49,9 +51,56 @@ def _load_networks(self, weights, xmin, xmax):
     self.xspan = self.xmax - self.xmin
 
 
+def _read_networks(nnfile, filters):
+    rd = h5io.read_dataset
+    weights = {k: [rd(nnfile, "%s/%s" % (f, k)) for f in filters] for k in _NN_KEYS}
+    xmin = np.array([rd(nnfile, "%s/xmin" % f) for f in filters])
+    xmax = np.array([rd(nnfile, "%s/xmax" % f) for f in filters])
+    return weights, xmin, xmax
+
+
+def _pack_weights(self):
+    """The networks as the kernels read them: one row per filter,
+    w1 (H1, 6) | b1 (H1) | w2 (H2, H1) | b2 (H2) | w3 (H2) | b3 (1)."""
+    return np.concatenate([a.reshape(self.NFILT, -1) for a in
+                           (self.w1, self.b1, self.w2, self.b2, self.w3, self.b3)], axis=1)
+
+
+def _corrections(mini, eep, feh, corr_params):
+    """The empirical corrections `(dlogt, dlogr)` of seds.py:1327-1356 / 349-384, elementwise, as
+    they are before `mini >= 1` zeroes them (each caller does that in its own shapes)."""
+    dtdm, drdm, msto_smooth, feh_scale = _CORR_DEFAULT if corr_params is None else corr_params
+    with np.errstate(all="ignore"):
+        scale = (1. - 1. / (1. + np.exp(-(eep - 454) / msto_smooth))) * np.exp(feh_scale * feh)
+        return np.log10(1. + (mini - 1.) * dtdm) * scale, np.log10(1. + (mini - 1.) * drdm) * scale
+
+
 class _DeviceSide(object):
-    """The device copies of one Isochrone on one device, and the buffers a call works in."""
+    """The device copies of one table (and its networks) on one device, and the buffers a call
+    works in."""
     pass
+
+
+def _device(self, table, device=None):
+    """`(device side, torch)` of `self` on `device` (default: the current one), made at the
+    first call: `table`, the axes `self.xgrid` and, if `self` has networks, their weights and
+    bounds.  `build_interpolator` drops the copies by emptying `self._dev`."""
+    torch = _torch()
+    dev = torch.device(device if device is not None
+                       else "cuda:%d" % torch.cuda.current_device())
+    if dev.index is None:
+        dev = torch.device("cuda:%d" % torch.cuda.current_device())
+    d = self._dev.get(str(dev))
+    if d is None:
+        d = _DeviceSide()
+        d.dev = dev
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
+        d.table, d.axes = up(table), up(np.concatenate(self.xgrid))
+        d.weights = d.xmin = d.xmax = d.ws = None
+        if hasattr(self, "w1"):
+            d.weights, d.xmin, d.xmax = up(_pack_weights(self)), up(self.xmin), up(self.xmax)
+        self._dev[str(dev)] = d
+    return d, torch
 
 
 class Isochrone(object):
@@ -63,7 +112,6 @@ class Isochrone(object):
     columns), `verbose`.  `Isochrone.from_arrays` builds the same object from arrays."""
 
     def __init__(self, filters=None, nnfile=None, mistfile=None, predictions=None, verbose=True):
-        from . import h5io
         if filters is None:
             filters = np.array(FILTERS)
         if verbose:
@@ -74,15 +122,12 @@ class Isochrone(object):
             mistfile = 'data/DATAFILES/MIST_1.2_iso_vvcrit0.0.h5'
         if verbose:
             sys.stderr.write('Constructing MIST isochrones...')
-        rd = h5io.read_dataset
-        feh, afe, loga, eep, pred = (rd(mistfile, n) for n in
+        feh, afe, loga, eep, pred = (h5io.read_dataset(mistfile, n) for n in
                                      ("feh", "afe", "loga", "eep", "predictions"))
         if verbose:
             sys.stderr.write('done!\n')
             sys.stderr.write('Initializing FastNN predictor...')
-        weights = {k: [rd(nnfile, "%s/%s" % (f, k)) for f in filters] for k in _NN_KEYS}
-        xmin = np.array([rd(nnfile, "%s/xmin" % f) for f in filters])
-        xmax = np.array([rd(nnfile, "%s/xmax" % f) for f in filters])
+        weights, xmin, xmax = _read_networks(nnfile, filters)
         if verbose:
             sys.stderr.write('done!\n')
         self._setup(feh, afe, loga, eep, pred, weights, xmin, xmax, filters, predictions)
@@ -144,28 +189,11 @@ class Isochrone(object):
 
     # ---- the device side ------------------------------------------------------------------
     def _device(self, device=None):
-        from .fitting import _torch
-        torch = _torch()
-        dev = torch.device(device if device is not None
-                           else "cuda:%d" % torch.cuda.current_device())
-        if dev.index is None:
-            dev = torch.device("cuda:%d" % torch.cuda.current_device())
-        d = self._dev.get(str(dev))
-        if d is None:
-            d = _DeviceSide()
-            d.dev = dev
-            up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
-            d.table = up(self.pred_grid)
-            d.axes = up(np.concatenate(self.xgrid))
-            nf = self.NFILT
-            d.weights = up(np.concatenate([a.reshape(nf, -1) for a in
-                                           (self.w1, self.b1, self.w2, self.b2, self.w3, self.b3)],
-                                          axis=1))
-            d.xmin, d.xmax = up(self.xmin), up(self.xmax)
-            d.status = torch.zeros(2, dtype=torch.int32, device=dev)
+        d, torch = _device(self, self.pred_grid, device)
+        if not hasattr(d, "status"):     # (k_iso_compact's flag and count, and their host copy)
+            d.status = torch.zeros(2, dtype=torch.int32, device=d.dev)
             d.h_status = torch.zeros(2, dtype=torch.int32).pin_memory()
             d.eepkey = d.smfkey = d.shape = None
-            self._dev[str(dev)] = d
         return d, torch
 
     def _params(self, neep, nsmf, flags, feh, afe, loga, av, rv, dist, mini_bound,
@@ -188,8 +216,6 @@ class Isochrone(object):
         tensor `out (Nsmf, Neep, Nfilt)` (None: a buffer of this object) on the current stream;
         returns the device side (d.mags, d.prim, d.sec, d.eep2 hold the results) and `mini` on
         the host."""
-        import ctypes as C
-        from .fitting import _stream_ptr
         d, torch = self._device(None if out is None else out.device)
         dev = d.dev
         eep = np.ascontiguousarray(self.eep_u if eep is None else eep, dtype=np.float64)
@@ -252,8 +278,6 @@ class Isochrone(object):
                         corr_params=None):
         """Predictions `(Neep, Npred)` at the given metallicity, log(age) and EEPs
         (seds.py:1218-1282)."""
-        import ctypes as C
-        from .fitting import _stream_ptr
         d, torch = self._device()
         eep = np.ascontiguousarray(np.atleast_1d(self.eep_u if eep is None else eep),
                                    dtype=np.float64)
@@ -276,12 +300,7 @@ class Isochrone(object):
         """The empirical corrections `(dlogt, dlogr)` of seds.py:1284-1358 for given labels (a
         few elementwise operations on the caller's arrays, in numpy; inside `get_predictions`
         and `get_seds` the kernels apply the same formula)."""
-        dtdm, drdm, msto_smooth, feh_scale = (_CORR_DEFAULT if corr_params is None
-                                              else corr_params)
-        with np.errstate(all="ignore"):
-            scale = (1. - 1. / (1. + np.exp(-(eep - 454) / msto_smooth))) * np.exp(feh_scale * feh)
-            dlogt = np.log10(1. + (mini - 1.) * dtdm) * scale
-            dlogr = np.log10(1. + (mini - 1.) * drdm) * scale
+        dlogt, dlogr = _corrections(mini, eep, feh, corr_params)
         if np.c_[mini, eep, feh].shape[0] == 1:
             return np.array([0., 0.]) if mini >= 1. else np.array([dlogt, dlogr])
         dlogt, dlogr = np.array(dlogt, dtype=float), np.array(dlogr, dtype=float)
@@ -334,7 +353,7 @@ rename = {"mini": "initial_mass", "eep": "EEP", "feh": "initial_[Fe/H]", "afe": 
           "mass": "star_mass", "feh_surf": "[Fe/H]", "afe_surf": "[a/Fe]", "loga": "log_age",
           "logt": "log_Teff", "logg": "log_g", "logl": "log_L", "logr": "log_R"}
 _TRACK_PREDICTIONS = ["loga", "logl", "logt", "logg", "feh_surf", "afe_surf"]
-_MAX_H1, _MAX_PRED, _MAX_FIT = 64, 16, 256          # the limits of csrc/sed_kernels.hpp
+_MAX_H1, _MAX_PRED, _MAX_FIT = 64, 16, 256          # the limits of csrc/seds_common.hpp, sed_kernels.hpp
 _CHUNK_BYTES = 256 << 20                            # device memory of one make_grid call
 
 
@@ -397,7 +416,6 @@ class MISTtracks(object):
     def make_lib(self, misth5, verbose=True):
         """The track file `misth5` (its name: the file is read through `h5io`) as `libparams`
         and `output` (seds.py:113-155).  A file without the [a/Fe] column gets zeros there."""
-        from . import h5io
         if verbose:
             sys.stderr.write("Constructing MIST library...")
         index = [z.decode() if isinstance(z, bytes) else str(z)
@@ -478,28 +496,7 @@ class MISTtracks(object):
 
     # ---- the device side ------------------------------------------------------------------------
     def _device(self, device=None):
-        from .fitting import _torch
-        torch = _torch()
-        dev = torch.device(device if device is not None
-                           else "cuda:%d" % torch.cuda.current_device())
-        if dev.index is None:
-            dev = torch.device("cuda:%d" % torch.cuda.current_device())
-        d = self._dev.get(str(dev))
-        if d is None:
-            d = _DeviceSide()
-            d.dev = dev
-            up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
-            d.table, d.axes = up(self.ygrid), up(np.concatenate(self.xgrid))
-            d.weights = d.xmin = d.xmax = None
-            if hasattr(self, "w1"):
-                nf = self.NFILT
-                d.weights = up(np.concatenate([a.reshape(nf, -1) for a in
-                                               (self.w1, self.b1, self.w2, self.b2, self.w3,
-                                                self.b3)], axis=1))
-                d.xmin, d.xmax = up(self.xmin), up(self.xmax)
-            d.ws = None
-            self._dev[str(dev)] = d
-        return d, torch
+        return _device(self, self.ygrid, device)
 
     def _params(self, nmodel, flags, corr_params, av=0., rv=3.3, dist=1000., loga_max=10.14,
                 eep_binary_max=480., mini_min=0., tol=1e-3, loga_target=0., nav=0, nrv=0):
@@ -519,8 +516,6 @@ class MISTtracks(object):
 
     def _tracks_call(self, labels5, p, out, device=None):
         """One call of `k_sed_tracks` alone: predictions (`out (N, Npred)`) or EEPs (`out (N,)`)."""
-        import ctypes as C
-        from .fitting import _stream_ptr
         d, torch = self._device(device)
         with torch.cuda.device(d.dev):
             lab = torch.from_numpy(np.ascontiguousarray(labels5, dtype=np.float64)).to(d.dev)
@@ -563,26 +558,12 @@ class MISTtracks(object):
         if ndim not in (1, 2):
             raise ValueError("Input `labels` not 1-D or 2-D.")
         mini, eep, feh = labels[[self.mini_idx, self.eep_idx, self.feh_idx]]
-        dtdm, drdm, msto_smooth, feh_scale = (_CORR_DEFAULT if corr_params is None
-                                              else corr_params)
-        with np.errstate(all="ignore"):
-            scale = (1 - 1. / (1. + np.exp(-(eep - 454) / msto_smooth))) * np.exp(feh_scale * feh)
-            dlogt = np.log10(1. + (mini - 1.) * dtdm) * scale
-            dlogr = np.log10(1. + (mini - 1.) * drdm) * scale
+        dlogt, dlogr = _corrections(mini, eep, feh, corr_params)
         if ndim == 1:
             return np.array([0., 0.]) if mini >= 1. else np.array([dlogt, dlogr])
         dlogt[mini >= 1.] = 0.
         dlogr[mini >= 1.] = 0.
         return np.c_[dlogt, dlogr]
-
-
-def _read_networks(nnfile, filters):
-    from . import h5io
-    rd = h5io.read_dataset
-    weights = {k: [rd(nnfile, "%s/%s" % (f, k)) for f in filters] for k in _NN_KEYS}
-    xmin = np.array([rd(nnfile, "%s/xmin" % f) for f in filters])
-    xmax = np.array([rd(nnfile, "%s/xmax" % f) for f in filters])
-    return weights, xmin, xmax
 
 
 def _fit_functionals(av_grid, av_wt, rv_grid, rv_wt):
@@ -647,8 +628,6 @@ class SEDmaker(MISTtracks):
     def _grid_call(self, d, torch, lab, p, eep2, fit, sed, param, param2, eep2_out, sel):
         """One call of the kernels on device tensors: `lab (N, 5)`, results into `sed`,
         `param`, `param2`, `eep2_out`, `sel`; `fit`: None or `(coef, av, rv)` on the device."""
-        import ctypes as C
-        from .fitting import _stream_ptr
         L = _lib.lib()
         n = lab.shape[0]
         need = L.brutus_sed_workspace_bytes(n, self.NFILT, p.nav * p.nrv)
@@ -843,7 +822,6 @@ class SEDmaker(MISTtracks):
         """Write the selected models of the last `make_grid` as a model-grid file that
         `utils.load_models` reads (reference utils.py:582-627): `mag_coeffs` (one `(3,)` field
         per filter), `labels` (the grid inputs) and `parameters` (the primary's predictions)."""
-        from . import h5io
         if not hasattr(self, "grid_sed"):
             raise ValueError("There is no grid yet: call `make_grid` first.")
         sel = self.grid_sel

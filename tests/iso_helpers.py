@@ -107,7 +107,72 @@ def make_lnl_data(get_seds):
     return phot, err, par, perr
 
 
-class HostIsochrone(object):
+# ---- what the numpy restatements of `seds.Isochrone` (below) and `seds.SEDmaker` (sed_helpers)
+# share: the table, the corrections, the networks ------------------------------------------------
+CORR_DEFAULT = (0.09, -0.09, 30., 0.5)
+
+
+def interp16(xgrid, table, q):
+    """`table (n0, n1, n2, n3, Npred)` over the axes `xgrid` at `q (N, 4)` -> `(N, Npred)`:
+    4-D multilinear, every corner enters, NaN outside.  (Under `np.errstate(all="ignore")`.)"""
+    n = q.shape[0]
+    idx, wts, inside = [], [], np.ones(n, bool)
+    for d, ax in enumerate(xgrid):
+        i = np.clip(np.searchsorted(ax, q[:, d], side="right") - 1, 0, len(ax) - 2)
+        idx.append(i)
+        wts.append((q[:, d] - ax[i]) / (ax[i + 1] - ax[i]))
+        inside &= (q[:, d] >= ax[0]) & (q[:, d] <= ax[-1])
+    out = np.zeros((n, table.shape[-1]))
+    for corner in range(16):
+        bits = [(corner >> (3 - d)) & 1 for d in range(4)]
+        w = np.ones(n)
+        for d in range(4):
+            w = w * (wts[d] if bits[d] else 1. - wts[d])
+        out = out + table[idx[0] + bits[0], idx[1] + bits[1], idx[2] + bits[2],
+                          idx[3] + bits[3]] * w[:, None]
+    out[~inside] = np.nan
+    return out
+
+
+def correct(out, col, mini, eep, feh, corr_params):
+    """The empirical corrections at (mini, eep, feh) onto the rows `out`, in place."""
+    dtdm, drdm, smooth, scale = CORR_DEFAULT if corr_params is None else corr_params
+    damp = (1. - 1. / (1. + np.exp(-(eep - 454.) / smooth))) * np.exp(scale * feh)
+    dlogt = np.where(mini >= 1., 0., np.log10(1. + (mini - 1.) * dtdm) * damp)
+    dlogr = np.where(mini >= 1., 0., np.log10(1. + (mini - 1.) * drdm) * damp)
+    out[:, col["logt"]] += dlogt
+    out[:, col["logl"]] += 2. * dlogr
+    out[:, col["logg"]] -= 2. * dlogr
+
+
+class HostNetworks(object):
+    """The networks of a restatement: `self.w`, `self.xmin`, `self.xmax` and `self.col` (name ->
+    column of a row of predictions) are the subclass's."""
+
+    def inputs(self, preds, av, rv):
+        """The networks' inputs of every row."""
+        c, n = self.col, preds.shape[0]
+        with np.errstate(all="ignore"):
+            return np.stack([10. ** preds[:, c["logt"]], preds[:, c["logg"]], preds[:, c["feh_surf"]],
+                             preds[:, c["afe_surf"]], np.full(n, av), np.full(n, rv)], axis=1)
+
+    def mags(self, preds, av, rv, dist):
+        """Apparent magnitudes `(N, Nfilt)`, NaN where an input is outside the networks' bounds."""
+        w = self.w
+        x = self.inputs(preds, av, rv)
+        with np.errstate(all="ignore"):
+            ok = np.all(np.isfinite(x), axis=1) & np.all((x >= self.xmin) & (x <= self.xmax), axis=1)
+            sig = lambda a: 1. / (1. + np.exp(-a))
+            xe = ((np.where(ok[:, None], x, self.xmin) - self.xmin) / (self.xmax - self.xmin)).T
+            a1 = sig(np.matmul(w["w1"], xe) + w["b1"])                       # (Nfilt, H1, N)
+            a2 = sig(np.matmul(w["w2"], a1) + w["b2"])
+            bc = (np.matmul(w["w3"], a2) + w["b3"])[:, 0, :].T               # (N, Nfilt)
+            m = (-2.5 * preds[:, self.col["logl"]] + 4.74)[:, None] - bc + (5. * np.log10(dist) - 5.)
+        m[~ok] = np.nan
+        return m
+
+
+class HostIsochrone(HostNetworks):
     """`seds.Isochrone` restated in numpy, whole arrays at a time: what a user could run on the
     host.  The secondaries' EEPs come from `np.interp`, as in the reference."""
 
@@ -132,55 +197,18 @@ class HostIsochrone(object):
     def get_predictions(self, feh=0., afe=0., loga=8.5, eep=None, apply_corr=True,
                         corr_params=None):
         eep = np.asarray(eep, float)
-        idx, wts, inside = [], [], np.ones(eep.shape, bool)
+        q = np.stack([np.broadcast_to(np.asarray(v, float), eep.shape)
+                      for v in (feh, afe, loga, eep)], axis=1)
         with np.errstate(all="ignore"):
-            for ax, q in zip(self.xgrid, (feh, afe, loga, eep)):
-                q = np.broadcast_to(np.asarray(q, float), eep.shape)
-                i = np.clip(np.searchsorted(ax, q, side="right") - 1, 0, len(ax) - 2)
-                idx.append(i)
-                wts.append((q - ax[i]) / (ax[i + 1] - ax[i]))
-                inside &= (q >= ax[0]) & (q <= ax[-1])
-            out = np.zeros(eep.shape + (self.pred_grid.shape[-1],))
-            for corner in range(16):
-                bits = [(corner >> (3 - d)) & 1 for d in range(4)]
-                w = np.ones(eep.shape)
-                for d in range(4):
-                    w = w * (wts[d] if bits[d] else 1. - wts[d])
-                out = out + self.pred_grid[idx[0] + bits[0], idx[1] + bits[1], idx[2] + bits[2],
-                                           idx[3] + bits[3]] * w[:, None]
-            out[~inside] = np.nan
+            out = interp16(self.xgrid, self.pred_grid, q)
             if apply_corr:
-                dtdm, drdm, smooth, scale = (0.09, -0.09, 30., 0.5) if corr_params is None else corr_params
-                mini = out[:, self.col["mini"]]
-                damp = (1. - 1. / (1. + np.exp(-(eep - 454.) / smooth))) * np.exp(scale * feh)
-                dlogt = np.where(mini >= 1., 0., np.log10(1. + (mini - 1.) * dtdm) * damp)
-                dlogr = np.where(mini >= 1., 0., np.log10(1. + (mini - 1.) * drdm) * damp)
-                out[:, self.col["logt"]] += dlogt
-                out[:, self.col["logl"]] += 2. * dlogr
-                out[:, self.col["logg"]] -= 2. * dlogr
+                correct(out, self.col, out[:, self.col["mini"]], eep, feh, corr_params)
         return out
 
-    def inputs(self, preds, av, rv):
-        """The networks' inputs of every row."""
-        c = self.col
-        n = preds.shape[0]
-        with np.errstate(all="ignore"):
-            return np.stack([10. ** preds[:, c["logt"]], preds[:, c["logg"]], preds[:, c["feh_surf"]],
-                             preds[:, c["afe_surf"]], np.full(n, av), np.full(n, rv)], axis=1)
-
     def _mags(self, preds, av, rv, dist, mini_bound):
-        c, w = self.col, self.w
-        x = self.inputs(preds, av, rv)
+        m = self.mags(preds, av, rv, dist)
         with np.errstate(all="ignore"):
-            ok = (np.all(np.isfinite(x), axis=1) & np.all((x >= self.xmin) & (x <= self.xmax), axis=1)
-                  & (preds[:, c["mini"]] >= mini_bound))
-            sig = lambda a: 1. / (1. + np.exp(-a))
-            xe = ((np.where(ok[:, None], x, self.xmin) - self.xmin) / (self.xmax - self.xmin)).T
-            a1 = sig(np.matmul(w["w1"], xe) + w["b1"])                       # (Nfilt, H1, N)
-            a2 = sig(np.matmul(w["w2"], a1) + w["b2"])
-            bc = (np.matmul(w["w3"], a2) + w["b3"])[:, 0, :].T               # (N, Nfilt)
-            m = (-2.5 * preds[:, c["logl"]] + 4.74)[:, None] - bc + (5. * np.log10(dist) - 5.)
-        m[~ok] = np.nan
+            m[~(preds[:, self.col["mini"]] >= mini_bound)] = np.nan
         return m
 
     def get_seds(self, feh=0., afe=0., loga=8.5, eep=None, av=0., rv=3.3, smf=0., dist=1000.,

@@ -7,12 +7,12 @@ from itertools import product
 
 import numpy as np
 
-from iso_helpers import make_networks  # noqa: F401  (the networks and their bounds are shared)
+# (the networks and their bounds, and the table / corrections / network arithmetic, are shared)
+from iso_helpers import CORR_DEFAULT, HostNetworks, correct, interp16, make_networks  # noqa: F401
 
 GOLDEN_SED = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "sedmaker.npz")
 LABELS = ["mini", "eep", "feh", "afe"]
 PREDICTIONS = ["loga", "logl", "logt", "logg", "feh_surf", "afe_surf"]     # (+ "agewt")
-CORR_DEFAULT = (0.09, -0.09, 30., 0.5)
 # name in the track file -> name here (the MIST column names)
 MIST_NAMES = {"mini": "initial_mass", "eep": "EEP", "feh": "initial_[Fe/H]", "afe": "initial_[a/Fe]",
               "mass": "star_mass", "feh_surf": "[Fe/H]", "afe_surf": "[a/Fe]", "loga": "log_age",
@@ -114,7 +114,7 @@ def default_grids():
     return av, (1e-5 + av) ** -1., np.arange(2.4, 4.2 + 1e-5, 0.3)
 
 
-class HostSEDmaker(object):
+class HostSEDmaker(HostNetworks):
     """`seds.SEDmaker` restated in numpy, whole arrays at a time: what a user could run on the
     host.  `get_eep` is the exact solve of the product (the first / nearest root of the
     piecewise-linear `loga` along the secondary's track), not the reference's minimiser."""
@@ -156,54 +156,11 @@ class HostSEDmaker(object):
     def get_predictions(self, labels, apply_corr=True, corr_params=None):
         """`labels (N, 4)` -> `(N, Npred)`: every corner enters, NaN outside."""
         q = np.atleast_2d(np.asarray(labels, float))
-        n = q.shape[0]
-        idx, wts, inside = [], [], np.ones(n, bool)
         with np.errstate(all="ignore"):
-            for d, ax in enumerate(self.xgrid):
-                i = np.clip(np.searchsorted(ax, q[:, d], side="right") - 1, 0, len(ax) - 2)
-                idx.append(i)
-                wts.append((q[:, d] - ax[i]) / (ax[i + 1] - ax[i]))
-                inside &= (q[:, d] >= ax[0]) & (q[:, d] <= ax[-1])
-            out = np.zeros((n, self.ygrid.shape[-1]))
-            for corner in range(16):
-                bits = [(corner >> (3 - d)) & 1 for d in range(4)]
-                w = np.ones(n)
-                for d in range(4):
-                    w = w * (wts[d] if bits[d] else 1. - wts[d])
-                out = out + self.ygrid[idx[0] + bits[0], idx[1] + bits[1], idx[2] + bits[2],
-                                       idx[3] + bits[3]] * w[:, None]
-            out[~inside] = np.nan
+            out = interp16(self.xgrid, self.ygrid, q)
             if apply_corr:
-                dtdm, drdm, smooth, scale = CORR_DEFAULT if corr_params is None else corr_params
-                mini, eep, feh = q[:, 0], q[:, 1], q[:, 2]
-                damp = (1. - 1. / (1. + np.exp(-(eep - 454.) / smooth))) * np.exp(scale * feh)
-                dlogt = np.where(mini >= 1., 0., np.log10(1. + (mini - 1.) * dtdm) * damp)
-                dlogr = np.where(mini >= 1., 0., np.log10(1. + (mini - 1.) * drdm) * damp)
-                out[:, self.col["logt"]] += dlogt
-                out[:, self.col["logl"]] += 2. * dlogr
-                out[:, self.col["logg"]] -= 2. * dlogr
+                correct(out, self.col, q[:, 0], q[:, 1], q[:, 2], corr_params)
         return out
-
-    def inputs(self, preds, av, rv):
-        """The networks' inputs of every row."""
-        c, n = self.col, preds.shape[0]
-        with np.errstate(all="ignore"):
-            return np.stack([10. ** preds[:, c["logt"]], preds[:, c["logg"]], preds[:, c["feh_surf"]],
-                             preds[:, c["afe_surf"]], np.full(n, av), np.full(n, rv)], axis=1)
-
-    def mags(self, preds, av, rv, dist):
-        w = self.w
-        x = self.inputs(preds, av, rv)
-        with np.errstate(all="ignore"):
-            ok = np.all(np.isfinite(x), axis=1) & np.all((x >= self.xmin) & (x <= self.xmax), axis=1)
-            sig = lambda a: 1. / (1. + np.exp(-a))
-            xe = ((np.where(ok[:, None], x, self.xmin) - self.xmin) / (self.xmax - self.xmin)).T
-            a1 = sig(np.matmul(w["w1"], xe) + w["b1"])
-            a2 = sig(np.matmul(w["w2"], a1) + w["b2"])
-            bc = (np.matmul(w["w3"], a2) + w["b3"])[:, 0, :].T
-            m = (-2.5 * preds[:, self.col["logl"]] + 4.74)[:, None] - bc + (5. * np.log10(dist) - 5.)
-        m[~ok] = np.nan
-        return m
 
     def get_eep(self, loga, mini=1., eep=350., feh=0., afe=0., smf=1., tol=1e-3):
         """The EEP where the track at `(mini * smf, feh, afe)` has age `loga`: the root of the
