@@ -87,7 +87,10 @@ __device__ __forceinline__ bool iso_interp4(const double *__restrict__ tab, cons
 }
 
 // np.interp(x, xp, fp, left=nan, right=nan) for increasing xp as a bisection of at most 32 steps.
+// A single node is numpy's special case: left below it, right above it and fp[0] otherwise -- for
+// a NaN x too, which no comparison moves off the node (with two nodes or more a NaN x gives NaN).
 __device__ __forceinline__ double iso_interp(double x, const double *xp, const double *fp, int n) {
+    if (n == 1) return x < xp[0] || x > xp[0] ? iso_nan() : fp[0];
     if (n <= 0 || !(x >= xp[0] && x <= xp[n - 1])) return iso_nan();
     if (x == xp[n - 1]) return fp[n - 1];
     int lo = 0, hi = n - 1;

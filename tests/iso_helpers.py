@@ -1,5 +1,6 @@
-"""Shared by tools/gen_golden.py (`gen_iso`) and the isochrone tests: the synthetic MIST-like
-table and networks that tests/golden/iso_seds.npz was made from, the list of its cases, and a
+"""Shared by tools/gen_golden.py (`gen_iso`, `gen_iso_edges`) and the isochrone tests: the
+synthetic MIST-like table and networks that tests/golden/iso_seds.npz and iso_edges.npz were
+made from, the lists of their cases, and a
 numpy restatement of `seds.Isochrone` (test infrastructure, not product; it is itself checked
 against the golden in tests/test_iso_host.py)."""
 import os
@@ -79,6 +80,86 @@ def case_arrays(name):
     w, xmin, xmax, filters = make_networks(*net)
     return dict(feh=feh, afe=afe, loga=loga, eep=eep, pred_grid=pred, weights=w, xmin=xmin,
                 xmax=xmax, filters=filters)
+
+
+# ---- the edge cases (tests/golden/iso_edges.npz, `tools/gen_golden.py iso_edges`) -----------------
+# Query sets that reach what EEP_QUERY does not in k_iso_compact (one workgroup, 256 shares of
+# per = ceil(Neep / 256) queries each), iso_cell / iso_interp4 (queries on nodes) and the padded
+# [alpha/Fe] pair.  All on the table and networks of "young".
+GOLDEN_ISO_EDGES = os.path.join(os.path.dirname(GOLDEN_ISO), "iso_edges.npz")
+EDGE_BASE = np.linspace(202., 808., 515)          # per = 3: 171 full shares, one of two, 84 empty
+_OUTSIDE = (np.nan, np.inf, 100., 900.)           # NaN, infinite, below the table, above it
+
+
+def _replaced(q, idx):
+    """`q` with the entries `idx` replaced by NaN, inf, 100., 900. in turn."""
+    q = q.copy()
+    idx = np.asarray(idx, dtype=int)
+    q[idx] = np.array(_OUTSIDE)[np.arange(len(idx)) % 4]
+    return q
+
+
+# the runs of holes515: leading (no finite predecessor), exactly share 2, a pair, shares 40..45
+# whole, a seeded half of 150..209, the last but one
+HOLE_RUNS = ([0, 1], [6, 7, 8], [100, 101], list(range(120, 138)),
+             sorted(150 + np.random.RandomState(5).permutation(60)[:30]), [513])
+
+
+def _swapped(i, j, nan=()):
+    q = EDGE_BASE.copy()
+    q[[i, j]] = q[[j, i]]
+    q[list(nan)] = np.nan
+    return q
+
+
+def _dup():
+    q = EDGE_BASE.copy()
+    q[201] = q[200]
+    return q
+
+
+def _one():
+    q = _replaced(np.zeros(300), np.arange(300))
+    q[137] = 350.
+    return q
+
+
+_NODES = np.linspace(200., 810., 61)
+# name -> (EEP queries, get_seds keywords, mass fractions, the flag status[0] of k_iso_compact)
+EDGE_CASES = {
+    "sorted515": (EDGE_BASE, dict(_BASE), (0.5, 0.95), 0),
+    "holes515": (_replaced(EDGE_BASE, np.concatenate(HOLE_RUNS)), dict(_BASE), (0.5, 0.95), 0),
+    "holes515_old": (_replaced(EDGE_BASE, np.concatenate(HOLE_RUNS)), dict(CASES["old"][2]), (0.5,), 0),
+    # (per = 2; the last share holds one query, index 256, and it is NaN)
+    "holes257": (_replaced(np.linspace(202., 808., 257), [256, 100, 101, 0]), dict(_BASE), (0.5,), 0),
+    # (all swaps below index 230: EEP 480, the binary cut, is index 235)
+    "swap_in_share": (_swapped(150, 151), dict(_BASE), (0.95,), 1),
+    "swap_across": (_swapped(152, 153), dict(_BASE), (0.95,), 1),
+    "swap_across_nan": (_swapped(155, 174, nan=range(156, 174)), dict(_BASE), (0.95,), 1),
+    "dup": (_dup(), dict(_BASE), (0.95,), 1),
+    "none": (_replaced(np.zeros(40), np.arange(40)), dict(_BASE), (0.5,), 0),
+    "one": (_one(), dict(_BASE), (0.5,), 0),
+    "n2": (np.linspace(300., 460., 2), dict(_BASE), (0.5,), 0),
+    "n3": (np.linspace(300., 460., 3), dict(_BASE), (0.5,), 0),
+    "nodes_mid": (_NODES, dict(_BASE, feh=-0.5, loga=9.0), (0.5,), 0),
+    "nodes_lo": (_NODES, dict(_BASE, feh=-1.0, loga=8.5), (0.5,), 0),
+    "nodes_hi": (_NODES, dict(_BASE, feh=0.5, loga=10.15), (0.5,), 0),
+    "afe_pair_0": (EEP_QUERY[::10], dict(_BASE, afe=0.), (0.,), 0),
+    "afe_pair_plus": (EEP_QUERY[::10], dict(_BASE, afe=1e-5), (0.,), 0),
+    "afe_pair_minus": (EEP_QUERY[::10], dict(_BASE, afe=-1e-5), (0.,), 0),
+    "afe_pair_outside": (EEP_QUERY[::10], dict(_BASE, afe=2e-5), (0.,), 0),
+}
+# A single query: the reference's get_seds cannot unpack it, so it has no golden and is compared
+# with the restatement alone.
+EDGE_N1 = (np.array([350.]), dict(_BASE), (0.5,), 0)
+# those whose every output row is NaN, and those meant to hold secondaries (>= 100 finite rows)
+EDGE_ALL_NAN = ("none", "afe_pair_outside")
+EDGE_WITH_SECONDARIES = ("sorted515", "holes515", "holes515_old", "swap_in_share", "swap_across",
+                         "swap_across_nan", "dup")
+
+
+def edge_entries():
+    return [(name, smf) for name, c in EDGE_CASES.items() for smf in c[2]]
 
 
 # The likelihood cases: 200 objects x 5 bands drawn from the isochrone itself.
@@ -250,10 +331,13 @@ class SedsOnly(object):
         self.get_seds = iso.get_seds
 
 
-def assert_matches(seds, p1, p2, golden, name, smf, kw):
+def assert_matches(seds, p1, p2, golden, name, smf, kw, params_key=None):
     """`get_seds(..., return_dict=False)` output against the golden of a case: identical NaN
-    pattern; finite values to 1e-9, absolute in magnitudes and relative in parameters."""
-    ref = (golden["%s_smf%g_seds" % (name, smf)], golden["%s_mb%g_params" % (name, kw["mini_bound"])],
+    pattern; finite values to 1e-9, absolute in magnitudes and relative in parameters.
+    `params_key`: the golden's key of the primaries' parameters (the edge cases keep one per
+    case, "<name>_params")."""
+    ref = (golden["%s_smf%g_seds" % (name, smf)],
+           golden[params_key or "%s_mb%g_params" % (name, kw["mini_bound"])],
            golden["%s_smf%g_params2" % (name, smf)])
     for what, got, want, rel in zip(("seds", "params", "params2"), (seds, p1, p2), ref,
                                     (False, True, True)):

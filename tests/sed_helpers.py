@@ -1,6 +1,6 @@
-"""Shared by tools/gen_golden.py (`gen_sedmaker`), tools/make_grid_rate.py and the SEDmaker
-tests: the synthetic MIST-like EEP tracks that tests/golden/sedmaker.npz was made from, its
-grids, and a numpy restatement of `seds.SEDmaker` (test infrastructure, not product; it is
+"""Shared by tools/gen_golden.py (`gen_sedmaker`, `gen_sedmaker_edges`), tools/make_grid_rate.py
+and the SEDmaker tests: the synthetic MIST-like EEP tracks that tests/golden/sedmaker.npz and
+sedmaker_edges.npz were made from, their grids, and a numpy restatement of `seds.SEDmaker` (test infrastructure, not product; it is
 itself checked against the golden in tests/test_sedmaker_host.py)."""
 import os
 from itertools import product
@@ -105,6 +105,93 @@ def case_arrays(name):
     labels, output = make_tracks(two_afe=CASES[name][0])
     w, xmin, xmax, filters = make_networks(*CASES[name][1])
     return dict(labels=labels, output=output, weights=w, xmin=xmin, xmax=xmax, filters=filters)
+
+
+# ---- the edge cases (tests/golden/sedmaker_edges.npz, `tools/gen_golden.py sedmaker_edges`) ------
+# Fit grids at the limits of k_sed_nn_fit (2 x 2, 256 points, 3 x 85, explicit weights, a point
+# outside the networks' bounds) on a small grid, and labels on the nodes of the track table.
+GOLDEN_SED_EDGES = os.path.join(os.path.dirname(GOLDEN_SED), "sedmaker_edges.npz")
+GRID_S = dict(mini_grid=np.array([0.55, 0.9, 1.1, 1.3]), eep_grid=np.array([215., 330., 410., 505.]),
+              feh_grid=np.array([-1., -0.3, 0.5]), afe_grid=np.array([0.]),
+              smf_grid=np.array([0., 0.7]))
+# (On GRID_S no secondary of mass 0.7 mini is as old as its primary at an EEP of the table, so its
+# binaries have no SED; GRID_S85 is the same grid with secondaries that exist.)
+GRID_S85 = dict(GRID_S, smf_grid=np.array([0., 0.85]))
+_NODES_AB = dict(mini_grid=np.array([0.3, 0.5, 0.9, 1.1, 2.0]),
+                 eep_grid=np.array([200., 400., 410., 430., 600., 610., 810.]),
+                 feh_grid=np.array([-1., 0., 0.5]), smf_grid=np.array([0.]))
+GRID_NODES_A = dict(_NODES_AB, afe_grid=np.array([0., 0.2, 0.4]))
+GRID_NODES_B = dict(_NODES_AB, afe_grid=np.array([0., 1e-5, -1e-5, 2e-5]))
+
+
+def _fit16(default_wt):
+    rng = np.random.RandomState(16)
+    fit = dict(av_grid=np.sort(rng.uniform(0., 3.9, 16)), rv_grid=np.sort(rng.uniform(1.1, 7.9, 16)),
+               av_wt=rng.uniform(0.5, 2., 16), rv_wt=rng.uniform(0.5, 2., 16))
+    if default_wt:
+        fit["av_grid"][0] = 0.
+        del fit["av_wt"], fit["rv_wt"]
+    return fit
+
+
+FITS = {
+    "fit2x2": dict(av_grid=np.array([0., 1.]), rv_grid=np.array([2.5, 4.])),
+    "fit16x16": _fit16(False),
+    "fit16x16_dw": _fit16(True),
+    "fit3x85": dict(av_grid=np.array([0.1, 0.7, 2.]), rv_grid=np.linspace(1.5, 7.5, 85)),
+    "fit_outside": dict(av_grid=np.array([0., 1., 2., 4.5]), rv_grid=np.array([2.5, 3.3, 4.])),
+}
+_NET, _NET64 = (5, 10, 7, 11), (3, 64, 64, 13)
+# name -> (two_afe, networks, grid, make_grid keywords); the fit cases first
+EDGE_CASES = {
+    "fit2x2": (False, _NET, GRID_S, dict(FITS["fit2x2"], apply_corr=False)),
+    "fit16x16": (False, _NET, GRID_S, dict(FITS["fit16x16"], apply_corr=False)),
+    "fit16x16_64": (False, _NET64, GRID_S, dict(FITS["fit16x16"], apply_corr=False)),
+    "fit16x16_dw": (False, _NET, GRID_S, dict(FITS["fit16x16_dw"], apply_corr=False)),
+    "fit3x85": (False, _NET, GRID_S, dict(FITS["fit3x85"], apply_corr=False)),
+    "fit_outside": (False, _NET, GRID_S, dict(FITS["fit_outside"], apply_corr=False)),
+    "fit16x16_s85": (False, _NET, GRID_S85, dict(FITS["fit16x16"], apply_corr=False)),
+    "on_nodes_A": (True, _NET, GRID_NODES_A, dict(mini_bound=0.1)),
+    "on_nodes_B": (False, _NET, GRID_NODES_B, dict(mini_bound=0.1)),
+}
+# Grids compared with the restatement alone (no golden): name -> (networks, grid, keywords)
+LIST_CASES = {
+    "only_binaries": (_NET, dict(GRID_S, smf_grid=np.array([0.7])), dict(apply_corr=False)),
+    "only_binaries85": (_NET, dict(GRID_S, smf_grid=np.array([0.85])), dict(apply_corr=False)),
+    "nothing": (_NET, GRID_S, dict(apply_corr=False, loga_max=5.)),
+    "one_model": (_NET, dict(mini_grid=np.array([1.1]), eep_grid=np.array([330.]),
+                             feh_grid=np.array([-0.3]), afe_grid=np.array([0.]),
+                             smf_grid=np.array([0.])), dict(apply_corr=False)),
+}
+
+
+def edge_kwargs(name):
+    kw = dict(EDGE_CASES[name][2])
+    kw.update(EDGE_CASES[name][3])
+    return kw
+
+
+def table_arrays(two_afe, net):
+    """The arguments of `SEDmaker.from_arrays`: table A (`two_afe`) or B with the networks `net`."""
+    labels, output = make_tracks(two_afe=two_afe)
+    w, xmin, xmax, filters = make_networks(*net)
+    return dict(labels=labels, output=output, weights=w, xmin=xmin, xmax=xmax, filters=filters)
+
+
+def edge_arrays(name):
+    return table_arrays(*EDGE_CASES[name][:2])
+
+
+def functional_slopes(host, lab, sel, e2, av_grid, rv_grid, av_wt=None, rv_wt=None, **kw):
+    """`(seda, sedr) (Nsel, Nfilt)` the way the device forms them: the coefficients of
+    `seds._fit_functionals` applied to the restatement's magnitudes at the fit points."""
+    from brutus_amd import seds
+    av_wt = (1e-5 + av_grid) ** -1. if av_wt is None else av_wt
+    coef = seds._fit_functionals(av_grid, av_wt, rv_grid, rv_wt)
+    with np.errstate(all="ignore"):
+        mags = np.array([[host.get_sed(lab[sel], av=a, rv=r, eep2=e2[sel], **kw)[0]
+                          for a in av_grid] for r in rv_grid])               # (Nrv, Nav, Nsel, Nfilt)
+        return np.einsum("ra,ranf->nf", coef[0], mags), np.einsum("ra,ranf->nf", coef[1], mags)
 
 
 def default_grids():

@@ -1,9 +1,11 @@
 """CPU: `brutus_amd.seds.Isochrone` without a device -- the golden file holds what its generator
 promises, the constructor's table equals the reference's, the C ABI refuses bad dimensions
 before any HIP call, the signatures are the reference's, and the numpy restatement of
-tests/iso_helpers.py (the host plug-in of the GPU tests) reproduces the golden."""
+tests/iso_helpers.py (the host plug-in of the GPU tests) reproduces the golden and the edge
+cases of tests/golden/iso_edges.npz."""
 import ctypes
 import inspect
+import os
 
 import numpy as np
 import pytest
@@ -125,3 +127,54 @@ def test_numpy_restatement_reproduces_the_golden(golden, name, smf):
     kw = H.case_kwargs(name, smf)
     seds, p1, p2 = host.get_seds(eep=H.EEP_QUERY, smf=smf, return_dict=False, **kw)
     H.assert_matches(seds, p1, p2, golden, name, smf, kw)
+
+
+# ---- the edge cases: tests/golden/iso_edges.npz ---------------------------------------------------
+@pytest.fixture(scope="module")
+def edges():
+    return np.load(H.GOLDEN_ISO_EDGES)
+
+
+def test_edge_golden_conditions(edges):
+    """What the edge cases are there for is in the file: the shares of k_iso_compact that the
+    query sets reach, finite rows around every run of holes, the flag each case has to raise,
+    counts of 0 and 1, >= 100 secondaries where they are meant to be."""
+    per = lambda n: -(-n // 256)
+    assert per(515) == 3 and per(257) == 2 and per(300) == 2 and per(61) == 1
+    assert {name for name, _ in H.edge_entries()} == set(H.EDGE_CASES)
+    for name, (eep, kw, smfs, flag) in H.EDGE_CASES.items():
+        mini = edges[name + "_params"][:, 0]
+        fin = np.isfinite(mini)
+        assert mini.shape == eep.shape
+        assert int(np.any(np.diff(mini[fin]) <= 0.)) == flag, name
+        for smf in smfs:
+            seds, p2 = edges["%s_smf%g_seds" % (name, smf)], edges["%s_smf%g_params2" % (name, smf)]
+            assert seds.shape == (len(eep), 5) and p2.shape == (len(eep), 8)
+            if name in H.EDGE_ALL_NAN:
+                assert np.isnan(seds).all() and np.isnan(p2).all() and not fin.any()
+            if name in H.EDGE_WITH_SECONDARIES:
+                assert np.isfinite(p2).all(axis=1).sum() >= 100, (name, smf)
+    mini = edges["holes515_params"][:, 0]
+    for run in H.HOLE_RUNS:
+        assert np.isnan(mini[run]).all()
+        assert all(np.isfinite(mini[k]) for k in (min(run) - 1, max(run) + 1) if k >= 0)
+    assert np.isnan(edges["holes257_params"][256]).all()          # the last share: one query, NaN
+    assert np.isfinite(edges["one_params"][:, 0]).sum() == 1
+    # a single node of np.interp serves the NaN queries too: secondaries without a primary
+    lone = np.isfinite(edges["one_smf0.5_params2"]).all(axis=1)
+    assert lone.sum() > 100 and not (lone & np.isfinite(edges["one_params"][:, 0])).any()
+    # the exchanged pairs: inside share 50, across 50 | 51, across six empty shares; the equal pair
+    for name, (i, j) in (("swap_in_share", (150, 151)), ("swap_across", (152, 153)),
+                         ("swap_across_nan", (155, 174)), ("dup", (200, 201))):
+        m = edges[name + "_params"][:, 0]
+        assert not m[j] > m[i] and np.isnan(m[i + 1:j]).all(), name
+    assert (150 // 3, 151 // 3, 152 // 3, 153 // 3, 155 // 3, 174 // 3) == (50, 50, 50, 51, 51, 58)
+    assert os.path.getsize(H.GOLDEN_ISO_EDGES) < 518536
+
+
+@pytest.mark.parametrize("name,smf", H.edge_entries())
+def test_numpy_restatement_reproduces_the_edge_golden(edges, name, smf):
+    host = H.HostIsochrone(**H.case_arrays("young"))
+    eep, kw = H.EDGE_CASES[name][:2]
+    seds, p1, p2 = host.get_seds(eep=eep, smf=smf, return_dict=False, **kw)
+    H.assert_matches(seds, p1, p2, edges, name, smf, kw, params_key=name + "_params")

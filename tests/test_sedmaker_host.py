@@ -3,7 +3,9 @@ its generator promises, construction from arrays and from a track file equals th
 table, the signatures are the reference's, the `rv_wt` default is the reference's (unweighted),
 the limits raise on the host, the C ABI refuses bad dimensions before any HIP call, `save_grid`
 writes what `utils.load_models` reads, and the numpy restatement of tests/sed_helpers.py (the
-host side of the GPU tests) reproduces the golden."""
+host side of the GPU tests) reproduces the golden and the edge cases of
+tests/golden/sedmaker_edges.npz, where the slopes are also formed by the device's route through
+`seds._fit_functionals`."""
 import ctypes
 import inspect
 import os
@@ -283,3 +285,66 @@ def test_save_grid_round_trip(tmp_path):
     singles = utils.load_models(path, filters=sm.filters, verbose=False)
     assert len(singles[0]) == (sel & (sm.grid_label["smf"] == 0.)).sum()
     assert "smf" not in singles[1].dtype.names
+
+
+# ---- the edge cases: tests/golden/sedmaker_edges.npz ----------------------------------------------
+@pytest.fixture(scope="module")
+def edges():
+    return np.load(H.GOLDEN_SED_EDGES)
+
+
+def _slope_err(got, want):
+    """Worst |difference| of two sets of slopes with the same NaN pattern (0 if none is finite)."""
+    assert np.array_equal(np.isnan(got), np.isnan(want))
+    fin = np.isfinite(want)
+    return float(np.max(np.abs(got[fin] - want[fin]))) if fin.any() else 0.
+
+
+@pytest.mark.parametrize("name", list(H.EDGE_CASES))
+def test_host_restatement_reproduces_the_edge_golden(edges, name):
+    """`HostSEDmaker` with the reference's `eep2` on every edge case: the same labels, selection
+    and NaN patterns, magnitudes and parameters to 1e-9, slopes to the 1e-8 of the test above.
+    Then the slopes by the route the device takes -- the coefficients of `seds._fit_functionals`
+    on the restatement's magnitudes at the fit points -- against the golden's.  The two errors
+    are printed: the larger is the `d` of the case in tests/test_gpu_seds_edges.py."""
+    h = H.HostSEDmaker(**H.edge_arrays(name))
+    kw = H.edge_kwargs(name)
+    lab, sed, par, sel, e2 = h.make_grid(eep2=edges[name + "_eep2"], **kw)
+    ref, want = edges[name + "_sed"], edges[name + "_param"]
+    assert np.array_equal(lab, edges[name + "_label"]) and np.array_equal(sel, edges[name + "_sel"])
+    fin = np.isfinite(want)
+    assert np.array_equal(np.isfinite(par), fin) and np.array_equal(np.isnan(par), np.isnan(want))
+    assert np.max(np.abs(par[fin] - want[fin]) / np.maximum(np.abs(want[fin]), 1e-300)) < 1e-9
+    assert np.array_equal(np.isnan(sed), np.isnan(ref)) and np.isnan(sed[~sel]).all()
+    assert np.isfinite(sed[sel][..., 0]).all()
+    assert np.max(np.abs(sed[sel][..., 0] - ref[sel][..., 0])) < 1e-9
+    err = _slope_err(sed[sel][..., 1:], ref[sel][..., 1:])
+    fit = {k: kw[k] for k in ("av_grid", "rv_grid", "av_wt", "rv_wt") if k in kw}
+    for k, g in zip(("av_grid", "_", "rv_grid"), H.default_grids()):
+        fit.setdefault(k, g)
+    fit.pop("_")
+    rest = {k: v for k, v in kw.items() if k in ("apply_corr", "corr_params", "mini_bound")}
+    seda, sedr = H.functional_slopes(h, lab, sel, edges[name + "_eep2"], **fit, **rest)
+    ferr = max(_slope_err(seda, ref[sel][..., 1]), _slope_err(sedr, ref[sel][..., 2]))
+    print("%s: %d selected; slopes against the golden: restatement (np.polyfit) %.3g, functionals %.3g"
+          % (name, sel.sum(), err, ferr))
+    if name == "fit_outside":             # a fit point outside the networks: NaN slopes, selection kept
+        assert np.isnan(sed[sel][..., 1:]).all() and sel.sum() == 37
+    else:
+        assert np.isfinite(sed[sel]).all()
+    assert err < 1e-8 and ferr < 1e-8
+
+
+@pytest.mark.parametrize("net", [(5, 8, 7, 11), (5, 10, 7, 11), (3, 64, 64, 13)],
+                         ids=lambda n: "h1_%d" % n[1])
+def test_functionals_against_polyfit_on_the_default_fit(net):
+    """The default 7 x 6 fit on GRID_S85, which has no golden: the functionals' slopes against
+    the restatement's np.polyfit (printed: the `d` of the restatement-only GPU tests)."""
+    h = H.HostSEDmaker(**H.table_arrays(False, net))
+    lab, sed, _, sel, e2 = h.make_grid(apply_corr=False, **H.GRID_S85)
+    av, _, rv = H.default_grids()
+    seda, sedr = H.functional_slopes(h, lab, sel, e2, av, rv, apply_corr=False)
+    ferr = max(_slope_err(seda, sed[sel][..., 1]), _slope_err(sedr, sed[sel][..., 2]))
+    print("h1 = %d: %d selected (%d binaries); functionals against np.polyfit %.3g"
+          % (net[1], sel.sum(), (sel & (lab[:, 4] > 0)).sum(), ferr))
+    assert sel.sum() > 30 and (sel & (lab[:, 4] > 0)).sum() >= 5 and ferr < 1e-8

@@ -352,36 +352,56 @@ def gen_cluster():
     np.savez_compressed(os.path.join(OUT, "cluster.npz"), **res)
 
 
+def _clear(v, bound, span=1.):
+    """No finite entry of `v` within 1e-6 (of `span`) of `bound`."""
+    v = np.asarray(v, float)
+    v = v[np.isfinite(v)]
+    return v.size == 0 or np.min(np.abs(v - bound)) > 1e-6 * span
+
+
+def _iso_reference(name):
+    """The reference's `Isochrone` and the numpy restatement on the arrays of a case of
+    tests/iso_helpers.py, and the reference module."""
+    import importlib
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import iso_helpers as H
+    S = importlib.import_module("brutus.seds")
+    a = H.case_arrays(name)
+    iso = object.__new__(S.Isochrone)
+    iso.filters, iso.predictions, iso.pred_labels = a["filters"], H.PREDICTIONS, H.PREDICTIONS
+    iso.feh_grid, iso.afe_grid, iso.loga_grid, iso.eep_grid = a["feh"], a["afe"], a["loga"], a["eep"]
+    iso.pred_grid = a["pred_grid"].copy()
+    iso.build_interpolator()
+    nn = object.__new__(S.FastNNPredictor)
+    nn.filters, nn.NFILT = a["filters"], len(a["filters"])
+    for k, v in a["weights"].items():
+        setattr(nn, k, v)
+    nn.xmin, nn.xmax, nn.xspan = a["xmin"], a["xmax"], a["xmax"] - a["xmin"]
+    iso.FNNP = nn
+    return iso, H.HostIsochrone(**a), S
+
+
+def _iso_off_thresholds(host, kw, tag, p1, p2, eep2):
+    """Nothing sits on a threshold: the networks' bounds, the mass cuts, the binary cut."""
+    for p in (p1, p2):
+        x = host.inputs(p, kw["av"], kw["rv"])
+        for d in range(6):
+            for b in (host.xmin[d], host.xmax[d]):
+                assert _clear(x[:, d], b, host.xmax[d] - host.xmin[d]), (tag, d)
+        assert _clear(p[:, 0], kw["mini_bound"]) and _clear(p[:, 0], 1.), tag
+    assert _clear(eep2, kw["eep_binary_max"]), tag
+
+
 def gen_iso():
     """`seds.Isochrone.get_seds` (reference seds.py:1360-1502) and `cluster.isochrone_loglike`
     with that isochrone, on the synthetic table and networks of tests/iso_helpers.py.  The
     conditions of the golden (no comparison hinges on a rounding flip) are asserted here, on
     the reference's own output."""
-    import importlib
     import inspect
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import iso_helpers as H
-    S = importlib.import_module("brutus.seds")
-
-    def reference(name):
-        a = H.case_arrays(name)
-        iso = object.__new__(S.Isochrone)
-        iso.filters, iso.predictions, iso.pred_labels = a["filters"], H.PREDICTIONS, H.PREDICTIONS
-        iso.feh_grid, iso.afe_grid, iso.loga_grid, iso.eep_grid = a["feh"], a["afe"], a["loga"], a["eep"]
-        iso.pred_grid = a["pred_grid"].copy()
-        iso.build_interpolator()
-        nn = object.__new__(S.FastNNPredictor)
-        nn.filters, nn.NFILT = a["filters"], len(a["filters"])
-        for k, v in a["weights"].items():
-            setattr(nn, k, v)
-        nn.xmin, nn.xmax, nn.xspan = a["xmin"], a["xmax"], a["xmax"] - a["xmin"]
-        iso.FNNP = nn
-        return iso, H.HostIsochrone(**a)
-
-    def clear(v, bound, span=1.):
-        v = np.asarray(v, float)
-        v = v[np.isfinite(v)]
-        return v.size == 0 or np.min(np.abs(v - bound)) > 1e-6 * span
+    reference = lambda name: _iso_reference(name)[:2]
+    S = _iso_reference("young")[2]
 
     res = {}
     for name, (_, _, _, smfs) in H.CASES.items():
@@ -410,13 +430,8 @@ def gen_iso():
             if 0. < smf < 1.:
                 ok = np.isfinite(mini)
                 eep2 = np.interp(mini * smf, mini[ok], H.EEP_QUERY[ok], left=np.nan, right=np.nan)
-            for p in (p1, p2):
-                x = host.inputs(p, kw["av"], kw["rv"])
-                for d in range(6):
-                    for b in (host.xmin[d], host.xmax[d]):
-                        assert clear(x[:, d], b, host.xmax[d] - host.xmin[d]), (tag, d)
-                assert clear(p[:, 0], kw["mini_bound"]) and clear(p[:, 0], 1.), tag
-            assert clear(H.EEP_QUERY, kw["eep_binary_max"]) and clear(eep2, kw["eep_binary_max"]), tag
+            _iso_off_thresholds(host, kw, tag, p1, p2, eep2)
+            assert _clear(H.EEP_QUERY, kw["eep_binary_max"]), tag
     for meth in ("__init__", "get_predictions", "get_corrections", "get_seds"):
         res["sig_" + meth] = str(inspect.signature(getattr(S.Isochrone, meth)))
 
@@ -439,6 +454,108 @@ def gen_iso():
     np.savez_compressed(os.path.join(OUT, "iso_seds.npz"), **res)
 
 
+def gen_iso_edges():
+    """`seds.Isochrone.get_seds` on the edge cases of tests/iso_helpers.py (`EDGE_CASES`): query
+    sets of 2 to 515 EEPs with holes, exchanged and equal neighbours, queries on the table's
+    nodes and on the padded [alpha/Fe] pair.  The reference objects are `gen_iso`'s; the
+    conditions are asserted on the reference's own output."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import iso_helpers as H
+    iso, host, _ = _iso_reference("young")
+    res = {}
+    for name, (eep, kw, smfs, flag) in H.EDGE_CASES.items():
+        for smf in smfs:
+            seds, p1, p2 = iso.get_seds(eep=eep, smf=smf, return_dict=False, **kw)
+            tag = "%s_smf%g" % (name, smf)
+            res[tag + "_seds"], res[tag + "_params2"], res[name + "_params"] = seds, p2, p1
+            mini = p1[:, 0]
+            ok = np.isfinite(mini)
+            nsec = int(np.all(np.isfinite(p2), axis=1).sum())
+            print("iso_edges", tag, "finite primaries", ok.sum(), "finite secondaries", nsec,
+                  "finite rows of magnitudes", np.all(np.isfinite(seds), axis=1).sum(), "of", len(eep))
+            if name in H.EDGE_ALL_NAN:
+                assert np.isnan(seds).all() and np.isnan(p1).all() and np.isnan(p2).all(), tag
+                continue
+            if name == "one":
+                # np.interp on a single node gives fp[0] to a NaN query: the rows whose own
+                # primary is NaN (and whose EEP is not above the cut) have a secondary
+                assert ok.sum() == 1 and nsec > 100 and not np.isfinite(p2[ok]).any(), tag
+            else:
+                # (n2, n3: the secondaries' masses fall below the first node or the networks'
+                # Teff bound is passed, no magnitude is finite; the parameters are what they pin)
+                assert ok.any() and (np.isfinite(seds).any() or name in ("n2", "n3")), tag
+            # the flag the device has to raise: a pair of finite masses that does not increase
+            assert int(np.any(np.diff(mini[ok]) <= 0.)) == flag, tag
+            eep2 = np.full_like(mini, np.nan)
+            if 0. < smf < 1.:
+                eep2 = np.interp(mini * smf, mini[ok], eep[ok], left=np.nan, right=np.nan)
+            # (the queries themselves are given, not computed: an EEP node may sit on the cut)
+            _iso_off_thresholds(host, kw, tag, p1, p2, eep2)
+            if name in H.EDGE_WITH_SECONDARIES:
+                assert nsec >= 100, (tag, nsec)
+            if flag:
+                # np.interp on an `xp` that is not increasing: no query mass within 1e-6
+                # (relative) of a node, so the last bits of `mini` cannot change its branch
+                x, xp = (mini * smf)[ok], mini[ok]
+                gap = np.min(np.abs(x[:, None] - xp[None, :]) / xp[None, :])
+                print("   nearest (query mass, node of xp): %.3g relative" % gap)
+                assert gap > 1e-6, (tag, gap)
+        if name == "holes515":
+            # finite rows on both sides of every run (the leading one has no left side), NaN inside
+            for run in H.HOLE_RUNS:
+                assert not ok[run].any(), run
+                for side in (min(run) - 1, max(run) + 1):
+                    assert side < 0 or ok[side], (run, side)
+            assert np.isnan(seds).all(axis=1).sum() > len(np.concatenate(H.HOLE_RUNS))
+    path = os.path.join(OUT, "iso_edges.npz")
+    np.savez_compressed(path, **res)
+    print("iso_edges.npz: %d bytes" % os.path.getsize(path))
+    assert os.path.getsize(path) < 518536
+
+
+def _sed_reference(a):
+    """The reference's `SEDmaker` on the arrays `a` (as `SEDmaker.from_arrays` takes them), the
+    `(eep2, residual)` its `get_eep` returned per call, and the numpy restatement."""
+    import importlib
+    import warnings
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import sed_helpers as H
+    np.float = float                      # (the reference's make_grid uses the removed alias)
+    S = importlib.import_module("brutus.seds")
+    sm = object.__new__(S.SEDmaker)
+    sm.labels, sm.predictions = list(H.LABELS), list(H.PREDICTIONS)
+    sm.ndim, sm.npred = 4, len(sm.predictions)
+    sm.mini_idx, sm.eep_idx, sm.feh_idx = 0, 1, 2
+    for n in ("logt", "logl", "logg"):
+        setattr(sm, n + "_idx", sm.predictions.index(n))
+    sm.libparams = np.zeros(len(a["labels"]), dtype=[(n, float) for n in H.LABELS])
+    for k, n in enumerate(H.LABELS):
+        sm.libparams[n] = a["labels"][:, k]
+    sm.output = a["output"].copy()
+    sm.lib_as_grid()
+    sm._ageidx = sm.predictions.index("loga")
+    sm.add_age_weights(verbose=False)
+    sm.build_interpolator()
+    sm.filters = a["filters"]
+    nn = object.__new__(S.FastNNPredictor)
+    nn.filters, nn.NFILT = a["filters"], len(a["filters"])
+    for k, v in a["weights"].items():
+        setattr(nn, k, v)
+    nn.xmin, nn.xmax, nn.xspan = a["xmin"], a["xmax"], a["xmax"] - a["xmin"]
+    sm.FNNP = nn
+    solved, inner = {}, sm.get_eep
+
+    def get_eep(loga, mini=1., eep=350., feh=0., afe=0., smf=1., tol=1e-3):
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            e2 = inner(loga, mini=mini, eep=eep, feh=feh, afe=afe, smf=smf, tol=tol)
+            fun = (sm.get_predictions([mini * smf, e2, feh, afe])[sm._ageidx] - loga) ** 2
+        solved[(loga, mini, eep, feh, smf)] = (e2, fun)
+        return e2
+    sm.get_eep = get_eep
+    return sm, solved, H.HostSEDmaker(**a)
+
+
 def gen_sedmaker():
     """`seds.MISTtracks` / `seds.SEDmaker` (reference seds.py:49-857): construction from a
     library, `get_predictions`, `get_corrections`, `get_sed` and `make_grid` on the synthetic
@@ -454,45 +571,8 @@ def gen_sedmaker():
     S = importlib.import_module("brutus.seds")
     TOL = 1e-3
 
-    def reference(name):
-        a = H.case_arrays(name)
-        sm = object.__new__(S.SEDmaker)
-        sm.labels, sm.predictions = list(H.LABELS), list(H.PREDICTIONS)
-        sm.ndim, sm.npred = 4, len(sm.predictions)
-        sm.mini_idx, sm.eep_idx, sm.feh_idx = 0, 1, 2
-        for n in ("logt", "logl", "logg"):
-            setattr(sm, n + "_idx", sm.predictions.index(n))
-        sm.libparams = np.zeros(len(a["labels"]), dtype=[(n, float) for n in H.LABELS])
-        for k, n in enumerate(H.LABELS):
-            sm.libparams[n] = a["labels"][:, k]
-        sm.output = a["output"].copy()
-        sm.lib_as_grid()
-        sm._ageidx = sm.predictions.index("loga")
-        sm.add_age_weights(verbose=False)
-        sm.build_interpolator()
-        sm.filters = a["filters"]
-        nn = object.__new__(S.FastNNPredictor)
-        nn.filters, nn.NFILT = a["filters"], len(a["filters"])
-        for k, v in a["weights"].items():
-            setattr(nn, k, v)
-        nn.xmin, nn.xmax, nn.xspan = a["xmin"], a["xmax"], a["xmax"] - a["xmin"]
-        sm.FNNP = nn
-        solved, inner = {}, sm.get_eep
-
-        def get_eep(loga, mini=1., eep=350., feh=0., afe=0., smf=1., tol=1e-3):
-            with warnings.catch_warnings():
-                warnings.simplefilter("ignore")
-                e2 = inner(loga, mini=mini, eep=eep, feh=feh, afe=afe, smf=smf, tol=tol)
-                fun = (sm.get_predictions([mini * smf, e2, feh, afe])[sm._ageidx] - loga) ** 2
-            solved[(loga, mini, eep, feh, smf)] = (e2, fun)
-            return e2
-        sm.get_eep = get_eep
-        return sm, solved, H.HostSEDmaker(**a)
-
-    def clear(v, bound, span=1.):
-        v = np.asarray(v, float)
-        v = v[np.isfinite(v)]
-        return v.size == 0 or np.min(np.abs(v - bound)) > 1e-6 * span
+    reference = lambda name: _sed_reference(H.case_arrays(name))
+    clear = _clear
 
     res = {}
     av_grid, _, rv_grid = H.default_grids()
@@ -584,6 +664,60 @@ def gen_sedmaker():
     path = os.path.join(OUT, "sedmaker.npz")
     np.savez_compressed(path, **res)
     print("sedmaker.npz: %d bytes" % os.path.getsize(path))
+
+
+def gen_sedmaker_edges():
+    """`seds.SEDmaker.make_grid` on the edge cases of tests/sed_helpers.py (`EDGE_CASES`): fit
+    grids of 2 x 2 to 256 points, explicit weights, a fit point outside the networks' bounds,
+    and labels on the nodes of the track table.  The reference objects are `gen_sedmaker`'s;
+    the conditions are asserted on the reference's own output."""
+    import warnings
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import sed_helpers as H
+    res = {}
+    for name, (two_afe, net, grid, _) in H.EDGE_CASES.items():
+        sm, solved, host = _sed_reference(H.edge_arrays(name))
+        kw = H.edge_kwargs(name)
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            sm.make_grid(verbose=False, **kw)
+        lab = np.array([list(r) for r in sm.grid_label])
+        sed = np.array([[sm.grid_sed[f][i] for f in sm.filters] for i in range(len(lab))])
+        par = np.array([list(r) for r in sm.grid_param])
+        sel = sm.grid_sel.copy()
+        eep2 = np.array([solved.get((la, m, e, f, s), (np.nan, np.nan))
+                         for (m, e, f, a, s), la in zip(lab, par[:, 0])])
+        fun, eep2 = eep2[:, 1], eep2[:, 0]
+        nbin = int((sel & np.isfinite(eep2)).sum())
+        print("sedmaker_edges", name, "models", len(lab), "selected", sel.sum(), "of them binaries", nbin,
+              "NaN slopes among the selected", int(np.isnan(sed[sel][..., 1:]).sum()))
+        assert sel.any() and not sel.all(), name
+        assert np.all(fun[np.isfinite(eep2)] < 1e-3 / 10.), name
+        assert np.all(np.isnan(sed[~sel])) and np.all(np.isfinite(sed[sel][..., 0])), name
+        if name == "fit_outside":         # (a fit point outside the networks: NaN slopes, selection kept)
+            assert np.isnan(sed[sel][..., 1:]).all(), name
+        else:
+            assert np.isfinite(sed[sel]).all(), name
+        if grid is H.GRID_S85:            # (GRID_S itself has no binary with a secondary)
+            assert nbin >= 5, name
+        # nothing computed sits on a threshold (the labels are given, and may sit on a node)
+        ckw = {k: kw[k] for k in ("apply_corr", "corr_params") if k in kw}
+        p1 = host.get_predictions(lab[:, :4], **ckw)
+        p2 = host.get_predictions(np.c_[lab[:, 0] * lab[:, 4], eep2, lab[:, 2:4]], **ckw)
+        for p in (p1, p2):
+            x = host.inputs(p, 0., 3.3)
+            for d in range(4):
+                for b in (host.xmin[d], host.xmax[d]):
+                    assert _clear(x[:, d], b, host.xmax[d] - host.xmin[d]), (name, d)
+        msec = lab[:, 0] * lab[:, 4]
+        assert _clear(p1[:, 0], 10.14) and _clear(msec, 0.5) and _clear(msec, kw.get("mini_bound", 0.5)), name
+        assert _clear(msec, sm.mini_bound) and _clear(msec, 1.), name
+        for k, v in (("label", lab), ("sed", sed), ("param", par), ("sel", sel), ("eep2", eep2)):
+            res["%s_%s" % (name, k)] = v
+    path = os.path.join(OUT, "sedmaker_edges.npz")
+    np.savez_compressed(path, **res)
+    print("sedmaker_edges.npz: %d bytes" % os.path.getsize(path))
+    assert os.path.getsize(path) < 518536
 
 
 def gen_orion():
@@ -974,8 +1108,12 @@ if __name__ == "__main__":
         gen_cluster()
     if "iso" in which:
         gen_iso()
+    if "iso_edges" in which:
+        gen_iso_edges()
     if "sedmaker" in which:
         gen_sedmaker()
+    if "sedmaker_edges" in which:
+        gen_sedmaker_edges()
     if "orion" in which:
         gen_orion()
     if "philox" in which:
