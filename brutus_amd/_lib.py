@@ -7,7 +7,7 @@ no GPU is visible, every compute entry point raises.
 import ctypes as C
 import os
 
-__all__ = ["lib", "Params", "PostParams", "BinpdfParams", "IsoParams", "SedParams", "check", "LIB_PATH", "BrutusError", "NVALS",
+__all__ = ["lib", "Params", "PostParams", "BinpdfParams", "IsoParams", "SedParams", "LosParams", "check", "LIB_PATH", "BrutusError", "NVALS",
            "MAX_BATCH", "MAX_FILT", "MAX_FILT_FIT"]
 
 # BRUTUS_AMD_LIB: another build of the same library (A/B kernel timing)
@@ -98,6 +98,13 @@ class BinpdfParams(C.Structure):
                 ("ysigma_bins", C.c_double), ("seed", C.c_uint64), ("object0", C.c_int64)]
 
 
+class LosParams(C.Structure):
+    """struct brutus_los_params (include/brutus_amd.h)."""
+    _fields_ = [("kernel", C.c_int32), ("additive_foreground", C.c_int32), ("rlims", C.c_double * 2)]
+
+
+LOS_MAX_CLOUDS, LOS_MAX_THETA, LOS_MAX_DRAWS, LOS_MAX_OBJ = 32, 65535, 4096, 1 << 22
+
 # name -> (restype, argtypes); mirrors include/brutus_amd.h (product ABI) and
 # include/brutus_amd_debug.h (test hooks / measurement aids, see DEBUG_NAMES) one to one
 DEBUG_NAMES = ("brutus_calibrate_traffic", "brutus_calibrate_copy16", "brutus_calibrate_issue", "brutus_debug_exp10", "brutus_debug_math", "brutus_debug_mt_stream", "brutus_debug_plan_streams", "brutus_debug_rng","brutus_debug_galprior", "brutus_debug_galprior_mc", "brutus_debug_galprior_sl", "brutus_debug_dist_table", "brutus_debug_zig_table", "brutus_debug_copy", "brutus_debug_sizeof_star32", "brutus_debug_fit_stats", "brutus_debug_pre32_time", "brutus_debug_binpdf_draws")
@@ -183,6 +190,9 @@ SIGNATURES = {
     "brutus_iso_seds_grid": (C.c_int, [C.POINTER(IsoParams)] + [_vp] * 14 + [_sz, _vp]),
     "brutus_sed_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "brutus_sed_grid": (C.c_int, [C.POINTER(SedParams)] + [_vp] * 17 + [_sz, _vp]),
+    "brutus_los_workspace_bytes": (_sz, [_i32, _i32]),
+    "brutus_los_loglike": (C.c_int, [_i32, _i32, _vp, _vp, _vp, _i32, _i32, _vp, C.POINTER(LosParams),
+                                     _vp, _vp, _vp, _sz, _vp]),
 }
 
 

@@ -1,0 +1,406 @@
+"""Line-of-sight (LOS) fitting utilities: brutus 0.8.3 `los.py` with the likelihood on the device.
+
+The reference fits a cumulative reddening profile of discrete clouds to the saved distance and
+reddening draws of the stars of one sightline (`fit(save_dar_draws=True)`); a nested sampler
+calls `LOS_clouds_loglike_samples` 10^5 - 10^6 times per sightline on data that never changes.
+`LOSSamples` keeps the sub-sampled draws on the GPU and evaluates one `theta` or a batch per
+call (`brutus_los_loglike`); the function of the reference's name is the host form (numpy) and,
+with `device=`, a one-shot wrapper of the class.
+
+Both forms weigh every sample against the ONE cloud bin its distance falls in, instead of the
+reference's `(Nclouds + 1, Nobj, Ndraws)` temporaries; the result is the reference's up to the
+order of its sums.
+"""
+import ctypes as C
+import warnings
+
+import numpy as np
+from scipy.stats import truncnorm
+
+from . import _lib
+
+__all__ = ["LOS_clouds_priortransform", "LOS_clouds_loglike_samples",
+           "kernel_tophat", "kernel_gauss", "kernel_lorentz", "LOSSamples"]
+
+_KERNEL_CODES = {'gauss': 0, 'lorentz': 1, 'tophat': 2}
+_TERMS_CHUNK_BYTES = 256 << 20     # per-object terms of one device call
+
+
+def LOS_clouds_priortransform(u, rlims=(0., 6.), dlims=(4., 19.),
+                              pb_params=(-3., 0.7, -np.inf, 0.),
+                              s_params=(-3., 0.3, -np.inf, 0.),
+                              dust_template=False, nlims=(0.2, 2)):
+    """
+    The "prior transform" for the LOS fit that converts from draws on the
+    N-dimensional unit cube to samples from the prior (reference los.py:24-116): a truncated
+    log-normal in the outlier fraction `pb` and in the two smoothing scales, uniform priors in
+    distance (sorted) and reddening.
+
+    Parameters
+    ----------
+    u : `~numpy.ndarray` of shape `(Nparams,)` or `(K, Nparams)`
+        Values drawn from the unit cube, laid out as `theta` of
+        `LOS_clouds_loglike_samples`.  A 2-d `u` is transformed row by row; every row equals
+        the single call.
+
+    rlims, dlims : 2-tuple, optional
+        Bounds of the reddenings and of the cloud distances.
+
+    pb_params, s_params : 4-tuple, optional
+        Mean, standard deviation, lower and upper bound of the truncated normal in
+        `ln pb` / `ln s0`, `ln s`.
+
+    dust_template : bool, optional
+        If `True` the cloud reddenings are rescalings of a template, uniform in `nlims`.
+
+    nlims : 2-tuple, optional
+        Bounds of the rescalings.
+
+    Returns
+    -------
+    x : `~numpy.ndarray` of the shape of `u`
+        The transformed parameters.
+    """
+    cube = np.asarray(u, dtype=np.float64)
+    rows = np.atleast_2d(cube)
+    if rows.ndim != 2 or rows.shape[1] < 4 or rows.shape[1] % 2:
+        raise ValueError("u must have shape (Nparams,) or (K, Nparams) with Nparams = 4 + 2 "
+                         "Nclouds; got %s" % (cube.shape,))
+
+    def lognormal(q, params):
+        """exp of the truncated normal (mean, std, low, high) at the quantiles `q`."""
+        mean, std, low, high = params
+        return np.exp(truncnorm.ppf(q, (low - mean) / std, (high - mean) / std, loc=mean, scale=std))
+
+    def uniform(q, lims):
+        return q * (lims[1] - lims[0]) + lims[0]
+
+    out = np.empty_like(rows)
+    out[:, 0] = lognormal(rows[:, 0], pb_params)
+    out[:, 1:3] = lognormal(rows[:, 1:3], s_params)
+    out[:, 3] = uniform(rows[:, 3], rlims)
+    # clouds in the order of their distances; each keeps its own reddening (or rescaling)
+    order = np.argsort(rows[:, 4::2], axis=1)
+    out[:, 4::2] = uniform(np.take_along_axis(rows[:, 4::2], order, axis=1), dlims)
+    out[:, 5::2] = uniform(np.take_along_axis(rows[:, 5::2], order, axis=1),
+                           nlims if dust_template else rlims)
+    return out.reshape(cube.shape)
+
+
+def kernel_tophat(reds, kp):
+    """Log-weights of the reddening draws `reds` under a top-hat kernel with
+    `kp = (mean, half-width)`: `-ln(2 half-width)` in `[mean - half-width, mean + half-width)`,
+    `-inf` outside (reference los.py:251-282)."""
+    centre, half = kp[0], kp[1]
+    inside = (reds >= centre - half) & (reds < centre + half)
+    return np.where(inside, 0., -np.inf) - np.log(2. * half)
+
+
+def kernel_gauss(reds, kp):
+    """Log-weights of the reddening draws `reds` under a Gaussian kernel with
+    `kp = (mean, standard deviation)` (reference los.py:285-312)."""
+    z = (reds - kp[0]) / kp[1]
+    return -0.5 * np.square(z) - np.log(np.sqrt(2 * np.pi) * kp[1])
+
+
+def kernel_lorentz(reds, kp):
+    """Log-weights of the reddening draws `reds` under a Lorentzian kernel with
+    `kp = (mean, half width at half maximum)` (reference los.py:315-342)."""
+    z = (reds - kp[0]) / kp[1]
+    return -np.log(1. + np.square(z)) - np.log(np.pi * kp[1])
+
+
+_KERNELS = {'tophat': kernel_tophat, 'gauss': kernel_gauss, 'lorentz': kernel_lorentz}
+
+
+def _check_kernel(kernel, device):
+    if isinstance(kernel, str) and kernel in _KERNELS:
+        return _KERNELS[kernel]
+    if callable(kernel):
+        if device:
+            raise ValueError("A callable kernel runs on the host path only (device=None); the "
+                             "device has 'gauss', 'lorentz' and 'tophat'.")
+        return kernel
+    raise ValueError("The kernel provided is not a valid function nor "
+                     "one of the pre-defined options. Please provide a "
+                     "valid kernel.")
+
+
+def _check_samples(dsamps, rsamps, template_reds, Ndraws):
+    """The sub-sampled draws `(Nobj, Nsamps)` as float64 (float32 converts exactly) and the
+    template `(Nobj,)` or None."""
+    dsamps, rsamps = np.asarray(dsamps), np.asarray(rsamps)
+    if dsamps.ndim != 2 or dsamps.shape != rsamps.shape:
+        raise ValueError("dsamps and rsamps must both have shape (Nobj, Nsamps); got %s and %s"
+                         % (dsamps.shape, rsamps.shape))
+    if int(Ndraws) < 1 or dsamps.shape[0] < 1 or dsamps.shape[1] < 1:
+        raise ValueError("Ndraws, Nobj and Nsamps must be at least 1")
+    ds = np.asarray(dsamps[:, :int(Ndraws)], dtype=np.float64)
+    rs = np.asarray(rsamps[:, :int(Ndraws)], dtype=np.float64)
+    if template_reds is not None:
+        template_reds = np.asarray(template_reds, dtype=np.float64)
+        if template_reds.shape != (ds.shape[0],):
+            raise ValueError("template_reds must have shape (Nobj,) = (%d,); got %s"
+                             % (ds.shape[0], template_reds.shape))
+    return ds, rs, template_reds
+
+
+def _check_theta(theta, monotonic, device):
+    """`theta` as `(K, Nparams)` float64, whether it was a single row, and per row: -inf where
+    `monotonic` forbids the reddenings, else NaN where a width is not positive, else 0.
+    ValueError for cloud distances that do not ascend (no row is evaluated then)."""
+    theta = np.asarray(theta, dtype=np.float64)
+    single = theta.ndim == 1
+    th = np.atleast_2d(theta)
+    if th.ndim != 2 or th.shape[1] < 4 or th.shape[1] % 2:
+        raise ValueError("theta must have shape (Nparams,) or (K, Nparams) with Nparams = 4 + 2 "
+                         "Nclouds: [pb, s0, s, fred, d1, r1, ...]; got %s" % (theta.shape,))
+    nclouds = (th.shape[1] - 4) // 2
+    if device and nclouds > _lib.LOS_MAX_CLOUDS:
+        raise ValueError("%d clouds: the device form takes at most %d; use the host path "
+                         "(device=None)." % (nclouds, _lib.LOS_MAX_CLOUDS))
+    reds, dists = th[:, 3::2], th[:, 4::2]
+    bad = np.nonzero(~np.all(np.sort(dists, axis=1) == dists, axis=1))[0]
+    if bad.size:
+        raise ValueError("Distances must be monotonically increasing." if single else
+                         "Distances must be monotonically increasing. (row %d of theta)" % bad[0])
+    preset = np.zeros(th.shape[0])
+    preset[~((th[:, 1] > 0.) & (th[:, 2] > 0.))] = np.nan
+    if monotonic:
+        preset[~np.all(np.sort(reds, axis=1) == reds, axis=1)] = -np.inf
+    return th, single, preset
+
+
+def _host_row(th, ds, rs, kern, rlims, template_reds, additive_foreground):
+    """(loglike, terms) of one checked row."""
+    pb, s0, s = th[0], th[1], th[2]
+    reds, dists = th[3::2], th[4::2]
+    area = rlims[1] - rlims[0]
+    nobj, nsamps = ds.shape
+    with warnings.catch_warnings(), np.errstate(all="ignore"):
+        warnings.simplefilter("ignore")
+        # the one bin of every sample: the number of cloud distances <= d (0 = foreground)
+        bins = np.searchsorted(dists, ds, side='right')
+        inside = (ds >= 0.) & (ds < 1e10)
+        # kernel mean per object and bin: clouds rescale the template, then the foreground is added
+        means = np.tile(reds, (nobj, 1))
+        if template_reds is not None:
+            means[:, 1:] *= template_reds[:, None]
+        if additive_foreground:
+            means[:, 1:] += means[:, :1]
+        kmean = np.take_along_axis(means, bins, axis=1)
+        kwidth = np.where(bins == 0, s0 * area, s * area)
+        logw = kern(rs, (kmean, kwidth)) + np.log(inside)
+        # max-shifted log-sum over an object's samples
+        bad = np.isnan(logw).any(axis=1)
+        amax = np.max(np.where(np.isnan(logw), -np.inf, logw), axis=1)
+        shift = np.where(np.isfinite(amax), amax, 0.)
+        logls = (np.log(np.sum(np.exp(logw - shift[:, None]), axis=1)) + shift) - np.log(nsamps)
+        logls[bad] = np.nan
+        # outlier mixture ln((1 - pb) e^l + pb / area), shifted by the larger of the two; a part
+        # whose weight is zero adds nothing, whatever its value (scipy's logsumexp with `b`)
+        a1 = np.where(1. - pb == 0., -np.inf, logls)
+        a2 = -np.inf if pb == 0. else -np.log(area)
+        mx = np.where(a1 > a2, a1, a2)
+        shift = np.where(np.isfinite(mx), mx, 0.)
+        terms = np.log((1. - pb) * np.exp(a1 - shift) + pb * np.exp(a2 - shift)) + mx
+    return np.sum(terms), terms
+
+
+def LOS_clouds_loglike_samples(theta, dsamps, rsamps, kernel='gauss',
+                               rlims=(0., 6.), template_reds=None,
+                               Ndraws=25, additive_foreground=False,
+                               monotonic=True, device=None, return_terms=False):
+    """
+    Compute the log-likelihood for the cumulative reddening along the
+    line of sight (LOS) parameterized by `theta`, given a set of input
+    reddening and distance draws (reference los.py:119-248). Assumes a uniform outlier model
+    in distance and reddening.
+
+    Parameters
+    ----------
+    theta : `~numpy.ndarray` of shape `(Nparams,)` or `(K, Nparams)`
+        `[pb, s0, s, fred, d1, r1, d2, r2, ...]`: the fraction of outliers `pb`, the fractional
+        reddening smoothing of the foreground `s0` and of the clouds `s` (kernel widths are
+        `s0 * area` and `s * area` with `area = rlims[1] - rlims[0]`), the foreground reddening
+        and one `(dist, red)` pair per cloud.  `pb` outside `[0, 1]` is not defined and is not
+        checked.  A 2-d `theta` gives one value per row; every row equals the single call.
+
+    dsamps, rsamps : `~numpy.ndarray` of shape `(Nobj, Nsamps)`
+        Distance and reddening samples of each object, in the units of `theta`.  A sample
+        belongs to the bin whose edges `[0, d1, ..., dn, 1e10]` hold its distance, the lower
+        edge included; any other sample (NaN too) has weight zero but counts in the divisor
+        `min(Ndraws, Nsamps)`.  A NaN reddening makes the object's term, and the total, NaN
+        (for `'tophat'` it has weight zero: the reference's comparison is False there).
+
+    kernel : str or function, optional
+        `'gauss'` (default), `'lorentz'`, `'tophat'`, or on the host path a function
+        `kernel(reds, (mean, width))` over arrays of shape `(Nobj, Nsamps)`.
+
+    rlims : 2-tuple, optional
+        The reddening bounds. Default is `(0., 6.)`.
+
+    template_reds : `~numpy.ndarray` of shape `(Nobj)`, optional
+        If given, cloud reddenings (not the foreground) are multiplied by the object's value.
+
+    Ndraws : int, optional
+        The number of draws to use for each star. Default is `25`.
+
+    additive_foreground : bool, optional
+        Whether `fred` is added to every later bin's mean (after the template). Default `False`.
+
+    monotonic : bool, optional
+        Whether reddenings `[fred, r1, ...]` that decrease anywhere give `-inf`. Default `True`.
+
+    device : None, str or `torch.device`, optional
+        `None` (default): the host path in numpy.  Otherwise a one-shot `LOSSamples` is built on
+        that GPU and called -- the slow way: the draws are copied for every call.  A sampler
+        builds `LOSSamples` once.
+
+    return_terms : bool, optional
+        Also return the per-object values after the outlier mixture, whose sum is the
+        log-likelihood: `(Nobj,)`, or `(K, Nobj)` for a batch.
+
+    Returns
+    -------
+    loglike : float, or `~numpy.ndarray` of shape `(K,)`
+        `ValueError` if the cloud distances of a row do not ascend (the row is named for a
+        batch, nothing is evaluated); a row whose `s0` or `s` is not `> 0` is NaN.
+    """
+    kern = _check_kernel(kernel, device is not None)
+    ds, rs, template_reds = _check_samples(dsamps, rsamps, template_reds, Ndraws)
+    if device is not None:
+        # (checked here only for its errors, so that they come before anything touches the GPU;
+        # LOSSamples checks theta again when it is called and uses the result)
+        _check_theta(theta, monotonic, True)
+        S = LOSSamples(ds, rs, template_reds=template_reds, Ndraws=Ndraws, kernel=kernel,
+                       rlims=rlims, additive_foreground=additive_foreground,
+                       monotonic=monotonic, device=device)
+        return S.terms(theta) if return_terms else S(theta)
+    th, single, preset = _check_theta(theta, monotonic, False)
+    out = np.array(preset)
+    terms = np.repeat(preset[:, None], ds.shape[0], axis=1)
+    for k in np.nonzero(preset == 0.)[0]:
+        out[k], terms[k] = _host_row(th[k], ds, rs, kern, rlims, template_reds,
+                                     additive_foreground)
+    if single:
+        return (float(out[0]), terms[0]) if return_terms else float(out[0])
+    return (out, terms) if return_terms else out
+
+
+class LOSSamples(object):
+    """The draws of one sightline on the device, callable with `theta`.
+
+    `LOSSamples(dsamps, rsamps, ...)` sub-samples the draws (`[:, :Ndraws]`), transposes them
+    once to draw-major float64 and keeps them, with the template, on `device`.  `S(theta)` is
+    `LOS_clouds_loglike_samples(theta, dsamps, rsamps, ...)` with the arguments given here:
+    a float for `theta` of shape `(Nparams,)`, a `(K,)` float64 array for `(K, Nparams)` -- a
+    live-point set or a vectorised sampler.  The value of a row does not depend on the other
+    rows or on its place among them, and the same call gives the same bytes.
+    `S.terms(theta)` returns `(loglike, terms)` with the per-object values `(Nobj,)` / `(K, Nobj)`.
+    At most 32 clouds; batches of any size (cut into chunks of 65535 rows).  `pb` outside
+    `[0, 1]` is not defined and is not checked.
+
+        S = los.LOSSamples(dsamps, rsamps, Ndraws=25)
+        sampler = dynesty.NestedSampler(S, los.LOS_clouds_priortransform, ndim)
+
+    There is no host fallback: without the library or a GPU the constructor raises
+    `BrutusError`.
+    """
+
+    def __init__(self, dsamps, rsamps, template_reds=None, Ndraws=25, kernel='gauss',
+                 rlims=(0., 6.), additive_foreground=False, monotonic=True, device="cuda"):
+        _check_kernel(kernel, True)
+        ds, rs, template_reds = _check_samples(dsamps, rsamps, template_reds, Ndraws)
+        rlims = (float(rlims[0]), float(rlims[1]))
+        if not (np.isfinite(rlims[0]) and np.isfinite(rlims[1]) and rlims[1] > rlims[0]):
+            raise ValueError("rlims must be finite and increasing; got %s" % (rlims,))
+        self.nobj, self.nsamps = ds.shape
+        if self.nobj > _lib.LOS_MAX_OBJ or self.nsamps > _lib.LOS_MAX_DRAWS:
+            raise ValueError("the device form takes at most %d objects and %d draws each; got %s"
+                             % (_lib.LOS_MAX_OBJ, _lib.LOS_MAX_DRAWS, ds.shape))
+        self.kernel, self.rlims, self.monotonic = kernel, rlims, bool(monotonic)
+        self._L = _lib.lib()
+        import torch
+        if not torch.cuda.is_available():
+            raise _lib.BrutusError("brutus_amd: no GPU visible (torch.cuda.is_available() is "
+                                   "False); LOSSamples only runs on the HIP path. The host "
+                                   "form is LOS_clouds_loglike_samples(device=None).")
+        self._torch = torch
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise ValueError("LOSSamples needs a GPU device; got %r" % (device,))
+        self._p = _lib.LosParams()
+        self._p.kernel = _KERNEL_CODES[kernel]
+        self._p.additive_foreground = int(bool(additive_foreground))
+        self._p.rlims[0], self._p.rlims[1] = rlims
+        self._ds = torch.from_numpy(np.array(ds.T, order='C')).to(self.device)
+        self._rs = torch.from_numpy(np.array(rs.T, order='C')).to(self.device)
+        self._templ = (None if template_reds is None else
+                       torch.from_numpy(np.array(template_reds)).to(self.device))
+        self._cap, self._ncol = 0, 0
+
+    def _buffers(self, k, ncol):
+        """Device theta / result / workspace for `k` rows of `ncol` parameters; they grow, and are
+        otherwise kept from call to call."""
+        if k > self._cap or ncol != self._ncol:
+            torch = self._torch
+            cap = max(k, self._cap if ncol == self._ncol else 0)
+            self._theta = torch.empty((cap, ncol), dtype=torch.float64, device=self.device)
+            self._out = torch.empty(cap, dtype=torch.float64, device=self.device)
+            self._ws_bytes = int(self._L.brutus_los_workspace_bytes(self.nobj, cap))
+            self._ws = torch.empty(self._ws_bytes, dtype=torch.uint8, device=self.device)
+            self._cap, self._ncol = cap, ncol
+        return self._theta, self._out
+
+    def _run(self, th, want_terms):
+        """Values (K,) and, if wanted, terms (K, Nobj) of checked rows, chunk by chunk."""
+        torch = self._torch
+        ktot, ncol = th.shape
+        out = np.empty(ktot)
+        terms = np.empty((ktot, self.nobj)) if want_terms else None
+        chunk = _lib.LOS_MAX_THETA
+        if want_terms:
+            chunk = int(max(1, min(chunk, _TERMS_CHUNK_BYTES // (8 * self.nobj))))
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream().cuda_stream
+            for a in range(0, ktot, chunk):
+                k = min(chunk, ktot - a)
+                t_theta, t_out = self._buffers(k, ncol)
+                t_theta[:k].copy_(torch.from_numpy(th[a:a + k]))
+                t_terms = (torch.empty((k, self.nobj), dtype=torch.float64, device=self.device)
+                           if want_terms else None)
+                _lib.check(self._L.brutus_los_loglike(
+                    self.nobj, self.nsamps, self._ds.data_ptr(), self._rs.data_ptr(),
+                    self._templ.data_ptr() if self._templ is not None else None, k,
+                    (ncol - 4) // 2, t_theta.data_ptr(), C.byref(self._p), t_out.data_ptr(),
+                    t_terms.data_ptr() if want_terms else None, self._ws.data_ptr(),
+                    self._ws_bytes, stream))
+                out[a:a + k] = t_out[:k].cpu().numpy()
+                if want_terms:
+                    terms[a:a + k] = t_terms.cpu().numpy()
+        return out, terms
+
+    def _eval(self, theta, want_terms):
+        # Rows the host decides (-inf under `monotonic`, NaN for a width that is not positive) are
+        # sent to the device with the rest and overwritten afterwards: rows do not influence one
+        # another, and a batch that is not compacted keeps one shape per call.
+        th, single, preset = _check_theta(theta, self.monotonic, True)
+        th = np.ascontiguousarray(th)
+        out, terms = self._run(th, want_terms)
+        fixed = preset != 0.
+        if fixed.any():
+            out[fixed] = preset[fixed]
+            if want_terms:
+                terms[fixed] = preset[fixed][:, None]
+        if single:
+            return (float(out[0]), terms[0]) if want_terms else float(out[0])
+        return (out, terms) if want_terms else out
+
+    def __call__(self, theta):
+        return self._eval(theta, False)
+
+    def terms(self, theta):
+        """`(loglike, terms)`: the per-object values after the outlier mixture, `(Nobj,)` or
+        `(K, Nobj)`; `loglike` is the value of `S(theta)`."""
+        return self._eval(theta, True)

@@ -587,6 +587,39 @@ int brutus_binpdf_regen(int nobj, int nsamps, const double *d_scale, const doubl
                         int32_t *d_status, float *d_out, void *d_workspace,
                         size_t workspace_bytes, void *stream);
 
+/* ---- line-of-sight cloud likelihood (reference los.py:119-248) ----------------------------
+ * ln L of ntheta cumulative-reddening profiles of nclouds clouds, given the (distance, reddening)
+ * draws of the nobj objects of one sightline.  Additive entry points: BRUTUS_ABI_VERSION stays.
+ *   d_dsamps, d_rsamps (ndraws, nobj) f64, DRAW-major: the draws that enter (the caller has
+ *                  sub-sampled them); ndraws is also the divisor of every object's sum
+ *   d_template (nobj) f64 or NULL: cloud reddenings are multiples of the object's value
+ *   d_theta (ntheta, 4 + 2 nclouds) f64: [pb, s0, s, fred, d1, r1, d2, r2, ...] per row, cloud
+ *                  distances ascending (the caller checks; rows are independent)
+ *   kernel         0 Gaussian, 1 Lorentzian, 2 top hat, of width s0 area (foreground) / s area
+ *                  with area = rlims[1] - rlims[0] > 0, finite
+ *   additive_foreground != 0: fred is added to every later bin's mean (after the template)
+ *   d_loglike (ntheta) f64 out; d_terms (ntheta, nobj) f64 out or NULL: the per-object values
+ *                  after the outlier mixture, whose sum is d_loglike
+ * A draw belongs to the bin whose edges [0, d1, ..., dn, 1e10] hold it (lower edge included);
+ * any other draw (NaN too) has weight zero; a NaN reddening makes the object's term NaN for the
+ * Gaussian and the Lorentzian and has weight zero for the top hat, as in the reference.
+ * Sums run in a fixed order: a row's value does not depend on the rest of the batch.
+ * Limits: 1 <= nobj <= 2^22, 1 <= ndraws <= 4096, 0 <= nclouds <= 32, 1 <= ntheta <= 65535;
+ * checked, like every pointer, before any HIP call.  BRUTUS_ENOMEM: workspace. */
+#define BRUTUS_LOS_MAX_OBJ (1 << 22)
+#define BRUTUS_LOS_MAX_DRAWS 4096
+#define BRUTUS_LOS_MAX_CLOUDS 32
+#define BRUTUS_LOS_MAX_THETA 65535
+typedef struct brutus_los_params {
+    int32_t kernel, additive_foreground;
+    double rlims[2];
+} brutus_los_params;
+size_t brutus_los_workspace_bytes(int nobj, int ntheta);   /* 0: bad sizes */
+int brutus_los_loglike(int nobj, int ndraws, const double *d_dsamps, const double *d_rsamps,
+                       const double *d_template, int ntheta, int nclouds, const double *d_theta,
+                       const brutus_los_params *params, double *d_loglike, double *d_terms,
+                       void *d_workspace, size_t workspace_bytes, void *stream);
+
 
 /* Name and average duration (HIP events on `stream`) of the kernels launched
  * by the last *_batch call; used by bench.py for the roofline line. */

@@ -1083,6 +1083,145 @@ def gen_fresh():
                         parallax=st["parallax"], parallax_err=st["parallax_err"],
                         coords=st["coords"], lnprior=lnprior, seed0=7, **res)
 
+LOS_KERNELS = ("gauss", "lorentz", "tophat")
+LOS_CLOUDS = (0, 1, 2, 4, 32)
+LOS_NDRAWS = (1, 25, 33)
+LOS_RLIMS = ((0., 6.), (0.5, 4.))
+
+
+def _los_catalogue(rng, nobj, nsamps, rlims=(0., 6.)):
+    """Draws of `nobj` stars behind a two-step profile (steps at distance modulus 8.5 and 12),
+    scatter 0.4 in distance and 0.15 in Av, clipped to `rlims`; float32 values."""
+    mu = rng.uniform(4., 19., nobj)
+    av = 0.3 + 0.9 * (mu > 8.5) + 1.4 * (mu > 12.)
+    ds = mu[:, None] + 0.4 * rng.normal(size=(nobj, nsamps))
+    rs = np.clip(av[:, None] + 0.15 * rng.normal(size=(nobj, nsamps)), *rlims)
+    return ds.astype(np.float32), rs.astype(np.float32)
+
+
+def _los_theta(rng, nclouds, rlims):
+    """pb, s0, s, fred and `nclouds` ascending (distance, reddening) pairs inside `rlims`."""
+    dists = np.sort(rng.uniform(5., 17., nclouds))
+    reds = rlims[0] + 0.3 + np.cumsum(rng.uniform(0., 2.5 / max(nclouds, 1), nclouds))
+    th = np.empty(4 + 2 * nclouds)
+    th[:4] = 0.07, 0.04, 0.06, rlims[0] + 0.3
+    th[4::2], th[5::2] = dists, reds
+    return th
+
+
+def los_edge_catalogue():
+    """(20, 8) draws with the samples the semantics speak of planted: one exactly on 9.25, one
+    each with d < 0, d = 1e10, +inf and NaN, an object (5) with no sample inside [0, 1e10); and
+    the same with NaN reddenings planted (object 7: at a valid distance; object 9: at an
+    invalid one)."""
+    rng = np.random.RandomState(41)
+    ds, rs = _los_catalogue(rng, 20, 8)
+    ds, rs = ds.astype(np.float64), rs.astype(np.float64)
+    ds[0, 3] = 9.25
+    rs[0, 3] = 1.25
+    ds[1, 0], ds[2, 1], ds[3, 2], ds[4, 7] = -0.5, 1e10, np.inf, np.nan
+    ds[5] = [-1., 1e10, np.inf, np.nan, -3., 2e10, -np.inf, 1e11]
+    rn = rs.copy()
+    rn[7, 2] = np.nan
+    ds[9, 4] = -2.
+    rn[9, 4] = np.nan
+    return ds, rs, rn
+
+
+def los_edge_cases():
+    """name, catalogue ('A' = the first regular one, 'E', 'En'), theta, keyword arguments."""
+    base = [0.05, 0.04, 0.06, 0.3, 9.25, 1.2, 12., 2.6]
+    cases = []
+    for k in LOS_KERNELS:
+        kw = dict(kernel=k)
+        cases += [
+            ("on_cloud_distance", "E", base, kw),
+            ("just_below_cloud_distance", "E", [0.05, 0.04, 0.06, 0.3, np.nextafter(9.25, 10.), 1.2, 12., 2.6], kw),
+            ("equal_distances", "E", [0.05, 0.04, 0.06, 0.3, 9.25, 1.2, 9.25, 1.9, 12., 2.6], kw),
+            ("no_clouds", "E", base[:4], kw),
+            ("pb0_object_without_weight", "E", [0.] + base[1:], kw),
+            ("pb1", "E", [1.] + base[1:], kw),
+            ("pb1_rlims", "E", [1.] + base[1:], dict(kernel=k, rlims=(0.5, 4.))),
+            ("template_additive", "E", [0.05, 0.04, 0.06, 0.3, 9.25, 0.8, 12., 1.7],
+             dict(kernel=k, template=True, additive_foreground=True)),
+            ("equal_reddenings_allowed", "E", [0.05, 0.04, 0.06, 1.2, 9.25, 1.2, 12., 1.2], kw),
+            ("not_monotonic", "E", [0.05, 0.04, 0.06, 0.3, 9.25, 2.6, 12., 1.2], kw),
+            ("not_monotonic_allowed", "E", [0.05, 0.04, 0.06, 0.3, 9.25, 2.6, 12., 1.2],
+             dict(kernel=k, monotonic=False)),
+            ("s0_zero", "E", [0.05, 0., 0.06] + base[3:], kw),
+            ("s_zero", "E", [0.05, 0.04, 0.] + base[3:], kw),
+            ("s_negative", "E", [0.05, 0.04, -0.06] + base[3:], kw),
+            ("s0_nan", "E", [0.05, np.nan, 0.06] + base[3:], kw),
+            ("nan_reddening", "En", base, kw),
+            ("nan_reddening_template", "En", base, dict(kernel=k, template=True, Ndraws=5)),
+            ("tiny_widths_pb0", "A", [0., 1e-6, 1e-6, 0.3, 8.5, 1.2, 12., 2.6], kw),
+        ]
+    return cases
+
+
+def gen_los():
+    """tests/golden/los.npz: the reference's `LOS_clouds_loglike_samples` totals and
+    `LOS_clouds_priortransform` outputs (data only; the per-object terms are not among the
+    reference's outputs)."""
+    import json
+    import warnings
+    import brutus.los as RL
+    rng = np.random.RandomState(40)
+    cats = {"A": _los_catalogue(rng, 67, 30), "B": _los_catalogue(rng, 300, 12)}
+    templ = {"A": rng.uniform(0.5, 2., 67), "B": rng.uniform(0.5, 2., 300)}
+    cats["one"], templ["one"] = (cats["A"][0][5:6], cats["A"][1][5:6]), templ["A"][5:6]
+    thetas = {(nc, q): _los_theta(rng, nc, rl) for nc in LOS_CLOUDS for q, rl in enumerate(LOS_RLIMS)}
+    out = dict(ds_A=cats["A"][0], rs_A=cats["A"][1], ds_B=cats["B"][0], rs_B=cats["B"][1],
+               templ_A=templ["A"], templ_B=templ["B"], one_index=5,
+               kernels=np.array(LOS_KERNELS), clouds=np.array(LOS_CLOUDS),
+               ndraws=np.array(LOS_NDRAWS), rlims=np.array(LOS_RLIMS))
+    for (nc, q), th in thetas.items():
+        out["theta_%d_%d" % (nc, q)] = th
+    # totals[catalogue, kernel, template, additive, clouds, ndraws, rlims]
+    names = ("A", "B", "one")
+    tot = np.empty((3, 3, 2, 2, len(LOS_CLOUDS), len(LOS_NDRAWS), len(LOS_RLIMS)))
+    for idx in np.ndindex(*tot.shape):
+        c, k, t, a, n, d, q = idx
+        ds, rs = (x.astype(np.float64) for x in cats[names[c]])
+        tot[idx] = RL.LOS_clouds_loglike_samples(
+            thetas[LOS_CLOUDS[n], q], ds, rs, kernel=LOS_KERNELS[k], rlims=LOS_RLIMS[q],
+            template_reds=templ[names[c]] if t else None, Ndraws=LOS_NDRAWS[d],
+            additive_foreground=bool(a))
+    assert np.all(np.isfinite(tot))
+    out["totals"] = tot
+    # edge cases
+    eds, ers, ern = los_edge_catalogue()
+    etempl = rng.uniform(0.5, 2., 20)
+    out.update(ds_E=eds, rs_E=ers, rs_En=ern, templ_E=etempl)
+    meta, etot = [], []
+    for name, cat, th, kw in los_edge_cases():
+        ds, rs = {"A": tuple(x.astype(np.float64) for x in cats["A"]), "E": (eds, ers),
+                  "En": (eds, ern)}[cat]
+        kw = dict(kw)
+        t = kw.pop("template", False)
+        tv = (templ["A"] if cat == "A" else etempl) if t else None
+        with warnings.catch_warnings(), np.errstate(all="ignore"):
+            warnings.simplefilter("ignore")
+            etot.append(RL.LOS_clouds_loglike_samples(np.array(th, dtype=float), ds, rs,
+                                                      template_reds=tv, **kw))
+        meta.append(dict(name=name, cat=cat, theta=[float(v) for v in th], template=t, **kw))
+    out["edge_meta"] = json.dumps(meta)
+    out["edge_totals"] = np.array(etot)
+    # prior transform
+    custom = dict(pb_params=(-2.5, 0.5, -6., -0.5), s_params=(-3.2, 0.4, -5., -1.))
+    for nc in (1, 4):
+        u = rng.uniform(size=(20, 4 + 2 * nc))
+        out["pt_u_%d" % nc] = u
+        for t in (0, 1):
+            for tag, kw in (("default", {}), ("custom", dict(custom, rlims=(0.5, 4.), dlims=(5., 16.),
+                                                             nlims=(0.1, 3.)))):
+                out["pt_x_%d_%d_%s" % (nc, t, tag)] = np.array(
+                    [RL.LOS_clouds_priortransform(row, dust_template=bool(t), **kw) for row in u])
+    out["pt_custom"] = json.dumps(dict(custom, rlims=(0.5, 4.), dlims=(5., 16.), nlims=(0.1, 3.)))
+    np.savez_compressed(os.path.join(OUT, "los.npz"), **out)
+    print("los done: %d regular totals, %d edge cases: %s" % (tot.size, len(meta), dict(
+        (m["name"] + "/" + m["kernel"], v) for m, v in zip(meta, etot))))
+
 
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
@@ -1130,4 +1269,6 @@ if __name__ == "__main__":
         gen_fit()
     if "fresh" in which:
         gen_fresh()
+    if "los" in which:
+        gen_los()
 
