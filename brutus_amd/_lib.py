@@ -7,7 +7,7 @@ no GPU is visible, every compute entry point raises.
 import ctypes as C
 import os
 
-__all__ = ["lib", "Params", "PostParams", "BinpdfParams", "IsoParams", "SedParams", "LosParams", "check", "LIB_PATH", "BrutusError", "NVALS",
+__all__ = ["lib", "Params", "PostParams", "BinpdfParams", "IsoParams", "SedParams", "LosParams", "ptr", "address", "fixed", "check", "LIB_PATH", "BrutusError", "NVALS",
            "MAX_BATCH", "MAX_FILT", "MAX_FILT_FIT"]
 
 # BRUTUS_AMD_LIB: another build of the same library (A/B kernel timing)
@@ -33,10 +33,6 @@ class Params(C.Structure):
                 ("ltol", C.c_double), ("ltol_subthresh", C.c_double),
                 ("init_thresh", C.c_double), ("wt_thresh", C.c_double),
                 ("dim_prior", C.c_int32), ("max_iter", C.c_int32)]
-
-
-_vp, _i64, _i32, _sz, _dbl = C.c_void_p, C.c_int64, C.c_int, C.c_size_t, C.c_double
-_u64 = C.c_uint64
 
 
 class PostParams(C.Structure):
@@ -105,94 +101,179 @@ class LosParams(C.Structure):
 
 LOS_MAX_CLOUDS, LOS_MAX_THETA, LOS_MAX_DRAWS, LOS_MAX_OBJ = 32, 65535, 4096, 1 << 22
 
+_i64, _i32, _sz, _dbl, _u64 = C.c_int64, C.c_int, C.c_size_t, C.c_double, C.c_uint64
+_stream = C.c_void_p    # `void *stream`: a hipStream_t, passed as an integer
+_MADE = (C.c_void_p, type(C.byref(C.c_int())))   # a pointer the caller made with ctypes: as it is
+_as_arg = C.c_void_p.from_param     # (an int returned by a `from_param` would be passed as a C int)
+_PTR = {}
+
+
+def ptr(mem, dtype=None):
+    """The `argtypes` class of one pointer parameter: `mem` = "d" (device memory: a contiguous
+    CUDA tensor) or "h" (host memory: a C-contiguous numpy array), `dtype` = the name of the
+    element type, None for `void *` (any).  `from_param` checks what it is handed, on the host
+    and before the library is entered: None -> NULL, an address the caller made (an int, a
+    `c_void_p`, a `byref`) as it is, anything but the declared kind of memory -> TypeError,
+    which ctypes reports as ArgumentError with the argument's position.  `address` is the
+    same check as a plain function that returns the address as an int."""
+    if (mem, dtype) in _PTR:
+        return _PTR[mem, dtype]
+    assert mem in "dh" and dtype in (None, "float64", "float32", "int32", "int64", "uint8",
+                                     "uint32", "uint64")
+    tname = "torch.%s" % dtype      # what str() of a tensor's dtype says
+
+    def address(x):
+        try:
+            if mem == "h":
+                if x.flags.c_contiguous and (dtype is None or x.dtype.name == dtype):
+                    return x.ctypes.data
+            elif x.is_cuda and x.is_contiguous():
+                if dtype is None or str(x.dtype) == tname:
+                    return x.data_ptr()
+        except AttributeError:
+            pass
+        got = type(x).__name__
+        if hasattr(x, "dtype"):       # a tensor or an array of the wrong kind
+            got += " (%s, %s%s)" % (x.dtype, getattr(x, "device", "host"),
+                                    "" if getattr(x, "is_contiguous", lambda: x.flags.c_contiguous)()
+                                    else ", not contiguous")
+        raise TypeError("expected None, an address or a contiguous %s of %s; got %s" % (
+            "CUDA tensor" if mem == "d" else "numpy array", dtype or "any dtype", got))
+
+    def from_param(x):
+        if x is None or isinstance(x, _MADE):
+            return x
+        return _as_arg(x if isinstance(x, int) else address(x))
+
+    cls = _PTR[mem, dtype] = type("ptr_%s_%s" % (mem, dtype or "void"), (object,), dict(
+        is_pointer=True, mem=mem, dtype=dtype, address=staticmethod(address),
+        from_param=staticmethod(from_param)))
+    return cls
+
+
+def address(x, mem, dtype=None):
+    """The address of tensor / array `x` (None: 0) as an int, checked like an argument of that
+    kind."""
+    return 0 if x is None else ptr(mem, dtype).address(x)
+
+
+def fixed(x, mem, dtype=None):
+    """`x` checked once, for a caller that passes the same buffers to many short calls: the
+    result, a `c_void_p`, passes every call as it is -- about 0.3 us less per argument and call
+    than the tensor, which matters where a whole call takes 70 us.  It holds `x` (`.held`): the
+    memory lives as long as the address is in use, and a caller that later allocates another
+    buffer and forgets to call `fixed` again passes the old buffer, not a freed address."""
+    p = C.c_void_p(address(x, mem, dtype))
+    p.held = x
+    return p
+
+
+_dv, _df64, _df32, _di32, _di64, _du8 = (ptr("d", t) for t in (
+    None, "float64", "float32", "int32", "int64", "uint8"))
+_hf64, _hf32, _hi32, _hi64, _hu32, _hu64 = (ptr("h", t) for t in (
+    "float64", "float32", "int32", "int64", "uint32", "uint64"))
+
 # name -> (restype, argtypes); mirrors include/brutus_amd.h (product ABI) and
-# include/brutus_amd_debug.h (test hooks / measurement aids, see DEBUG_NAMES) one to one
+# include/brutus_amd_debug.h (test hooks / measurement aids, see DEBUG_NAMES) one to one,
+# parameter by parameter: `const double *d_x` is _df64, `int32_t *h_k` is _hi32, `void *d_ws` is _dv
+# (tests/test_cabi.py compares the table and the structures above with the headers)
 DEBUG_NAMES = ("brutus_calibrate_traffic", "brutus_calibrate_copy16", "brutus_calibrate_issue", "brutus_debug_exp10", "brutus_debug_math", "brutus_debug_mt_stream", "brutus_debug_plan_streams", "brutus_debug_rng","brutus_debug_galprior", "brutus_debug_galprior_mc", "brutus_debug_galprior_sl", "brutus_debug_dist_table", "brutus_debug_zig_table", "brutus_debug_copy", "brutus_debug_sizeof_star32", "brutus_debug_fit_stats", "brutus_debug_pre32_time", "brutus_debug_binpdf_draws")
 SIGNATURES = {
     "brutus_abi_version": (C.c_int, []),
     "brutus_last_error": (C.c_char_p, []),
     "brutus_padded_filters": (C.c_int, [_i32]),
     "brutus_grid_soa_bytes": (_sz, [_i64, _i32]),
-    "brutus_grid_relayout": (C.c_int, [_vp, _i64, _i32, _vp, _vp]),
+    "brutus_grid_relayout": (C.c_int, [_df32, _i64, _i32, _df32, _stream]),
     "brutus_workspace_bytes": (_sz, [_i64, _i32, _i32]),
-    "brutus_loglike_batch": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp,
-                                       _vp, _i32, C.POINTER(Params), _vp, _sz,
-                                       _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                       _vp, _vp, _vp, _vp]),
-    "brutus_fit_batch": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp,
-                                   _i32, C.POINTER(Params), _vp, _sz, _i64, _vp, _vp,
-                                   _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "brutus_loglike_batch": (C.c_int, [_df32, _i64, _i32, _i32, _df64, _df64, _du8, _df64, _df64, _i32,
+                                       C.POINTER(Params), _dv, _sz, _df64, _df64, _df64, _df64, _df64,
+                                       _df64, _di32, _hi32, _hi32, _df64, _df64, _stream]),
+    "brutus_fit_batch": (C.c_int, [_df32, _i64, _i32, _i32, _df64, _df64, _du8, _df64, _df64, _i32,
+                                   C.POINTER(Params), _dv, _sz, _i64, _di32, _di32, _df64, _di64, _di32,
+                                   _hi32, _hi32, _hi64, _stream]),
     "brutus_cut_workspace_bytes": (_sz, [_i64, _i32]),
-    "brutus_cut_batch": (C.c_int, [_i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32,
-                                   _vp, _vp, _dbl, _vp, _sz, _i64, _i64, _vp, _vp, _vp, _vp, _vp,
-                                   _vp]),
+    "brutus_cut_batch": (C.c_int, [_i64, _i32, _df64, _df64, _df64, _df64, _df64, _df64, _df64, _df64,
+                                   _i32, _i32, _df64, _df64, _dbl, _dv, _sz, _i64, _i64, _di32, _di32,
+                                   _df64, _di64, _hi64, _stream]),
     "brutus_last_timing": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_char_p),
                                      C.POINTER(C.c_float), C.c_int]),
     "brutus_enable_timing": (None, [C.c_int]),
-    "brutus_calibrate_traffic": (C.c_int, [_vp, _vp, _i64, _vp]),
-    "brutus_calibrate_copy16": (C.c_int, [_vp, _vp, _i64, _vp]),
-    "brutus_calibrate_issue": (C.c_int, [_i32, _i32, _i32, _vp, _i64, _vp]),
-    "brutus_debug_exp10": (C.c_int, [_vp, _vp, _i64, _vp]),
-    "brutus_debug_math": (C.c_int, [_i32, _vp, _vp, _i64, _vp]),
+    "brutus_calibrate_traffic": (C.c_int, [_df32, _df64, _i64, _stream]),
+    "brutus_calibrate_copy16": (C.c_int, [_dv, _dv, _i64, _stream]),
+    "brutus_calibrate_issue": (C.c_int, [_i32, _i32, _i32, _df32, _i64, _stream]),
+    "brutus_debug_exp10": (C.c_int, [_df64, _df64, _i64, _stream]),
+    "brutus_debug_math": (C.c_int, [_i32, _df64, _df64, _i64, _stream]),
     "brutus_post_workspace_bytes": (_sz, [_i32, _i64, _i32]),
-    "brutus_post_batch": (C.c_int, [_i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                    _vp, C.POINTER(PostParams), _vp, _sz, _vp, _vp, _vp,
-                                    _vp, _vp, _vp]),
-    "brutus_post_batch_numpy": (C.c_int, [_i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                          _vp, C.POINTER(PostParams), _vp, _sz, _vp, _vp, _vp,
-                                          _vp, _i32, _vp, _vp, _sz, _vp]),
-    "brutus_post_batch_numpy_phase": (C.c_int, [_i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                                _vp, _vp, C.POINTER(PostParams), _vp, _sz, _vp,
-                                                _vp, _vp, _vp, _i32, _vp, _vp, _sz, _i32, _vp]),
-    "brutus_debug_mt_stream": (C.c_int, [_i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp]),
-    "brutus_debug_plan_streams": (C.c_int, [_i32, _vp, _vp, _vp, _i32, _vp, _vp, _i64, _vp, _i64]),
-    "brutus_set_mt_jump": (C.c_int, [_vp, _i32, _i64, _i64]),
-    "brutus_post_set_dust": (C.c_int, [_vp, _vp, _i32, _dbl, _dbl, _dbl, _dbl]),
-    "brutus_post_set_dist_table": (C.c_int, [_vp, _i32, _i32]),
-    "brutus_post_set_after_jump": (C.c_int, [_vp, _vp]),
-    "brutus_debug_dist_table": (C.c_int, [_i32, _vp, _i64, _vp, _vp, _vp]),
+    "brutus_post_batch": (C.c_int, [_i32, _i64, _di32, _di32, _df64, _di64, _df64, _df64, _df64, _df64,
+                                    _df64, _df64, C.POINTER(PostParams), _dv, _sz, _di32, _df64, _hf64,
+                                    _hi32, _hu64, _stream]),
+    "brutus_post_batch_numpy": (C.c_int, [_i32, _i64, _di32, _di32, _df64, _di64, _df64, _df64, _df64,
+                                          _df64, _df64, _df64, C.POINTER(PostParams), _dv, _sz, _di32,
+                                          _df64, _hf64, _hi32, _i32, _hu32, _df64, _sz, _stream]),
+    "brutus_post_batch_numpy_phase": (C.c_int, [_i32, _i64, _di32, _di32, _df64, _di64, _df64, _df64,
+                                                _df64, _df64, _df64, _df64, C.POINTER(PostParams), _dv,
+                                                _sz, _di32, _df64, _hf64, _hi32, _i32, _hu32, _df64,
+                                                _sz, _i32, _stream]),
+    "brutus_debug_mt_stream": (C.c_int, [_i32, _i32, _hu32, _hi64, _i32, _df64, _df64, _stream]),
+    "brutus_debug_plan_streams": (C.c_int, [_i32, _hi32, _hi32, _hi64, _i32, _hi64, _hi64, _i64, _hi64,
+                                            _i64]),
+    "brutus_set_mt_jump": (C.c_int, [_hu32, _i32, _i64, _i64]),
+    "brutus_post_set_dust": (C.c_int, [_df64, _di32, _i32, _dbl, _dbl, _dbl, _dbl]),
+    "brutus_post_set_dist_table": (C.c_int, [_df64, _i32, _i32]),
+    "brutus_post_set_after_jump": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "brutus_debug_dist_table": (C.c_int, [_i32, _df64, _i64, _df64, _df64, _stream]),
     "brutus_binpdf_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32, _i32]),
-    "brutus_binpdf_saved": (C.c_int, [_i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
-                                      C.POINTER(BinpdfParams), _vp, _vp, _sz, _vp]),
-    "brutus_binpdf_regen": (C.c_int, [_i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                      C.POINTER(PostParams), _vp, _i32, _vp, _vp, _vp,
-                                      C.POINTER(BinpdfParams), _vp, _vp, _vp, _sz, _vp]),
-    "brutus_debug_binpdf_draws": (C.c_int, [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "brutus_debug_rng": (C.c_int, [_u64, _u64, _i64, _vp, _vp, _vp]),
-    "brutus_debug_zig_table": (C.c_int, [_vp, _vp, _i32]),
-    "brutus_debug_fit_stats": (C.c_int, [_vp, _vp]),
-    "brutus_debug_galprior": (C.c_int, [C.POINTER(PostParams), _i32, _vp, _vp, _vp, _vp,
-                                        _vp, _vp]),
-    "brutus_debug_galprior_mc": (C.c_int, [C.POINTER(PostParams), _i32, _vp, _vp, _vp, _vp,
-                                           _vp, _vp]),
-    "brutus_debug_galprior_sl": (C.c_int, [C.POINTER(PostParams), _i32, _vp, _vp, _vp, _vp,
-                                           _vp, _vp, _vp]),
-    "brutus_debug_copy": (C.c_int, [_vp, _sz, _i64, _i32, _i32, _i32, _vp, _sz, _vp]),
+    "brutus_binpdf_saved": (C.c_int, [_i32, _i32, _df64, _df64, _df64, _df64, _df64, _df64,
+                                      C.POINTER(BinpdfParams), _df32, _dv, _sz, _stream]),
+    "brutus_binpdf_regen": (C.c_int, [_i32, _i32, _df64, _df64, _df64, _df64, _df64, _df64, _df64,
+                                      C.POINTER(PostParams), _df64, _i32, _df64, _df64, _df64,
+                                      C.POINTER(BinpdfParams), _di32, _df32, _dv, _sz, _stream]),
+    "brutus_debug_binpdf_draws": (C.c_int, [_i32, _i32, _i32, _dv, _df64, _df64, _df64, _df64,
+                                            _stream]),
+    "brutus_debug_rng": (C.c_int, [_u64, _u64, _i64, _df64, _df64, _stream]),
+    "brutus_debug_zig_table": (C.c_int, [_hf64, _hf64, _i32]),
+    "brutus_debug_fit_stats": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "brutus_debug_galprior": (C.c_int, [C.POINTER(PostParams), _i32, _df64, _df64, _df64, _df64, _df64,
+                                        _stream]),
+    "brutus_debug_galprior_mc": (C.c_int, [C.POINTER(PostParams), _i32, _df64, _df64, _df64, _df64,
+                                           _df64, _stream]),
+    "brutus_debug_galprior_sl": (C.c_int, [C.POINTER(PostParams), _i32, _df64, _df64, _df64, _df64,
+                                           _df64, _di32, _stream]),
+    "brutus_debug_copy": (C.c_int, [_dv, _sz, _i64, _i32, _i32, _i32, _dv, _sz, _stream]),
     "brutus_debug_sizeof_star32": (C.c_int, []),
-    "brutus_debug_pre32_time": (C.c_int, [_vp, _sz, _vp, _i64, _i32, _i32, C.POINTER(Params), _i32, _i32,
-                                          C.POINTER(C.c_float), _vp]),
-    "brutus_cluster_points": (C.c_int, [_i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "brutus_cluster_points_grid": (C.c_int, [_i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "brutus_offsets_weights": (C.c_int, [_i32, _i32, _i32, _i64] + [_vp] * 12 + [_i32, _vp, _vp, _vp]),
-    "brutus_offsets_workspace_bytes": (C.c_size_t, [_i32, _i32]),
-    "brutus_offsets_bootstrap": (C.c_int, [_i32] * 6 + [_vp] * 7 + [C.c_size_t, _vp, _vp]),
+    "brutus_debug_pre32_time": (C.c_int, [_dv, _sz, _df32, _i64, _i32, _i32, C.POINTER(Params), _i32,
+                                          _i32, _hf32, _stream]),
+    "brutus_cluster_points": (C.c_int, [_i64, _i32, _di32, _df64, _df64, _df64, _df64, _stream]),
+    "brutus_cluster_points_grid": (C.c_int, [_i64, _i32, _i32, _di32, _df64, _df64, _df64, _df64, _df64,
+                                             _stream]),
+    "brutus_offsets_weights": (C.c_int, [_i32, _i32, _i32, _i64, _df32, _di64, _df64, _df64, _df64,
+                                         _df64, _df64, _du8, _df64, _df64, _du8, _du8, _i32, _df64,
+                                         _df64, _stream]),
+    "brutus_offsets_workspace_bytes": (_sz, [_i32, _i32]),
+    "brutus_offsets_bootstrap": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i32, _di32, _df64, _df64,
+                                           _df64, _df64, _df64, _dv, _sz, _df64, _stream]),
     "brutus_cluster_workspace_bytes": (_sz, [_i32]),
-    "brutus_cluster_lnl": (C.c_int, [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
-                                     _vp, _i32, _vp, _sz, _vp, _vp]),
+    "brutus_cluster_lnl": (C.c_int, [_i32, _i32, _i32, _df64, _df64, _df64, _df64, _df64, _df64, _di32,
+                                     _i32, _dv, _sz, _df64, _stream]),
     "brutus_cluster_chunks": (C.c_int, []),
-    "brutus_cluster_lnl_part": (C.c_int, [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
-                                          _vp, _i32, _vp, _sz, _i32, _i32, _vp]),
-    "brutus_cluster_lnl_part_mags": (C.c_int, [_i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
-                                               _vp, _vp, _vp, _i32, _vp, _sz, _i32, _i32, _vp]),
-    "brutus_cluster_lnl_merge": (C.c_int, [_i32, _i32, _vp, _sz, _vp, _vp]),
-    "brutus_cluster_mix": (C.c_int, [_i32, _vp, _vp, C.c_double, C.c_double, _vp, _vp, _vp]),
+    "brutus_cluster_lnl_part": (C.c_int, [_i32, _i32, _i32, _df64, _df64, _df64, _df64, _df64, _df64,
+                                          _di32, _i32, _dv, _sz, _i32, _i32, _stream]),
+    "brutus_cluster_lnl_part_mags": (C.c_int, [_i32, _i32, _i32, _i32, _di32, _df64, _df64, _df64,
+                                               _df64, _df64, _df64, _df64, _di32, _i32, _dv, _sz, _i32,
+                                               _i32, _stream]),
+    "brutus_cluster_lnl_merge": (C.c_int, [_i32, _i32, _dv, _sz, _df64, _stream]),
+    "brutus_cluster_mix": (C.c_int, [_i32, _df64, _df64, _dbl, _dbl, _df64, _df64, _stream]),
     "brutus_iso_workspace_bytes": (_sz, [_i32, _i32, _i32]),
-    "brutus_iso_seds_grid": (C.c_int, [C.POINTER(IsoParams)] + [_vp] * 14 + [_sz, _vp]),
+    "brutus_iso_seds_grid": (C.c_int, [C.POINTER(IsoParams), _df64, _df64, _df64, _df64, _df64, _df64,
+                                       _df64, _df64, _df64, _df64, _df64, _df64, _di32, _dv, _sz,
+                                       _stream]),
     "brutus_sed_workspace_bytes": (_sz, [_i32, _i32, _i32]),
-    "brutus_sed_grid": (C.c_int, [C.POINTER(SedParams)] + [_vp] * 17 + [_sz, _vp]),
+    "brutus_sed_grid": (C.c_int, [C.POINTER(SedParams), _df64, _df64, _df64, _df64, _df64, _df64, _df64,
+                                  _df64, _df64, _df64, _df64, _df64, _df64, _df64, _du8, _di32, _dv,
+                                  _sz, _stream]),
     "brutus_los_workspace_bytes": (_sz, [_i32, _i32]),
-    "brutus_los_loglike": (C.c_int, [_i32, _i32, _vp, _vp, _vp, _i32, _i32, _vp, C.POINTER(LosParams),
-                                     _vp, _vp, _vp, _sz, _vp]),
+    "brutus_los_loglike": (C.c_int, [_i32, _i32, _df64, _df64, _df64, _i32, _i32, _df64,
+                                     C.POINTER(LosParams), _df64, _df64, _dv, _sz, _stream]),
 }
 
 
@@ -225,7 +306,7 @@ def lib():
         import numpy as np
         z = np.load(jp)
         polys = np.ascontiguousarray(z["polys"], dtype=np.uint32)
-        check_rc = L.brutus_set_mt_jump(polys.ctypes.data, int(polys.shape[0]),
+        check_rc = L.brutus_set_mt_jump(polys, int(polys.shape[0]),
                                         int(z["strides"][0]), int(z["strides"][1]))
         if check_rc != 0:
             raise BrutusError("brutus_amd: mt_jump.npz does not match the library")

@@ -17,6 +17,7 @@ import warnings
 import numpy as np
 
 from . import _lib
+from ._dev import _stream_ptr, _torch, to_device
 
 __all__ = ["isochrone_loglike"]
 
@@ -132,7 +133,6 @@ def _isochrone_loglike(theta, isochrone, phot, err, cluster_params, offsets, cor
     offers `get_seds_grid_device(smf_grid=, out=, ...same keywords...) -> mini (Neep,)`
     (`seds.Isochrone`) is asked once instead, for all mass fractions, and fills the device tensor
     `out (Nsmf, Neep, Nbands)` the sum reads: its magnitudes never visit the host."""
-    from .fitting import _torch, _stream_ptr
     from scipy.stats import chi2 as chisquare
     if phot is None:
         raise ValueError("The photometry must be provided to compute the "
@@ -204,10 +204,7 @@ def _isochrone_loglike(theta, isochrone, phot, err, cluster_params, offsets, cor
     ln_fout = np.log(1. - cluster_prob * (1. - fout))
 
     with torch.cuda.device(dev):
-        up = lambda a, dt=np.float64: torch.from_numpy(
-            np.ascontiguousarray(a, dtype=dt)).to(dev)
         stream = _stream_ptr(torch)
-        ws, ws_n = ds.ws.data_ptr(), ds.ws.numel()
         objs = []
 
         def obj_args():
@@ -216,41 +213,39 @@ def _isochrone_loglike(theta, isochrone, phot, err, cluster_params, offsets, cor
             flux kernel of that group run under this."""
             if objs:
                 return objs[0]
-            t_ln = None
             if np.all(Xb == 1.):
-                t_d, t_iv, t_ln = ds.t_d, ds.t_iv, ds.t_ln0
+                per_object = ds.p_d, ds.p_iv, ds.p_cp, ds.p_ln0
             else:                                  # multiplicative offsets (cluster.py:327-333)
                 phot_t, err_t = phot * Xb, err * Xb
                 with np.errstate(all="ignore"):
                     ivar = np.where(ds.phot_mask, 1. / err_t ** 2, 0.)
                     lnorm = np.nansum(np.log(2. * np.pi * err_t ** 2), axis=1) + ds.lnorm_p
-                t_d, t_iv = up(np.where(ds.phot_mask, phot_t, 0.)), up(ivar)
-                t_ln = up(lnorm)
+                t_d = to_device(np.where(ds.phot_mask, phot_t, 0.), np.float64, dev)
+                t_iv, t_ln = to_device(ivar, np.float64, dev), to_device(lnorm, np.float64, dev)
+                # (in the tuple until the call returns: they outlive the launches that read them)
+                per_object = t_d, t_iv, ds.p_cp, t_ln
             ds.h_cp.numpy()[...] = chi2_p
-            t_cp = ds.t_cp.copy_(ds.h_cp, non_blocking=True)
-            # (the tensors ride along: they must outlive the launches that read them)
-            objs.append(((t_d.data_ptr(), t_iv.data_ptr(), t_cp.data_ptr(), t_ln.data_ptr(),
-                          ds.t_n.data_ptr(), 1 if dim_prior else 0, ws, ws_n),
-                         (t_d, t_iv, t_cp, t_ln)))
+            ds.t_cp.copy_(ds.h_cp, non_blocking=True)
+            objs.append((*per_object, ds.p_n, 1 if dim_prior else 0, ds.p_ws, ds.ws.numel()))
             _mark("objects up")
             return objs[0]
 
         def part(t_flux, t_lnw, npts, chunk_lo, chunk_n):
             """The sum over `npts` points as partials in chunks [chunk_lo, chunk_lo + chunk_n)."""
             _lib.check(L.brutus_cluster_lnl_part(
-                Nobjs, Nbands, npts, t_flux.data_ptr() if npts else None,
-                t_lnw.data_ptr() if npts else None, *obj_args()[0], chunk_lo, chunk_n, stream))
+                Nobjs, Nbands, npts, t_flux if npts else None, t_lnw if npts else None,
+                *obj_args(), chunk_lo, chunk_n, stream))
 
         def part_mags(t_src, t_mags, t_lng, t_lnsmf, neep, npts, chunk_lo, chunk_n):
             """The same straight from the plug-in's magnitudes (kept rows `t_src` of `t_mags`)."""
             _lib.check(L.brutus_cluster_lnl_part_mags(
-                Nobjs, Nbands, npts, neep, t_src.data_ptr() if npts else None, t_mags.data_ptr(),
-                t_lng.data_ptr(), t_lnsmf.data_ptr(), *obj_args()[0], chunk_lo, chunk_n, stream))
+                Nobjs, Nbands, npts, neep, t_src if npts else None, t_mags, t_lng, t_lnsmf,
+                *obj_args(), chunk_lo, chunk_n, stream))
 
         # ---- isochrone points of every SMF slice (cluster.py:336-366) -------------
         tab, nchunk = _point_table(isochrone, feh, loga, av, rv, dist, corr_coef, smf_grid,
                                    grad_smf, eep_grid, mini_bound, eep_binary_max, Nbands, dev,
-                                   torch, L, up, cache, part, part_mags)
+                                   torch, L, cache, part, part_mags)
         _mark("table")
         if tab is None:
             lnl = np.full(Nobjs, -np.inf)
@@ -259,17 +254,15 @@ def _isochrone_loglike(theta, isochrone, phot, err, cluster_params, offsets, cor
             lnl_tot = np.sum(lnl_mix)
         else:
             if nchunk:      # the pieces were summed while the plug-in worked on the next one
-                _lib.check(L.brutus_cluster_lnl_merge(Nobjs, nchunk, ws, ws_n,
-                                                      ds.out.data_ptr(), stream))
+                _lib.check(L.brutus_cluster_lnl_merge(Nobjs, nchunk, ds.p_ws, ds.ws.numel(),
+                                                      ds.p_out, stream))
             else:           # a table met before
                 t_flux, t_lnw = tab[1:]
                 _lib.check(L.brutus_cluster_lnl(
-                    Nobjs, Nbands, t_lnw.numel(), t_flux.data_ptr(), t_lnw.data_ptr(),
-                    *obj_args()[0], ds.out.data_ptr(), stream))
+                    Nobjs, Nbands, t_lnw.numel(), t_flux, t_lnw, *obj_args(), ds.p_out, stream))
             # ---- outlier mixture and total (cluster.py:410-414), on the device -------------
-            _lib.check(L.brutus_cluster_mix(Nobjs, ds.out.data_ptr(), ds.t_lo.data_ptr(),
-                                            float(ln_fin), float(ln_fout), ds.t_mix.data_ptr(),
-                                            ds.t_mix[Nobjs:].data_ptr(), stream))
+            _lib.check(L.brutus_cluster_mix(Nobjs, ds.p_out, ds.p_lo, float(ln_fin),
+                                            float(ln_fout), ds.p_mix, ds.p_tot, stream))
             if return_lnls:
                 ds.h_mix.copy_(ds.t_mix, non_blocking=True)
             else:
@@ -294,7 +287,6 @@ class _Dataset(object):
 
 def _dataset(phot, err, parallax, parallax_err, dim_prior, device, cache):
     from scipy.stats import chi2 as chisquare
-    from .fitting import _torch
     def check():    # the reference's data check comes before anything is computed (cluster.py:296)
         if np.any(np.sum(np.isfinite(phot) & np.isfinite(err), axis=1) == 0):
             raise ValueError("At least one object has no valid data entries!")
@@ -351,11 +343,10 @@ def _dataset(phot, err, parallax, parallax_err, dim_prior, device, cache):
         ivar = np.where(ds.phot_mask, 1. / err ** 2, 0.)
         ds.lnorm0 = np.nansum(np.log(2. * np.pi * err ** 2), axis=1) + ds.lnorm_p
     with torch.cuda.device(dev):
-        up = lambda a, dt=np.float64: torch.from_numpy(
-            np.ascontiguousarray(a, dtype=dt)).to(dev)
-        ds.t_d, ds.t_iv = up(np.where(ds.phot_mask, phot, 0.)), up(ivar)
-        ds.t_n = up(phot_n, np.int32)
-        ds.t_ln0 = up(ds.lnorm0)
+        ds.t_d = to_device(np.where(ds.phot_mask, phot, 0.), np.float64, dev)
+        ds.t_iv = to_device(ivar, np.float64, dev)
+        ds.t_n = to_device(phot_n, np.int32, dev)
+        ds.t_ln0 = to_device(ds.lnorm0, np.float64, dev)
         ds.h_cp = torch.empty(Nobjs, dtype=torch.float64).pin_memory()
         ds.t_cp = torch.empty(Nobjs, dtype=torch.float64, device=dev)
         ds.ws = torch.empty(L.brutus_cluster_workspace_bytes(Nobjs), dtype=torch.uint8, device=dev)
@@ -363,9 +354,17 @@ def _dataset(phot, err, parallax, parallax_err, dim_prior, device, cache):
         ds.h_out = torch.empty(Nobjs, dtype=torch.float64).pin_memory()
         # outlier mixture and total on the device (cluster.py:410-414): what comes back is one
         # float64, and the per-object values only when they are asked for
-        ds.t_lo = up(ds.lnl_outlier)
+        ds.t_lo = to_device(ds.lnl_outlier, np.float64, dev)
         ds.t_mix = torch.empty(Nobjs + 1, dtype=torch.float64, device=dev)      # [mix | total]
         ds.h_mix = torch.empty(Nobjs + 1, dtype=torch.float64).pin_memory()
+        # every evaluation of this catalogue passes these buffers to several short calls: checked
+        # once, here where they are allocated (`_lib.fixed` addresses hold their tensors); a
+        # buffer that is ever replaced is replaced together with its `p_` twin
+        for name, t in (("d", ds.t_d), ("iv", ds.t_iv), ("ln0", ds.t_ln0), ("cp", ds.t_cp),
+                        ("out", ds.out), ("lo", ds.t_lo), ("mix", ds.t_mix),
+                        ("tot", ds.t_mix[Nobjs:])):
+            setattr(ds, "p_" + name, _lib.fixed(t, "d", "float64"))
+        ds.p_n, ds.p_ws = _lib.fixed(ds.t_n, "d", "int32"), _lib.fixed(ds.ws, "d")
     if cache:
         _lru_put(_DATA_CACHE, key, ds, _DATA_CACHE_MAX)
     return ds
@@ -385,6 +384,7 @@ def _staging(nrow, nb, dev, torch):
         st.h_lnw = torch.empty(nrow, dtype=torch.float64).pin_memory()
         st.d_mags = torch.empty((nrow, nb), dtype=torch.float64, device=dev)
         st.d_lnw = torch.empty(nrow, dtype=torch.float64, device=dev)
+        st.p_mags = _lib.fixed(st.d_mags, "d", "float64")    # (as for the catalogue's buffers)
         st.src = st.t_src = None
         st.hook_out = {}
         _STAGE[key] = st
@@ -424,7 +424,7 @@ def _group_bounds(nsmf, ngroup, growth=_PIPELINE_GROWTH):
 
 
 def _point_table(isochrone, feh, loga, av, rv, dist, corr_coef, smf_grid, grad_smf, eep_grid,
-                 mini_bound, eep_binary_max, Nbands, dev, torch, L, up, cache, part, part_mags):
+                 mini_bound, eep_binary_max, Nbands, dev, torch, L, cache, part, part_mags):
     """Device-resident isochrone points `(flux (Npts, Nbands), lnw (Npts))` of all
     secondary-mass-fraction slices, or None if no slice has a usable point
     (cluster.py:336-366), and the number of partial-sum chunks filled on the way: a table
@@ -433,7 +433,6 @@ def _point_table(isochrone, feh, loga, av, rv, dist, corr_coef, smf_grid, grad_s
     `brutus_cluster_points` turns them into fluxes and drops the all-NaN points, `part`
     (brutus_cluster_lnl_part) sums the group into its share of the chunks."""
     import os
-    from .fitting import _stream_ptr
     key = (id(isochrone), getattr(isochrone, "cache_token", None), feh, loga, av, rv, dist,
            None if corr_coef is None else tuple(corr_coef), smf_grid.tobytes(),
            eep_grid.tobytes(), mini_bound, eep_binary_max, str(dev))
@@ -448,8 +447,8 @@ def _point_table(isochrone, feh, loga, av, rv, dist, corr_coef, smf_grid, grad_s
                 t_flux = torch.empty((npts, Nbands), dtype=torch.float64, device=dev)
                 t_lnw = torch.empty(npts, dtype=torch.float64, device=dev)
                 _lib.check(L.brutus_cluster_points_grid(
-                    npts, Nbands, neep_, t_src.data_ptr(), t_mags.data_ptr(), t_lng.data_ptr(),
-                    t_lnsmf.data_ptr(), t_flux.data_ptr(), t_lnw.data_ptr(), _stream_ptr(torch)))
+                    npts, Nbands, neep_, t_src, t_mags, t_lng, t_lnsmf, t_flux, t_lnw,
+                    _stream_ptr(torch)))
                 tab = ("flux", t_flux, t_lnw)
                 _lru_put(_TABLE_CACHE, key, (tab, isochrone), _TABLE_CACHE_MAX)
             return tab, 0
@@ -494,7 +493,8 @@ def _point_table(isochrone, feh, loga, av, rv, dist, corr_coef, smf_grid, grad_s
     smfkey = smf_grid.tobytes()
     if getattr(stage, "smfkey", None) != smfkey:
         with np.errstate(all="ignore"):
-            stage.smfkey, stage.d_lnsmf = smfkey, up(np.log(grad_smf))
+            stage.smfkey, stage.d_lnsmf = smfkey, to_device(np.log(grad_smf), np.float64, dev)
+            stage.p_lnsmf = _lib.fixed(stage.d_lnsmf, "d", "float64")
     d_lnsmf, mini0, d_lng, posb, pos = stage.d_lnsmf, None, None, None, None
     late = eep_grid > eep_binary_max                    # evolved stars: first slice only
     lateb = late.tobytes()
@@ -560,11 +560,12 @@ def _point_table(isochrone, feh, loga, av, rv, dist, corr_coef, smf_grid, grad_s
                     keep = np.repeat(pos[None, :], b - a, axis=0)
                     keep[(1 if a == 0 else 0):, late] = False        # (slice 0 keeps its evolved stars)
                     src = (np.flatnonzero(keep) + a * neep).astype(np.int32)
-                    stage.src[g], stage.t_src[g], stage.srckey[g] = src, up(src, np.int32), srckey
+                    stage.src[g], stage.srckey[g] = src, srckey
+                    stage.t_src[g] = to_device(src, np.int32, dev)
                 n = stage.src[g].size
                 if os.environ.get("BRUTUS_CLUSTER_MAGS", "1") != "0":
                     # fluxes and weights are formed by the sum itself, from the staged magnitudes
-                    part_mags(stage.t_src[g], stage.d_mags, d_lng, d_lnsmf, neep, n, c0, c1 - c0)
+                    part_mags(stage.t_src[g], stage.p_mags, d_lng, stage.p_lnsmf, neep, n, c0, c1 - c0)
                     _mark("group %d out" % g)
                     off += n
                     shared += 1
@@ -573,9 +574,8 @@ def _point_table(isochrone, feh, loga, av, rv, dist, corr_coef, smf_grid, grad_s
                     t_flux, t_lnw = flux_table()
                 if n:
                     _lib.check(L.brutus_cluster_points_grid(
-                        n, Nbands, neep, stage.t_src[g].data_ptr(), stage.d_mags.data_ptr(),
-                        d_lng.data_ptr(), d_lnsmf.data_ptr(), t_flux[off:].data_ptr(),
-                        t_lnw[off:].data_ptr(), stream))
+                        n, Nbands, neep, stage.t_src[g], stage.d_mags, d_lng, d_lnsmf,
+                        t_flux[off:], t_lnw[off:], stream))
             else:
                 gmini = np.gradient(mini, axis=1)
                 keep = gmini > 0.
@@ -592,12 +592,12 @@ def _point_table(isochrone, feh, loga, av, rv, dist, corr_coef, smf_grid, grad_s
                     stage.d_lnw[a * neep:b * neep].copy_(stage.h_lnw[a * neep:b * neep],
                                                          non_blocking=True)
                     if stage.src[g] is None or not np.array_equal(stage.src[g], src):
-                        stage.src[g], stage.t_src[g] = src, up(src, np.int32)   # (rarely changes)
+                        stage.src[g] = src                                # (rarely changes)
+                        stage.t_src[g] = to_device(src, np.int32, dev)
                     stage.srckey[g] = None
                     _lib.check(L.brutus_cluster_points(
-                        n, Nbands, stage.t_src[g].data_ptr(), stage.d_mags.data_ptr(),
-                        stage.d_lnw.data_ptr(), t_flux[off:].data_ptr(), t_lnw[off:].data_ptr(),
-                        stream))
+                        n, Nbands, stage.t_src[g], stage.d_mags, stage.d_lnw, t_flux[off:],
+                        t_lnw[off:], stream))
             part(t_flux[off:off + n], t_lnw[off:off + n], n, c0, c1 - c0)
             _mark("group %d out" % g)
             off += n

@@ -29,6 +29,7 @@ import warnings
 import numpy as np
 
 from . import _lib
+from ._dev import _stream_ptr, _torch, to_device
 from . import pdf as _pdf
 from .rng import PhiloxRandomState, numpy_stream, state_to_words, words_to_state
 from .pdf import (imf_lnprior, parallax_lnprior, parallax_to_scale, ps1_MrLF_lnprior,
@@ -43,22 +44,8 @@ except ImportError:  # pragma: no cover
 __all__ = ["loglike", "lnpost", "BruteForce", "DeviceGrid", "loglike_batch"]
 
 
-def _torch():
-    import torch
-    if not torch.cuda.is_available():
-        raise _lib.BrutusError(
-            "brutus_amd: no GPU visible (torch.cuda.is_available() is False); "
-            "the grid likelihood only runs on the HIP path, there is no CPU "
-            "fallback.")
-    return torch
-
-
 def _is_tensor(x):
     return type(x).__module__.startswith("torch")
-
-
-def _stream_ptr(torch):
-    return torch.cuda.current_stream().cuda_stream
 
 
 def _make_params(avlim, av_gauss, rvlim, rv_gauss, ltol, ltol_subthresh,
@@ -140,8 +127,7 @@ class DeviceGrid(object):
         self.soa = torch.empty(nbytes // 4, dtype=torch.float32,
                                device=self.device)
         with torch.cuda.device(self.device):
-            _lib.check(L.brutus_grid_relayout(aos.data_ptr(), self.nmodel,
-                                              self.nfilt, self.soa.data_ptr(),
+            _lib.check(L.brutus_grid_relayout(aos, self.nmodel, self.nfilt, self.soa,
                                               _stream_ptr(torch)))
             torch.cuda.current_stream().synchronize()
 
@@ -281,15 +267,13 @@ class _Engine(object):
         if F != self.grid.nfilt:
             raise ValueError("data has %d bands but the grid has %d"
                              % (F, self.grid.nfilt))
-        f = torch.from_numpy(np.ascontiguousarray(flux, dtype=np.float64)).to(dev)
-        e = torch.from_numpy(np.ascontiguousarray(err, dtype=np.float64)).to(dev)
+        f, e = to_device(flux, np.float64, dev), to_device(err, np.float64, dev)
         m = torch.from_numpy(np.ascontiguousarray(mask).astype(np.uint8)).to(dev)
         if parallax is None or parallax_err is None:
             has_par, p, pe = 0, None, None
         else:
             has_par = 1
-            p = torch.from_numpy(np.ascontiguousarray(parallax, dtype=np.float64)).to(dev)
-            pe = torch.from_numpy(np.ascontiguousarray(parallax_err, dtype=np.float64)).to(dev)
+            p, pe = to_device(parallax, np.float64, dev), to_device(parallax_err, np.float64, dev)
         return f, e, m, p, pe, has_par
 
     def loglike_batch(self, flux, err, mask, parallax, parallax_err, params,
@@ -305,7 +289,7 @@ class _Engine(object):
             a = np.ascontiguousarray(a, dtype=np.float64)
             if a.shape != (g.nmodel,):
                 raise ValueError("`%s` must have one value per model" % name)
-            return torch.from_numpy(a).to(g.device)
+            return to_device(a, np.float64, g.device)
         with torch.cuda.device(g.device):
             t_av0, t_rv0 = init(av_init, "av_init"), init(rv_init, "rv_init")
             f, e, m, p, pe, has_par = self._upload(flux, err, mask, parallax,
@@ -322,16 +306,8 @@ class _Engine(object):
             k1 = np.zeros(S, dtype=np.int32)
             k2 = np.zeros(S, dtype=np.int32)
             _lib.check(L.brutus_loglike_batch(
-                g.soa.data_ptr(), g.nmodel, g.nfilt, S, f.data_ptr(),
-                e.data_ptr(), m.data_ptr(),
-                p.data_ptr() if p is not None else None,
-                pe.data_ptr() if pe is not None else None, has_par, params,
-                ws.data_ptr(), ws.numel(), lnl.data_ptr(), chi2.data_ptr(),
-                scale.data_ptr(), av.data_ptr(), rv.data_ptr(), icov.data_ptr(),
-                ndim.data_ptr(), k1.ctypes.data, k2.ctypes.data,
-                t_av0.data_ptr() if t_av0 is not None else None,
-                t_rv0.data_ptr() if t_rv0 is not None else None,
-                _stream_ptr(torch)))
+                g.soa, g.nmodel, g.nfilt, S, f, e, m, p, pe, has_par, params, ws, ws.numel(),
+                lnl, chi2, scale, av, rv, icov, ndim, k1, k2, t_av0, t_rv0, _stream_ptr(torch)))
             out = dict(lnl=lnl.cpu().numpy(), chi2=chi2.cpu().numpy(),
                        scale=scale.cpu().numpy(), av=av.cpu().numpy(),
                        rv=rv.cpu().numpy(), icov6=icov.cpu().numpy(),
@@ -368,12 +344,8 @@ class _Engine(object):
             idx, slot, vals = buffers
             capacity = idx.numel()
             rc = L.brutus_fit_batch(
-                g.soa.data_ptr(), g.nmodel, g.nfilt, S, f.data_ptr(), e.data_ptr(),
-                m.data_ptr(), p.data_ptr() if p is not None else None,
-                pe.data_ptr() if pe is not None else None, has_par, params,
-                ws.data_ptr(), ws.numel(), capacity, idx.data_ptr(), slot.data_ptr(),
-                vals.data_ptr(), off.data_ptr(), ndim.data_ptr(),
-                k1.ctypes.data, k2.ctypes.data, counts.ctypes.data, _stream_ptr(torch))
+                g.soa, g.nmodel, g.nfilt, S, f, e, m, p, pe, has_par, params, ws, ws.numel(),
+                capacity, idx, slot, vals, off, ndim, k1, k2, counts, _stream_ptr(torch))
             if rc == -2 and grow and b"record buffer too small" in L.brutus_last_error():
                 # the flux phase keeps its results in the record planes themselves, so a
                 # batch that does not fit is redone as a whole
@@ -461,18 +433,15 @@ class _Engine(object):
                 ws = self._workspace(n)
                 out = fg.view(-1)[:_lib.NVALS * n * g.nmodel].view(_lib.NVALS, n, g.nmodel)   # lnl chi2 scale av rv | icov[6]
                 k1c, k2c = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
-                pa = p[a:b].data_ptr() if p is not None else None
-                pea = pe[a:b].data_ptr() if pe is not None else None
+                pa = p[a:b] if p is not None else None
+                pea = pe[a:b] if pe is not None else None
                 _lib.check(L.brutus_loglike_batch(
-                    g.soa.data_ptr(), g.nmodel, g.nfilt, n, f[a:b].data_ptr(), e[a:b].data_ptr(),
-                    m[a:b].data_ptr(), pa, pea, has_par, params,
-                    ws.data_ptr(), ws.numel(), out[0].data_ptr(), out[1].data_ptr(),
-                    out[2].data_ptr(), out[3].data_ptr(), out[4].data_ptr(), out[5].data_ptr(),
-                    ndim[a:b].data_ptr(), k1c.ctypes.data, k2c.ctypes.data, None, None,
-                    _stream_ptr(torch)))
+                    g.soa, g.nmodel, g.nfilt, n, f[a:b], e[a:b], m[a:b], pa, pea, has_par, params,
+                    ws, ws.numel(), out[0], out[1], out[2], out[3], out[4], out[5],
+                    ndim[a:b], k1c, k2c, None, None, _stream_ptr(torch)))
                 k1[a:b], k2[a:b] = k1c, k2c
                 if n_ext:
-                    ext_t = torch.from_numpy(np.ascontiguousarray(ext_par[:, a:b])).to(dev)
+                    ext_t = to_device(ext_par[:, a:b], np.float64, dev)
                 if keep_all:
                     # no cut was asked for: every model is a record, the planes are the values
                     counts[1] = base + n * g.nmodel
@@ -489,13 +458,10 @@ class _Engine(object):
                     idx, slot, vals = buffers
                     capacity = idx.numel()
                     rc = L.brutus_cut_batch(
-                        g.nmodel, n, out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(),
-                        out[3].data_ptr(), out[4].data_ptr(), out[5].data_ptr(), pa, pea, has_par,
-                        n_ext, labels_t.data_ptr() if n_ext else None,
-                        ext_t.data_ptr() if n_ext else None, float(params.wt_thresh),
-                        cws.data_ptr(), cws.numel(), capacity, base, idx.data_ptr(),
-                        slot.data_ptr(), vals.data_ptr(), off[a:].data_ptr(), counts.ctypes.data,
-                        _stream_ptr(torch))
+                        g.nmodel, n, out[0], out[1], out[2], out[3], out[4], out[5], pa, pea,
+                        has_par, n_ext, labels_t if n_ext else None, ext_t if n_ext else None,
+                        float(params.wt_thresh), cws, cws.numel(), capacity, base, idx, slot, vals,
+                        off[a:], counts, _stream_ptr(torch))
                     if rc == -2 and b"record buffer too small" in L.brutus_last_error():
                         # the planes are untouched: larger buffers, then the cut of this chunk again
                         idx = slot = vals = None
@@ -539,9 +505,9 @@ class _Engine(object):
 
     def _post_inputs(self, rec, coords, parallax, parallax_err):
         """What a post call reads of one batch, on the device (`_PostInputs`)."""
-        torch, dev = self.torch, self.grid.device
-        up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
-        return _PostInputs(rec, up(coords), up(parallax), up(parallax_err))
+        dev = self.grid.device
+        return _PostInputs(rec, *(to_device(a, np.float64, dev)
+                                  for a in (coords, parallax, parallax_err)))
 
     def _post_outputs(self, nstar, ndraws, nbase=None):
         """Fresh outputs of one post call: draws on the device, per-object values on the host."""
@@ -555,13 +521,9 @@ class _Engine(object):
         """The 19 arguments the three `brutus_post_batch*` entry points begin with."""
         lnprior, feh, loga = statics
         rec = inp.rec
-        return (nstar, rec.capacity, rec.idx.data_ptr(), rec.slot.data_ptr(), rec.vals.data_ptr(),
-                rec.off.data_ptr(), lnprior.data_ptr(),
-                feh.data_ptr() if feh is not None else None,
-                loga.data_ptr() if loga is not None else None, inp.coords.data_ptr(),
-                inp.parallax.data_ptr(), inp.parallax_err.data_ptr(), pp, ws.data_ptr(),
-                ws.numel(), out.out_idx.data_ptr(), out.out_vals.data_ptr(),
-                out.star_out.ctypes.data, out.flags.ctypes.data)
+        return (nstar, rec.capacity, rec.idx, rec.slot, rec.vals, rec.off, lnprior, feh, loga,
+                inp.coords, inp.parallax, inp.parallax_err, pp, ws, ws.numel(), out.out_idx,
+                out.out_vals, out.star_out, out.flags)
 
     def post_batch_device(self, rec, nstar, statics,
                           coords, parallax, parallax_err, pp, np_states=None, dust=None,
@@ -578,16 +540,14 @@ class _Engine(object):
         inp = self._post_inputs(rec, coords, parallax, parallax_err)
         out = self._post_outputs(nstar, pp.ndraws, np.zeros(nstar + 1, dtype=np.uint64))
         lead = self._post_leading_args(nstar, inp, statics, pp, ctx.ws, out)
-        assert np_states is None or (np_states.dtype == np.uint32 and np_states.flags.c_contiguous)
         while True:
             self._set_tables(dust, dtab)          # one-shot context: before EVERY (re)try
             if np_states is None:
-                rc = L.brutus_post_batch(*lead + (out.nbase.ctypes.data, _stream_ptr(torch)))
+                rc = L.brutus_post_batch(*lead + (out.nbase, _stream_ptr(torch)))
             else:
                 zb = ctx.zbuf
                 rc = L.brutus_post_batch_numpy(*lead + (
-                    int(np_states.shape[0]), np_states.ctypes.data, zb.data_ptr(), zb.numel(),
-                    _stream_ptr(torch)))
+                    int(np_states.shape[0]), np_states, zb, zb.numel(), _stream_ptr(torch)))
                 if rc == -2 and b"normal buffer too small" in L.brutus_last_error() \
                         and zb.numel() * 8 < 96 * 2 ** 30:
                     # one object alone exceeds the buffer (the states were not touched): grow
@@ -608,11 +568,11 @@ class _Engine(object):
         replace flag), or None."""
         if dust is not None:
             t_los, t_ok = dust
-            _lib.check(self.L.brutus_post_set_dust(t_los.data_ptr(), t_ok.data_ptr(),
-                                                   int(t_los.shape[2]), 0., 1., 1., 0.2))
+            _lib.check(self.L.brutus_post_set_dust(t_los, t_ok, int(t_los.shape[2]),
+                                                   0., 1., 1., 0.2))
         if dtab is not None:
             t_tab, replace = dtab
-            _lib.check(self.L.brutus_post_set_dist_table(t_tab.data_ptr(), int(t_tab.shape[2]),
+            _lib.check(self.L.brutus_post_set_dist_table(t_tab, int(t_tab.shape[2]),
                                                          1 if replace else 0))
 
     # ---- brutus_post_batch_numpy in two halves (pipelined across batches) --------------
@@ -634,16 +594,13 @@ class _Engine(object):
         # tables too, by `run`: phase 2 evaluates them inside the Monte Carlo integral)
         ctx.inputs = self._post_inputs(rec, coords, parallax, parallax_err)
         ctx.out = self._post_outputs(nstar, pp.ndraws)
-        assert np_states.dtype == np.uint32 and np_states.flags.c_contiguous
         lead = self._post_leading_args(nstar, ctx.inputs, statics, pp, ctx.ws, ctx.out)
-        tail = (int(np_states.shape[0]), np_states.ctypes.data, ctx.zbuf.data_ptr(),
-                ctx.zbuf.numel())
+        tail = (int(np_states.shape[0]), np_states, ctx.zbuf, ctx.zbuf.numel())
 
         def run(phase):
             # (the distance table in both phases: phase 2 picks its kernel by it)
             self._set_tables(call.dust if phase == 1 else None, call.dtab)
             return L.brutus_post_batch_numpy_phase(*lead + tail + (phase, _stream_ptr(torch)))
-        ctx.run = run
         fired = [after_jump is None]
         if after_jump is not None:
             import ctypes as C
@@ -665,6 +622,9 @@ class _Engine(object):
         if rc == -2 and b"normal buffer too small" in L.brutus_last_error():
             return False
         _lib.check(rc)
+        # (kept only for a batch that awaits phase 2: `run` holds the slot's buffers, and
+        # `post_batch_device` frees and regrows the normal buffer of slot 0 after a False here)
+        ctx.run = run
         return True
 
     def post_numpy_end(self, slot):
@@ -1611,9 +1571,8 @@ class BruteForce(object):
                 # columns go to the device once, the cut follows the full-grid pipeline there
                 torch = eng.torch
                 keys = list(lnprior_ext.keys())
-                ext = (torch.from_numpy(np.ascontiguousarray(
-                           np.stack([self.models_labels[k] for k in keys]), dtype=np.float64)
-                       ).to(eng.grid.device),
+                ext = (to_device(np.stack([self.models_labels[k] for k in keys]), np.float64,
+                                 eng.grid.device),
                        np.stack([np.asarray(lnprior_ext[k], dtype=np.float64).reshape(-1, 2)
                                  for k in keys]))
             yield from self._fit_device_post(eng, params, eng.batch, stars, opts, stream,
@@ -1688,10 +1647,9 @@ class BruteForce(object):
         torch, dev = eng.torch, eng.grid.device
         lngalprior, dlabels = opts.lngalprior, opts.dlabels
         names = dlabels.dtype.names if dlabels is not None else ()
-        up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
-        statics = (up(opts.lnprior),
-                   up(dlabels['feh']) if 'feh' in names else None,
-                   up(dlabels['loga']) if 'loga' in names else None)
+        statics = (to_device(opts.lnprior, np.float64, dev),
+                   to_device(dlabels['feh'], np.float64, dev) if 'feh' in names else None,
+                   to_device(dlabels['loga'], np.float64, dev) if 'loga' in names else None)
         # a tabulated distance prior (pdf.DistancePriorTable): the parameters are its base
         # hook's (the defaults when it replaces the Galactic prior), the table goes up per batch
         dist_prior = lngalprior if isinstance(lngalprior, _pdf.DistancePriorTable) else None
@@ -1749,11 +1707,11 @@ class BruteForce(object):
             dust = dtab = None
             if dust_tables is not None:      # this batch's sightlines; the engine hands
                 los, ok = dust_tables(a, b)  # them to every post call and retry and keeps
-                dust = (torch.from_numpy(np.ascontiguousarray(los)).to(dev),     # them alive
-                        torch.from_numpy(np.ascontiguousarray(ok)).to(dev))
+                dust = (to_device(los, np.float64, dev),     # them alive
+                        to_device(ok, np.int32, dev))
             if dist_prior is not None:       # kept alive like the dust tables
-                dtab = (torch.from_numpy(_pdf.dist_tables(
-                            dist_prior, stars.coords[a:b])).to(dev), dist_prior.base is None)
+                dtab = (to_device(_pdf.dist_tables(dist_prior, stars.coords[a:b]), np.float64, dev),
+                        dist_prior.base is None)
             return _PostCall(pp, np_states, dust, dtab)
 
         def inputs(k, scanned):      # the leading arguments of both forms of the post call

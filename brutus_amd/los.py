@@ -18,6 +18,7 @@ import numpy as np
 from scipy.stats import truncnorm
 
 from . import _lib
+from ._dev import _stream_ptr, _torch, to_device
 
 __all__ = ["LOS_clouds_priortransform", "LOS_clouds_loglike_samples",
            "kernel_tophat", "kernel_gauss", "kernel_lorentz", "LOSSamples"]
@@ -321,12 +322,8 @@ class LOSSamples(object):
                              % (_lib.LOS_MAX_OBJ, _lib.LOS_MAX_DRAWS, ds.shape))
         self.kernel, self.rlims, self.monotonic = kernel, rlims, bool(monotonic)
         self._L = _lib.lib()
-        import torch
-        if not torch.cuda.is_available():
-            raise _lib.BrutusError("brutus_amd: no GPU visible (torch.cuda.is_available() is "
-                                   "False); LOSSamples only runs on the HIP path. The host "
-                                   "form is LOS_clouds_loglike_samples(device=None).")
-        self._torch = torch
+        self._torch = torch = _torch("LOSSamples only runs on the HIP path. The host form is "
+                                     "LOS_clouds_loglike_samples(device=None).")
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise ValueError("LOSSamples needs a GPU device; got %r" % (device,))
@@ -334,10 +331,16 @@ class LOSSamples(object):
         self._p.kernel = _KERNEL_CODES[kernel]
         self._p.additive_foreground = int(bool(additive_foreground))
         self._p.rlims[0], self._p.rlims[1] = rlims
-        self._ds = torch.from_numpy(np.array(ds.T, order='C')).to(self.device)
-        self._rs = torch.from_numpy(np.array(rs.T, order='C')).to(self.device)
+        # (draw-major copies: the caller's arrays may be read-only)
+        self._ds = to_device(np.array(ds.T, order='C'), np.float64, self.device)
+        self._rs = to_device(np.array(rs.T, order='C'), np.float64, self.device)
         self._templ = (None if template_reds is None else
-                       torch.from_numpy(np.array(template_reds)).to(self.device))
+                       to_device(np.array(template_reds), np.float64, self.device))
+        # the six buffers of a call are the same from call to call: checked here and in
+        # `_buffers`, passed as `_lib.fixed` addresses (a single-theta call takes 70 us).  Each
+        # holds its tensor; whoever replaces one of the tensors replaces its address with it
+        self._draws = tuple(_lib.fixed(t, "d", "float64")
+                            for t in (self._ds, self._rs, self._templ))
         self._cap, self._ncol = 0, 0
 
     def _buffers(self, k, ncol):
@@ -350,6 +353,9 @@ class LOSSamples(object):
             self._out = torch.empty(cap, dtype=torch.float64, device=self.device)
             self._ws_bytes = int(self._L.brutus_los_workspace_bytes(self.nobj, cap))
             self._ws = torch.empty(self._ws_bytes, dtype=torch.uint8, device=self.device)
+            # (with the tensors above, always: the call passes these, not the tensors)
+            self._bufs = (_lib.fixed(self._theta, "d", "float64"),
+                          _lib.fixed(self._out, "d", "float64"), _lib.fixed(self._ws, "d"))
             self._cap, self._ncol = cap, ncol
         return self._theta, self._out
 
@@ -363,7 +369,7 @@ class LOSSamples(object):
         if want_terms:
             chunk = int(max(1, min(chunk, _TERMS_CHUNK_BYTES // (8 * self.nobj))))
         with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream().cuda_stream
+            stream = _stream_ptr(torch)
             for a in range(0, ktot, chunk):
                 k = min(chunk, ktot - a)
                 t_theta, t_out = self._buffers(k, ncol)
@@ -371,11 +377,9 @@ class LOSSamples(object):
                 t_terms = (torch.empty((k, self.nobj), dtype=torch.float64, device=self.device)
                            if want_terms else None)
                 _lib.check(self._L.brutus_los_loglike(
-                    self.nobj, self.nsamps, self._ds.data_ptr(), self._rs.data_ptr(),
-                    self._templ.data_ptr() if self._templ is not None else None, k,
-                    (ncol - 4) // 2, t_theta.data_ptr(), C.byref(self._p), t_out.data_ptr(),
-                    t_terms.data_ptr() if want_terms else None, self._ws.data_ptr(),
-                    self._ws_bytes, stream))
+                    self.nobj, self.nsamps, *self._draws, k, (ncol - 4) // 2, self._bufs[0],
+                    C.byref(self._p), self._bufs[1], t_terms, self._bufs[2], self._ws_bytes,
+                    stream))
                 out[a:a + k] = t_out[:k].cpu().numpy()
                 if want_terms:
                     terms[a:a + k] = t_terms.cpu().numpy()

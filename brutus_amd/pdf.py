@@ -12,6 +12,7 @@ import warnings
 
 import numpy as np
 
+from ._dev import _stream_ptr, to_device
 from .galprior import (gal_lnprior, logn_disk, logn_halo, logp_age_from_feh,   # noqa: F401
                        logp_feh)
 
@@ -572,14 +573,10 @@ def _bin_pdfs_device(data, regenerate, cdf, ebv, dist_type, lndistprior, coord, 
                          "(nx, ny <= 65536, nx ny <= 2**28, Nsamps Nr <= 2**24)")
     chunk = int(max(1, min(nobjs, 65535, _BINPDF_WS_LIMIT // one)))
     with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream().cuda_stream
-
-        def up(a):
-            return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
-
+        stream = _stream_ptr(torch)
         ws_bytes = L.brutus_binpdf_workspace_bytes(chunk, nx, ny, nsamps, nr_ws)
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        t_xe, t_ye = up(xbins), up(ybins)
+        t_xe, t_ye = to_device(xbins, np.float64, dev), to_device(ybins, np.float64, dev)
         if device_out:
             out = torch.empty((nobjs, nx, ny), dtype=torch.float32, device=dev)
         else:
@@ -589,34 +586,33 @@ def _bin_pdfs_device(data, regenerate, cdf, ebv, dist_type, lndistprior, coord, 
         for a in range(0, nobjs, chunk):
             b = min(nobjs, a + chunk)
             dst = out[a:b] if device_out else t_out[:b - a]
-            t_xs = up(xsig[a:b])
+            t_xs = to_device(xsig[a:b], np.float64, dev)
             if not regenerate:
-                t = [up(np.asarray(data[q])[a:b]) for q in range(3 if ebv else 2)]
+                t = [to_device(np.asarray(data[q])[a:b], np.float64, dev)
+                     for q in range(3 if ebv else 2)]
                 _lib.check(L.brutus_binpdf_saved(
-                    b - a, nsamps, t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr() if ebv else None,
-                    t_xe.data_ptr(), t_ye.data_ptr(), t_xs.data_ptr(), C.byref(bp), dst.data_ptr(),
-                    ws.data_ptr(), ws_bytes, stream))
+                    b - a, nsamps, t[0], t[1], t[2] if ebv else None, t_xe, t_ye, t_xs,
+                    C.byref(bp), dst, ws, ws_bytes, stream))
             else:
-                t = [up(np.asarray(data[q])[a:b]) for q in range(4)]
+                t = [to_device(np.asarray(data[q])[a:b], np.float64, dev) for q in range(4)]
                 if tuple(t[3].shape) != (b - a, nsamps, 3, 3):
                     raise ValueError("covs_sar must be (Nobj, Nsamps, 3, 3)")
-                t_par, t_perr, t_crd = up(parallaxes[a:b]), up(parallax_errors[a:b]), up(crd[a:b])
-                t_tab = up(dist_tables(table, crd[a:b])) if table is not None else None
+                t_par, t_perr, t_crd = (to_device(x[a:b], np.float64, dev)
+                                        for x in (parallaxes, parallax_errors, crd))
+                t_tab = (to_device(dist_tables(table, crd[a:b]), np.float64, dev)
+                         if table is not None else None)
                 t_st = torch.empty((b - a, 3), dtype=torch.int32, device=dev)
                 bp.object0 = int(object0) + a
                 _lib.check(L.brutus_binpdf_regen(
-                    b - a, nsamps, t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr(), t[3].data_ptr(),
-                    t_par.data_ptr(), t_perr.data_ptr(), t_crd.data_ptr(), C.byref(pp),
-                    t_tab.data_ptr() if table is not None else None,
-                    table.dist.size if table is not None else 0, t_xe.data_ptr(), t_ye.data_ptr(),
-                    t_xs.data_ptr(), C.byref(bp), t_st.data_ptr(), dst.data_ptr(), ws.data_ptr(),
-                    ws_bytes, stream))
+                    b - a, nsamps, t[0], t[1], t[2], t[3], t_par, t_perr, t_crd, C.byref(pp),
+                    t_tab, table.dist.size if table is not None else 0, t_xe, t_ye, t_xs,
+                    C.byref(bp), t_st, dst, ws, ws_bytes, stream))
                 status[a:b] = t_st.cpu().numpy()
                 if _BINPDF_KEEP_DRAWS is not None:
                     kept = [torch.empty((b - a, nsamps, bp.nr), dtype=torch.float64, device=dev)
                             for _ in range(4)]
-                    _lib.check(L.brutus_debug_binpdf_draws(b - a, nsamps, bp.nr, ws.data_ptr(),
-                                                           *[k.data_ptr() for k in kept], stream))
+                    _lib.check(L.brutus_debug_binpdf_draws(b - a, nsamps, bp.nr, ws, *kept,
+                                                           stream))
                     _BINPDF_KEEP_DRAWS.append(tuple(k.cpu().numpy() for k in kept))
             if not device_out:
                 out[a:b] = dst.cpu().numpy()

@@ -19,7 +19,7 @@ import numpy as np
 
 from . import _lib, h5io
 from .filters import FILTERS
-from .fitting import _stream_ptr, _torch
+from ._dev import _stream_ptr, _torch, to_device
 
 __all__ = ["MISTtracks", "SEDmaker", "Isochrone"]
 
@@ -94,11 +94,16 @@ def _device(self, table, device=None):
     if d is None:
         d = _DeviceSide()
         d.dev = dev
-        up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
-        d.table, d.axes = up(table), up(np.concatenate(self.xgrid))
+        d.table = to_device(table, np.float64, dev)
+        d.axes = to_device(np.concatenate(self.xgrid), np.float64, dev)
         d.weights = d.xmin = d.xmax = d.ws = None
         if hasattr(self, "w1"):
-            d.weights, d.xmin, d.xmax = up(_pack_weights(self)), up(self.xmin), up(self.xmax)
+            d.weights, d.xmin, d.xmax = (to_device(a, np.float64, dev)
+                                         for a in (_pack_weights(self), self.xmin, self.xmax))
+        # (what every call reads, checked once: `Isochrone._run` is called per likelihood and
+        # passes these `_lib.fixed` addresses, which hold their tensors, not the tensors)
+        d.p_tab = tuple(_lib.fixed(t, "d", "float64")
+                        for t in (d.table, d.axes, d.weights, d.xmin, d.xmax))
         self._dev[str(dev)] = d
     return d, torch
 
@@ -223,11 +228,10 @@ class Isochrone(object):
         neep, nsmf, nf, npred = len(eep), len(smf), self.NFILT, int(self.grid_dims[4])
         L = _lib.lib()
         with torch.cuda.device(dev):
-            up = lambda a: torch.from_numpy(a).to(dev)
             if d.eepkey != eep.tobytes():
-                d.eepkey, d.eep = eep.tobytes(), up(eep)
+                d.eepkey, d.eep = eep.tobytes(), to_device(eep, np.float64, dev)
             if d.smfkey != smf.tobytes():
-                d.smfkey, d.smf = smf.tobytes(), up(smf)
+                d.smfkey, d.smf = smf.tobytes(), to_device(smf, np.float64, dev)
             if d.shape != (neep, nsmf):
                 new = lambda *s: torch.empty(s, dtype=torch.float64, device=dev)
                 d.shape = (neep, nsmf)
@@ -236,6 +240,10 @@ class Isochrone(object):
                 d.h_mini = torch.empty(neep, dtype=torch.float64).pin_memory()
                 d.ws = torch.empty(max(1, L.brutus_iso_workspace_bytes(neep, nsmf, nf)),
                                    dtype=torch.uint8, device=dev)
+                # (with the tensors above, always: `launch` passes these, not the tensors)
+                d.p_res = tuple(_lib.fixed(t, "d", "float64")
+                                for t in (d.prim, d.sec, d.mini, d.eep2))
+                d.p_ws = _lib.fixed(d.ws, "d")
             if out is None:
                 out = d.own_mags
             elif (tuple(out.shape) != (nsmf, neep, nf) or out.dtype != torch.float64
@@ -250,10 +258,8 @@ class Isochrone(object):
 
             def launch():
                 _lib.check(L.brutus_iso_seds_grid(
-                    C.byref(p), d.table.data_ptr(), d.axes.data_ptr(), d.weights.data_ptr(),
-                    d.xmin.data_ptr(), d.xmax.data_ptr(), d.eep.data_ptr(), d.smf.data_ptr(),
-                    out.data_ptr(), d.prim.data_ptr(), d.sec.data_ptr(), d.mini.data_ptr(),
-                    d.eep2.data_ptr(), d.status.data_ptr(), d.ws.data_ptr(), d.ws.numel(), stream))
+                    C.byref(p), *d.p_tab, d.eep, d.smf, out, *d.p_res, d.status, d.p_ws,
+                    d.ws.numel(), stream))
                 d.h_mini.copy_(d.mini, non_blocking=True)
                 d.h_status.copy_(d.status, non_blocking=True)
                 torch.cuda.current_stream().synchronize()
@@ -268,7 +274,7 @@ class Isochrone(object):
                     for s in np.flatnonzero((smf > 0.) & (smf < 1.)):
                         eep2[s] = np.interp(mini * smf[s], mini[fin], eep[fin],
                                             left=np.nan, right=np.nan)
-                d.eep2.copy_(up(eep2))
+                d.eep2.copy_(to_device(eep2, np.float64, dev))
                 p.flags = flags | _lib.ISO_EEP2_GIVEN
                 launch()
         return d, mini
@@ -287,13 +293,12 @@ class Isochrone(object):
         flags = _lib.ISO_PRED_ONLY | (_lib.ISO_APPLY_CORR if apply_corr else 0)
         p = self._params(neep, 1, flags, feh, afe, loga, 0., 3.3, 1000., 0., 0., corr_params)
         with torch.cuda.device(d.dev):
-            t_eep = torch.from_numpy(eep).to(d.dev)
+            t_eep = to_device(eep, np.float64, d.dev)
             prim = torch.empty((neep, npred), dtype=torch.float64, device=d.dev)
             mini = torch.empty(neep, dtype=torch.float64, device=d.dev)
             _lib.check(_lib.lib().brutus_iso_seds_grid(
-                C.byref(p), d.table.data_ptr(), d.axes.data_ptr(), None, None, None,
-                t_eep.data_ptr(), None, None, prim.data_ptr(), None, mini.data_ptr(), None, None,
-                None, 0, _stream_ptr(torch)))
+                C.byref(p), d.table, d.axes, None, None, None, t_eep, None, None, prim, None, mini,
+                None, None, None, 0, _stream_ptr(torch)))
             return prim.cpu().numpy()
 
     def get_corrections(self, mini=1., feh=0., eep=350., corr_params=None):
@@ -518,13 +523,12 @@ class MISTtracks(object):
         """One call of `k_sed_tracks` alone: predictions (`out (N, Npred)`) or EEPs (`out (N,)`)."""
         d, torch = self._device(device)
         with torch.cuda.device(d.dev):
-            lab = torch.from_numpy(np.ascontiguousarray(labels5, dtype=np.float64)).to(d.dev)
+            lab = to_device(labels5, np.float64, d.dev)
             res = torch.empty(out, dtype=torch.float64, device=d.dev)
             eep_only = bool(p.flags & _lib.SED_EEP_ONLY)
             _lib.check(_lib.lib().brutus_sed_grid(
-                C.byref(p), d.table.data_ptr(), d.axes.data_ptr(), None, None, None,
-                lab.data_ptr(), None, None, None, None, None,
-                None if eep_only else res.data_ptr(), None, res.data_ptr() if eep_only else None,
+                C.byref(p), d.table, d.axes, None, None, None, lab, None, None, None, None, None,
+                None if eep_only else res, None, res if eep_only else None,
                 None, None, None, 0, _stream_ptr(torch)))
             return res.cpu().numpy()
 
@@ -635,13 +639,10 @@ class SEDmaker(MISTtracks):
             raise ValueError("bad grid dimensions (%d models x %d filters)" % (n, self.NFILT))
         if d.ws is None or d.ws.numel() < need:
             d.ws = torch.empty(need, dtype=torch.uint8, device=d.dev)
-        ptr = lambda t: None if t is None else t.data_ptr()
         coef, av, rv = fit if fit is not None else (None, None, None)
         _lib.check(L.brutus_sed_grid(
-            C.byref(p), d.table.data_ptr(), d.axes.data_ptr(), d.weights.data_ptr(),
-            d.xmin.data_ptr(), d.xmax.data_ptr(), lab.data_ptr(), ptr(eep2), ptr(coef), ptr(av),
-            ptr(rv), sed.data_ptr(), param.data_ptr(), param2.data_ptr(), eep2_out.data_ptr(),
-            sel.data_ptr(), None, d.ws.data_ptr(), d.ws.numel(), _stream_ptr(torch)))
+            C.byref(p), d.table, d.axes, d.weights, d.xmin, d.xmax, lab, eep2, coef, av, rv,
+            sed, param, param2, eep2_out, sel, None, d.ws, d.ws.numel(), _stream_ptr(torch)))
 
     def _flags(self, apply_corr, eep2_given):
         return ((_lib.SED_APPLY_CORR if apply_corr else 0)
@@ -787,8 +788,7 @@ class SEDmaker(MISTtracks):
                          mini_min=max(self.mini_bound, mini_bound), nav=nav, nrv=nrv)
         with torch.cuda.device(d.dev):
             new = lambda *s: torch.empty(s, dtype=torch.float64, device=d.dev)
-            up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(d.dev)
-            fit = (up(coef), up(av_grid), up(rv_grid))
+            fit = tuple(to_device(a, np.float64, d.dev) for a in (coef, av_grid, rv_grid))
             rows = Ngrid if device_out else chunk
             sed, par = new(rows, nf, 3), new(rows, npred)
             sel = torch.empty(rows, dtype=torch.uint8, device=d.dev)
@@ -801,8 +801,9 @@ class SEDmaker(MISTtracks):
                     h_label[lo:hi, k] = axes[k][idx[k]]
                 o = lo if device_out else 0
                 p.nmodel = n
-                self._grid_call(d, torch, up(h_label[lo:hi]), p,
-                                None if eep2 is None else up(eep2[lo:hi]), fit,
+                self._grid_call(d, torch, to_device(h_label[lo:hi], np.float64, d.dev), p,
+                                None if eep2 is None else to_device(eep2[lo:hi], np.float64, d.dev),
+                                fit,
                                 sed[o:o + n], par[o:o + n], par2[:n], e2_out[:n], sel[o:o + n])
                 h_sed[lo:hi] = sed[o:o + n].cpu().numpy()
                 h_param[lo:hi] = par[o:o + n].cpu().numpy()

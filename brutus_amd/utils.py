@@ -423,7 +423,7 @@ def _photometric_offsets_device(phot, err, mask, models, idxs, reds, dreds, dist
     `choice` calls, utils.py:1381-1385) and takes median / std of the Nmc medians."""
     import sys
     from . import _lib
-    from .fitting import _torch, _stream_ptr
+    from ._dev import _stream_ptr, _torch, to_device
     phot, err = np.asarray(phot, float), np.asarray(err, float)
     mask = np.asarray(mask, dtype=bool)
     Nobj, Nfilt = phot.shape
@@ -454,29 +454,23 @@ def _photometric_offsets_device(phot, err, mask, models, idxs, reds, dreds, dist
     dev = torch.device("cuda:%d" % torch.cuda.current_device() if device in (True, "cuda")
                        else device)
 
-    def up(a, dt):
-        return torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)
-
     subsets = _offsets_subsets(mask, sel, weights, mask_fit)
     use = np.zeros((Nfilt, Nobj), dtype=np.uint8)
     for b, s in enumerate(subsets):
         use[b, s] = 1
     with torch.cuda.device(dev):
         sp = _stream_ptr(torch)
-        t_models = up(models, np.float32)
-        t_phot, t_err = up(phot, np.float64), up(err, np.float64)
-        t_w = up(weights, np.float64)
         t_flux = torch.empty((Nfilt, Nobj, Nsamps), dtype=torch.float64, device=dev)
         t_cdf = torch.empty((Nfilt, Nobj, Nsamps), dtype=torch.float64, device=dev)
-        keep = [up(idxs, np.int64), up(reds, np.float64), up(dreds, np.float64),
-                up(dists, np.float64), up(mask, np.uint8), up(old_offsets, np.float64),
-                up(use, np.uint8), up(mask_fit, np.uint8)]
-        _lib.check(L.brutus_offsets_weights(
-            Nobj, Nsamps, Nfilt, models.shape[0], t_models.data_ptr(), keep[0].data_ptr(),
-            keep[1].data_ptr(), keep[2].data_ptr(), keep[3].data_ptr(), t_phot.data_ptr(),
-            t_err.data_ptr(), keep[4].data_ptr(), t_w.data_ptr(), keep[5].data_ptr(),
-            keep[6].data_ptr(), keep[7].data_ptr(), int(bool(dim_prior)), t_flux.data_ptr(),
-            t_cdf.data_ptr(), sp))
+        # the inputs in the order the call takes them
+        ins = [to_device(a, dt, dev) for a, dt in (
+            (models, np.float32), (idxs, np.int64), (reds, np.float64), (dreds, np.float64),
+            (dists, np.float64), (phot, np.float64), (err, np.float64), (mask, np.uint8),
+            (weights, np.float64), (old_offsets, np.float64), (use, np.uint8),
+            (mask_fit, np.uint8))]
+        t_phot = ins[5]
+        _lib.check(L.brutus_offsets_weights(Nobj, Nsamps, Nfilt, models.shape[0], *ins,
+                                            int(bool(dim_prior)), t_flux, t_cdf, sp))
         ratios, ratios_err = np.ones(Nfilt), np.zeros(Nfilt)
         nratio = np.zeros(Nfilt, dtype=int)
         sample = getattr(rstate, "random_sample", None) or rstate.random
@@ -500,11 +494,11 @@ def _photometric_offsets_device(phot, err, mask, models, idxs, reds, dreds, dist
             cdf_obj = wt_obj.cumsum()
             cdf_obj /= cdf_obj[-1]
             u = sample(2 * n * Nmc)         # round j: n object draws, then n model draws
-            t_u, t_s, t_co = up(u, np.float64), up(s, np.int32), up(cdf_obj, np.float64)
+            t_s, t_co = to_device(s, np.int32, dev), to_device(cdf_obj, np.float64, dev)
+            t_u = to_device(u, np.float64, dev)
             _lib.check(L.brutus_offsets_bootstrap(
-                b, Nobj, Nsamps, Nfilt, n, Nmc, t_s.data_ptr(), t_co.data_ptr(), t_u.data_ptr(),
-                t_flux.data_ptr(), t_cdf.data_ptr(), t_phot.data_ptr(), t_ws.data_ptr(),
-                t_ws.numel(), t_meds.data_ptr(), sp))
+                b, Nobj, Nsamps, Nfilt, n, Nmc, t_s, t_co, t_u, t_flux, t_cdf, t_phot, t_ws,
+                t_ws.numel(), t_meds, sp))
             meds = t_meds.cpu().numpy()
             ratios[b], ratios_err[b] = np.median(meds), np.std(meds)
     if verbose:
