@@ -34,6 +34,11 @@ k_po_flux(int nobj, int nsamps, int nfilt, int64_t nmodel, const float *__restri
           const uint8_t *__restrict__ mask, const double *__restrict__ old_off,
           const uint8_t *__restrict__ use, const uint8_t *__restrict__ mask_fit, int dim_prior,
           double *__restrict__ flux, double *__restrict__ lnl) {
+    // Every product below is rounded before it is added, as numpy rounds it (a fused
+    // `mag + Av rvec` moves `sed` by an ulp in a few per cent of the draws, the flux by 9 - 19).
+    // Plain operators under the pragma: HIP's __dmul_rn / __dadd_rn multiply and add inside the
+    // header, out of the pragma's reach, and are contracted into FMAs once inlined.
+#pragma clang fp contract(off)
     const int64_t t = (int64_t)blockIdx.x * PO_T + threadIdx.x;
     if (t >= (int64_t)nobj * nsamps) return;
     const int o = (int)(t / nsamps);
@@ -42,21 +47,20 @@ k_po_flux(int nobj, int nsamps, int nfilt, int64_t nmodel, const float *__restri
     i = i < 0 ? 0 : (i >= nmodel ? nmodel - 1 : i);
     const float *row = models + i * (3 * (int64_t)nfilt);
     const double av = reds[t], rv = dreds[t], d = dists[t];
-    const double d2 = __dmul_rn(d, d);
+    const double d2 = d * d;
     double term[NBMAX];
     bool on[NBMAX];
     for (int j = 0; j < nfilt; ++j) {
-        // utils.py:286-347: rvec = R0 + Rv dR, sed = mag + Av rvec (no contraction: the
-        // reference rounds every product)
-        const double rvec = __dadd_rn((double)row[3 * j + 1], __dmul_rn(rv, (double)row[3 * j + 2]));
-        const double sed = __dadd_rn((double)row[3 * j], __dmul_rn(av, rvec));
-        const double f = exp10(__dmul_rn(-0.4, sed)) / d2;
+        // utils.py:286-347: rvec = R0 + Rv dR, sed = mag + Av rvec
+        const double rvec = (double)row[3 * j + 1] + rv * (double)row[3 * j + 2];
+        const double sed = (double)row[3 * j] + av * rvec;
+        const double f = exp10(-0.4 * sed) / d2;
         flux[((int64_t)j * nobj + o) * nsamps + (t - (int64_t)o * nsamps)] = f;
         on[j] = mask[(int64_t)o * nfilt + j] != 0;
         const double off = old_off[j];
-        const double r = __dmul_rn(phot[(int64_t)o * nfilt + j], off) - f;
-        const double e = __dmul_rn(err[(int64_t)o * nfilt + j], off);
-        term[j] = on[j] ? __dmul_rn(r, r) / __dmul_rn(e, e) : 0.;
+        const double r = phot[(int64_t)o * nfilt + j] * off - f;
+        const double e = err[(int64_t)o * nfilt + j] * off;
+        term[j] = on[j] ? (r * r) / (e * e) : 0.;
     }
     for (int b = 0; b < nfilt; ++b) {
         if (!mask_fit[b] || !use[(int64_t)b * nobj + o]) continue;
@@ -64,7 +68,7 @@ k_po_flux(int nobj, int nsamps, int nfilt, int64_t nmodel, const float *__restri
         int ndim = 0;
         for (int j = 0; j < nfilt; ++j)
             if (j != b && on[j]) {
-                chi2 = __dadd_rn(chi2, term[j]);
+                chi2 = chi2 + term[j];
                 ++ndim;
             }
         // utils.py:1203-1213 without the terms that are the same for every draw of the
@@ -78,6 +82,30 @@ k_po_flux(int nobj, int nsamps, int nfilt, int64_t nmodel, const float *__restri
     }
 }
 
+// Running maximum over a workgroup of PO_T threads of values >= 0 (so 0 is the neutral element);
+// `slot` is LDS scratch of PO_T / 64 values, `total` the maximum over the workgroup.  A NaN stays
+// where it is and is not carried on.
+__device__ __forceinline__ double po_running_max(double v, double *slot, double &total) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const double o = __shfl_up(v, off, 64);
+        if (lane >= off && o > v) v = o;
+    }
+    __syncthreads();                       // (slot free: everybody is past the previous use)
+    if (lane == 63) slot[w] = v;
+    __syncthreads();
+    double pre = 0., tot = 0.;
+#pragma unroll
+    for (int q = 0; q < PO_T / 64; ++q) {
+        const double x = slot[q];
+        if (q < w && x > pre) pre = x;
+        if (x > tot) tot = x;
+    }
+    total = tot;
+    return pre > v ? pre : v;
+}
+
 // In place: lnl (band, object, :) -> cumulative weights, last entry exactly 1
 // (utils.py:1358-1370: exp(lnl - logsumexp) * weights, normalised; `choice` then
 // searches cumsum(p) / cumsum(p)[-1]).
@@ -86,6 +114,7 @@ k_po_cdf(int nobj, int nsamps, const double *__restrict__ weights,
          const uint8_t *__restrict__ use, const uint8_t *__restrict__ mask_fit,
          double *__restrict__ cdf) {
     __shared__ double s_slot[PO_T / 64 + 1];
+    __shared__ double s_mslot[PO_T / 64];
     __shared__ double s_red[PO_T / 64];
     __shared__ double s_bc;
     const int o = blockIdx.x, b = blockIdx.y;
@@ -111,18 +140,27 @@ k_po_cdf(int nobj, int nsamps, const double *__restrict__ weights,
         mx = s_bc;
         if (!(mx > -INFINITY)) mx = 0.;
     }
-    double carry = 0.;
+    // The parallel sum groups the terms of neighbouring lanes differently, so where a draw has
+    // no weight its entry can come out an ulp BELOW the one before it; the searches of k_po_boot
+    // (and numpy's searchsorted) need a non-decreasing row, and a draw without weight must keep
+    // an entry equal to its predecessor's so that it is never taken.  Hence the running maximum
+    // over the sums; the row is divided by its own last entry, which is then exactly 1.
+    double carry = 0., top = 0.;
     for (int k0 = 0; k0 < nsamps; k0 += PO_T) {
         const int k = k0 + threadIdx.x;
         double v = 0.;
         if (k < nsamps) v = fit ? exp(row[k] - mx) * w[k] : w[k];
-        double tot;
+        double tot, mtot;
         const double inc = block_inclusive_sum<double, PO_T>(v, s_slot, tot);
-        if (k < nsamps) row[k] = carry + inc;
+        const double run = po_running_max(k < nsamps ? carry + inc : 0., s_mslot, mtot);
+        if (k < nsamps) row[k] = top > run ? top : run;
         carry += tot;
+        top = mtot > top ? mtot : top;
     }
     __syncthreads();
-    for (int k = threadIdx.x; k < nsamps; k += PO_T) row[k] = row[k] / carry;
+    // (a NaN among the sums reaches `carry`, not `top`: the whole row is NaN then, as before)
+    const double last = carry != carry ? carry : top;
+    for (int k = threadIdx.x; k < nsamps; k += PO_T) row[k] = row[k] / last;
 }
 
 // count of entries <= u in a non-decreasing array (numpy searchsorted(side='right'))

@@ -1223,6 +1223,81 @@ def gen_los():
         (m["name"] + "/" + m["kernel"], v) for m, v in zip(meta, etot))))
 
 
+PO_INPUTS = ("phot", "err", "mask", "models", "idxs", "reds", "dreds", "dists", "sel", "weights",
+             "mask_fit")
+
+
+def gen_consumers():
+    """The `po_*` arrays of tests/golden/consumers.npz: `utils.photometric_offsets` (utils.py:
+    1218-1400) with Nmc = 20, RandomState(5) and a 5 per cent prior around 1.  The inputs were
+    drawn once and their seeds were not kept, so they are read back from the file; the three
+    outputs are recomputed from them.  The file is rewritten only if an output differs by a
+    bit (it does not: the run then says so and leaves the file as it is)."""
+    path = os.path.join(OUT, "consumers.npz")
+    with np.load(path) as z:
+        old = {k: z[k] for k in z.files}
+    kw = {k: old["po_" + k].copy() for k in PO_INPUTS}
+    kw["models"] = kw["models"].astype(np.float64)
+    r, re_, n = U.photometric_offsets(
+        Nmc=20, old_offsets=old["po_old"].copy(), prior_mean=np.ones(6),
+        prior_std=np.full(6, 0.05), verbose=False, rstate=np.random.RandomState(5), **kw)
+    new = dict(old, po_ratios=r, po_ratios_err=re_, po_nratio=n)
+    if all(np.array_equal(new[k], old[k]) and new[k].dtype == old[k].dtype for k in new):
+        print("consumers.npz: po_ratios, po_ratios_err, po_nratio reproduced bit for bit; "
+              "file left as it is")
+        return
+    np.savez_compressed(path, **new)
+    print("wrote consumers.npz (po_* outputs changed)")
+
+
+def gen_offsets_edges():
+    """tests/golden/offsets_edges.npz: `utils.photometric_offsets` where consumers.npz does
+    not go -- 40 objects x 20 draws x 6 bands; the -99 sentinel index on draws of zero weight;
+    band 2 outside the fit; band 5 observed for one qualifying object only; negative fluxes
+    in observed bands; an object without weight and a deselected one; both `dim_prior`.
+    (The reference's `choice` refuses NaN probabilities: no NaN case here.)"""
+    rng = np.random.RandomState(61)
+    nobj, nsamps, nfilt, nmodel, nmc, seed = 40, 20, 6, 150, 15, 17
+    models = np.empty((nmodel, nfilt, 3), dtype=np.float32)
+    models[:, :, 0] = rng.uniform(12., 16., nfilt)[None, :] + 0.002 * np.arange(nmodel)[:, None]
+    models[:, :, 1] = rng.uniform(0.5, 3., nfilt)[None, :] + 1e-3 * rng.normal(size=(nmodel, nfilt))
+    models[:, :, 2] = rng.uniform(0., 0.3, nfilt)[None, :] + 1e-4 * rng.normal(size=(nmodel, nfilt))
+    idxs = rng.randint(20, 130, (nobj, 1)) + rng.randint(-4, 5, (nobj, nsamps))
+    reds, dreds = rng.uniform(0., 1., (nobj, nsamps)), rng.uniform(3., 3.6, (nobj, nsamps))
+    dists = rng.uniform(0.5, 3., (nobj, 1)) * (1. + 0.01 * rng.normal(size=(nobj, nsamps)))
+    f0 = np.stack([star_from_model(models, idxs[o, 0], reds[o, 0], dreds[o, 0], dists[o, 0],
+                                   0.05, rng, noise=False)[0] for o in range(nobj)])
+    phot = f0 * (1. + 0.05 * rng.normal(size=f0.shape))
+    err = 0.05 * np.abs(phot)
+    neg = rng.uniform(size=phot.shape) < 0.1
+    phot[neg], err[neg] = -0.3 * f0[neg], 0.5 * f0[neg]
+    mask = rng.uniform(size=phot.shape) > 0.12
+    mask[:, 5] = False
+    mask[7, :] = True                       # the one object of band 5
+    weights = rng.uniform(0.1, 1., (nobj, nsamps))
+    gone = rng.uniform(size=weights.shape) < 0.15
+    gone[:, 0] = False
+    weights[gone], idxs[gone] = 0., -99
+    weights[11] = 0.
+    sel = np.ones(nobj, dtype=bool)
+    sel[19] = False
+    mask_fit = np.array([1, 1, 0, 1, 1, 1], dtype=bool)
+    old = np.linspace(0.97, 1.03, nfilt)
+    res = dict(phot=phot, err=err, mask=mask, models=models, idxs=idxs, reds=reds, dreds=dreds,
+               dists=dists, sel=sel, weights=weights, mask_fit=mask_fit, old_offsets=old,
+               nmc=nmc, seed=seed)
+    for d in (0, 1):
+        r, re_, n = U.photometric_offsets(
+            phot.copy(), err.copy(), mask.copy(), models.astype(np.float64), idxs.copy(),
+            reds.copy(), dreds.copy(), dists.copy(), sel=sel.copy(), weights=weights.copy(),
+            mask_fit=mask_fit.copy(), Nmc=nmc, old_offsets=old.copy(), dim_prior=bool(d),
+            verbose=False, rstate=np.random.RandomState(seed))
+        assert n[5] == 1 and np.all(np.isfinite(r)) and np.all(np.isfinite(re_))
+        res["ratios_%d" % d], res["ratios_err_%d" % d], res["nratio_%d" % d] = r, re_, n
+    np.savez_compressed(os.path.join(OUT, "offsets_edges.npz"), **res)
+    print("wrote offsets_edges.npz: nratio", res["nratio_1"], "ratios", res["ratios_1"])
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     which = sys.argv[1:] or ["loglike", "fit", "helpers", "setup", "galprior",
@@ -1271,4 +1346,8 @@ if __name__ == "__main__":
         gen_fresh()
     if "los" in which:
         gen_los()
+    if "consumers" in which:
+        gen_consumers()
+    if "offsets_edges" in which:
+        gen_offsets_edges()
 
