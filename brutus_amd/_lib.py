@@ -276,6 +276,19 @@ SIGNATURES = {
                                      C.POINTER(LosParams), _df64, _df64, _dv, _sz, _stream]),
 }
 
+# the same for include/brutus_amd_batch.h (K thetas per call; tests/test_cluster_batch_host.py
+# compares this table with that header parameter by parameter)
+BATCH_SIGNATURES = {
+    "brutus_iso_batch_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32, _i32]),
+    "brutus_iso_seds_grid_batch": (C.c_int, [C.POINTER(IsoParams), _i32, _df64, _df64, _df64, _df64,
+                                             _df64, _df64, _df64, _df64, _df64, _df64, _di32, _dv, _sz,
+                                             _stream]),
+    "brutus_cluster_batch_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32, _i32]),
+    "brutus_cluster_lnl_batch": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _df64, _df64, _df64, _df64,
+                                           _dbl, _df64, _df64, _di32, _df64, _df64, _df64, _di32,
+                                           _df64, _i32, _df64, _dv, _sz, _df64, _df64, _stream]),
+}
+
 
 def lib():
     """Load (once) and return the shared library; raise loudly if absent."""
@@ -293,7 +306,7 @@ def lib():
     # runtime then finds "no ROCm-capable device".
     import torch  # noqa: F401
     L = C.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(BATCH_SIGNATURES.items()):
         fn = getattr(L, name)   # AttributeError if the .so is stale
         fn.restype = res
         fn.argtypes = args

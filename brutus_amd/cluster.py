@@ -11,6 +11,7 @@ marginalisation over mass and mass fraction (cluster.py:379-407) -- runs in the
 HIP kernel `k_cluster` through `brutus_cluster_lnl`.
 """
 import collections
+import ctypes as C
 import threading
 import warnings
 
@@ -19,7 +20,7 @@ import numpy as np
 from . import _lib
 from ._dev import _stream_ptr, _torch, to_device
 
-__all__ = ["isochrone_loglike"]
+__all__ = ["isochrone_loglike", "IsochroneLikelihood", "unpack_thetas"]
 
 _DEFAULT_SMF = (0., 0.2, 0.35, 0.45, 0.5, 0.55, 0.6, 0.65, 0.7, 0.75, 0.8,
                 0.85, 0.9, 0.95, 1.0)
@@ -133,45 +134,9 @@ def _isochrone_loglike(theta, isochrone, phot, err, cluster_params, offsets, cor
     offers `get_seds_grid_device(smf_grid=, out=, ...same keywords...) -> mini (Neep,)`
     (`seds.Isochrone`) is asked once instead, for all mass fractions, and fills the device tensor
     `out (Nsmf, Neep, Nbands)` the sum reads: its magnitudes never visit the host."""
-    from scipy.stats import chi2 as chisquare
-    if phot is None:
-        raise ValueError("The photometry must be provided to compute the "
-                         "log-likelihood!")
-    if err is None:
-        raise ValueError("The errors on the photometry must be provided to "
-                         "compute the log-likelihood!")
-    phot = np.asarray(phot, dtype=np.float64)
-    err = np.asarray(err, dtype=np.float64)
+    phot, err, smf_grid, grad_smf, eep_grid = _checked(
+        phot, err, cluster_params, offsets, corr_params, smf_grid, eep_grid, parallax, parallax_err)
     Nobjs, Nbands = phot.shape
-    if smf_grid is None:            # (copies: the plug-in is handed slices of it)
-        smf_grid, grad_smf = _DEFAULT_SMF_ARR.copy(), _DEFAULT_SMF_GRAD.copy()
-    else:
-        smf_grid = np.asarray(smf_grid, float)
-        grad_smf = np.gradient(smf_grid) if len(smf_grid) > 1 else np.array([1.])
-    if eep_grid is None:
-        eep_grid = np.linspace(202., 808., 2000)
-    eep_grid = np.asarray(eep_grid, dtype=np.float64)
-    free_str = lambda v: isinstance(v, str) and v == 'free'
-    if parallax is None and parallax_err is None:          # cluster.py:200-208
-        if free_str(offsets) and (free_str(cluster_params)
-                                  or cluster_params[4] is None):
-            raise ValueError("Without any measured parallaxes, there is a "
-                             "degeneracy between the photometry offsets "
-                             "and the distance. Please provide either a "
-                             "distance value in `cluster_params` or at "
-                             "least one offset in `offsets`.")
-    if not (isinstance(corr_params, str) and corr_params == 'fixed'):
-        if ((corr_params[0] is None or corr_params[1] is None)
-                and corr_params[3] is None):               # cluster.py:212-217
-            raise ValueError("If `feh_scale` is not provided, then `dtdm` and "
-                             "`drdm` must be fixed since the parameters are "
-                             "perfectly degenerate.")
-    if parallax is None and parallax_err is not None:
-        raise ValueError("You forgot to provide the parallaxes to go along "
-                         "with the errors!")
-    if parallax is not None and parallax_err is None:
-        raise ValueError("You forgot to provide the parallax errors to go "
-                         "along with the parallaxes!")
 
     _mark("checked")
     # ---- unpack theta (cluster.py:227-290) ------------------------------------
@@ -277,6 +242,50 @@ def _isochrone_loglike(theta, isochrone, phot, err, cluster_params, offsets, cor
     if return_lnls:
         return lnl_tot, lnl_mix
     return lnl_tot
+
+
+def _checked(phot, err, cluster_params, offsets, corr_params, smf_grid, eep_grid, parallax,
+             parallax_err):
+    """The argument checks of reference cluster.py:183-223 and the default grids:
+    `(phot, err, smf_grid, grad_smf, eep_grid)` as float64 arrays."""
+    if phot is None:
+        raise ValueError("The photometry must be provided to compute the "
+                         "log-likelihood!")
+    if err is None:
+        raise ValueError("The errors on the photometry must be provided to "
+                         "compute the log-likelihood!")
+    phot = np.asarray(phot, dtype=np.float64)
+    err = np.asarray(err, dtype=np.float64)
+    if smf_grid is None:            # (copies: the plug-in is handed slices of it)
+        smf_grid, grad_smf = _DEFAULT_SMF_ARR.copy(), _DEFAULT_SMF_GRAD.copy()
+    else:
+        smf_grid = np.asarray(smf_grid, float)
+        grad_smf = np.gradient(smf_grid) if len(smf_grid) > 1 else np.array([1.])
+    if eep_grid is None:
+        eep_grid = np.linspace(202., 808., 2000)
+    eep_grid = np.asarray(eep_grid, dtype=np.float64)
+    free_str = lambda v: isinstance(v, str) and v == 'free'
+    if parallax is None and parallax_err is None:          # cluster.py:200-208
+        if free_str(offsets) and (free_str(cluster_params)
+                                  or cluster_params[4] is None):
+            raise ValueError("Without any measured parallaxes, there is a "
+                             "degeneracy between the photometry offsets "
+                             "and the distance. Please provide either a "
+                             "distance value in `cluster_params` or at "
+                             "least one offset in `offsets`.")
+    if not (isinstance(corr_params, str) and corr_params == 'fixed'):
+        if ((corr_params[0] is None or corr_params[1] is None)
+                and corr_params[3] is None):               # cluster.py:212-217
+            raise ValueError("If `feh_scale` is not provided, then `dtdm` and "
+                             "`drdm` must be fixed since the parameters are "
+                             "perfectly degenerate.")
+    if parallax is None and parallax_err is not None:
+        raise ValueError("You forgot to provide the parallaxes to go along "
+                         "with the errors!")
+    if parallax is not None and parallax_err is None:
+        raise ValueError("You forgot to provide the parallax errors to go "
+                         "along with the parallaxes!")
+    return phot, err, smf_grid, grad_smf, eep_grid
 
 
 class _Dataset(object):
@@ -624,3 +633,261 @@ def _point_table(isochrone, feh, loga, av, rv, dist, corr_coef, smf_grid, grad_s
     if cache:      # (the plug-in object is kept alive with its tables: `id` stays unique)
         _lru_put(_TABLE_CACHE, key, (tab, isochrone), _TABLE_CACHE_MAX)
     return tab, nchunk
+
+
+# ---- many thetas per call: the catalogue resident on the device ----------------------------------
+def unpack_thetas(thetas, cluster_params, offsets, corr_params, nbands):
+    """Rows of `thetas (K, Ncol)` unpacked as `_isochrone_loglike` unpacks one `theta`:
+    `(cp (K, 6), Xb (K, nbands), corr (K, 4) or None)` with `cp` = `(feh, loga, av, rv, dist,
+    fout)`, `fout` clipped to `[1e-10, 1 - 1e-10]`.  A group declared `'fixed'` (offsets: ones,
+    corrections: None, the plug-in's defaults) still takes its columns' places, so the groups
+    after it are read past them.  `Ncol` must be the place after the last value that is read."""
+    thetas = np.asarray(thetas, dtype=np.float64)
+    if thetas.ndim != 2:
+        raise ValueError("`thetas` must have shape (K, Nparams); got %s" % (thetas.shape,))
+    fixed = lambda v: isinstance(v, str) and v == 'fixed'
+    K = thetas.shape[0]
+    groups = [(cluster_params, 6)]
+    groups.append((None, nbands) if fixed(offsets) else (offsets, nbands))
+    groups.append((None, 4) if fixed(corr_params) else (corr_params, 4))
+    # the place of every value that is read, and the place after the last of them
+    pos, need, cols = 0, 0, []
+    for spec, n in groups:
+        col = [None] * n
+        if spec is None:
+            pos += n
+        else:
+            for i in range(n):
+                if (isinstance(spec, str) and spec == 'free') or spec[i] is None:
+                    col[i] = pos
+                    pos += 1
+                    need = pos
+        cols.append(col)
+    if thetas.shape[1] != need:
+        raise ValueError("`thetas` must have %d columns for these `cluster_params`, `offsets` and "
+                         "`corr_params` (%d given)" % (need, thetas.shape[1]))
+
+    def take(spec, col, n):
+        out = np.empty((K, n))
+        for i in range(n):
+            out[:, i] = thetas[:, col[i]] if col[i] is not None else spec[i]
+        return out
+    cp = take(cluster_params, cols[0], 6)
+    cp[:, 5] = np.maximum(np.minimum(1. - 1e-10, cp[:, 5]), 1e-10)
+    Xb = np.ones((K, nbands)) if fixed(offsets) else take(offsets, cols[1], nbands)
+    corr = None if fixed(corr_params) else take(corr_params, cols[2], 4)
+    return cp, Xb, corr
+
+
+_BATCH_BYTES = 1 << 30        # device memory of one pass of IsochroneLikelihood (default max_batch)
+
+
+def _log10(x):
+    """The C library's log10, NaN / -inf where it has them (the library forms the distance modulus
+    of the single call with it)."""
+    import math
+    return math.log10(x) if x > 0. else (-np.inf if x == 0. else np.nan)
+
+
+_ISO_NTH, _OBJ_NTH = 10, 3    # values per theta of brutus_iso_seds_grid_batch / brutus_cluster_lnl_batch
+
+
+class IsochroneLikelihood(object):
+    """`isochrone_loglike` of one catalogue on the device, callable with many `theta` at once.
+
+    `L = IsochroneLikelihood(isochrone, phot, err, ...)` takes the arguments of
+    `isochrone_loglike` (same defaults and meaning; `afe` stays at the plug-in's default), raises
+    its argument errors, and computes what depends on the catalogue alone once.  `L(theta)` is
+    `isochrone_loglike(theta, isochrone, phot, err, ...)`: a float for `theta` of shape
+    `(Nparams,)`, a `(K,)` float64 array for `(K, Nparams)` -- a sampler's walkers or live
+    points.  `L.terms(theta)` returns `(lnl_tot, lnl_mix)` with the per-object values `(Nobj,)`
+    / `(K, Nobj)`.  The value of a row does not depend on the other rows, their number or its
+    place among them, and the same call gives the same bytes.
+
+        L = cluster.IsochroneLikelihood(iso, phot, err, parallax=par, parallax_err=perr)
+        sampler = emcee.EnsembleSampler(nwalkers, ndim, L, vectorize=True)
+
+    `isochrone` must be a `seds.Isochrone`: isochrones, weights, kept rows, the sum and the
+    outlier mixture of a pass of `max_batch` thetas (default: what fits 1 GiB of device memory)
+    run on the device without a visit to the host in between.  A theta whose initial masses do
+    not increase with EEP is recomputed with `isochrone_loglike` (its secondaries need
+    `np.interp`); `L.fallback_rows` counts those of the last call.  There is no host fallback:
+    without the library or a GPU the constructor raises `BrutusError`."""
+
+    def __init__(self, isochrone, phot, err, cluster_params='free', offsets='fixed',
+                 corr_params='fixed', mini_bound=0.08, eep_binary_max=480., smf_grid=None,
+                 eep_grid=None, parallax=None, parallax_err=None, cluster_prob=0.95,
+                 dim_prior=True, device="cuda", max_batch=None):
+        from . import seds
+        if not isinstance(isochrone, seds.Isochrone):
+            raise TypeError("IsochroneLikelihood needs a seds.Isochrone (it owns the device table "
+                            "and networks); use isochrone_loglike with any other plug-in")
+        phot, err, smf_grid, grad_smf, eep_grid = _checked(
+            phot, err, cluster_params, offsets, corr_params, smf_grid, eep_grid, parallax,
+            parallax_err)
+        # (copies: the object outlives the caller's arrays being edited)
+        phot, err, smf_grid, eep_grid = phot.copy(), err.copy(), smf_grid.copy(), eep_grid.copy()
+        if eep_grid.ndim != 1 or len(eep_grid) < 2:
+            raise ValueError("`eep_grid` needs two EEPs or more: the weights are the gradient of "
+                             "the initial masses along it")
+        import torch
+        if torch.device(device).type != "cuda":
+            raise ValueError("IsochroneLikelihood needs a GPU device; got %r" % (device,))
+        self._par = None if parallax is None else np.array(parallax, dtype=np.float64)
+        self._perr = None if parallax_err is None else np.array(parallax_err, dtype=np.float64)
+        self.dim_prior = bool(dim_prior)
+        # ---- what the catalogue alone decides (cluster.py:292-325), once: the data check, then
+        # BrutusError without the library or a GPU -----------------------------------------------
+        with _LOCK:
+            ds = self._ds = _dataset(phot, err, self._par, self._perr, self.dim_prior, device, False)
+        self._L, self._torch = L, torch = _lib.lib(), _torch()
+        dev = ds.dev
+        if dev.index is None:
+            dev = torch.device("cuda:%d" % torch.cuda.current_device())
+        self.device = dev
+        self.isochrone = isochrone
+        self.cluster_params, self.offsets, self.corr_params = cluster_params, offsets, corr_params
+        self.mini_bound, self.eep_binary_max = float(mini_bound), float(eep_binary_max)
+        self.cluster_prob = cluster_prob
+        self.smf_grid, self.eep_grid = smf_grid, eep_grid
+        self._phot, self._err = phot, err
+        self.nobj, self.nbands = phot.shape
+        if self.nbands != isochrone.NFILT:
+            raise ValueError("the photometry has %d bands, the isochrone %d filters"
+                             % (self.nbands, isochrone.NFILT))
+        self.fallback_rows = 0
+        self._corr_default = seds._CORR_DEFAULT
+        nsmf, neep, nb, nobj = len(smf_grid), len(eep_grid), self.nbands, self.nobj
+        if L.brutus_cluster_batch_workspace_bytes(1, nobj, nb, nsmf, neep) == 0:
+            raise ValueError("the device form takes at most %d bands and %d x %d x %d isochrone "
+                             "magnitudes below 2^31" % (_lib.MAX_FILT_FIT, nsmf, neep, nb))
+        with torch.cuda.device(dev), np.errstate(all="ignore"):
+            errmask = np.zeros(nobj, dtype=np.int64)
+            for b in range(nb):         # (a band with an error enters the ln-normalisation)
+                errmask |= (~np.isnan(err[:, b])).astype(np.int64) << b
+            zeros = np.zeros(nobj)
+            self._t_cat = [
+                ds.t_d, ds.t_iv, to_device(errmask.astype(np.uint32).view(np.int32), np.int32, dev),
+                to_device(ds.par0 if ds.pmask is not None else zeros, np.float64, dev),
+                to_device(ds.ivar0 if ds.pmask is not None else zeros, np.float64, dev),
+                ds.t_ln0, ds.t_n, ds.t_lo]
+            self._t_eep = to_device(eep_grid, np.float64, dev)
+            self._t_smf = to_device(smf_grid, np.float64, dev)
+            self._t_lnsmf = to_device(np.log(grad_smf), np.float64, dev)
+        self._iso_dev = isochrone._device(dev)[0]
+        self._p = isochrone._params(neep, nsmf, _lib.ISO_APPLY_CORR, 0., 0., 0., 0., 0., 1.,
+                                    self.mini_bound, self.eep_binary_max, None)
+        npred = int(isochrone.grid_dims[4])
+        self._sizes = lambda k: (
+            int(L.brutus_iso_batch_workspace_bytes(k, neep, nsmf, nb, npred)),
+            int(L.brutus_cluster_batch_workspace_bytes(k, nobj, nb, nsmf, neep)))
+        # device memory per theta: the two workspaces (predictions of the secondaries, kept rows,
+        # partial sums, ...) by the library's own count, the magnitudes, the masses, the results
+        two, one = self._sizes(2), self._sizes(1)
+        self.bytes_per_theta = (two[0] - one[0] + two[1] - one[1]
+                                + 8 * (nsmf * neep * nb + neep + 2 + nobj + _ISO_NTH + _OBJ_NTH + nb))
+        if max_batch is None:
+            max_batch = _BATCH_BYTES // self.bytes_per_theta
+        self.max_batch = int(max(1, min(int(max_batch), 65535)))
+        self._cap = 0
+
+    def _buffers(self, k):
+        """The buffers of a pass of `k` thetas; they grow, and are otherwise kept."""
+        if k > self._cap:
+            torch, dev = self._torch, self.device
+            nsmf, neep, nb, nobj = len(self.smf_grid), len(self.eep_grid), self.nbands, self.nobj
+            f64 = lambda *s: torch.empty(s, dtype=torch.float64, device=dev)
+            nth = _ISO_NTH + _OBJ_NTH + nb
+            self._mags, self._mini = f64(k, nsmf, neep, nb), f64(k, neep)
+            self._theta, self._h_theta = f64(k * nth), torch.empty(k * nth, dtype=torch.float64).pin_memory()
+            # [totals (k) | status (k, 2) int32 | per-object values (k, nobj)]: one copy back
+            self._res = f64(k * (2 + nobj))
+            self._h_res = torch.empty(k * (2 + nobj), dtype=torch.float64).pin_memory()
+            b_iso, b_cl = self._sizes(k)
+            self._ws_iso = torch.empty(b_iso, dtype=torch.uint8, device=dev)
+            self._ws_cl = torch.empty(b_cl, dtype=torch.uint8, device=dev)
+            self._cap = k
+        return self._cap
+
+    def _pass(self, cp, Xb, corr, want_terms):
+        """One device pass: `(totals (k,), per-object values (k, Nobj) or None, status (k, 2))`."""
+        torch, L, d = self._torch, self._L, self._iso_dev
+        k, nb, nobj = cp.shape[0], self.nbands, self.nobj
+        nsmf, neep = len(self.smf_grid), len(self.eep_grid)
+        cap = self._buffers(k)
+        h = self._h_theta.numpy()
+        iso_th = h[:k * _ISO_NTH].reshape(k, _ISO_NTH)
+        obj_th = h[cap * _ISO_NTH:cap * _ISO_NTH + k * (_OBJ_NTH + nb)].reshape(k, _OBJ_NTH + nb)
+        iso_th[:, 0], iso_th[:, 1], iso_th[:, 2:5] = cp[:, 0], 0., cp[:, 1:4]       # afe: the default
+        iso_th[:, 6:] = self._corr_default if corr is None else corr
+        obj_th[:, 0] = 1e3 / cp[:, 4]
+        for j in range(k):      # (row by row, as the single call takes them: the same bits)
+            fout = float(cp[j, 5])
+            with np.errstate(all="ignore"):         # (a distance <= 0: NaN, as in the single call)
+                iso_th[j, 5] = 5. * _log10(float(cp[j, 4])) - 5.
+            obj_th[j, 1] = np.log(self.cluster_prob * (1. - fout))
+            obj_th[j, 2] = np.log(1. - self.cluster_prob * (1. - fout))
+        obj_th[:, _OBJ_NTH:] = Xb
+        n_iso, n_obj = cap * _ISO_NTH, k * (_OBJ_NTH + nb)
+        t_iso, t_obj = self._theta[:k * _ISO_NTH], self._theta[n_iso:n_iso + n_obj]
+        res = self._res[:k * (2 + nobj) if want_terms else 2 * k]
+        t_tot, t_status = res[:k], res[k:2 * k].view(torch.int32)
+        t_mix = res[2 * k:] if want_terms else None
+        stream = _stream_ptr(torch)
+        self._theta[:n_iso + n_obj].copy_(self._h_theta[:n_iso + n_obj], non_blocking=True)
+        _lib.check(L.brutus_iso_seds_grid_batch(
+            C.byref(self._p), k, t_iso, *d.p_tab, self._t_eep, self._t_smf, self._mags, self._mini,
+            t_status, self._ws_iso, self._ws_iso.numel(), stream))
+        _lib.check(L.brutus_cluster_lnl_batch(
+            k, nobj, nb, nsmf, neep, self._mags, self._mini, self._t_eep, self._t_lnsmf,
+            self.eep_binary_max, *self._t_cat, 1 if self.dim_prior else 0, t_obj, self._ws_cl,
+            self._ws_cl.numel(), t_tot, t_mix, stream))
+        h_res = self._h_res[:res.numel()]
+        h_res.copy_(res, non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+        out = h_res.numpy()
+        return (out[:k].copy(), out[2 * k:].reshape(k, nobj).copy() if want_terms else None,
+                out[k:2 * k].view(np.int32).reshape(k, 2).copy())
+
+    def _eval(self, theta, want_terms):
+        th = np.asarray(theta, dtype=np.float64)
+        single = th.ndim == 1
+        th = np.ascontiguousarray(np.atleast_2d(th))
+        cp, Xb, corr = unpack_thetas(th, self.cluster_params, self.offsets, self.corr_params,
+                                     self.nbands)
+        K = th.shape[0]
+        tot = np.empty(K)
+        mix = np.empty((K, self.nobj)) if want_terms else None
+        # (np.interp only matters where a slice has a secondary of its own)
+        binaries = bool(np.any((self.smf_grid > 0.) & (self.smf_grid < 1.)))
+        self.fallback_rows = 0
+        with _LOCK, self._torch.cuda.device(self.device):
+            for a in range(0, K, self.max_batch):
+                b = min(K, a + self.max_batch)
+                tot[a:b], m, status = self._pass(cp[a:b], Xb[a:b],
+                                                 None if corr is None else corr[a:b], want_terms)
+                if want_terms:
+                    mix[a:b] = m
+                for j in (np.flatnonzero(status[:, 0]) if binaries else ()):
+                    # masses that do not increase with EEP: the secondaries' EEPs are np.interp's
+                    r = isochrone_loglike(
+                        th[a + j], self.isochrone, self._phot, self._err, self.cluster_params,
+                        self.offsets, self.corr_params, self.mini_bound, self.eep_binary_max,
+                        self.smf_grid, self.eep_grid, self._par, self._perr, self.cluster_prob,
+                        self.dim_prior, return_lnls=want_terms, device=self.device, cache=False)
+                    if want_terms:
+                        tot[a + j], mix[a + j] = r
+                    else:
+                        tot[a + j] = r
+                    self.fallback_rows += 1
+        if single:
+            return (float(tot[0]), mix[0]) if want_terms else float(tot[0])
+        return (tot, mix) if want_terms else tot
+
+    def __call__(self, theta):
+        return self._eval(theta, False)
+
+    def terms(self, theta):
+        """`(lnl_tot, lnl_mix)`: the per-object values after the outlier mixture, `(Nobj,)` or
+        `(K, Nobj)`; `lnl_tot` is the value of `L(theta)`."""
+        return self._eval(theta, True)

@@ -163,6 +163,108 @@ int brutus_cluster_points_grid(int64_t npts, int nfilt, int neep, const int32_t 
     return 0;
 }
 
+// ---- K thetas in one call (cluster.IsochroneLikelihood) -----------------------------------------
+extern "C++" {
+namespace {
+// what a theta of a batch keeps between the kernels, each array (K, ...):
+// [ln w_eep | kept rows | their number | partial maxima | partial sums | lnl before the mixture]
+struct ClusterBatchWs {
+    double *lnw_eep, *part_m, *part_s, *lnl;
+    int32_t *src, *cnt;
+    size_t bytes;
+};
+static void carve_cluster_batch(char *base, size_t k, int nobj, int nsmf, int neep, ClusterBatchWs &w) {
+    Carver cv(base);
+    const size_t d = sizeof(double), nrow = (size_t)nsmf * neep;
+    w.lnw_eep = (double *)cv.take(d * k * neep);
+    w.src = (int32_t *)cv.take(sizeof(int32_t) * k * nrow);
+    w.cnt = (int32_t *)cv.take(sizeof(int32_t) * k);
+    w.part_m = (double *)cv.take(d * k * CLB_CHUNKS * nobj);
+    w.part_s = (double *)cv.take(d * k * CLB_CHUNKS * nobj);
+    w.lnl = (double *)cv.take(d * k * nobj);
+    w.bytes = cv.off;
+}
+// (neep >= 2: np.gradient needs two masses; the table rows of a theta are indexed by an int)
+static bool cluster_batch_dims_ok(int ntheta, int nobj, int nfilt, int nsmf, int neep) {
+    return ntheta >= 1 && ntheta <= BRUTUS_CLUSTER_MAX_THETA && nobj >= 1 && nfilt >= 1 &&
+           nfilt <= BRUTUS_MAX_FILT_FIT && nsmf >= 1 && neep >= 2 &&
+           (int64_t)nsmf * neep * (int64_t)nfilt < ((int64_t)1 << 31);
+}
+}  // namespace
+}  // extern "C++"
+
+size_t brutus_cluster_batch_workspace_bytes(int ntheta, int nobj, int nfilt, int nsmf, int neep) {
+    if (!cluster_batch_dims_ok(ntheta, nobj, nfilt, nsmf, neep)) return 0;
+    ClusterBatchWs w;
+    carve_cluster_batch(nullptr, (size_t)ntheta, nobj, nsmf, neep, w);
+    return w.bytes;
+}
+
+int brutus_cluster_lnl_batch(int ntheta, int nobj, int nfilt, int nsmf, int neep, const double *d_mags,
+                             const double *d_mini, const double *d_eep, const double *d_lnw_smf,
+                             double eep_binary_max, const double *d_phot, const double *d_ivar,
+                             const int32_t *d_errmask, const double *d_par, const double *d_par_ivar,
+                             const double *d_lnorm0, const int32_t *d_ndim,
+                             const double *d_lnl_outlier, int dim_prior, const double *d_obj_theta,
+                             void *d_workspace, size_t workspace_bytes, double *d_lnl_tot,
+                             double *d_lnl_mix, void *stream) {
+    if (nfilt > BRUTUS_MAX_FILT_FIT)
+        return fail(BRUTUS_EINVAL, "cluster likelihood: at most %d bands (%d given)", BRUTUS_MAX_FILT_FIT, nfilt);
+    if (!cluster_batch_dims_ok(ntheta, nobj, nfilt, nsmf, neep))
+        return fail(BRUTUS_EINVAL,
+                    "bad cluster batch dimensions (ntheta=%d, at most %d; nobj=%d, nfilt=%d, nsmf=%d, neep=%d, "
+                    "at least 2)", ntheta, BRUTUS_CLUSTER_MAX_THETA, nobj, nfilt, nsmf, neep);
+    if (!d_mags || !d_mini || !d_eep || !d_lnw_smf || !d_phot || !d_ivar || !d_errmask || !d_par || !d_par_ivar ||
+        !d_lnorm0 || !d_ndim || !d_lnl_outlier || !d_obj_theta || !d_workspace || !d_lnl_tot)
+        return fail(BRUTUS_EINVAL, "NULL device pointer");
+    if (workspace_bytes < brutus_cluster_batch_workspace_bytes(ntheta, nobj, nfilt, nsmf, neep))
+        return fail(BRUTUS_ENOMEM, "cluster batch workspace too small");
+    const unsigned K = (unsigned)ntheta;
+    ClusterBatchWs w;
+    carve_cluster_batch((char *)d_workspace, K, nobj, nsmf, neep, w);
+    ClusterBatch B;
+    B.phot = d_phot;
+    B.ivar = d_ivar;
+    B.par = d_par;
+    B.par_ivar = d_par_ivar;
+    B.lnorm0 = d_lnorm0;
+    B.errmask = d_errmask;
+    B.ndim = d_ndim;
+    B.obj_theta = d_obj_theta;
+    B.src = w.src;
+    B.cnt = w.cnt;
+    B.mags = d_mags;
+    B.lnw_eep = w.lnw_eep;
+    B.lnw_smf = d_lnw_smf;
+    B.neep = neep;
+    B.nrow = nsmf * neep;
+    hipStream_t st = (hipStream_t)stream;
+    Timer tm(st);
+    tm.begin("k_cluster_keep");
+    hipLaunchKernelGGL(k_cluster_keep, dim3(K), dim3(CK_T), 0, st, nsmf, neep, nfilt, d_mini, d_eep,
+                       eep_binary_max, d_mags, w.lnw_eep, w.src, w.cnt);
+    tm.end();
+    tm.begin("k_cluster_batch");
+    const dim3 g((nobj + CL_T - 1) / CL_T, CLB_CHUNKS, K);
+    if (!with_nb(padded_nb(nfilt), FitBands{}, [&](auto NB) {
+            hipLaunchKernelGGL((k_cluster_batch<decltype(NB)::value>), g, dim3(CL_T), 0, st, nobj, nfilt, B,
+                               dim_prior, w.part_m, w.part_s);
+        }))
+        return fail(BRUTUS_EINVAL, "cluster likelihood: at most %d bands (%d given)", BRUTUS_MAX_FILT_FIT, nfilt);
+    tm.end();
+    tm.begin("k_cluster_merge_batch");
+    hipLaunchKernelGGL(k_cluster_merge_batch, dim3((nobj + CM_O - 1) / CM_O, K), dim3(CM_O * CM_J), 0, st, nobj,
+                       (const double *)w.part_m, (const double *)w.part_s, w.lnl);
+    tm.end();
+    tm.begin("k_cluster_mix_batch");
+    hipLaunchKernelGGL(k_cluster_mix_batch, dim3(K), dim3(CX_T), 0, st, nobj, nfilt, (const double *)w.lnl,
+                       d_lnl_outlier, d_obj_theta, d_lnl_mix, d_lnl_tot);
+    tm.end();
+    HIP_TRY(hipGetLastError());
+    tm.collect();
+    return 0;
+}
+
 // ---- utils.photometric_offsets on the device (offsets_kernels.hpp) ----------
 int brutus_offsets_weights(int nobj, int nsamps, int nfilt, int64_t nmodel, const float *d_models,
                            const int64_t *d_idxs, const double *d_reds, const double *d_dreds,

@@ -11,6 +11,11 @@
 //   k_iso_nn         one lane per row, one filter per workgroup: magnitudes of the primaries
 //                    (SECOND = false) or of the secondaries + the combination (SECOND = true)
 //
+// Each kernel is a `__device__` body and two launch forms: for one theta, whose IsoCall comes as a
+// kernel argument, and `_batch`, for K thetas (brutus_iso_seds_grid_batch): the theta index is the
+// last grid dimension, the IsoCall is the shared one with the theta's row of (feh, afe, loga, av,
+// rv, mu, corr[4]) read from device memory, and every array a theta writes is its own slice.
+//
 // The networks: plain FMAs.  A row's first hidden layer (H1 <= 64 values) lives in registers,
 // the filter's weights in LDS, read as broadcasts (every lane of a wave works on the same
 // filter); the second layer is consumed unit by unit by the third.  v_mfma_f64_16x16x4_f64 would
@@ -46,9 +51,27 @@ __device__ void iso_predict(const SedsTable &T, const IsoCall &c, double eep, do
     out[T.i_logg] -= 2. * dlogr;
 }
 
-__global__ void __launch_bounds__(SEDS_T)
-k_iso_primary(SedsTable T, IsoCall c, const double *__restrict__ eep, double *__restrict__ prim,
-              double *__restrict__ mini) {
+// The IsoCall of one theta of a batch: `c` holds what the thetas share (dimensions, flags, cuts),
+// `th` the theta's ISO_NTH values (feh, afe, loga, av, rv, mu = 5 log10(dist [pc]) - 5, dtdm, drdm,
+// msto_smooth, feh_scale; mu from the host, as the single call gets it: the same bits).
+constexpr int ISO_NTH = 10;
+__device__ __forceinline__ IsoCall iso_call_row(IsoCall c, const double *__restrict__ th) {
+    c.feh = th[0];
+    c.afe = th[1];
+    c.loga = th[2];
+    c.av = th[3];
+    c.rv = th[4];
+    c.mu = th[5];
+    c.dtdm = th[6];
+    c.drdm = th[7];
+    c.msto_smooth = th[8];
+    c.feh_scale = th[9];
+    return c;
+}
+
+__device__ __forceinline__ void iso_primary_body(const SedsTable &T, const IsoCall &c,
+                                                 const double *__restrict__ eep,
+                                                 double *__restrict__ prim, double *__restrict__ mini) {
     const int i = blockIdx.x * SEDS_T + threadIdx.x;
     if (i >= c.neep) return;
     double *row = prim + (size_t)i * T.npred;
@@ -56,11 +79,27 @@ k_iso_primary(SedsTable T, IsoCall c, const double *__restrict__ eep, double *__
     mini[i] = row[T.i_first];
 }
 
+__global__ void __launch_bounds__(SEDS_T)
+k_iso_primary(SedsTable T, IsoCall c, const double *__restrict__ eep, double *__restrict__ prim,
+              double *__restrict__ mini) {
+    iso_primary_body(T, c, eep, prim, mini);
+}
+
+__global__ void __launch_bounds__(SEDS_T)
+k_iso_primary_batch(SedsTable T, IsoCall c0, const double *__restrict__ theta,
+                    const double *__restrict__ eep, double *__restrict__ prim,
+                    double *__restrict__ mini) {
+    const size_t k = blockIdx.y;
+    const IsoCall c = iso_call_row(c0, theta + k * ISO_NTH);
+    iso_primary_body(T, c, eep, prim + k * c.neep * T.npred, mini + k * c.neep);
+}
+
 // The finite primaries, in order: xp = mini, fp = eep (seds.py:1470-1473).  status[0] = 1 if
 // a pair of neighbours is not increasing (np.interp is then not a bisection), status[1] = count.
-__global__ void __launch_bounds__(SEDS_T)
-k_iso_compact(int neep, const double *__restrict__ mini, const double *__restrict__ eep,
-              double *__restrict__ xp, double *__restrict__ fp, int32_t *__restrict__ status) {
+__device__ __forceinline__ void iso_compact_body(int neep, const double *__restrict__ mini,
+                                                 const double *__restrict__ eep,
+                                                 double *__restrict__ xp, double *__restrict__ fp,
+                                                 int32_t *__restrict__ status) {
     __shared__ int s_cnt[SEDS_T];
     __shared__ int s_bad;
     const int tid = threadIdx.x;
@@ -104,11 +143,26 @@ k_iso_compact(int neep, const double *__restrict__ mini, const double *__restric
 }
 
 __global__ void __launch_bounds__(SEDS_T)
-k_iso_secondary(SedsTable T, IsoCall c, const double *__restrict__ eep,
-                const double *__restrict__ smf, const double *__restrict__ mini,
-                const double *__restrict__ xp, const double *__restrict__ fp,
-                const int32_t *__restrict__ status, double *__restrict__ eep2,
-                double *__restrict__ sec) {
+k_iso_compact(int neep, const double *__restrict__ mini, const double *__restrict__ eep,
+              double *__restrict__ xp, double *__restrict__ fp, int32_t *__restrict__ status) {
+    iso_compact_body(neep, mini, eep, xp, fp, status);
+}
+
+__global__ void __launch_bounds__(SEDS_T)
+k_iso_compact_batch(int neep, const double *__restrict__ mini, const double *__restrict__ eep,
+                    double *__restrict__ xp, double *__restrict__ fp, int32_t *__restrict__ status) {
+    const size_t k = blockIdx.x;
+    iso_compact_body(neep, mini + k * neep, eep, xp + k * neep, fp + k * neep, status + 2 * k);
+}
+
+__device__ __forceinline__ void iso_secondary_body(const SedsTable &T, const IsoCall &c,
+                                                   const double *__restrict__ eep,
+                                                   const double *__restrict__ smf,
+                                                   const double *__restrict__ mini,
+                                                   const double *__restrict__ xp,
+                                                   const double *__restrict__ fp,
+                                                   const int32_t *__restrict__ status,
+                                                   double *__restrict__ eep2, double *__restrict__ sec) {
     const int r = blockIdx.x * SEDS_T + threadIdx.x;
     if (r >= c.nsmf * c.neep) return;
     const int s = r / c.neep, i = r - s * c.neep;
@@ -123,6 +177,28 @@ k_iso_secondary(SedsTable T, IsoCall c, const double *__restrict__ eep,
     if (e2 > c.eep_binary_max || eep[i] > c.eep_binary_max) e2 = iso_nan();
     eep2[r] = e2;
     iso_predict(T, c, e2, row);
+}
+
+__global__ void __launch_bounds__(SEDS_T)
+k_iso_secondary(SedsTable T, IsoCall c, const double *__restrict__ eep,
+                const double *__restrict__ smf, const double *__restrict__ mini,
+                const double *__restrict__ xp, const double *__restrict__ fp,
+                const int32_t *__restrict__ status, double *__restrict__ eep2,
+                double *__restrict__ sec) {
+    iso_secondary_body(T, c, eep, smf, mini, xp, fp, status, eep2, sec);
+}
+
+__global__ void __launch_bounds__(SEDS_T)
+k_iso_secondary_batch(SedsTable T, IsoCall c0, const double *__restrict__ theta,
+                      const double *__restrict__ eep, const double *__restrict__ smf,
+                      const double *__restrict__ mini, const double *__restrict__ xp,
+                      const double *__restrict__ fp, const int32_t *__restrict__ status,
+                      double *__restrict__ eep2, double *__restrict__ sec) {
+    const size_t k = blockIdx.y;
+    const IsoCall c = iso_call_row(c0, theta + k * ISO_NTH);
+    const size_t nrow = (size_t)c.nsmf * c.neep;
+    iso_secondary_body(T, c, eep, smf, mini + k * c.neep, xp + k * c.neep, fp + k * c.neep,
+                       status + 2 * k, eep2 + k * nrow, sec + k * nrow * T.npred);
 }
 
 // Apparent magnitude of one row in one filter (seds.py:1062-1076 under the mass cut of
@@ -161,12 +237,15 @@ __device__ __forceinline__ double iso_mag(const SedsTable &T, const IsoCall &c,
 }
 
 template <int HP, bool SECOND>
-__global__ void __launch_bounds__(SEDS_T)
-k_iso_nn(SedsTable T, IsoCall c, const double *__restrict__ weights,
-         const double *__restrict__ xmin, const double *__restrict__ xmax,
-         const double *__restrict__ eep, const double *__restrict__ smf,
-         const double *__restrict__ rows, const double *__restrict__ mag_prim,
-         double *__restrict__ out) {
+__device__ __forceinline__ void iso_nn_body(const SedsTable &T, const IsoCall &c,
+                                            const double *__restrict__ weights,
+                                            const double *__restrict__ xmin,
+                                            const double *__restrict__ xmax,
+                                            const double *__restrict__ eep,
+                                            const double *__restrict__ smf,
+                                            const double *__restrict__ rows,
+                                            const double *__restrict__ mag_prim,
+                                            double *__restrict__ out) {
     extern __shared__ double sw[];
     const int f = blockIdx.y;
     nn_stage<HP>(sw, weights, f, c.h1, c.h2);
@@ -188,4 +267,30 @@ k_iso_nn(SedsTable T, IsoCall c, const double *__restrict__ weights,
         if (eep[i] <= c.eep_binary_max) m -= 2.5 * log10(2.);
     }
     out[(size_t)r * c.nfilt + f] = m;
+}
+
+template <int HP, bool SECOND>
+__global__ void __launch_bounds__(SEDS_T)
+k_iso_nn(SedsTable T, IsoCall c, const double *__restrict__ weights,
+         const double *__restrict__ xmin, const double *__restrict__ xmax,
+         const double *__restrict__ eep, const double *__restrict__ smf,
+         const double *__restrict__ rows, const double *__restrict__ mag_prim,
+         double *__restrict__ out) {
+    iso_nn_body<HP, SECOND>(T, c, weights, xmin, xmax, eep, smf, rows, mag_prim, out);
+}
+
+// (rows, out: (K, neep, ...) of the primaries, (K, nsmf * neep, ...) of the secondaries)
+template <int HP, bool SECOND>
+__global__ void __launch_bounds__(SEDS_T)
+k_iso_nn_batch(SedsTable T, IsoCall c0, const double *__restrict__ theta,
+               const double *__restrict__ weights, const double *__restrict__ xmin,
+               const double *__restrict__ xmax, const double *__restrict__ eep,
+               const double *__restrict__ smf, const double *__restrict__ rows,
+               const double *__restrict__ mag_prim, double *__restrict__ out) {
+    const size_t k = blockIdx.z;
+    const IsoCall c = iso_call_row(c0, theta + k * ISO_NTH);
+    const size_t nrow = SECOND ? (size_t)c.nsmf * c.neep : (size_t)c.neep;
+    iso_nn_body<HP, SECOND>(T, c, weights, xmin, xmax, eep, smf, rows + k * nrow * T.npred,
+                            SECOND ? mag_prim + k * c.neep * c.nfilt : nullptr,
+                            out + k * nrow * c.nfilt);
 }

@@ -627,6 +627,9 @@ int brutus_last_timing(int *n_entries, const char **names, float *ms,
                        int max_entries);
 void brutus_enable_timing(int on);
 
+/* ---- K thetas per call: seds.Isochrone and the cluster likelihood in batches ---- */
+#include "brutus_amd_batch.h"
+
 #ifdef __cplusplus
 }
 #endif
