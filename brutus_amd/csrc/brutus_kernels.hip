@@ -366,6 +366,7 @@ struct FitCall {
     // set by dispatch_fit
     int flux_rounds = 4;    // BRUTUS_FLUX_ROUNDS (development switch): continuations of the device-driven flux phase
     bool list_fast = true;  // BRUTUS_LIST_FAST (development switch): the plane passes that skip dead blocks
+    int list_run = -LIST_RUN;       // BRUTUS_LIST_RUN (development switch): the list kernels' run length, see ItemWalk
     bool audited = false;   // this call's float32 bound is audited and ENFORCED (audit_verdict)
     float *aud = nullptr;   // w.aud on an audited call and with BRUTUS_AUDIT=1 (recorded for the caller to read)
 };
@@ -476,7 +477,8 @@ void launch_fflux(const FitCall &c, int nblocks, const int32_t *ids, int nact, c
     const Workspace &w = c.w;
     hipLaunchKernelGGL((k_fflux<NB, RVF, OPENING>), dim3(nblocks), dim3(TILE), 0, c.st, c.grid, c.nmodel,
                        c.nmodel_pad, c.nstar, w.stars, c.p, w.k1, w.k2, w.surv_idx, w.surv_off, w.wbase_surv,
-                       w.items_surv, c.rec, w.step_st, w.lnprob_st, w.part, w.lnpr32, w.thr_cull, ids, nact, nact_dev);
+                       w.items_surv, c.rec, w.step_st, w.lnprob_st, w.part, w.lnpr32, w.thr_cull, ids, nact, nact_dev,
+                       c.list_run);
 }
 template <int NB, bool RVF>
 void fflux_open(const FitCall &c) { launch_fflux<NB, RVF, true>(c, PERSIST_BLOCKS, nullptr, 0, nullptr); }
@@ -702,7 +704,7 @@ void select_and_derive(FitCall &c) {
     c.tm.end();
     c.tm.begin("k_derive");
     hipLaunchKernelGGL((k_derive<NB, RVF>), dim3(PERSIST_BLOCKS), blk, 0, c.st, c.grid, c.nmodel_pad, nstar,
-                       w.stars, c.p, w.k1, w.surv_idx, w.wbase_der, w.items_der, w.surv_off, c.rec);
+                       w.stars, c.p, w.k1, w.surv_idx, w.wbase_der, w.items_der, w.surv_off, c.rec, c.list_run);
     c.tm.end();
 }
 
@@ -777,6 +779,9 @@ int dispatch_fit(int nb, FitCall &c) {
     c.flux_rounds = env_int("BRUTUS_FLUX_ROUNDS", 4);
     // BRUTUS_LIST_FAST=0: the plane passes of the cull and the first cut as they were, every block read (A/B, tests)
     c.list_fast = env_int("BRUTUS_LIST_FAST", 1) != 0;
+    // BRUTUS_LIST_RUN=<n>: runs of exactly n work items in the list kernels, 1 = item by item (A/B, tests)
+    c.list_run = env_int("BRUTUS_LIST_RUN", 0);
+    if (c.list_run < 1 || c.list_run > 64) c.list_run = -LIST_RUN;
     // (two translation units, one definition of the shared layout: pre32_types.hpp)
     if (brutus_i_pre32_layout(0) != (int)sizeof(Star32) || brutus_i_pre32_layout(1) != (int)sizeof(P32) ||
         brutus_i_pre32_layout(2) != F2_T || brutus_i_pre32_layout(3) != TILE || brutus_i_pre32_layout(4) != NV32)

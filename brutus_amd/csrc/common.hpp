@@ -66,6 +66,41 @@ __device__ __forceinline__ double wave_max(double v) {
     return v;
 }
 
+// The same maximum without the LDS crossbar (wave_max: six dependent stages of two
+// ds_bpermute_b32 each).  The double becomes an unsigned 64-bit key of the same order
+// (negative: all bits flipped; otherwise: sign bit set); the maximum of the high words
+// is taken on the DPP data path, then the maximum of the low words among the lanes that
+// hold that high word.  Exact for every non-NaN input (callers map NaN to -inf first);
+// of +0 and -0 it returns +0.  The result is wave-uniform (read from lane 63).
+// gfx9 DPP controls: quad_perm [1, 0, 3, 2] = 0xB1, [2, 3, 0, 1] = 0x4E, row_half_mirror =
+// 0x141, row_mirror = 0x140 make every row of 16 lanes uniform; row_bcast:15 / :31 (see
+// wave_inclusive_sum below) carry the rows' maxima into lane 63.  Builtins, not asm: the
+// compiler sees the VALU-write -> DPP-read dependence and places the wait states.
+template <int CTRL, int ROWMASK>
+__device__ __forceinline__ unsigned dpp_max_u32(unsigned x) {
+    const unsigned o = (unsigned)__builtin_amdgcn_update_dpp((int)x, (int)x, CTRL, ROWMASK, 0xf, false);
+    return o > x ? o : x;        // (lanes the pattern leaves without a source see themselves)
+}
+__device__ __forceinline__ unsigned wave_max_u32(unsigned x) {
+    x = dpp_max_u32<0xB1, 0xf>(x);
+    x = dpp_max_u32<0x4E, 0xf>(x);
+    x = dpp_max_u32<0x141, 0xf>(x);
+    x = dpp_max_u32<0x140, 0xf>(x);
+    x = dpp_max_u32<0x142, 0xa>(x);
+    x = dpp_max_u32<0x143, 0xc>(x);
+    return (unsigned)__builtin_amdgcn_readlane((int)x, 63);
+}
+__device__ __forceinline__ double wave_max_dpp(double v) {
+    const unsigned long long b = __builtin_bit_cast(unsigned long long, v);
+    const unsigned long long key = (long long)b < 0 ? ~b : b | 0x8000000000000000ull;
+    const unsigned hi = (unsigned)(key >> 32), lo = (unsigned)key;
+    const unsigned mh = wave_max_u32(hi);
+    const unsigned ml = wave_max_u32(hi == mh ? lo : 0u);
+    const unsigned long long mk = ((unsigned long long)mh << 32) | ml;
+    const unsigned long long r = (long long)mk < 0 ? mk & 0x7fffffffffffffffull : ~mk;
+    return __builtin_bit_cast(double, r);
+}
+
 // Combine one value per lane into a single per-(tile, star) maximum.  NaN lanes
 // must already be mapped to -inf by the caller.  `slot` is LDS scratch (4 doubles).
 __device__ __forceinline__ void block_max_store(double v, double *slot, double *out) {

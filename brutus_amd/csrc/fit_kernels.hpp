@@ -799,31 +799,59 @@ __global__ void k_items(int nstar, const int32_t *__restrict__ wbase,
 // Walk of the work items that gives every XCD whole model chunks: workgroups are dispatched
 // round-robin over the 8 XCDs, so workgroup b runs on XCD b % 8 and takes the chunks
 // c = b % 8, b % 8 + 8, ...; inside a chunk the XCD's workers (`nw` of them, this one is
-// number `me`) take the items in turn.  A chunk's coefficient rows then cross the fabric
-// once, into ONE L2, and serve all stars from there (chunk-major numbering alone still
-// fetched them into all eight).
+// number `me`) take RUNS of `run` consecutive items in turn.  A chunk's coefficient rows
+// then cross the fabric once, into ONE L2, and serve all stars from there (chunk-major
+// numbering alone still fetched them into all eight).
+// Why runs: a chunk's items are numbered star-major and a (chunk, star) segment is some
+// ten items long on the survey workload, so a run mostly stays with one star -- its
+// constants are then served by the scalar cache (taken in turn, consecutive items of a
+// worker belong to different stars, and 128 stars' constants are four times that cache),
+// and k_fflux reduces its maxima once per star and run instead of once per item.
+// The runs of an XCD's chunks are dealt out as ONE sequence (`rot`: the worker at which the
+// previous chunks' runs ended): a chunk has fewer runs than the XCD has workers, and dealt
+// from worker 0 in every chunk the low-numbered workgroups would get them all.  A launch
+// with few items (sharp posteriors) shortens the runs to what gives every worker one
+// (run_ < 0: the product's setting, -LIST_RUN).  run_ > 0 is taken as it is, and run_ = 1 is
+// the walk item by item as it was (BRUTUS_LIST_RUN=<n>: A/B, tests).
+constexpr int LIST_RUN = 16;
 struct ItemWalk {
     const int32_t *wbase;
-    int nstar, c, item, me, nw;
-    __device__ __forceinline__ void seek() {      // first chunk from c on with an item for `me`
+    int nstar, c, item, me, nw, run, left, end, rot;
+    __device__ __forceinline__ void seek() {      // first chunk from c on with a run for `me`
         for (; c < NCHUNK; c += 8) {
-            item = wbase[c * nstar] + me;
-            if (item < wbase[(c + 1) * nstar]) return;
+            const int base = wbase[c * nstar];
+            end = wbase[(c + 1) * nstar];
+            int r = me - rot;
+            if (r < 0) r += nw;
+            if (run > 1) rot = (rot + (end - base + run - 1) / run) % nw;
+            item = base + r * run;
+            left = run;
+            if (item < end) return;
         }
         item = -1;
     }
-    __device__ __forceinline__ void init(const int32_t *wb, int ns, int xcd, int me_, int nw_) {
+    __device__ __forceinline__ void init(const int32_t *wb, int ns, int xcd, int me_, int nw_, int run_) {
         wbase = wb;
         nstar = ns;
         me = me_;
         nw = nw_;
+        run = run_;
+        if (run_ < 0) {     // at most -run_, and not longer than every worker's even share of the items
+            const int even = wb[NCHUNK * ns] / (8 * nw_);
+            run = -run_ < even ? -run_ : even > 1 ? even : 1;
+        }
+        rot = 0;
         c = xcd;
         seek();
     }
     __device__ __forceinline__ bool done() const { return item < 0; }
     __device__ __forceinline__ void next() {
-        item += nw;
-        if (item >= wbase[(c + 1) * nstar]) {
+        ++item;
+        if (--left == 0) {
+            item += (nw - 1) * run;
+            left = run;
+        }
+        if (item >= end) {
             c += 8;
             seek();
         }
@@ -961,7 +989,7 @@ k_fflux(const float *__restrict__ grid, int64_t nmodel, int64_t nmodel_pad, int 
         const ItemGeom *__restrict__ items, RecPlanes rec, double *__restrict__ step_st,
         double *__restrict__ lnprob_st, double *__restrict__ part, float *__restrict__ surv32,
         const double *__restrict__ thr_cull, const int32_t *__restrict__ act, int nact,
-        const int32_t *__restrict__ nact_dev) {
+        const int32_t *__restrict__ nact_dev, int run) {
     // continuation launches: the list of stars still iterating and its length may have been
     // put together on the device (k_fflux_decide); the launch has a fixed size and its
     // workgroups share the NCHUNK * nact * CONT_P segment pieces in turns
@@ -978,8 +1006,10 @@ k_fflux(const float *__restrict__ grid, int64_t nmodel, int64_t nmodel_pad, int 
     constexpr int niter = FIRST ? 2 : 1;
     // this lane's model in a work item, requested one item ahead (a dead lane reads the
     // item's last entry: no select on the loaded value, so nothing waits for it here)
+    int s_nxt = 0;      // the star of the item lane_model was last asked for
     auto lane_model = [&](int item) -> int32_t {
         const ItemGeom ig = items[item < 0 ? 0 : item];      // (past the end: item 0 again, unused)
+        s_nxt = ig.s;
         const int64_t q = ig.q0 + threadIdx.x;
         const int64_t last = ig.q0 + ig.n - 1;
         return cand_idx[q < last ? q : last];
@@ -992,6 +1022,9 @@ k_fflux(const float *__restrict__ grid, int64_t nmodel, int64_t nmodel_pad, int 
     // register allocation went from 248 VGPRs to 256 + 180 bytes of scratch, 1.65 -> 2.2 ms)
     auto walk = [&](auto &wk) {
     int32_t i_nxt = lane_model(wk.item);
+    // the lanes' maxima over the items of ONE star so far (see the reduction at the loop's end)
+    constexpr bool PER_STAR = FIRST && NB <= 12;     // (a continuation launch is a twentieth of the opening one)
+    double aL = -INFINITY, aT = -INFINITY, aM = -INFINITY;
     while (!wk.done()) {
         const int item = wk.item;
         wk.next();
@@ -999,6 +1032,7 @@ k_fflux(const float *__restrict__ grid, int64_t nmodel, int64_t nmodel_pad, int 
         const int s = ig.s;
         const int32_t i_me = i_nxt;
         i_nxt = lane_model(wk.item);
+        // (a skipped star has no live item: the previous star's maxima left at its last item)
         if (k2state[s] < 0) {
             landed(i_nxt);      // (every path into the loop head has taken it: no wait there)
             continue;
@@ -1038,8 +1072,9 @@ k_fflux(const float *__restrict__ grid, int64_t nmodel, int64_t nmodel_pad, int 
                     GramR G;
                     if constexpr (WIDE) gram_init_rf_wide<NB>(c, p.rv_mean, sp, G);
                     else gram_init_rf<NB>(c, R, sp, G);
-                    // (a single sweep would do, see k_k1probe; the loop form keeps this
-                    // kernel's register allocation below the spill line)
+                    // (a single sweep would do, see k_k1probe, and measured +1 % on the survey line;
+                    // the loop form keeps this kernel's register allocation below the spill line: with
+                    // the single sweep the 12-band opening kernel stands at 256 of 256 VGPRs)
                     for (int k = 0; k < K; ++k) {
                         double a_, c_;
                         gram_sweep_rf(G, sp.S, p, av, a_, c_);
@@ -1131,9 +1166,27 @@ k_fflux(const float *__restrict__ grid, int64_t nmodel, int64_t nmodel_pad, int 
         }
         // one partial per wave: no workgroup barrier in the loop, the four waves drift
         // apart and overlap each other's gather latency
-        L = wave_max(L);
-        T = wave_max(T);
-        M = wave_max(M);
+        // The decision needs the maxima per STAR (k_fflux_decide takes the maximum over all of a
+        // star's items): the lanes carry theirs along while the walk stays with the star and the
+        // wave reduces them once, at the star's last item here; the items before it read -inf.
+        // (From 16 bands on the opening kernel has no registers for three more doubles -- 68 / 148
+        // bytes of scratch became 184 / 180 -- and the wave reduces per item.)
+        if constexpr (PER_STAR) {
+            aL = L > aL ? L : aL;
+            aT = T > aT ? T : aT;
+            aM = M > aM ? M : aM;
+            L = T = M = -INFINITY;
+            if (wk.done() || s_nxt != s) {
+                L = wave_max_dpp(aL);
+                T = wave_max_dpp(aT);
+                M = wave_max_dpp(aM);
+                aL = aT = aM = -INFINITY;
+            }
+        } else {
+            L = wave_max_dpp(L);
+            T = wave_max_dpp(T);
+            M = wave_max_dpp(M);
+        }
         if ((threadIdx.x & 63) == 0) {
             double *out = part + ((int64_t)item * (TILE / 64) + (threadIdx.x >> 6)) * 3;
             out[0] = L;
@@ -1144,7 +1197,7 @@ k_fflux(const float *__restrict__ grid, int64_t nmodel, int64_t nmodel_pad, int 
     };
     if constexpr (FIRST) {
         ItemWalk wk;
-        wk.init(wbase, nstar, blockIdx.x & 7, blockIdx.x >> 3, (gridDim.x + 7 - (blockIdx.x & 7)) >> 3);
+        wk.init(wbase, nstar, blockIdx.x & 7, blockIdx.x >> 3, (gridDim.x + 7 - (blockIdx.x & 7)) >> 3, run);
         walk(wk);
     } else {
         const int nunit = NCHUNK * nact * CONT_P;
@@ -1304,7 +1357,7 @@ k_derive(const float *__restrict__ grid, int64_t nmodel_pad, int nstar,
          const StarPrep *__restrict__ stars, DevParams p, const int32_t *__restrict__ k1,
          const int32_t *__restrict__ der_idx, const int32_t *__restrict__ wbase,
          const ItemGeom *__restrict__ items, const int64_t *__restrict__ cand_off,
-         RecPlanes rec) {
+         RecPlanes rec, int run) {
     __shared__ double s_tbl[64];
     stage_exp_table(s_tbl);
     __syncthreads();
@@ -1320,7 +1373,7 @@ k_derive(const float *__restrict__ grid, int64_t nmodel_pad, int nstar,
     };
     const int64_t slot0 = cand_off[nstar];
     ItemWalk wk;
-    wk.init(wbase, nstar, blockIdx.x & 7, blockIdx.x >> 3, (gridDim.x + 7 - (blockIdx.x & 7)) >> 3);
+    wk.init(wbase, nstar, blockIdx.x & 7, blockIdx.x >> 3, (gridDim.x + 7 - (blockIdx.x & 7)) >> 3, run);
     if (wk.done()) return;
     // Software pipeline over the work items (two waves per SIMD cannot hide a gather AND a
     // write acknowledgement per item): while item k is computed, the coefficient rows of item

@@ -99,7 +99,9 @@ int brutus_calibrate_issue(int kind, int iters, int waves_per_simd, float *d_scr
 /* Test hooks: y[i] = the kernels' own elementary functions for n inputs.  `which` in
  * brutus_debug_math: 0 10^x, 1 e^x, 2 ln x (the general forms); 3 sqrt x, 4 1/sqrt x, 5 1/x
  * (hardware seed + Newton); 6 e^x for finite x, 7 ln x for normal positive x (the
- * select-free forms of the Galactic prior), 8 / 9 the branch-free ln x / e^x. */
+ * select-free forms of the Galactic prior), 8 / 9 the branch-free ln x / e^x; 10: not a
+ * function of x[i] alone but the flux kernel's LDS-free wave maximum -- y[i] = the maximum of
+ * the 64 values x[64 w .. 64 w + 63] around i (n a multiple of 64, no NaN among them). */
 int brutus_debug_exp10(const double *d_x, double *d_y, int64_t n, void *stream);
 int brutus_debug_math(int which, const double *d_x, double *d_y, int64_t n,
                       void *stream);
