@@ -12,7 +12,11 @@ HIP kernel `k_cluster` through `brutus_cluster_lnl`.
 """
 import collections
 import ctypes as C
+import inspect
+import math
+import os
 import threading
+import time
 import warnings
 
 import numpy as np
@@ -43,7 +47,6 @@ _TRACE = None
 
 def _mark(label):
     if _TRACE is not None:
-        import time
         _TRACE.append((label, time.perf_counter()))
 
 
@@ -81,44 +84,86 @@ def _lru_put(cache, key, val, cap):
         cache.popitem(last=False)
 
 
-def _take(theta, pos, spec, n):
-    """Read `n` values: from `theta` where `spec[i] is None`, else the fixed
-    value (the reference's 'free' / per-entry constraint convention)."""
-    out = np.zeros(n)
-    for i in range(n):
-        if spec == 'free' or spec[i] is None:
-            out[i] = theta[pos]
-            pos += 1
-        else:
-            out[i] = spec[i]
-    return out, pos
+def _theta_plan(cluster_params, offsets, corr_params, nbands):
+    """Where `theta` holds each value (cluster.py:227-290): `(cols, end)`, `cols` one list per
+    group (6 cluster parameters, `nbands` offsets, 4 correction coefficients) with the place of
+    every free value and None for a fixed one, `end` the place after the last value read.  A group
+    declared `'fixed'` is None as a whole and still takes its columns' places."""
+    pos, end, cols = 0, 0, []
+    for spec, n in ((cluster_params, 6), (offsets, nbands), (corr_params, 4)):
+        word = spec if isinstance(spec, str) else None
+        if cols and word == 'fixed':                # (the cluster parameters have no such form)
+            cols.append(None)
+            pos += n
+            continue
+        col = [None] * n
+        for i in range(n):
+            if word == 'free' or spec[i] is None:
+                col[i], pos = pos, pos + 1
+                end = pos
+        cols.append(col)
+    return cols, end
 
 
-def isochrone_loglike(theta, isochrone, phot, err, cluster_params='free',
-                      offsets='fixed', corr_params='fixed', mini_bound=0.08,
-                      eep_binary_max=480., smf_grid=None, eep_grid=None,
-                      parallax=None, parallax_err=None, cluster_prob=0.95,
+def _read(theta, spec, col):
+    """One group's values along the last axis of `theta`, `(Ncol,)` or `(K, Ncol)`: from the
+    places `col` where free, else the fixed value of `spec`."""
+    th, out = theta.T, np.empty((len(col),) + theta.shape[:-1])
+    for i, c in enumerate(col):
+        out[i] = th[c] if c is not None else spec[i]
+    return np.ascontiguousarray(out.T)
+
+
+def _ln_mixture(cluster_prob, fout):
+    """`(ln_fin, ln_fout)`, the logarithms of the outlier mixture's weights (cluster.py:410-414)."""
+    return np.log(cluster_prob * (1. - fout)), np.log(1. - cluster_prob * (1. - fout))
+
+
+class _Call(object):
+    """One evaluation's context: the library, torch, the device and its stream (made under
+    `torch.cuda.device(ds.dev)`), the catalogue's terms `ds`, and the objects' side of the kernel."""
+
+    def __init__(self, torch, ds, phot, err, Xb, chi2_p, dim_prior):
+        self.torch, self.L, self.ds, self.dev = torch, _lib.lib(), ds, ds.dev
+        self.stream = _stream_ptr(torch)
+        self.Nobjs, self.Nbands = phot.shape
+        self.phot, self.err, self.Xb, self.chi2_p, self.dim_prior = phot, err, Xb, chi2_p, dim_prior
+        self._objs = None
+
+    def obj_args(self):
+        """The objects' side of the kernel (cluster.py:292-333).  Prepared when the first group of
+        isochrone points is on its way to the device: its copy and flux kernel run under this."""
+        if self._objs is not None:
+            return self._objs
+        ds, Xb = self.ds, self.Xb
+        if np.all(Xb == 1.):
+            per_object = ds.p_d, ds.p_iv, ds.p_cp, ds.p_ln0
+        else:                                  # multiplicative offsets (cluster.py:327-333)
+            phot_t, err_t = self.phot * Xb, self.err * Xb
+            with np.errstate(all="ignore"):
+                ivar = np.where(ds.phot_mask, 1. / err_t ** 2, 0.)
+                lnorm = np.nansum(np.log(2. * np.pi * err_t ** 2), axis=1) + ds.lnorm_p
+            t_d = to_device(np.where(ds.phot_mask, phot_t, 0.), np.float64, self.dev)
+            t_iv, t_ln = to_device(ivar, np.float64, self.dev), to_device(lnorm, np.float64, self.dev)
+            # (in the tuple until the call returns: they outlive the launches that read them)
+            per_object = t_d, t_iv, ds.p_cp, t_ln
+        ds.h_cp.numpy()[...] = self.chi2_p
+        ds.t_cp.copy_(ds.h_cp, non_blocking=True)
+        self._objs = (*per_object, ds.p_n, 1 if self.dim_prior else 0, ds.p_ws, ds.ws.numel())
+        _mark("objects up")
+        return self._objs
+
+
+def isochrone_loglike(theta, isochrone, phot, err, cluster_params='free', offsets='fixed',
+                      corr_params='fixed', mini_bound=0.08, eep_binary_max=480., smf_grid=None,
+                      eep_grid=None, parallax=None, parallax_err=None, cluster_prob=0.95,
                       dim_prior=True, return_lnls=False, device=None, cache=True):
-    """See `_isochrone_loglike`; calls are serialised (the caches own the buffers a call
-    works in)."""
-    with _LOCK:
-        return _isochrone_loglike(theta, isochrone, phot, err, cluster_params, offsets,
-                                  corr_params, mini_bound, eep_binary_max, smf_grid, eep_grid,
-                                  parallax, parallax_err, cluster_prob, dim_prior, return_lnls,
-                                  device, cache)
-
-
-def _isochrone_loglike(theta, isochrone, phot, err, cluster_params, offsets, corr_params,
-                       mini_bound, eep_binary_max, smf_grid, eep_grid, parallax, parallax_err,
-                       cluster_prob, dim_prior, return_lnls, device, cache):
-    """ln-likelihood of a co-eval stellar population.  Arguments, defaults and
-    return value follow reference cluster.py:23-168: `theta` packs
-    `(feh, loga, av, rv, dist[pc], fout)`, then per-band multiplicative offsets
-    and four empirical-correction coefficients, each group only where it is
-    declared free.  `isochrone` must provide
-    `get_seds(feh=, loga=, av=, rv=, eep=, smf=, dist=, mini_bound=,
-    eep_binary_max=, corr_params=) -> (seds (Neep, Nbands) mags, params, params2)`
-    with `params['mini']` the initial-mass grid.
+    """ln-likelihood of a co-eval stellar population.  Arguments, defaults and return value follow
+    reference cluster.py:23-168: `theta` packs `(feh, loga, av, rv, dist[pc], fout)`, then per-band
+    multiplicative offsets and four empirical-correction coefficients, each group only where it
+    is declared free.  `isochrone` must provide
+    `get_seds(feh=, loga=, av=, rv=, eep=, smf=, dist=, mini_bound=, eep_binary_max=, corr_params=)
+    -> (seds (Neep, Nbands) mags, params, params2)` with `params['mini']` the initial-mass grid.
 
     Extensions: `device`; `cache` (default True) keeps the per-dataset terms and the
     isochrone point tables of recent calls (`clear_caches()` drops them).  A cached point
@@ -133,115 +178,66 @@ def _isochrone_loglike(theta, isochrone, phot, err, cluster_params, offsets, cor
     turns a group into fluxes and sums it while the plug-in works on the next one.  A plug-in that
     offers `get_seds_grid_device(smf_grid=, out=, ...same keywords...) -> mini (Neep,)`
     (`seds.Isochrone`) is asked once instead, for all mass fractions, and fills the device tensor
-    `out (Nsmf, Neep, Nbands)` the sum reads: its magnitudes never visit the host."""
-    phot, err, smf_grid, grad_smf, eep_grid = _checked(
-        phot, err, cluster_params, offsets, corr_params, smf_grid, eep_grid, parallax, parallax_err)
-    Nobjs, Nbands = phot.shape
+    `out (Nsmf, Neep, Nbands)` the sum reads: its magnitudes never visit the host.
 
-    _mark("checked")
-    # ---- unpack theta (cluster.py:227-290) ------------------------------------
-    pos = 0
-    (feh, loga, av, rv, dist, fout), pos = _take(theta, pos, cluster_params, 6)
-    fout = max(min(1. - 1e-10, fout), 1e-10)
-    if isinstance(offsets, str) and offsets == 'fixed':
-        Xb = np.ones(Nbands)
-        pos += Nbands
-    else:
-        Xb, pos = _take(theta, pos, offsets, Nbands)
-    if isinstance(corr_params, str) and corr_params == 'fixed':
-        corr_coef = None
-        pos += 4
-    else:
-        corr_coef, pos = _take(theta, pos, corr_params, 4)
+    Calls are serialised: the caches own the buffers a call works in."""
+    with _LOCK:
+        phot, err, smf_grid, grad_smf, eep_grid = _checked(
+            phot, err, cluster_params, offsets, corr_params, smf_grid, eep_grid, parallax,
+            parallax_err)
+        Nobjs, Nbands = phot.shape
+        _mark("checked")
+        # ---- unpack theta (cluster.py:227-290; a longer `theta` is accepted, as there) --------
+        cols, _ = _theta_plan(cluster_params, offsets, corr_params, Nbands)
+        theta = np.asarray(theta, dtype=np.float64)
+        feh, loga, av, rv, dist, fout = _read(theta, cluster_params, cols[0])
+        fout = max(min(1. - 1e-10, fout), 1e-10)
+        Xb = np.ones(Nbands) if cols[1] is None else _read(theta, offsets, cols[1])
+        corr_coef = None if cols[2] is None else _read(theta, corr_params, cols[2])
+        _mark("theta")
+        ds = _dataset(phot, err, parallax, parallax_err, dim_prior, device, cache)
+        _mark("dataset")
+        # ---- per-object terms that move with theta (cluster.py:292-325) -----------------------
+        chi2_p = np.zeros(Nobjs) if ds.pmask is None else (ds.par0 - 1e3 / dist) ** 2 * ds.ivar0
+        ln_fin, ln_fout = _ln_mixture(cluster_prob, fout)
+        torch = _torch()
+        with torch.cuda.device(ds.dev):
+            ctx = _Call(torch, ds, phot, err, Xb, chi2_p, dim_prior)
+            # ---- isochrone points of every SMF slice (cluster.py:336-366) ---------------------
+            npts, tab, nchunk = _point_table(
+                ctx, isochrone, (feh, loga, av, rv, dist, corr_coef), smf_grid, grad_smf, eep_grid,
+                mini_bound, eep_binary_max, cache)
+            _mark("table")
+            lnl_tot, lnl_mix = _mixed(ctx, npts, tab, nchunk, ln_fin, ln_fout, return_lnls)
+        _mark("mixed")
+        return (lnl_tot, lnl_mix) if return_lnls else lnl_tot
 
-    _mark("theta")
-    ds = _dataset(phot, err, parallax, parallax_err, dim_prior, device, cache)
-    _mark("dataset")
-    torch, dev = _torch(), ds.dev
-    L = _lib.lib()
 
-    # ---- per-object terms that move with theta (cluster.py:292-325) ---------------
-    if ds.pmask is not None:
-        chi2_p = (ds.par0 - 1e3 / dist) ** 2 * ds.ivar0
-    else:
-        chi2_p = np.zeros(Nobjs)
-    ln_fin = np.log(cluster_prob * (1. - fout))
-    ln_fout = np.log(1. - cluster_prob * (1. - fout))
-
-    with torch.cuda.device(dev):
-        stream = _stream_ptr(torch)
-        objs = []
-
-        def obj_args():
-            """The objects' side of the kernel (cluster.py:292-333).  Prepared when the first
-            group of isochrone points is already on its way to the device: the copy and the
-            flux kernel of that group run under this."""
-            if objs:
-                return objs[0]
-            if np.all(Xb == 1.):
-                per_object = ds.p_d, ds.p_iv, ds.p_cp, ds.p_ln0
-            else:                                  # multiplicative offsets (cluster.py:327-333)
-                phot_t, err_t = phot * Xb, err * Xb
-                with np.errstate(all="ignore"):
-                    ivar = np.where(ds.phot_mask, 1. / err_t ** 2, 0.)
-                    lnorm = np.nansum(np.log(2. * np.pi * err_t ** 2), axis=1) + ds.lnorm_p
-                t_d = to_device(np.where(ds.phot_mask, phot_t, 0.), np.float64, dev)
-                t_iv, t_ln = to_device(ivar, np.float64, dev), to_device(lnorm, np.float64, dev)
-                # (in the tuple until the call returns: they outlive the launches that read them)
-                per_object = t_d, t_iv, ds.p_cp, t_ln
-            ds.h_cp.numpy()[...] = chi2_p
-            ds.t_cp.copy_(ds.h_cp, non_blocking=True)
-            objs.append((*per_object, ds.p_n, 1 if dim_prior else 0, ds.p_ws, ds.ws.numel()))
-            _mark("objects up")
-            return objs[0]
-
-        def part(t_flux, t_lnw, npts, chunk_lo, chunk_n):
-            """The sum over `npts` points as partials in chunks [chunk_lo, chunk_lo + chunk_n)."""
-            _lib.check(L.brutus_cluster_lnl_part(
-                Nobjs, Nbands, npts, t_flux if npts else None, t_lnw if npts else None,
-                *obj_args(), chunk_lo, chunk_n, stream))
-
-        def part_mags(t_src, t_mags, t_lng, t_lnsmf, neep, npts, chunk_lo, chunk_n):
-            """The same straight from the plug-in's magnitudes (kept rows `t_src` of `t_mags`)."""
-            _lib.check(L.brutus_cluster_lnl_part_mags(
-                Nobjs, Nbands, npts, neep, t_src if npts else None, t_mags, t_lng, t_lnsmf,
-                *obj_args(), chunk_lo, chunk_n, stream))
-
-        # ---- isochrone points of every SMF slice (cluster.py:336-366) -------------
-        tab, nchunk = _point_table(isochrone, feh, loga, av, rv, dist, corr_coef, smf_grid,
-                                   grad_smf, eep_grid, mini_bound, eep_binary_max, Nbands, dev,
-                                   torch, L, cache, part, part_mags)
-        _mark("table")
-        if tab is None:
-            lnl = np.full(Nobjs, -np.inf)
-            with np.errstate(all="ignore"):     # outlier mixture (cluster.py:410-414)
-                lnl_mix = np.logaddexp(lnl + ln_fin, ds.lnl_outlier + ln_fout)
-            lnl_tot = np.sum(lnl_mix)
-        else:
-            if nchunk:      # the pieces were summed while the plug-in worked on the next one
-                _lib.check(L.brutus_cluster_lnl_merge(Nobjs, nchunk, ds.p_ws, ds.ws.numel(),
-                                                      ds.p_out, stream))
-            else:           # a table met before
-                t_flux, t_lnw = tab[1:]
-                _lib.check(L.brutus_cluster_lnl(
-                    Nobjs, Nbands, t_lnw.numel(), t_flux, t_lnw, *obj_args(), ds.p_out, stream))
-            # ---- outlier mixture and total (cluster.py:410-414), on the device -------------
-            _lib.check(L.brutus_cluster_mix(Nobjs, ds.p_out, ds.p_lo, float(ln_fin),
-                                            float(ln_fout), ds.p_mix, ds.p_tot, stream))
-            if return_lnls:
-                ds.h_mix.copy_(ds.t_mix, non_blocking=True)
-            else:
-                ds.h_mix[Nobjs:].copy_(ds.t_mix[Nobjs:], non_blocking=True)
-            _mark("enqueued")
-            torch.cuda.current_stream().synchronize()
-            _mark("synced")
-            h = ds.h_mix.numpy()
-            lnl_tot = h[Nobjs]            # (a numpy scalar: a copy)
-            lnl_mix = h[:Nobjs].copy() if return_lnls else None
-    _mark("mixed")
+def _mixed(ctx, npts, tab, nchunk, ln_fin, ln_fout, return_lnls):
+    """The sum over the points, the outlier mixture and the total: `(lnl_tot, lnl_mix or None)`."""
+    ds, L, Nobjs = ctx.ds, ctx.L, ctx.Nobjs
+    if not npts:        # no usable point: the outlier term alone
+        lnl = np.full(Nobjs, -np.inf)
+        with np.errstate(all="ignore"):
+            lnl_mix = np.logaddexp(lnl + ln_fin, ds.lnl_outlier + ln_fout)
+        return np.sum(lnl_mix), lnl_mix
+    if nchunk:          # the pieces were summed while the plug-in worked on the next one
+        _lib.check(L.brutus_cluster_lnl_merge(Nobjs, nchunk, ds.p_ws, ds.ws.numel(), ds.p_out,
+                                              ctx.stream))
+    else:               # a table met before
+        _lib.check(L.brutus_cluster_lnl(Nobjs, ctx.Nbands, npts, tab.t_flux, tab.t_lnw,
+                                        *ctx.obj_args(), ds.p_out, ctx.stream))
+    _lib.check(L.brutus_cluster_mix(Nobjs, ds.p_out, ds.p_lo, float(ln_fin), float(ln_fout),
+                                    ds.p_mix, ds.p_tot, ctx.stream))
     if return_lnls:
-        return lnl_tot, lnl_mix
-    return lnl_tot
+        ds.h_mix.copy_(ds.t_mix, non_blocking=True)
+    else:
+        ds.h_mix[Nobjs:].copy_(ds.t_mix[Nobjs:], non_blocking=True)
+    _mark("enqueued")
+    ctx.torch.cuda.current_stream().synchronize()
+    _mark("synced")
+    h = ds.h_mix.numpy()
+    return h[Nobjs], (h[:Nobjs].copy() if return_lnls else None)    # (h[Nobjs]: a scalar, a copy)
 
 
 def _checked(phot, err, cluster_params, offsets, corr_params, smf_grid, eep_grid, parallax,
@@ -379,6 +375,92 @@ def _dataset(phot, err, parallax, parallax_err, dim_prior, device, cache):
     return ds
 
 
+def _kept_rows(pos, a, b, late, neep):
+    """Rows of the whole `(slice, EEP)` table that slices `a:b` keep (int32, offset `a * neep`): where
+    the initial mass increases with EEP, `pos (neep,)` for all slices or `(b - a, neep)`, and the
+    evolved stars `late (neep,)` in slice 0 only (cluster.py:351-357)."""
+    keep = np.repeat(pos[None, :], b - a, axis=0) if pos.ndim == 1 else pos.copy()
+    keep[(1 if a == 0 else 0):, late] = False
+    return (np.flatnonzero(keep) + a * neep).astype(np.int32)
+
+
+def _f64_pair(torch, n, nb, dev):
+    return (torch.empty((n, nb), dtype=torch.float64, device=dev),
+            torch.empty(n, dtype=torch.float64, device=dev))
+
+
+class _Staging(object):
+    """The buffers the calls of one table shape on one device stage their isochrone in, and what the
+    next call can use again (`src`, `t_src`, `srckey`: every group's kept rows and their origin)."""
+
+    def __init__(self, nrow, nb, dev, torch):
+        self.torch, self.dev, self.nrow, self.nb = torch, dev, nrow, nb
+        self.h_mags = torch.empty((nrow, nb), dtype=torch.float64).pin_memory()
+        self.h_lnw = torch.empty(nrow, dtype=torch.float64).pin_memory()
+        self.np_mags, self.np_lnw = self.h_mags.numpy(), self.h_lnw.numpy()
+        self.d_mags, self.d_lnw = _f64_pair(torch, nrow, nb, dev)
+        self.p_mags = _lib.fixed(self.d_mags, "d", "float64")    # (as for the catalogue's buffers)
+        self.src = self.t_src = self.srckey = self.h_lng = self.d_lng = None
+        self.smfkey = self.d_lnsmf = self.p_lnsmf = None
+        self.src_all_key = self.t_src_all = self.t_flux = self.t_lnw = None
+
+    def groups(self, ngroup, neep):
+        """Room for `ngroup` groups of slices of `neep` points; another split forgets the rows."""
+        if self.src is None or len(self.src) != ngroup or tuple(self.h_lng.shape) != (ngroup, neep):
+            self.src, self.t_src, self.srckey = [None] * ngroup, [None] * ngroup, [None] * ngroup
+            self.h_lng = self.torch.empty((ngroup, neep), dtype=self.torch.float64).pin_memory()
+            self.d_lng = self.torch.empty((ngroup, neep), dtype=self.torch.float64, device=self.dev)
+
+    def lnsmf(self, smf_grid, grad_smf):
+        """`ln(grad smf)` on the device and its fixed address, remade when the grid's bytes change
+        (replaced, never rewritten in place: a cached table may share the tensor)."""
+        key = smf_grid.tobytes()
+        if self.smfkey != key:
+            with np.errstate(all="ignore"):
+                self.smfkey, self.d_lnsmf = key, to_device(np.log(grad_smf), np.float64, self.dev)
+            self.p_lnsmf = _lib.fixed(self.d_lnsmf, "d", "float64")
+
+    def lng_row(self, g, gmini, pos):
+        """Group `g`'s row of `ln(gradient of mini)`, -inf where `pos` is false, sent on its way."""
+        h_lng = self.h_lng.numpy()[g]
+        h_lng[...] = -np.inf
+        np.log(gmini, out=h_lng, where=pos)
+        d_lng = self.d_lng[g]
+        d_lng.copy_(self.h_lng[g], non_blocking=True)
+        return d_lng
+
+    def rows(self, g, pos, a, b, late, neep):
+        """How many rows group `g` keeps; the list is looked up by what it is made from, not rebuilt."""
+        key = (pos.tobytes(), a, b, late.tobytes())
+        if self.srckey[g] != key:
+            self.src[g], self.srckey[g] = _kept_rows(pos, a, b, late, neep), key
+            self.t_src[g] = to_device(self.src[g], np.int32, self.dev)
+        return self.src[g].size
+
+    def put_rows(self, g, src):
+        """Group `g` keeps the rows `src`, made from a mass grid of its own (they rarely change)."""
+        if self.src[g] is None or not np.array_equal(self.src[g], src):
+            self.src[g], self.t_src[g] = src, to_device(src, np.int32, self.dev)
+        self.srckey[g] = None
+
+    def all_rows(self):
+        """The kept rows of all groups as one tensor (replaced when a list changes, as `d_lnsmf`)."""
+        key = tuple(self.srckey)
+        if self.src_all_key != key:
+            self.src_all_key, self.t_src_all = key, self.torch.cat(self.t_src)
+        return self.t_src_all
+
+    def flux_pair(self, fresh):
+        """`(flux (nrow, nb), lnw (nrow,))`: `fresh` for a table that will be cached (it keeps its
+        tensors), else the one pair that is used again."""
+        if not fresh and self.t_flux is not None:
+            return self.t_flux, self.t_lnw
+        pair = _f64_pair(self.torch, self.nrow, self.nb, self.dev)
+        if not fresh:
+            self.t_flux, self.t_lnw = pair
+        return pair
+
+
 _STAGE = {}
 
 
@@ -388,16 +470,25 @@ def _staging(nrow, nb, dev, torch):
     if st is None:
         if len(_STAGE) > 4:
             _STAGE.clear()
-        st = _Dataset()
-        st.h_mags = torch.empty((nrow, nb), dtype=torch.float64).pin_memory()
-        st.h_lnw = torch.empty(nrow, dtype=torch.float64).pin_memory()
-        st.d_mags = torch.empty((nrow, nb), dtype=torch.float64, device=dev)
-        st.d_lnw = torch.empty(nrow, dtype=torch.float64, device=dev)
-        st.p_mags = _lib.fixed(st.d_mags, "d", "float64")    # (as for the catalogue's buffers)
-        st.src = st.t_src = None
-        st.hook_out = {}
-        _STAGE[key] = st
+        st = _STAGE[key] = _Staging(nrow, nb, dev, torch)
     return st
+
+
+# The two forms of a point table.  A cache entry holds one of them, or None: no usable point.
+_FluxTable = collections.namedtuple("_FluxTable", "t_flux t_lnw")    # (Npts, Nbands), (Npts,)
+
+
+class _MagTable(collections.namedtuple("_MagTable", "t_src t_mags t_lng t_lnsmf neep npts")):
+    """The plug-in's magnitudes and the kept rows, when all groups shared the one mass grid."""
+    __slots__ = ()
+
+    def as_flux(self, ctx):
+        """The flux table, made at the first revisit: its sum is 3 % faster than the sum from magnitudes."""
+        t_flux, t_lnw = _f64_pair(ctx.torch, self.npts, ctx.Nbands, ctx.dev)
+        _lib.check(ctx.L.brutus_cluster_points_grid(
+            self.npts, ctx.Nbands, self.neep, self.t_src, self.t_mags, self.t_lng, self.t_lnsmf,
+            t_flux, t_lnw, ctx.stream))
+        return _FluxTable(t_flux, t_lnw)
 
 
 # The plug-in is asked for a few secondary-mass-fraction slices at a time; while it works on
@@ -432,212 +523,185 @@ def _group_bounds(nsmf, ngroup, growth=_PIPELINE_GROWTH):
     return [0] + [int(x) for x in b]
 
 
-def _point_table(isochrone, feh, loga, av, rv, dist, corr_coef, smf_grid, grad_smf, eep_grid,
-                 mini_bound, eep_binary_max, Nbands, dev, torch, L, cache, part, part_mags):
-    """Device-resident isochrone points `(flux (Npts, Nbands), lnw (Npts))` of all
-    secondary-mass-fraction slices, or None if no slice has a usable point
-    (cluster.py:336-366), and the number of partial-sum chunks filled on the way: a table
-    met before comes back from the cache with 0 chunks (the caller sums it in one go), a new
-    one is built group by group -- the plug-in's magnitudes go to the device as they are,
-    `brutus_cluster_points` turns them into fluxes and drops the all-NaN points, `part`
-    (brutus_cluster_lnl_part) sums the group into its share of the chunks."""
-    import os
+_TAKES_OUT = {}       # type of plug-in -> does its `get_seds_grid` take `out=`?
+
+
+class _Plugin(object):
+    """What the plug-in offers, behind one operation: `fill(stage, a, b)` puts the magnitudes of
+    slices `a:b` into the staging buffers -- page-locked host memory, or the device tensor for a
+    plug-in that makes them on the device (`on_device`) -- and returns `mini` as float64."""
+
+    def __init__(self, isochrone, smf_grid, nbands, kw):
+        self.iso, self.smf_grid, self.kw = isochrone, smf_grid, kw
+        self.shape = (len(smf_grid), len(kw["eep"]), nbands)
+        self.on_device = hasattr(isochrone, "get_seds_grid_device")
+        self.grid_hook = not self.on_device and hasattr(isochrone, "get_seds_grid")
+        if self.grid_hook and type(isochrone) not in _TAKES_OUT:
+            _TAKES_OUT[type(isochrone)] = \
+                "out" in inspect.signature(isochrone.get_seds_grid).parameters
+        # the slice boundaries of the groups it is asked for: a plug-in that works on the device is
+        # asked once, for all slices (there is no host work to hide behind groups)
+        self.bounds = [0, len(smf_grid)] if self.on_device else _group_bounds(
+            len(smf_grid), int(os.environ.get("BRUTUS_CLUSTER_PIPELINE", _PIPELINE_GROUPS)))
+
+    def fill(self, stage, a, b):
+        iso, smf, kw = self.iso, self.smf_grid[a:b], self.kw
+        if self.on_device:
+            mini = np.asarray(iso.get_seds_grid_device(
+                smf_grid=smf, out=stage.d_mags.view(self.shape)[a:b], **kw), dtype=np.float64)
+            if mini.ndim != 1:
+                raise RuntimeError("get_seds_grid_device must return the one (Neep,) mass "
+                                   "grid all slices share")
+            return mini
+        h_mags = stage.np_mags.reshape(self.shape)
+        if self.grid_hook:
+            out = dict(out=h_mags[a:b]) if _TAKES_OUT[type(iso)] else {}   # straight into pinned memory
+            mags, mini = iso.get_seds_grid(smf_grid=smf, **out, **kw)
+            mags = np.asarray(mags, dtype=np.float64)
+            if not np.may_share_memory(mags, h_mags):
+                h_mags[a:b] = mags
+            return np.asarray(mini, dtype=np.float64)
+        mini = np.empty((b - a, self.shape[1]))
+        for i in range(a, b):
+            seds, params, _ = iso.get_seds(smf=self.smf_grid[i], **kw)
+            h_mags[i] = seds
+            mini[i - a] = params['mini']
+        return mini
+
+
+class _Build(object):
+    """A new point table, group by group: `shared_group` or `slice_group` by the shape of the group's
+    mass grid (`c0`, `nc`: its first partial-sum chunk and their number; `off`: the points so far),
+    then `table()`."""
+
+    def __init__(self, ctx, stage, ngroup, smf_grid, grad_smf, eep_grid, eep_binary_max, cache):
+        self.ctx, self.stage, self.ngroup, self.cache = ctx, stage, ngroup, cache
+        self.neep = len(eep_grid)
+        stage.groups(ngroup, self.neep)
+        stage.lnsmf(smf_grid, grad_smf)
+        self.late = eep_grid > eep_binary_max               # evolved stars: first slice only
+        self.ln_gsmf = np.log(grad_smf)
+        self.mini0 = self.pos = self.d_lng = None
+        self.t_flux = self.t_lnw = None    # (flux table: only for per-slice mass grids, on demand)
+        self.off = self.shared = 0
+
+    def shared_group(self, g, a, b, c0, nc, mini):
+        """One `(Neep,)` mass grid for all slices: 2 000 logarithms per call, kept rows that are
+        looked up; the sum itself forms weights and fluxes, from the staged magnitudes."""
+        st, ctx = self.stage, self.ctx
+        if self.mini0 is None:
+            self.mini0 = mini
+            gmini = np.gradient(mini)
+            self.pos = gmini > 0.
+            self.d_lng = st.lng_row(g, gmini, self.pos)
+        elif not (mini is self.mini0 or np.array_equal(mini, self.mini0)):
+            # (a "shared" grid is one grid: the table kept for a revisit holds ONE vector of
+            # ln(d mini) for all groups, and so does the reference, whose `mini` comes from
+            # the EEP / [Fe/H] / age of the isochrone alone, cluster.py:342-349)
+            raise RuntimeError("isochrone plug-in returned different 1-D mass grids for "
+                               "different groups of mass fractions; return a (slices, EEP) "
+                               "array if the grid depends on the slice")
+        n = st.rows(g, self.pos, a, b, self.late, self.neep)
+        _lib.check(ctx.L.brutus_cluster_lnl_part_mags(
+            ctx.Nobjs, ctx.Nbands, n, self.neep, st.t_src[g] if n else None, st.p_mags, self.d_lng,
+            st.p_lnsmf, *ctx.obj_args(), c0, nc, ctx.stream))
+        self.off += n
+        self.shared += 1
+
+    def slice_group(self, g, a, b, c0, nc, mini):
+        """A mass grid per slice, `(b - a, Neep)`: weights and kept rows are made here, the kept
+        magnitudes become the group's share of the flux table, and that is summed."""
+        st, ctx, neep, off = self.stage, self.ctx, self.neep, self.off
+        gmini = np.gradient(mini, axis=1)
+        pos = gmini > 0.
+        lnw = np.where(pos, np.log(gmini) + self.ln_gsmf[a:b, None], -np.inf)
+        lnw[(1 if a == 0 else 0):, self.late] = -np.inf     # (slice 0 keeps its evolved stars)
+        src = _kept_rows(pos, a, b, self.late, neep)
+        n = src.size
+        if self.t_flux is None:
+            self.t_flux, self.t_lnw = st.flux_pair(fresh=self.cache)
+        if n:
+            st.np_lnw.reshape(-1, neep)[a:b] = lnw
+            st.d_lnw[a * neep:b * neep].copy_(st.h_lnw[a * neep:b * neep], non_blocking=True)
+            st.put_rows(g, src)
+            _lib.check(ctx.L.brutus_cluster_points(
+                n, ctx.Nbands, st.t_src[g], st.d_mags, st.d_lnw, self.t_flux[off:],
+                self.t_lnw[off:], ctx.stream))
+        _lib.check(ctx.L.brutus_cluster_lnl_part(
+            ctx.Nobjs, ctx.Nbands, n, self.t_flux[off:off + n] if n else None,
+            self.t_lnw[off:off + n] if n else None, *ctx.obj_args(), c0, nc, ctx.stream))
+        self.off += n
+
+    def table(self):
+        """What the cache keeps: None without a usable point; the magnitudes and kept rows if all groups
+        shared the one mass grid (copies: the next call stages in the same buffers); else the fluxes."""
+        st = self.stage
+        if not self.off:
+            return None
+        if self.shared == self.ngroup:
+            return _MagTable(st.all_rows(), st.d_mags.clone(), self.d_lng.clone(), st.d_lnsmf,
+                             self.neep, self.off) if self.cache else None
+        if self.shared:
+            raise RuntimeError("isochrone plug-in returned a shared mass grid for some groups of "
+                               "mass fractions and per-slice grids for others")
+        return _FluxTable(self.t_flux[:self.off], self.t_lnw[:self.off])
+
+
+def _point_table(ctx, isochrone, pars, smf_grid, grad_smf, eep_grid, mini_bound, eep_binary_max,
+                 cache):
+    """The isochrone points of all secondary-mass-fraction slices (cluster.py:336-366):
+    `(npts, table, nchunk)`, `npts == 0` if no slice has a usable point.  A table met before
+    comes back from the cache as a `_FluxTable` with 0 chunks: the caller sums it in one go.  A
+    new one is built group by group -- the plug-in's magnitudes go to the device as they are and
+    the group is summed into its share of the `nchunk` partial-sum chunks while the plug-in works
+    on the next one -- and `table` is what the cache keeps of it."""
+    feh, loga, av, rv, dist, corr_coef = pars
     key = (id(isochrone), getattr(isochrone, "cache_token", None), feh, loga, av, rv, dist,
            None if corr_coef is None else tuple(corr_coef), smf_grid.tobytes(),
-           eep_grid.tobytes(), mini_bound, eep_binary_max, str(dev))
-    if cache:
-        tab = _lru_get(_TABLE_CACHE, key)
-        if tab is not None:
-            tab = tab[0]
-            if tab is not None and tab[0] == "mags":
-                # first revisit of a table kept as magnitudes: make the flux table once (the sum
-                # over fluxes is 3 % faster than the one that forms them on the way)
-                _, t_src, t_mags, t_lng, t_lnsmf, neep_, npts = tab
-                t_flux = torch.empty((npts, Nbands), dtype=torch.float64, device=dev)
-                t_lnw = torch.empty(npts, dtype=torch.float64, device=dev)
-                _lib.check(L.brutus_cluster_points_grid(
-                    npts, Nbands, neep_, t_src, t_mags, t_lng, t_lnsmf, t_flux, t_lnw,
-                    _stream_ptr(torch)))
-                tab = ("flux", t_flux, t_lnw)
-                _lru_put(_TABLE_CACHE, key, (tab, isochrone), _TABLE_CACHE_MAX)
-            return tab, 0
+           eep_grid.tobytes(), mini_bound, eep_binary_max, str(ctx.dev))
+    hit = _lru_get(_TABLE_CACHE, key) if cache else None
+    if hit is not None:
+        tab = hit[0]
+        if isinstance(tab, _MagTable):              # first revisit of a table kept as magnitudes
+            tab = tab.as_flux(ctx)
+            _lru_put(_TABLE_CACHE, key, (tab, isochrone), _TABLE_CACHE_MAX)
+        return (0 if tab is None else tab.t_lnw.numel()), tab, 0
     _mark("table key")
-    kw = dict(feh=feh, loga=loga, av=av, rv=rv, eep=eep_grid, dist=dist,
-              mini_bound=mini_bound, eep_binary_max=eep_binary_max, corr_params=corr_coef)
+    plug = _Plugin(isochrone, smf_grid, ctx.Nbands, dict(
+        feh=feh, loga=loga, av=av, rv=rv, eep=eep_grid, dist=dist, mini_bound=mini_bound,
+        eep_binary_max=eep_binary_max, corr_params=corr_coef))
     nsmf, neep = len(smf_grid), len(eep_grid)
-    nrow = nsmf * neep
-    # a plug-in that makes its magnitudes on the device (seds.Isochrone) is asked once, for all
-    # slices, straight into the staging tensor: there is no host work to hide behind groups
-    dev_hook = hasattr(isochrone, "get_seds_grid_device")
-    bounds = [0, nsmf] if dev_hook else \
-        _group_bounds(nsmf, int(os.environ.get("BRUTUS_CLUSTER_PIPELINE", _PIPELINE_GROUPS)))
-    ngroup = len(bounds) - 1
-    nchunk = L.brutus_cluster_chunks()
+    bounds = plug.bounds
+    ngroup, nchunk = len(bounds) - 1, ctx.L.brutus_cluster_chunks()
     cbounds = [0]                                   # partial-sum chunks in proportion, >= 1 each
     for g in range(ngroup):
         cbounds.append(min(max(nchunk * bounds[g + 1] // nsmf, cbounds[-1] + 1),
                            nchunk - (ngroup - 1 - g)))
-    stage = _staging(nrow, Nbands, dev, torch)
-    h_mags = stage.h_mags.numpy().reshape(nsmf, neep, Nbands)
-    h_lnw = stage.h_lnw.numpy().reshape(nsmf, neep)
-    grid_hook = hasattr(isochrone, "get_seds_grid")
-    if grid_hook and stage.hook_out.get(type(isochrone)) is None:   # does the hook take `out=`?
-        import inspect
-        stage.hook_out[type(isochrone)] = \
-            "out" in inspect.signature(isochrone.get_seds_grid).parameters
-    t_flux = t_lnw = None          # (flux table: only for per-slice mass grids, made on demand)
-
-    def flux_table():
-        if cache:      # a cached table keeps its tensors; without the cache one pair is reused
-            return (torch.empty((nrow, Nbands), dtype=torch.float64, device=dev),
-                    torch.empty(nrow, dtype=torch.float64, device=dev))
-        if getattr(stage, "t_flux", None) is None:
-            stage.t_flux = torch.empty((nrow, Nbands), dtype=torch.float64, device=dev)
-            stage.t_lnw = torch.empty(nrow, dtype=torch.float64, device=dev)
-        return stage.t_flux, stage.t_lnw
-    if stage.src is None or len(stage.src) != ngroup or tuple(stage.h_lng.shape) != (ngroup, neep):
-        stage.src, stage.t_src, stage.srckey = [None] * ngroup, [None] * ngroup, [None] * ngroup
-        stage.h_lng = torch.empty((ngroup, neep), dtype=torch.float64).pin_memory()
-        stage.d_lng = torch.empty((ngroup, neep), dtype=torch.float64, device=dev)
-    smfkey = smf_grid.tobytes()
-    if getattr(stage, "smfkey", None) != smfkey:
-        with np.errstate(all="ignore"):
-            stage.smfkey, stage.d_lnsmf = smfkey, to_device(np.log(grad_smf), np.float64, dev)
-            stage.p_lnsmf = _lib.fixed(stage.d_lnsmf, "d", "float64")
-    d_lnsmf, mini0, d_lng, posb, pos = stage.d_lnsmf, None, None, None, None
-    late = eep_grid > eep_binary_max                    # evolved stars: first slice only
-    lateb = late.tobytes()
-    ln_gsmf = np.log(grad_smf)
-    stream = _stream_ptr(torch)
-    off = shared = 0
+    stage = _staging(nsmf * neep, ctx.Nbands, ctx.dev, ctx.torch)
+    build = _Build(ctx, stage, ngroup, smf_grid, grad_smf, eep_grid, eep_binary_max, cache)
     with warnings.catch_warnings(), np.errstate(all="ignore"):
         warnings.simplefilter("ignore")
         for g in range(ngroup):
             a, b = bounds[g], bounds[g + 1]
-            c0, c1 = cbounds[g], cbounds[g + 1]
-            if dev_hook:
-                mini = np.asarray(isochrone.get_seds_grid_device(
-                    smf_grid=smf_grid[a:b], out=stage.d_mags.view(nsmf, neep, Nbands)[a:b], **kw),
-                    dtype=np.float64)
-                if mini.ndim != 1:
-                    raise RuntimeError("get_seds_grid_device must return the one (Neep,) mass "
-                                       "grid all slices share")
-            elif grid_hook:
-                if stage.hook_out[type(isochrone)]:             # straight into pinned memory
-                    mags, mini = isochrone.get_seds_grid(smf_grid=smf_grid[a:b], out=h_mags[a:b],
-                                                         **kw)
-                else:
-                    mags, mini = isochrone.get_seds_grid(smf_grid=smf_grid[a:b], **kw)
-                mags = np.asarray(mags, dtype=np.float64)
-                mini = np.asarray(mini, dtype=np.float64)
-                if not np.may_share_memory(mags, h_mags):
-                    h_mags[a:b] = mags
-            else:
-                mini = np.empty((b - a, neep))
-                for i in range(a, b):
-                    seds, params, _ = isochrone.get_seds(smf=smf_grid[i], **kw)
-                    h_mags[i] = seds
-                    mini[i - a] = params['mini']
+            mini = plug.fill(stage, a, b)
             _mark("plug-in %d" % g)
             # the group's host -> device copy starts now, from page-locked memory, and runs
-            # under the host arithmetic below
-            if not dev_hook:
+            # under the host arithmetic of its stage
+            if not plug.on_device:
                 stage.d_mags[a * neep:b * neep].copy_(stage.h_mags[a * neep:b * neep],
                                                       non_blocking=True)
-            if mini.ndim == 1:
-                # one mass grid for all slices: 2 000 logarithms per call, the (slice, EEP) table
-                # of weights is formed on the device and the kept rows are looked up, not rebuilt
-                if mini0 is not None and not (mini is mini0 or np.array_equal(mini, mini0)):
-                    # (a "shared" grid is one grid: the table kept for a revisit holds ONE vector of
-                    # ln(d mini) for all groups, and so does the reference, whose `mini` comes from
-                    # the EEP / [Fe/H] / age of the isochrone alone, cluster.py:342-349)
-                    raise RuntimeError("isochrone plug-in returned different 1-D mass grids for "
-                                       "different groups of mass fractions; return a (slices, EEP) "
-                                       "array if the grid depends on the slice")
-                if mini0 is None:
-                    mini0 = mini
-                    gmini = np.gradient(mini)
-                    pos = gmini > 0.
-                    h_lng = stage.h_lng.numpy()[g]
-                    h_lng[...] = -np.inf
-                    np.log(gmini, out=h_lng, where=pos)
-                    d_lng = stage.d_lng[g]
-                    d_lng.copy_(stage.h_lng[g], non_blocking=True)
-                    posb = pos.tobytes()
-                srckey = (posb, a, b, lateb)
-                if stage.srckey[g] != srckey:
-                    keep = np.repeat(pos[None, :], b - a, axis=0)
-                    keep[(1 if a == 0 else 0):, late] = False        # (slice 0 keeps its evolved stars)
-                    src = (np.flatnonzero(keep) + a * neep).astype(np.int32)
-                    stage.src[g], stage.srckey[g] = src, srckey
-                    stage.t_src[g] = to_device(src, np.int32, dev)
-                n = stage.src[g].size
-                if os.environ.get("BRUTUS_CLUSTER_MAGS", "1") != "0":
-                    # fluxes and weights are formed by the sum itself, from the staged magnitudes
-                    part_mags(stage.t_src[g], stage.p_mags, d_lng, stage.p_lnsmf, neep, n, c0, c1 - c0)
-                    _mark("group %d out" % g)
-                    off += n
-                    shared += 1
-                    continue
-                if t_flux is None:
-                    t_flux, t_lnw = flux_table()
-                if n:
-                    _lib.check(L.brutus_cluster_points_grid(
-                        n, Nbands, neep, stage.t_src[g], stage.d_mags, d_lng, d_lnsmf,
-                        t_flux[off:], t_lnw[off:], stream))
-            else:
-                gmini = np.gradient(mini, axis=1)
-                keep = gmini > 0.
-                lnw = np.where(keep, np.log(gmini) + ln_gsmf[a:b, None], -np.inf)
-                first = 1 if a == 0 else 0                  # (slice 0 keeps its evolved stars)
-                keep[first:, late] = False
-                lnw[first:, late] = -np.inf
-                src = (np.flatnonzero(keep) + a * neep).astype(np.int32)
-                n = src.size
-                if t_flux is None:
-                    t_flux, t_lnw = flux_table()
-                if n:
-                    h_lnw[a:b] = lnw
-                    stage.d_lnw[a * neep:b * neep].copy_(stage.h_lnw[a * neep:b * neep],
-                                                         non_blocking=True)
-                    if stage.src[g] is None or not np.array_equal(stage.src[g], src):
-                        stage.src[g] = src                                # (rarely changes)
-                        stage.t_src[g] = to_device(src, np.int32, dev)
-                    stage.srckey[g] = None
-                    _lib.check(L.brutus_cluster_points(
-                        n, Nbands, stage.t_src[g], stage.d_mags, stage.d_lnw, t_flux[off:],
-                        t_lnw[off:], stream))
-            part(t_flux[off:off + n], t_lnw[off:off + n], n, c0, c1 - c0)
+            group = build.shared_group if mini.ndim == 1 else build.slice_group
+            group(g, a, b, cbounds[g], cbounds[g + 1] - cbounds[g], mini)
             _mark("group %d out" % g)
-            off += n
-    if not off:
-        tab = None
-    elif shared == ngroup:
-        # every group shared the one mass grid: the table IS the magnitudes + the kept rows.
-        # Kept for a revisit as copies of the staging buffers (they are reused by the next call).
-        tab = None
-        if cache:
-            srckey = tuple(stage.srckey)
-            if getattr(stage, "src_all_key", None) != srckey:
-                stage.src_all_key, stage.t_src_all = srckey, torch.cat(stage.t_src)
-            # (d_lnsmf and t_src_all are replaced, never rewritten in place, when their keys
-            # change -- stage.smfkey / stage.src_all_key above --, so the table may share them)
-            tab = ("mags", stage.t_src_all, stage.d_mags.clone(), d_lng.clone(), d_lnsmf, neep, off)
-        else:
-            tab = ("mags",)                                  # (summed already; not kept)
-    elif shared:
-        raise RuntimeError("isochrone plug-in returned a shared mass grid for some groups of "
-                           "mass fractions and per-slice grids for others")
-    else:
-        tab = ("flux", t_flux[:off], t_lnw[:off])
+    tab = build.table()
     if cache:      # (the plug-in object is kept alive with its tables: `id` stays unique)
         _lru_put(_TABLE_CACHE, key, (tab, isochrone), _TABLE_CACHE_MAX)
-    return tab, nchunk
+    return build.off, tab, nchunk
 
 
 # ---- many thetas per call: the catalogue resident on the device ----------------------------------
 def unpack_thetas(thetas, cluster_params, offsets, corr_params, nbands):
-    """Rows of `thetas (K, Ncol)` unpacked as `_isochrone_loglike` unpacks one `theta`:
+    """Rows of `thetas (K, Ncol)` unpacked as `isochrone_loglike` unpacks one `theta`:
     `(cp (K, 6), Xb (K, nbands), corr (K, 4) or None)` with `cp` = `(feh, loga, av, rv, dist,
     fout)`, `fout` clipped to `[1e-10, 1 - 1e-10]`.  A group declared `'fixed'` (offsets: ones,
     corrections: None, the plug-in's defaults) still takes its columns' places, so the groups
@@ -645,37 +709,14 @@ def unpack_thetas(thetas, cluster_params, offsets, corr_params, nbands):
     thetas = np.asarray(thetas, dtype=np.float64)
     if thetas.ndim != 2:
         raise ValueError("`thetas` must have shape (K, Nparams); got %s" % (thetas.shape,))
-    fixed = lambda v: isinstance(v, str) and v == 'fixed'
-    K = thetas.shape[0]
-    groups = [(cluster_params, 6)]
-    groups.append((None, nbands) if fixed(offsets) else (offsets, nbands))
-    groups.append((None, 4) if fixed(corr_params) else (corr_params, 4))
-    # the place of every value that is read, and the place after the last of them
-    pos, need, cols = 0, 0, []
-    for spec, n in groups:
-        col = [None] * n
-        if spec is None:
-            pos += n
-        else:
-            for i in range(n):
-                if (isinstance(spec, str) and spec == 'free') or spec[i] is None:
-                    col[i] = pos
-                    pos += 1
-                    need = pos
-        cols.append(col)
+    cols, need = _theta_plan(cluster_params, offsets, corr_params, nbands)
     if thetas.shape[1] != need:
         raise ValueError("`thetas` must have %d columns for these `cluster_params`, `offsets` and "
                          "`corr_params` (%d given)" % (need, thetas.shape[1]))
-
-    def take(spec, col, n):
-        out = np.empty((K, n))
-        for i in range(n):
-            out[:, i] = thetas[:, col[i]] if col[i] is not None else spec[i]
-        return out
-    cp = take(cluster_params, cols[0], 6)
+    cp = _read(thetas, cluster_params, cols[0])
     cp[:, 5] = np.maximum(np.minimum(1. - 1e-10, cp[:, 5]), 1e-10)
-    Xb = np.ones((K, nbands)) if fixed(offsets) else take(offsets, cols[1], nbands)
-    corr = None if fixed(corr_params) else take(corr_params, cols[2], 4)
+    Xb = np.ones((len(thetas), nbands)) if cols[1] is None else _read(thetas, offsets, cols[1])
+    corr = None if cols[2] is None else _read(thetas, corr_params, cols[2])
     return cp, Xb, corr
 
 
@@ -685,7 +726,6 @@ _BATCH_BYTES = 1 << 30        # device memory of one pass of IsochroneLikelihood
 def _log10(x):
     """The C library's log10, NaN / -inf where it has them (the library forms the distance modulus
     of the single call with it)."""
-    import math
     return math.log10(x) if x > 0. else (-np.inf if x == 0. else np.nan)
 
 
@@ -825,8 +865,7 @@ class IsochroneLikelihood(object):
             fout = float(cp[j, 5])
             with np.errstate(all="ignore"):         # (a distance <= 0: NaN, as in the single call)
                 iso_th[j, 5] = 5. * _log10(float(cp[j, 4])) - 5.
-            obj_th[j, 1] = np.log(self.cluster_prob * (1. - fout))
-            obj_th[j, 2] = np.log(1. - self.cluster_prob * (1. - fout))
+            obj_th[j, 1:3] = _ln_mixture(self.cluster_prob, fout)
         obj_th[:, _OBJ_NTH:] = Xb
         n_iso, n_obj = cap * _ISO_NTH, k * (_OBJ_NTH + nb)
         t_iso, t_obj = self._theta[:k * _ISO_NTH], self._theta[n_iso:n_iso + n_obj]

@@ -382,6 +382,47 @@ def test_plugin_groups_grow_and_cover_every_slice():
             assert np.all(np.diff(sizes) >= -1)              # (growing, up to rounding)
 
 
+def _kept_rows_by_hand(pos, a, b, late, neep):
+    """Slice by slice, point by point: a row is kept where the initial mass increases, the
+    evolved stars in slice 0 only (reference cluster.py:351-357)."""
+    rows = []
+    for s in range(a, b):
+        p = pos if pos.ndim == 1 else pos[s - a]
+        rows += [s * neep + e for e in range(neep) if p[e] and not (late[e] and s > 0)]
+    return np.array(rows, dtype=np.int32)
+
+
+@pytest.mark.parametrize("late_kind", ["none", "mixed", "all"])
+def test_kept_rows_of_a_group_and_of_all_groups(late_kind):
+    """`_kept_rows`: groups that do and do not hold slice 0, one slice wide and wider, a mass
+    gradient with holes (shared by the slices, or one per slice), no / some / only evolved
+    stars; the lists of consecutive groups put together are the list of the whole grid."""
+    from brutus_amd.cluster import _group_bounds, _kept_rows
+    rng = np.random.RandomState(6)
+    neep, nsmf = 23, 7
+    late = {"none": np.zeros(neep, bool), "mixed": np.arange(neep) > 13,
+            "all": np.ones(neep, bool)}[late_kind]
+    pos = rng.uniform(size=neep) > 0.25                          # holes
+    assert not pos.all() and pos.any()
+    pos2 = rng.uniform(size=(nsmf, neep)) > 0.25
+    for a, b in ((0, 1), (0, 3), (1, 2), (2, 7), (6, 7), (0, 7)):
+        for p in (pos, pos2[a:b], np.ones(neep, bool), np.zeros(neep, bool)):
+            keep, p0 = p.copy(), p.copy()
+            got = _kept_rows(p, a, b, late, neep)
+            assert np.array_equal(p, p0)                          # (the argument is not edited)
+            assert got.dtype == np.int32 and np.array_equal(got, _kept_rows_by_hand(keep, a, b, late, neep))
+            assert got.size == 0 or (a * neep <= got.min() and got.max() < b * neep)
+    for ngroup in (1, 2, 3, 7):
+        bounds = _group_bounds(nsmf, ngroup)
+        for p, whole in ((pos, pos), (pos2, pos2)):
+            parts = [_kept_rows(p if p.ndim == 1 else p[a:b], a, b, late, neep)
+                     for a, b in zip(bounds[:-1], bounds[1:])]
+            assert np.array_equal(np.concatenate(parts), _kept_rows(whole, 0, nsmf, late, neep))
+    if late_kind == "all":      # only slice 0 is left
+        assert np.array_equal(_kept_rows(pos, 0, nsmf, late, neep), np.flatnonzero(pos))
+        assert _kept_rows(pos, 1, nsmf, late, neep).size == 0
+
+
 def test_cache_keys_follow_content_not_identity():
     """The cluster caches are keyed by address, layout and a digest of the CONTENT of the
     catalogue arrays (CPU-only check of the helpers): an in-place edit, a copy, a view with
@@ -480,3 +521,123 @@ def test_cluster_magnitude_path_counts_a_band_by_its_magnitude(dim_prior):
     assert relerr(want, out["flux"]) < 1e-10
     assert relerr(want, out["mags"]) < 1e-10
     assert relerr(out["flux"], out["mags"]) < 1e-13
+
+
+# ---- the plug-in kinds, mass-grid shapes and cache states of the point-table builder, on the
+# smallest inputs on which all of them are live: three groups of one slice, EEPs on both sides of
+# `eep_binary_max`, NaN bands, objects without parallax ----------------------------------------
+class _SedsOnly(object):
+    """The reference's plug-in surface only."""
+
+    def __init__(self, iso):
+        self.iso = iso
+
+    def get_seds(self, **kw):
+        return self.iso.get_seds(**kw)
+
+
+@pytest.fixture(scope="module")
+def tiny():
+    from brutus_amd import cluster, synth
+    iso = synth.TableIsochrone(nbands=5, neep=33, smf_grid=(0., 0.5, 1.))
+    phot, err, par, perr = synth.make_cluster(iso, 40)
+    kw = dict(parallax=par, parallax_err=perr, eep_grid=iso.eep_grid, smf_grid=iso.smf_grid,
+              return_lnls=True)
+    assert np.isnan(phot).any() and np.isnan(par).any()
+    assert (iso.eep_grid > 480.).any() and (iso.eep_grid < 480.).any()
+    ref = cluster.isochrone_loglike(THETA, _SedsOnly(iso), phot, err, cache=False, **kw)
+    return iso, phot, err, kw, ref
+
+
+def _same(a, b, tol=1e-12):
+    return relerr(a[1], b[1]) < tol and abs(a[0] - b[0]) <= tol * abs(a[0])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("takes_out", [True, False])
+def test_grid_hook_with_per_slice_masses_changes_nothing(tiny, takes_out):
+    """A `get_seds_grid` hook that returns `mini` as `(slices, Neep)` goes through the flux
+    table group by group; it gives what the same hook with the one shared grid and what a
+    `get_seds`-only plug-in give (1e-12, the bound of
+    test_batched_plugin_hook_and_caches_change_nothing for the same comparison)."""
+    from brutus_amd import cluster
+    iso, phot, err, kw, ref = tiny
+    asked = []
+
+    def two_d(mini, smf_grid):
+        asked.append(len(smf_grid))
+        return np.broadcast_to(mini, (len(smf_grid), mini.size)).copy()
+
+    class WithOut(_SedsOnly):
+        def get_seds_grid(self, smf_grid=None, out=None, **kw):
+            mags, mini = self.iso.get_seds_grid(smf_grid=smf_grid, out=out, **kw)
+            return mags, two_d(mini, smf_grid)
+
+    class WithoutOut(_SedsOnly):
+        def get_seds_grid(self, smf_grid=None, **kw):
+            mags, mini = self.iso.get_seds_grid(smf_grid=smf_grid, **kw)
+            return mags, two_d(mini, smf_grid)
+
+    plug = (WithOut if takes_out else WithoutOut)(iso)
+    shared = cluster.isochrone_loglike(THETA, iso, phot, err, cache=False, **kw)
+    got = cluster.isochrone_loglike(THETA, plug, phot, err, cache=False, **kw)
+    assert asked == [1, 1, 1]
+    assert np.all(np.isfinite(ref[1])) and _same(ref, shared) and _same(ref, got) and _same(shared, got)
+    cluster.clear_caches()
+    for n in range(3):          # built and kept as fluxes, then met again
+        assert _same(ref, cluster.isochrone_loglike(THETA, plug, phot, err, **kw)), n
+    assert asked == [1, 1, 1] * 2
+
+
+@pytest.mark.gpu
+def test_plugin_contract_errors(tiny):
+    """The three things a plug-in must not do with its mass grids, each with its message."""
+    from brutus_amd import cluster
+    iso, phot, err, kw, _ = tiny
+
+    class Hook(_SedsOnly):
+        def __init__(self, iso, change):
+            self.iso, self.change, self.calls = iso, change, 0
+
+        def get_seds_grid(self, smf_grid=None, **kw):
+            mags, mini = self.iso.get_seds_grid(smf_grid=smf_grid, **kw)
+            self.calls += 1
+            return mags, self.change(mini, self.calls, len(smf_grid))
+
+    drifting = Hook(iso, lambda mini, call, n: mini * (1. + 0.01 * (call - 1)))
+    with pytest.raises(RuntimeError, match="different 1-D mass grids for different groups"):
+        cluster.isochrone_loglike(THETA, drifting, phot, err, cache=False, **kw)
+    mixed = Hook(iso, lambda mini, call, n: mini if call == 1 else np.tile(mini, (n, 1)))
+    with pytest.raises(RuntimeError, match="a shared mass grid for some groups of mass fractions "
+                                           "and per-slice grids for others"):
+        cluster.isochrone_loglike(THETA, mixed, phot, err, cache=False, **kw)
+    assert mixed.calls == 3                                  # (raised by the end stage)
+
+    class FakeDevice(_SedsOnly):
+        def get_seds_grid_device(self, smf_grid=None, out=None, **kw):
+            import torch
+            mags, mini = self.iso.get_seds_grid(smf_grid=smf_grid, **kw)
+            out.copy_(torch.from_numpy(np.ascontiguousarray(mags)))
+            return np.tile(mini, (len(smf_grid), 1))
+    with pytest.raises(RuntimeError, match=r"must return the one \(Neep,\) mass grid all slices share"):
+        cluster.isochrone_loglike(THETA, FakeDevice(iso), phot, err, cache=False, **kw)
+
+
+@pytest.mark.gpu
+def test_first_call_revisit_and_flux_table_return_equal_bytes(tiny):
+    """With `cache=True` the first call sums the groups from the staged magnitudes and keeps
+    them, the second turns what was kept into the flux table, the third sums that table: the
+    three return the same bytes."""
+    from brutus_amd import cluster
+    iso, phot, err, kw, ref = tiny
+    cluster.clear_caches()
+    forms, calls = [], []
+    for n in range(3):
+        calls.append(cluster.isochrone_loglike(THETA, iso, phot, err, cache=True, **kw))
+        (tab, _), = cluster._TABLE_CACHE.values()
+        forms.append(type(tab))
+    assert forms == [cluster._MagTable, cluster._FluxTable, cluster._FluxTable]
+    for c in calls[1:]:
+        assert c[0] == calls[0][0] and np.array_equal(c[1], calls[0][1])
+    assert _same(ref, calls[0])
+    cluster.clear_caches()

@@ -1,7 +1,8 @@
 """CPU: the batched cluster likelihood as far as it goes without a GPU -- the two entry points
 (`brutus_iso_seds_grid_batch`, `brutus_cluster_lnl_batch`) reject bad arguments before any HIP
-call and size their workspaces, `cluster.unpack_thetas` unpacks rows as `_isochrone_loglike`
-unpacks one theta, and the batched sum kernel keeps its registers."""
+call and size their workspaces, `cluster.unpack_thetas` unpacks rows as `isochrone_loglike`
+unpacks one theta (one column plan, `_theta_plan`, for both), and the batched sum kernel keeps its
+registers."""
 import ctypes as C
 import os
 import re
@@ -146,10 +147,22 @@ def test_cluster_batch_rejects_bad_arguments_without_a_gpu():
     assert _cluster_call(L, ntheta=0) == EINVAL and err().startswith("bad cluster batch dimensions")
 
 
-# ---- unpack_thetas against the `_take` sequence of `_isochrone_loglike` ----------------------------
+# ---- unpack_thetas against the reference's read-in-order sequence (cluster.py:227-290) ------------
+def _take(theta, pos, spec, n):
+    """Read `n` values: from `theta` where `spec[i] is None`, else the fixed
+    value (the reference's 'free' / per-entry constraint convention)."""
+    out = np.zeros(n)
+    for i in range(n):
+        if spec == 'free' or spec[i] is None:
+            out[i] = theta[pos]
+            pos += 1
+        else:
+            out[i] = spec[i]
+    return out, pos
+
+
 def _unpack_one(theta, cluster_params, offsets, corr_params, nbands):
-    """`_isochrone_loglike`'s own lines (cluster.py, "unpack theta")."""
-    from brutus_amd.cluster import _take
+    """One `theta` read value by value, in order, as the reference does."""
     pos = 0
     (feh, loga, av, rv, dist, fout), pos = _take(theta, pos, cluster_params, 6)
     fout = max(min(1. - 1e-10, fout), 1e-10)
@@ -202,6 +215,40 @@ def test_unpack_thetas_equals_take_row_by_row(name):
             cluster.unpack_thetas(np.ones((2, wrong)), nbands=5, **kw)
     with pytest.raises(ValueError, match=r"\(K, Nparams\)"):
         cluster.unpack_thetas(np.ones(ncol), nbands=5, **kw)
+
+
+def test_theta_plan_places_every_value_and_the_end():
+    """`_theta_plan`, the one column plan of the single call and of `unpack_thetas`: `'free'`,
+    lists mixing None and fixed entries, `'fixed'` offsets and corrections skipping their
+    columns, and the place after the last value that is read."""
+    from brutus_amd.cluster import _read, _theta_plan
+    cols, end = _theta_plan('free', 'free', 'free', 5)
+    assert cols == [list(range(6)), list(range(6, 11)), list(range(11, 15))] and end == 15
+    cols, end = _theta_plan('free', 'fixed', 'fixed', 5)
+    assert cols == [list(range(6)), None, None] and end == 6
+    cols, end = _theta_plan([None, None, None, 3.3, 900., None], [1.0] + [None] * 4, 'fixed', 5)
+    assert cols == [[0, 1, 2, None, None, 3], [None, 4, 5, 6, 7], None] and end == 8
+    # 'fixed' offsets keep their places: the corrections are read past them
+    cols, end = _theta_plan('free', 'fixed', [0.1, None, 25., None], 5)
+    assert cols == [list(range(6)), None, [None, 11, None, 12]] and end == 13
+    # 'fixed' corrections after free offsets are not read: the end is the last offset's
+    cols, end = _theta_plan('free', [None, 1., None], 'fixed', 3)
+    assert cols == [list(range(6)), [6, None, 7], None] and end == 8
+    # nothing free at all; six bands (the cluster parameters are never 'fixed' as a whole)
+    cols, end = _theta_plan([0., 9., 0., 3.3, 1e3, 0.1], 'fixed', [0., 0., 30., 0.5], 6)
+    assert cols == [[None] * 6, None, [None] * 4] and end == 0
+    # a single theta longer than `end` is read as the reference reads it
+    for name, (kw, ncol) in sorted(_UNPACK_CASES.items()):
+        th = np.random.RandomState(4).uniform(0.1, 0.9, size=ncol + 3)
+        cols, end = _theta_plan(nbands=5, **kw)
+        assert end == ncol, name
+        want = _unpack_one(th, nbands=5, **kw)
+        assert np.array_equal(_read(th, kw["cluster_params"], cols[0]), want[0]), name
+        if cols[1] is not None:
+            assert np.array_equal(_read(th, kw["offsets"], cols[1]), want[1]), name
+        assert (cols[2] is None) == (want[2] is None)
+        if cols[2] is not None:
+            assert np.array_equal(_read(th, kw["corr_params"], cols[2]), want[2]), name
 
 
 def test_batched_sum_kernel_does_not_spill():
