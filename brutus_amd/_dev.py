@@ -19,6 +19,9 @@ def _stream_ptr(torch):
 
 def to_device(a, dtype, dev):
     """`a` as a C-contiguous array of `dtype`, copied to device `dev`: what a `d_` parameter of
-    that element type takes."""
+    that element type takes.  A tensor (the device form of `pdf.los_tables`) stays where it is:
+    on `dev` with that element type it is handed on as it is, never copied through the host."""
     import torch
+    if isinstance(a, torch.Tensor):
+        return a.to(device=dev, dtype=torch.from_numpy(np.empty(0, dtype=dtype)).dtype).contiguous()
     return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(dev)

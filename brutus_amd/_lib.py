@@ -289,6 +289,15 @@ BATCH_SIGNATURES = {
                                            _df64, _i32, _df64, _dv, _sz, _df64, _df64, _stream]),
 }
 
+# and for include/brutus_amd_dust.h (brutus_amd.dust; tests/test_dust_host.py compares this table
+# with that header parameter by parameter)
+DUST_SIGNATURES = {
+    "brutus_dust_lb2pix": (C.c_int, [_i64, _df64, _df64, _i32, _di64, _stream]),
+    "brutus_dust_query": (C.c_int, [_i32, _hi32, _hi64, _hi64, _di64, _di64, _i64, _i32, _df32, _df32,
+                                    _df64, _i64, _df64, _df64, _di64, _df32, _df32, _df64, _di32,
+                                    _stream]),
+}
+
 
 def lib():
     """Load (once) and return the shared library; raise loudly if absent."""
@@ -306,7 +315,8 @@ def lib():
     # runtime then finds "no ROCm-capable device".
     import torch  # noqa: F401
     L = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(BATCH_SIGNATURES.items()):
+    for name, (res, args) in (list(SIGNATURES.items()) + list(BATCH_SIGNATURES.items())
+                              + list(DUST_SIGNATURES.items())):
         fn = getattr(L, name)   # AttributeError if the .so is stale
         fn.restype = res
         fn.argtypes = args

@@ -1310,9 +1310,9 @@ class BruteForce(object):
         if lndustprior is None and dustfile is not None:
             # reference fitting.py:1391-1395: the built-in 3-D dust prior.  Here the
             # line-of-sight profiles come from a caller-supplied table
-            # (pdf.LOSTable) instead of the Bayestar map + healpy.
+            # (pdf.LOSTable) or from a Bayestar map on disk (dust.Bayestar).
             from .pdf import _los_provider, dust_lnprior
-            _los_provider(dustfile)           # raises for a Bayestar HDF5 path
+            _los_provider(dustfile)           # raises for a path that does not exist
             lndustprior = dust_lnprior
         elif lndustprior is None and av_gauss is None:
             av_gauss = (0, 1e6)                       # fitting.py:1396-1398
@@ -1548,14 +1548,17 @@ class BruteForce(object):
             # returns that `los_tables` cannot tabulate but the host `dust_lnprior` accepts
             # keeps the host stage for the whole call (as before the device dust stage
             # existed); later provider errors surface to the caller.
+            # A Bayestar map answers a batch with one device call (`brutus_dust_query`) and
+            # hands over tensors that are on the device already.
             b0 = min(Ndata, eng.batch)
+            los_dev = eng.grid.device if _pdf._bayestar(dustfile) is not None else None
             try:
-                first = _pdf.los_tables(dustfile, data_coords[:b0])
+                first = _pdf.los_tables(dustfile, data_coords[:b0], device=los_dev)
             except Exception:
                 first = None
             if first is not None:
                 dust_tables = lambda a, b: (first if (a, b) == (0, b0) else
-                                            _pdf.los_tables(dustfile, data_coords[a:b]))
+                                            _pdf.los_tables(dustfile, data_coords[a:b], device=los_dev))
         dust_ok = (not apply_av_prior and lndustprior is None) or dust_tables is not None
         stars = _Stars(data, data_err, data_mask, parallax, parallax_err, data_coords)
         opts = _PostOptions(Nmc_prior, lnprior, wt_thresh, cdf_thresh, lngalprior, lndustprior,

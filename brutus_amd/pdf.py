@@ -116,7 +116,7 @@ def scale_parallax_lnprior(scales, scale_errs, p_meas, p_err, snr_lim=4.):
 
 
 # ---------------------------------------------------------------------------
-# 3-D dust prior without Bayestar / healpy
+# 3-D dust prior: caller-supplied sightline tables, or a Bayestar map through brutus_amd.dust
 # ---------------------------------------------------------------------------
 class LOSTable(object):
     """Line-of-sight reddening profiles supplied by the caller: what the reference
@@ -154,31 +154,58 @@ class LOSTable(object):
         return self.dist, self.av_mean[k], self.av_err[k]
 
 
+_BAYESTAR = {}      # path -> dust.Bayestar (a map is read once per process)
+
+
+def _bayestar(dustfile):
+    """The `dust.Bayestar` behind `dustfile` -- an instance, or the path of an existing HDF5 map
+    (read once, cached per path) -- or None for every other kind of provider."""
+    from .dust import Bayestar
+    if isinstance(dustfile, Bayestar):
+        return dustfile
+    if isinstance(dustfile, str) and not dustfile.endswith(".npz") and os.path.isfile(dustfile):
+        key = os.path.abspath(dustfile)
+        if key not in _BAYESTAR:
+            _BAYESTAR[key] = Bayestar(dustfile)
+        return _BAYESTAR[key]
+    return None
+
+
 def _los_provider(dustfile):
     if dustfile is None:
         raise ValueError("dust_lnprior needs a line-of-sight table: pass "
                          "`dustfile=` a LOSTable, an object with `.query(coord)`, a "
-                         "callable `coord -> (dist, av_mean, av_err)` or the path of "
-                         "an .npz file with arrays l, b, dist, av_mean, av_err")
+                         "callable `coord -> (dist, av_mean, av_err)`, the path of "
+                         "an .npz file with arrays l, b, dist, av_mean, av_err or the path of "
+                         "a Bayestar HDF5 map")
     if hasattr(dustfile, "query"):
         return dustfile.query
     if callable(dustfile):
         return dustfile
     if isinstance(dustfile, str) and dustfile.endswith(".npz"):
         return LOSTable.load(dustfile).query
+    bay = _bayestar(dustfile)
+    if bay is not None:
+        return bay.query
     raise NotImplementedError(
-        "dustfile=%r: reading the Bayestar HDF5 map needs healpy, which is outside "
-        "this package's scope; convert the sightlines you need to a LOSTable "
-        "(see brutus_amd.pdf.LOSTable)" % (dustfile,))
+        "dustfile=%r: no such file.  Dust maps are not downloaded: give the path of a Bayestar "
+        "HDF5 map that is on disk (brutus_amd.dust.Bayestar), or a table of the sightlines "
+        "you need (brutus_amd.pdf.LOSTable)" % (dustfile,))
 
 
-def los_tables(dustfile, coords):
+def los_tables(dustfile, coords, device=None):
     """Line-of-sight profiles of a batch of objects as one array for the device stage:
     `(los (N, 3, nd) = dist, Av_mean, Av_err; ok (N,) int32)`.  Profiles shorter than the
     longest of the batch are padded by repeating their last node, which leaves
     `numpy.interp` (end value beyond the table) and the device's interpolation unchanged.
     Called per batch (`coords[a:b]`), so neither the Python loop over sightlines nor the
-    table ever spans the whole catalogue."""
+    table ever spans the whole catalogue.  A Bayestar map (`dust.Bayestar`, or the path of one)
+    answers the whole batch with one query and no loop; with `device` given that is one
+    `brutus_dust_query` call and the two results are tensors on that device.  `device` has no
+    effect on any other provider."""
+    bay = _bayestar(dustfile)
+    if bay is not None:
+        return bay.los_tables(np.asarray(coords, dtype=np.float64).reshape(-1, 2), device=device)
     q = _los_provider(dustfile)
     rows, ok = [], []
     for c in np.asarray(coords, dtype=np.float64):

@@ -630,6 +630,9 @@ void brutus_enable_timing(int on);
 /* ---- K thetas per call: seds.Isochrone and the cluster likelihood in batches ---- */
 #include "brutus_amd_batch.h"
 
+/* ---- Bayestar 3-D dust map: nested HEALPix pixels and the map query (reference dust.py) ---- */
+#include "brutus_amd_dust.h"
+
 #ifdef __cplusplus
 }
 #endif
