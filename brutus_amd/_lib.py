@@ -298,6 +298,14 @@ DUST_SIGNATURES = {
                                     _stream]),
 }
 
+# and for include/brutus_amd_summary.h (pdf.PosteriorSummary; tests/test_summary_host.py compares
+# this table with that header parameter by parameter)
+SUMMARY_SIGNATURES = {
+    "brutus_summary_quantiles": (C.c_int, [_i64, _i32, _di32, _df64, _df64, _df64, _df64, _i64, _i32,
+                                           _df64, _i32, _df64, _df64, _stream]),
+}
+SUMMARY_MAX_DRAWS, SUMMARY_MAX_LABELS, SUMMARY_MAX_Q, SUMMARY_MAX_OBJ = 4096, 32, 64, 1 << 21
+
 
 def lib():
     """Load (once) and return the shared library; raise loudly if absent."""
@@ -316,7 +324,7 @@ def lib():
     import torch  # noqa: F401
     L = C.CDLL(LIB_PATH)
     for name, (res, args) in (list(SIGNATURES.items()) + list(BATCH_SIGNATURES.items())
-                              + list(DUST_SIGNATURES.items())):
+                              + list(DUST_SIGNATURES.items()) + list(SUMMARY_SIGNATURES.items())):
         fn = getattr(L, name)   # AttributeError if the .so is stale
         fn.restype = res
         fn.argtypes = args

@@ -1,7 +1,7 @@
 // host.hpp -- the host side that the translation units of the library share: the error string
 // and the kernel-timing state (ONE copy, defined in host_unit.hip, hidden from the dynamic symbol
 // table), HIP_TRY, Timer and the small pure helpers.  Included by brutus_kernels.hip,
-// post_unit.hip, aux_unit.hip, los_unit.hip, dust_unit.hip, host_unit.hip and, through seds_host.hpp (what the two model
+// post_unit.hip, aux_unit.hip, los_unit.hip, dust_unit.hip, summary_unit.hip, host_unit.hip and, through seds_host.hpp (what the two model
 // generators share on top of this), iso_unit.hip and sed_unit.hip; includes common.hpp (TILE).
 #pragma once
 

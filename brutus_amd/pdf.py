@@ -17,14 +17,15 @@ from .galprior import (gal_lnprior, logn_disk, logn_halo, logp_age_from_feh,   #
                        logp_feh)
 
 # the reference's `brutus.pdf.__all__` (pdf.py:30-35), plus the table type of the Bayestar-free
-# dust interface
+# dust interface and the per-object posterior summaries
 __all__ = ["imf_lnprior", "ps1_MrLF_lnprior", "parallax_lnprior",
            "scale_parallax_lnprior", "parallax_to_scale",
            "logn_disk", "logn_halo",
            "logp_feh", "logp_age_from_feh",
            "gal_lnprior", "dust_lnprior",
            "bin_pdfs_distred",
-           "LOSTable", "DistancePriorTable", "dist_tables"]
+           "LOSTable", "DistancePriorTable", "dist_tables",
+           "posterior_quantiles", "PosteriorSummary"]
 
 
 def _kroupa_segment(m, alpha_low, alpha_high, mass_break):
@@ -654,3 +655,210 @@ def _bin_pdfs_device(data, regenerate, cdf, ebv, dist_type, lndistprior, coord, 
                       "that found no draw inside the bounds carry no weight"
                       % (int(status[:, 2].sum()), int(status[:, 1].sum())), RuntimeWarning)
     return out, xbins, ybins
+
+
+# ---- per-object posterior summaries: the quantile half of `plotting.cornerplot` --------------
+#: the four columns that follow the labels (reference plotting.py:302)
+_SUMMARY_DRAW_NAMES = ("av", "rv", "parallax", "dist")
+_SUMMARY_Q = (0.025, 0.16, 0.5, 0.84, 0.975)
+#: bytes of input a chunk of objects may take on the device
+_SUMMARY_CHUNK_LIMIT = 1 << 30
+
+
+def _summary_table(params, names):
+    """`(table (Nmodel, Nlab) float64 C-contiguous, label names)` of a structured label array (a
+    field named `agewt` is left out, plotting.py:250) or of a 2-D array with `names`."""
+    params = np.asarray(params)
+    if params.dtype.names is not None:
+        if names is not None:
+            raise ValueError("`names` goes with a 2-D array; a structured `params` carries its own")
+        if params.ndim != 1:
+            raise ValueError("a structured `params` must be 1-D; got shape %s" % (params.shape,))
+        names = [n for n in params.dtype.names if n != 'agewt']
+        table = np.empty((params.shape[0], len(names)), dtype=np.float64)
+        for k, n in enumerate(names):
+            table[:, k] = params[n]
+        return table, names
+    if params.ndim != 2 or names is None or len(names) != params.shape[1]:
+        raise ValueError("`params` must be a structured label array, or a 2-D array with one of "
+                         "`names` per column")
+    keep = [k for k, n in enumerate(names) if n != 'agewt']
+    return np.ascontiguousarray(params[:, keep], dtype=np.float64), [str(names[k]) for k in keep]
+
+
+def _summary_q(q):
+    q = np.atleast_1d(np.asarray(q, dtype=np.float64))
+    if q.ndim != 1 or q.size < 1:
+        raise ValueError("`q` must hold at least one quantile")
+    if not np.all((q >= 0.) & (q <= 1.)):
+        raise ValueError("Quantiles must be between 0. and 1.")
+    return np.ascontiguousarray(q)
+
+
+def _summary_shapes(idxs, data, weights):
+    """`(Nobj, Nsamps)` after the checks the host and the device form share."""
+    if len(data) == 4:
+        raise ValueError("posterior_quantiles takes the saved draws `(dists, reds, dreds)`; "
+                         "`(scales, avs, rvs, covs_sar)` would have to be regenerated -- fit with "
+                         "fit(save_dar_draws=True)")
+    if len(data) != 3:
+        raise ValueError("`data` must be `(dists, reds, dreds)`")
+    shape = tuple(idxs.shape)
+    if len(shape) != 2:
+        raise ValueError("`idxs` must be (Nobj, Nsamps); got shape %s" % (shape,))
+    for a in tuple(data) + (() if weights is None else (weights,)):
+        if tuple(a.shape) != shape:
+            raise ValueError("`idxs`, the draws and the weights must share one shape (Nobj, Nsamps); "
+                             "got %s and %s" % (shape, tuple(a.shape)))
+    if shape[1] < 2:
+        raise ValueError("quantiles need at least 2 samples per object; got Nsamps = %d" % shape[1])
+    return shape
+
+
+def _summary_host(idxs, data, weights, table, q):
+    """The host form: `utils.quantile`, weighted branch, over objects and columns."""
+    from .utils import quantile
+    idxs = np.asarray(idxs)
+    dists, reds, dreds = (np.asarray(a, dtype=np.float64) for a in data)
+    weights = None if weights is None else np.asarray(weights, dtype=np.float64)
+    nobj, nsamps = idxs.shape
+    nlab = table.shape[1]
+    out = np.empty((nobj, nlab + 4, q.size), dtype=np.float64)
+    ones = np.ones(nsamps)
+    cols = np.empty((nlab + 4, nsamps))
+    for o in range(nobj):
+        ok = (idxs[o] >= 0) & (idxs[o] < table.shape[0])
+        cols[:nlab] = np.nan
+        cols[:nlab, ok] = table[idxs[o][ok].astype(np.int64)].T
+        with np.errstate(all="ignore"):
+            cols[nlab:] = reds[o], dreds[o], 1. / dists[o], dists[o]
+        w = ones if weights is None else weights[o]
+        for c in range(nlab + 4):
+            x = cols[c]
+            if weights is not None:
+                # the sum without the last sorted sample's weight has to be > 0
+                nan = np.flatnonzero(np.isnan(x))
+                last = nan[-1] if nan.size else nsamps - 1 - int(np.argmax(x[::-1]))
+                if not np.delete(w, last).sum() > 0.:
+                    out[o, c] = np.nan
+                    continue
+            with np.errstate(all="ignore"):
+                out[o, c] = quantile(x, q, weights=w)
+    return out
+
+
+class PosteriorSummary(object):
+    """Quantiles of every object's posterior draws on the device, callable with the saved draws.
+
+    `PosteriorSummary(params, q, names, device)` copies the label table -- the structured array
+    `load_models` returns, or a 2-D float array with `names` -- to `device` once, model-major.
+    `S(idxs, (dists, reds, dreds), weights=None)` returns `(Nobj, Ncol, Nq)` float64: for every
+    object the quantiles `q` of the labels at `idxs` (in table order, without `agewt`), then of
+    Av, Rv, parallax and distance -- `S.names` -- as the first half of reference
+    `plotting.cornerplot` computes them: `utils.quantile` with weights (ones by default).  Equal
+    samples keep the order they came in.  An index outside the table (`fit()` writes -99 for an
+    object it did not fit) gives NaN labels; the four draw columns are computed all the same.
+    The inputs are numpy arrays or tensors already on the device, `idxs` of any integer type;
+    `device_out=True` leaves the result on the device.  Objects go in chunks whose inputs stay
+    under about 1 GiB.  An object's values do not depend on the batch it is in.
+
+        S = pdf.PosteriorSummary(labels)
+        quants = S(idxs, (dists, reds, dreds))            # (Nobj, len(S.names), 5)
+
+    At most 4096 draws, 32 labels and 64 quantiles.  There is no host fallback: without the
+    library or a GPU the constructor raises `BrutusError`; the host form is
+    `posterior_quantiles(device=None)`.
+    """
+
+    def __init__(self, params, q=_SUMMARY_Q, names=None, device="cuda"):
+        from . import _lib
+        from ._dev import _torch
+        table, labels = _summary_table(params, names)
+        self.q = _summary_q(q)
+        if table.shape[1] > _lib.SUMMARY_MAX_LABELS or self.q.size > _lib.SUMMARY_MAX_Q:
+            raise ValueError("PosteriorSummary takes at most %d labels and %d quantiles; got %d and %d"
+                             % (_lib.SUMMARY_MAX_LABELS, _lib.SUMMARY_MAX_Q, table.shape[1], self.q.size))
+        if table.shape[0] >= 1 << 31 or (table.shape[1] and not table.shape[0]):
+            raise ValueError("PosteriorSummary: the label table must have 1 to 2**31 - 1 rows")
+        self.names = list(labels) + list(_SUMMARY_DRAW_NAMES)
+        self.nmodel, self.nlab = table.shape
+        self._L = _lib.lib()
+        self._torch = torch = _torch("PosteriorSummary only runs on the HIP path. The host form is "
+                                     "posterior_quantiles(device=None).")
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise ValueError("PosteriorSummary needs a GPU device; got %r" % (device,))
+        self._table = to_device(table, np.float64, self.device) if self.nlab else None
+        self._q = to_device(self.q, np.float64, self.device)
+
+    def _indices(self, idxs):
+        """A chunk's indices as an int32 device tensor; what does not fit the table becomes -1
+        BEFORE the narrowing, which would otherwise wrap."""
+        torch = self._torch
+        if isinstance(idxs, torch.Tensor):
+            if idxs.dtype != torch.int32:
+                idxs = torch.where((idxs >= 0) & (idxs < self.nmodel), idxs, -1)
+        else:
+            idxs = np.asarray(idxs)
+            if idxs.dtype.kind not in "iu":
+                raise ValueError("`idxs` must be integers; got %s" % idxs.dtype)
+            if idxs.dtype != np.int32:
+                idxs = np.where((idxs >= 0) & (idxs < self.nmodel), idxs, -1)
+        return to_device(idxs, np.int32, self.device)
+
+    def __call__(self, idxs, data, weights=None, device_out=False):
+        from . import _lib
+        torch = self._torch
+        nobj, nsamps = _summary_shapes(idxs, data, weights)
+        if nsamps > _lib.SUMMARY_MAX_DRAWS:
+            raise ValueError("PosteriorSummary: at most %d draws per object; got %d"
+                             % (_lib.SUMMARY_MAX_DRAWS, nsamps))
+        ncol, nq = self.nlab + 4, self.q.size
+        if device_out:
+            out = torch.empty((nobj, ncol, nq), dtype=torch.float64, device=self.device)
+        else:
+            out = np.empty((nobj, ncol, nq), dtype=np.float64)
+        if nobj == 0:
+            return out
+        per_obj = nsamps * (4 + 3 * 8 + (0 if weights is None else 8))
+        chunk = int(max(1, min(nobj, _lib.SUMMARY_MAX_OBJ, _SUMMARY_CHUNK_LIMIT // per_obj)))
+        with torch.cuda.device(self.device):
+            stream = _stream_ptr(torch)
+            t_out = None if device_out else torch.empty((chunk, ncol, nq), dtype=torch.float64,
+                                                        device=self.device)
+            for a in range(0, nobj, chunk):
+                b = min(nobj, a + chunk)
+                t_idx = self._indices(idxs[a:b])
+                t_d, t_r, t_dr = (to_device(x[a:b], np.float64, self.device) for x in data)
+                t_w = None if weights is None else to_device(weights[a:b], np.float64, self.device)
+                dst = out[a:b] if device_out else t_out[:b - a]
+                _lib.check(self._L.brutus_summary_quantiles(
+                    b - a, nsamps, t_idx, t_d, t_r, t_dr, t_w, self.nmodel, self.nlab, self._table, nq,
+                    self._q, dst, stream))
+                if not device_out:
+                    out[a:b] = dst.cpu().numpy()
+            if device_out:
+                torch.cuda.current_stream().synchronize()
+        return out
+
+
+def posterior_quantiles(idxs, data, params, q=_SUMMARY_Q, weights=None, names=None, device=None,
+                        device_out=False):
+    """Per-object posterior summaries: `(quantiles (Nobj, Ncol, Nq) float64, names)`, the
+    quantiles `q` of each label at the saved model indices `idxs` (Nobj, Nsamps), then of Av, Rv,
+    parallax and distance from `data = (dists, reds, dreds)` as `fit(save_dar_draws=True)` saves
+    them -- what the first half of reference `plotting.cornerplot` computes for one object
+    (plotting.py:249-322): `utils.quantile` with `weights` (ones by default, never
+    `numpy.percentile`).  `params` is the structured label array of `load_models` (its `agewt`
+    is left out) or a 2-D array with `names`.  An index outside the table gives NaN labels.
+
+    `device=None`: numpy on the host, a loop of `utils.quantile` over objects and columns.
+    Otherwise a one-shot `PosteriorSummary` on that GPU; a catalogue in pieces keeps one
+    `PosteriorSummary`, whose label table travels once."""
+    if device is not None:
+        S = PosteriorSummary(params, q=q, names=names, device=device)
+        return S(idxs, data, weights=weights, device_out=device_out), S.names
+    table, labels = _summary_table(params, names)
+    q = _summary_q(q)
+    _summary_shapes(idxs, data, weights)
+    return _summary_host(idxs, data, weights, table, q), list(labels) + list(_SUMMARY_DRAW_NAMES)

@@ -633,6 +633,9 @@ void brutus_enable_timing(int on);
 /* ---- Bayestar 3-D dust map: nested HEALPix pixels and the map query (reference dust.py) ---- */
 #include "brutus_amd_dust.h"
 
+/* ---- per-object posterior summaries: quantiles of the saved draws (reference plotting.py) ---- */
+#include "brutus_amd_summary.h"
+
 #ifdef __cplusplus
 }
 #endif

@@ -1298,6 +1298,94 @@ def gen_offsets_edges():
     print("wrote offsets_edges.npz: nratio", res["nratio_1"], "ratios", res["ratios_1"])
 
 
+def gen_post_quantiles():
+    """tests/golden/post_quantiles.npz: the quantile half of `plotting.cornerplot` -- the sample
+    matrix of plotting.py:250-302 and `utils.quantile(samples[i], q, weights=weights)` per object
+    and column -- with unit weights, with dyadic weights (multiples of 1/8 in [0, 4]: every
+    partial sum is exact) and, at 250 draws, with weights uniform in [0.5, 1.5].
+
+    A 500-model table of 9 labels and `agewt`; `logg` is NaN for one model in twelve.  The
+    reference sorts with numpy's default `argsort`, which orders equal samples arbitrarily, and
+    its knots depend on that order wherever equal samples carry different weights.  The fixture
+    keeps the recorded values free of that: an object's draws are resampled from a pool of
+    distinct models, each with ONE distance, Av, Rv and weight, so equal samples are copies of
+    one pool entry (the NaN labels share the weight 0 / 1), and the result is checked to be the
+    same for the reversed sample order.  Zero weights sit on the nearest and the farthest pool
+    entry, on the NaN labels (the end of that column), on a run of three neighbours in distance,
+    and at random.  Objects are redrawn until every column's normaliser is positive and no
+    quantile lies within `MARGIN` of a knot where the result jumps (tests/summary_helpers.py)."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import summary_helpers as H
+    rng = np.random.RandomState(20261020)
+    nmodel = 500
+    names = ["mini", "feh", "eep", "loga", "agewt", "logl", "logt", "logg", "feh_surf", "afe_surf"]
+    lo = dict(mini=0.1, feh=-4., eep=202., loga=6., agewt=0., logl=-3., logt=3.4, logg=-1.,
+              feh_surf=-4., afe_surf=-0.2)
+    hi = dict(mini=8., feh=0.5, eep=808., loga=10.14, agewt=1., logl=5., logt=4.6, logg=5.5,
+              feh_surf=0.5, afe_surf=0.6)
+    params = np.empty(nmodel, dtype=[(n, np.float64) for n in names])
+    for n in names:
+        params[n] = rng.uniform(lo[n], hi[n], nmodel)
+    params["logg"][rng.uniform(size=nmodel) < 1. / 12.] = np.nan
+    q = np.array([0., 0.025, 0.16, 0.5, 0.84, 0.975, 1.])
+    res = dict(params=params, q=q)
+    tries = 0
+
+    def draw_object(n):
+        k = n if n < 8 else min(max(8, n // 3), 400)       # pool size: ties from 8 draws on
+        pool = rng.choice(nmodel, k, replace=False)
+        pd = np.exp(rng.normal(0., 0.6, k))
+        pr, pdr = rng.uniform(0., 3., k), rng.uniform(2.5, 4.5, k)
+        wd = rng.randint(0, 33, k) / 8.
+        wd[rng.uniform(size=k) < 0.2] = 0.
+        wf = rng.uniform(0.5, 1.5, k)
+        isnan = np.isnan(params["logg"][pool])
+        wf[isnan] = 1.
+        wd[isnan] = 0.
+        if k >= 8:
+            order = np.argsort(pd)
+            start = rng.randint(1, k - 4)
+            wd[order[0]] = wd[order[-1]] = 0.
+            wd[order[start:start + 3]] = 0.
+        pick = rng.randint(0, k, n)
+        return pool[pick].astype(np.int32), pd[pick], pr[pick], pdr[pick], wd[pick], wf[pick]
+
+    def acceptable(cols, weights):
+        try:
+            return all(H.margin(x, w, q) > H.MARGIN for w in weights for x in cols)
+        except AssertionError:
+            return False
+
+    for n in H.NSAMPS:
+        objs = []
+        while len(objs) < H.nobj_of(n):
+            tries += 1
+            idx, d, r, dr, wd, wf = draw_object(n)
+            cols = H.columns(params, idx, d, r, dr)
+            if acceptable(cols, [np.ones(n), wd] + ([wf] if n == H.NFLOAT else [])):
+                objs.append((idx, d, r, dr, wd, wf, cols))
+        for key, k in (("idx", 0), ("dist", 1), ("red", 2), ("dred", 3), ("wd", 4)):
+            res["%s_%d" % (key, n)] = np.stack([o[k] for o in objs])
+        kinds = [("unit", lambda o: np.ones(n)), ("dyad", lambda o: o[4])]
+        if n == H.NFLOAT:
+            res["wf_%d" % n] = np.stack([o[5] for o in objs])
+            kinds.append(("float", lambda o: o[5]))
+        for kind, wof in kinds:
+            ref = np.empty((len(objs), len(names) - 1 + 4, q.size))
+            for i, o in enumerate(objs):
+                w = wof(o)
+                for c, x in enumerate(o[6]):
+                    ref[i, c] = U.quantile(x, q, weights=w)
+                    back = U.quantile(x[::-1], q, weights=w[::-1])
+                    assert np.array_equal(ref[i, c], back, equal_nan=True), (n, kind, i, c)
+            res["ref_%s_%d" % (kind, n)] = ref
+    assert any(np.isnan(res["ref_unit_%d" % n]).any() for n in H.NSAMPS)
+    np.savez_compressed(os.path.join(OUT, "post_quantiles.npz"), **res)
+    print("wrote post_quantiles.npz: %d objects drawn for %d kept, %d bytes"
+          % (tries, sum(H.nobj_of(n) for n in H.NSAMPS),
+             os.path.getsize(os.path.join(OUT, "post_quantiles.npz"))))
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     which = sys.argv[1:] or ["loglike", "fit", "helpers", "setup", "galprior",
@@ -1350,4 +1438,6 @@ if __name__ == "__main__":
         gen_consumers()
     if "offsets_edges" in which:
         gen_offsets_edges()
+    if "post_quantiles" in which:
+        gen_post_quantiles()
 
