@@ -177,7 +177,7 @@ _hf64, _hf32, _hi32, _hi64, _hu32, _hu64 = (ptr("h", t) for t in (
 # include/brutus_amd_debug.h (test hooks / measurement aids, see DEBUG_NAMES) one to one,
 # parameter by parameter: `const double *d_x` is _df64, `int32_t *h_k` is _hi32, `void *d_ws` is _dv
 # (tests/test_cabi.py compares the table and the structures above with the headers)
-DEBUG_NAMES = ("brutus_calibrate_traffic", "brutus_calibrate_copy16", "brutus_calibrate_issue", "brutus_debug_exp10", "brutus_debug_math", "brutus_debug_mt_stream", "brutus_debug_plan_streams", "brutus_debug_rng","brutus_debug_galprior", "brutus_debug_galprior_mc", "brutus_debug_galprior_sl", "brutus_debug_dist_table", "brutus_debug_zig_table", "brutus_debug_copy", "brutus_debug_sizeof_star32", "brutus_debug_fit_stats", "brutus_debug_pre32_time", "brutus_debug_binpdf_draws")
+DEBUG_NAMES = ("brutus_calibrate_traffic", "brutus_calibrate_copy16", "brutus_calibrate_issue", "brutus_debug_exp10", "brutus_debug_math", "brutus_debug_mt_stream", "brutus_debug_plan_streams", "brutus_debug_rng","brutus_debug_galprior", "brutus_debug_galprior_mc", "brutus_debug_galprior_sl", "brutus_debug_dist_table", "brutus_debug_zig_table", "brutus_debug_copy", "brutus_debug_sizeof_star32", "brutus_debug_fit_stats", "brutus_debug_pre32_time", "brutus_debug_binpdf_draws", "brutus_debug_cluster_batch_layout")
 SIGNATURES = {
     "brutus_abi_version": (C.c_int, []),
     "brutus_last_error": (C.c_char_p, []),
@@ -243,6 +243,7 @@ SIGNATURES = {
     "brutus_debug_sizeof_star32": (C.c_int, []),
     "brutus_debug_pre32_time": (C.c_int, [_dv, _sz, _df32, _i64, _i32, _i32, C.POINTER(Params), _i32,
                                           _i32, _hf32, _stream]),
+    "brutus_debug_cluster_batch_layout": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _hu64]),
     "brutus_cluster_points": (C.c_int, [_i64, _i32, _di32, _df64, _df64, _df64, _df64, _stream]),
     "brutus_cluster_points_grid": (C.c_int, [_i64, _i32, _i32, _di32, _df64, _df64, _df64, _df64, _df64,
                                              _stream]),

@@ -8,6 +8,7 @@
 #include <stdint.h>
 
 #include "../../include/brutus_amd.h"
+#include "../../include/brutus_amd_debug.h"
 
 #include "host.hpp"
 #include "common.hpp"
@@ -171,17 +172,22 @@ namespace {
 struct ClusterBatchWs {
     double *lnw_eep, *part_m, *part_s, *lnl;
     int32_t *src, *cnt;
-    size_t bytes;
+    size_t off[6], bytes;       // (byte offsets of the six arrays, in the order above)
 };
 static void carve_cluster_batch(char *base, size_t k, int nobj, int nsmf, int neep, ClusterBatchWs &w) {
     Carver cv(base);
     const size_t d = sizeof(double), nrow = (size_t)nsmf * neep;
-    w.lnw_eep = (double *)cv.take(d * k * neep);
-    w.src = (int32_t *)cv.take(sizeof(int32_t) * k * nrow);
-    w.cnt = (int32_t *)cv.take(sizeof(int32_t) * k);
-    w.part_m = (double *)cv.take(d * k * CLB_CHUNKS * nobj);
-    w.part_s = (double *)cv.take(d * k * CLB_CHUNKS * nobj);
-    w.lnl = (double *)cv.take(d * k * nobj);
+    int n = 0;
+    auto take = [&](size_t bytes) {
+        w.off[n++] = cv.off;
+        return cv.take(bytes);
+    };
+    w.lnw_eep = (double *)take(d * k * neep);
+    w.src = (int32_t *)take(sizeof(int32_t) * k * nrow);
+    w.cnt = (int32_t *)take(sizeof(int32_t) * k);
+    w.part_m = (double *)take(d * k * CLB_CHUNKS * nobj);
+    w.part_s = (double *)take(d * k * CLB_CHUNKS * nobj);
+    w.lnl = (double *)take(d * k * nobj);
     w.bytes = cv.off;
 }
 // (neep >= 2: np.gradient needs two masses; the table rows of a theta are indexed by an int)
@@ -198,6 +204,18 @@ size_t brutus_cluster_batch_workspace_bytes(int ntheta, int nobj, int nfilt, int
     ClusterBatchWs w;
     carve_cluster_batch(nullptr, (size_t)ntheta, nobj, nsmf, neep, w);
     return w.bytes;
+}
+
+// Test hook: where carve_cluster_batch puts the six arrays of a batch (no HIP call).
+int brutus_debug_cluster_batch_layout(int ntheta, int nobj, int nfilt, int nsmf, int neep, size_t *h_offsets) {
+    if (!cluster_batch_dims_ok(ntheta, nobj, nfilt, nsmf, neep))
+        return fail(BRUTUS_EINVAL, "bad cluster batch dimensions (ntheta=%d, nobj=%d, nfilt=%d, nsmf=%d, neep=%d)",
+                    ntheta, nobj, nfilt, nsmf, neep);
+    if (!h_offsets) return fail(BRUTUS_EINVAL, "NULL offsets");
+    ClusterBatchWs w;
+    carve_cluster_batch(nullptr, (size_t)ntheta, nobj, nsmf, neep, w);
+    for (int i = 0; i < 6; ++i) h_offsets[i] = w.off[i];
+    return 0;
 }
 
 int brutus_cluster_lnl_batch(int ntheta, int nobj, int nfilt, int nsmf, int neep, const double *d_mags,

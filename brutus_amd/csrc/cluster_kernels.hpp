@@ -119,7 +119,10 @@ cluster_sum(int nb, const double *__restrict__ pts_flux, const double *__restric
             bool hole = false, any = false;
             for (int b = 0; b < NB; ++b) {
                 const double v = b < nb ? src[b] : 0.;
-                hole = hole || (v != v);
+                // (an infinite flux -- a magnitude of -inf -- takes the nansum path too: against a
+                // band without weight its term is inf * 0, a NaN that is dropped like the
+                // reference's; with weight it is an infinite chi2, clamped like any other)
+                hole = hole || !(fabs(v) < INFINITY);
                 // (fluxes from the caller's table: any non-NaN band; staged from magnitudes:
                 // any band whose magnitude was finite -- not the -0.0 of +inf, not the inf of -inf)
                 if constexpr (MAGS) any = any || (b < nb && fabs(v) < INFINITY && !(v == 0. && signbit(v)));
@@ -149,8 +152,8 @@ cluster_sum(int nb, const double *__restrict__ pts_flux, const double *__restric
                 for (int b = 0; b < NB; ++b) fb[b] = f[b];
                 double chi2 = 0.;
                 // nansum (cluster.py:381): d and iv are finite (masked bands carry iv = 0),
-                // so a term is NaN exactly when the point lacks band b -- rare, and the
-                // same for every lane
+                // so a term is NaN exactly when the point lacks band b, or has an infinite flux
+                // there against a band without weight -- rare, and the same for every lane
                 if (f[NB + 1] == 0.) {
 #pragma unroll
                     for (int b = 0; b < NB; ++b) {

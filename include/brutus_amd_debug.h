@@ -135,6 +135,15 @@ int brutus_debug_binpdf_draws(int nobj, int nsamps, int nr, const void *d_worksp
                               double *d_scale, double *d_av, double *d_rv, double *d_weight,
                               void *stream);
 
+/* Test hook: the byte offsets, in the workspace of brutus_cluster_lnl_batch with these
+ * dimensions, of the six arrays a batch keeps between its kernels: h_offsets[0..5] = ln w_eep
+ * (ntheta, neep) f64; kept table rows (ntheta, nsmf * neep) i32, ascending; their number (ntheta)
+ * i32; partial maxima and partial sums (ntheta, 32, nobj) f64 each; lnl before the mixture
+ * (ntheta, nobj) f64.  From the function that carves the workspace of the real call.
+ * BRUTUS_EINVAL for dimensions that call refuses.  Needs no GPU. */
+int brutus_debug_cluster_batch_layout(int ntheta, int nobj, int nfilt, int nsmf, int neep,
+                                      size_t *h_offsets);
+
 #ifdef __cplusplus
 }
 #endif

@@ -188,7 +188,7 @@ _STRUCTS = {"brutus_params": "Params", "brutus_post_params": "PostParams",
             "brutus_iso_params": "IsoParams", "brutus_sed_params": "SedParams",
             "brutus_binpdf_params": "BinpdfParams", "brutus_los_params": "LosParams"}
 _ELEMENT = {"double": "float64", "float": "float32", "int32_t": "int32", "int64_t": "int64",
-            "uint8_t": "uint8", "uint32_t": "uint32", "uint64_t": "uint64", "void": None}
+            "uint8_t": "uint8", "uint32_t": "uint32", "uint64_t": "uint64", "size_t": "uint64", "void": None}
 # host out-parameters the header declares without a prefix, the hook and its argument
 _UNPREFIXED = {("brutus_last_timing", "n_entries"): ctypes.POINTER(ctypes.c_int),
                ("brutus_last_timing", "names"): ctypes.POINTER(ctypes.c_char_p),
@@ -206,7 +206,7 @@ def test_table_matches_the_headers_parameter_by_parameter():
               "uint64_t": C.c_uint64}
     returns = dict(scalar, **{"void": None, "const char *": C.c_char_p})
     protos = _prototypes()
-    assert len(protos) == len(_lib.SIGNATURES) == 59
+    assert len(protos) == len(_lib.SIGNATURES) == 60
     seen = set()
     for name, (res, argtypes) in _lib.SIGNATURES.items():
         assert name in protos, name
