@@ -7,10 +7,16 @@ rank fits a contiguous range of the catalogue and there is NO collective on the
 data path.  The only collective is the one-off broadcast of the model grid in
 kernel layout (108 MB at 750k x 12) and of the static prior vector.
 """
+import collections
+import functools
+import os
+import queue
+import threading
+import time
+
 import numpy as np
 
-__all__ = ["shard_range", "shard_bounds", "broadcast_grid", "broadcast_array", "gather_rows",
-           "fit_sharded"]
+__all__ = ["shard_range", "shard_bounds", "broadcast_grid", "broadcast_array", "fit_sharded"]
 
 
 def shard_range(n, rank, world):
@@ -71,19 +77,393 @@ def broadcast_array(arr, src=0, device=None):
     return arr
 
 
-def gather_rows(local_rows, dst=0):
-    """Gather per-rank lists of result rows on `dst` in rank order (the row
-    order of the sharded catalogue).  Host-side; results are small."""
-    import torch.distributed as dist
-    world = dist.get_world_size()
-    out = [None] * world if dist.get_rank() == dst else None
-    dist.gather_object(local_rows, out, dst=dst)
-    if out is None:
-        return None
-    rows = []
-    for part in out:
-        rows.extend(part)
-    return rows
+# Where a `BruteForce.fit` keyword goes in `fit_sharded`.  "setup": to `_setup` alone, which hands
+# back what `_fit` needs of it and `fit_sharded` passes that on by name; "both": to `_setup` and to
+# `_fit`; "drop": to neither (`_fit` gets a stream per object instead of `rstate`).  The driver's
+# own options are `_Options`; a keyword that is in neither goes to `_fit` ("fit").
+_FIT_KWARGS = {
+    "phot_offsets": "setup", "parallax": "setup", "parallax_err": "setup", "av_gauss": "setup",
+    "lnprior": "setup", "wt_thresh": "setup", "apply_agewt": "setup", "apply_grad": "setup",
+    "lngalprior": "setup", "lndustprior": "setup", "data_coords": "setup", "mag_max": "setup",
+    "merr_max": "setup",
+    "cdf_thresh": "both", "dustfile": "both", "ltol_subthresh": "both", "logl_initthresh": "both",
+    "verbose": "drop", "rstate": "drop"}
+
+_Options = collections.namedtuple("_Options", "resume Ndraws save_dar_draws running_io lnprior_ext")
+
+
+def _split_fit_kwargs(fit_kwargs):
+    """`(options, _setup keywords, _fit keywords)` of `fit_sharded`'s `**fit_kwargs`."""
+    kw = dict(fit_kwargs)
+    opts = _Options(bool(kw.pop("resume", False)), kw.pop("Ndraws", 250),
+                    kw.pop("save_dar_draws", True), kw.pop("running_io", True),
+                    kw.pop("lnprior_ext", None))
+    skw = {k: v for k, v in kw.items() if _FIT_KWARGS.get(k) in ("setup", "both")}
+    fkw = {k: v for k, v in kw.items() if _FIT_KWARGS.get(k, "fit") in ("both", "fit")}
+    fkw.setdefault("logl_dim_prior", True)
+    return opts, skw, fkw
+
+
+class _Plan(collections.namedtuple(
+        "_Plan", "rank bounds save_file lo hi per_rank owner my_path my_rows my_first index_path "
+                 "index_taken")):
+    """Who writes what: one file on rank 0 (rows arrive over the side group), or a part per rank
+    with rows and an index on rank 0.  `owner`: this rank opens `my_path` (`my_rows` rows, the
+    first one catalogue row `my_first`)."""
+    __slots__ = ()
+
+    def part_path(self, r):
+        return _part_path(self.save_file, r)
+
+    def index_parts(self):
+        """`(lo, hi, file name beside the index)` of every part, for `h5io.write_virtual_index`."""
+        return [(a, b, os.path.basename(self.part_path(r)))
+                for r, (a, b) in enumerate(self.bounds) if b > a]
+
+
+def _part_path(save_file, r):
+    return "{0}.r{1:02d}.h5".format(save_file, r)
+
+
+def _make_plan(rank, bounds, writer, save_file, resume):
+    """The `_Plan` of `rank`; `bounds` are every rank's `[lo, hi)`."""
+    if writer not in ("rank0", "per_rank"):
+        raise ValueError("fit_sharded: writer must be 'rank0' or 'per_rank'")
+    per_rank = writer == "per_rank"
+    lo, hi = bounds[rank]
+    index_path = "{0}.h5".format(save_file)
+    # the index is written LAST; that it cannot be created ("w-", reference fitting.py:1632)
+    # is said now (`_open_results`), not after the whole catalogue has been fitted
+    taken = per_rank and rank == 0 and not resume and os.path.exists(index_path)
+    return _Plan(rank, tuple(bounds), save_file, lo, hi, per_rank,
+                 owner=not taken and (hi > lo if per_rank else rank == 0),
+                 my_path=_part_path(save_file, rank) if per_rank else index_path,
+                 my_rows=(hi - lo) if per_rank else bounds[-1][1],
+                 my_first=lo if per_rank else 0, index_path=index_path, index_taken=taken)
+
+
+class _SideGroup(object):
+    """The gloo side group of the hand-off (`dist.new_group(backend="gloo")`: host memory to host
+    memory, nothing is pickled and nothing passes through RCCL).  With one rank there is no group:
+    a gather returns the caller's own vector and nothing else is ever called."""
+
+    def __init__(self, world):
+        import torch
+        import torch.distributed as dist
+        self.torch, self.dist, self.world = torch, dist, world
+        self.group = dist.new_group(backend="gloo") if world > 1 else None
+
+    def all_gather_i64(self, vec):
+        """Every rank's `vec` (a few integers), as a `(world, len(vec))` array."""
+        if self.group is None:
+            return np.asarray(vec, dtype=np.int64)[None, :]
+        torch = self.torch
+        parts = [torch.empty(len(vec), dtype=torch.int64) for _ in range(self.world)]
+        self.dist.all_gather(parts, torch.tensor(vec, dtype=torch.int64), group=self.group)
+        return torch.stack(parts).numpy()
+
+    def send(self, payload, dst):
+        self.dist.send(self.torch.from_numpy(payload), dst=dst, group=self.group)
+
+    def recv(self, nbytes, src):
+        buf = self.torch.empty(nbytes, dtype=self.torch.uint8)
+        self.dist.recv(buf, src=src, group=self.group)
+        return buf.numpy()
+
+    def broadcast_u8(self, state, src=0):
+        """`state` (a uint8 array) of `src` into everybody's, in place."""
+        if self.group is not None:
+            self.dist.broadcast(self.torch.from_numpy(state), src=src, group=self.group)
+
+    def destroy(self):
+        if self.group is not None:
+            self.dist.destroy_process_group(self.group)
+
+
+def _open_results(plan, opts, data_labels):
+    """`(out, open_error)`: this rank's `ResultsFile` (None unless it owns one), or why not."""
+    from . import h5io
+    if plan.index_taken:
+        return None, OSError("fit_sharded: %s exists already" % plan.index_path)
+    if not plan.owner:
+        return None, None
+    try:
+        if opts.resume:
+            # the interrupted file(s): rows whose `model_idx[:, 0]` still holds the sentinel
+            # -99 were never fitted (reference fitting.py:1635)
+            return h5io.ResultsFile.resume(plan.my_path, plan.my_rows, opts.Ndraws,
+                                           opts.save_dar_draws), None
+        lab = data_labels
+        if plan.per_rank and lab is not None:
+            lab = np.asarray(lab)[plan.lo:plan.hi]
+        return h5io.ResultsFile(plan.my_path, plan.my_rows, opts.Ndraws, lab, opts.save_dar_draws,
+                                running_io=opts.running_io), None
+    except BaseException as e:
+        return None, e
+
+
+def _open_handshake(side, plan, out, open_error, resume):
+    """One handshake for every way of opening: a rank that could not create / re-open its file
+    says so before anybody enters the hand-off protocol, and EVERY rank raises (without it
+    the others would wait for the failed rank in the first round of headers)."""
+    oks = side.all_gather_i64([0 if open_error is not None else 1])
+    bad = [r for r in range(side.world) if not int(oks[r, 0])]
+    if not bad:
+        return
+    if out is not None:
+        try:
+            out.close()
+            if not resume:
+                os.remove(plan.my_path)     # created a moment ago, holds nothing: a rerun must not trip over it
+        except BaseException:
+            pass
+    side.destroy()
+    raise open_error or RuntimeError(
+        "fit_sharded: rank(s) %s could not open their results file; this rank stops too"
+        % ", ".join(str(r) for r in bad))
+
+
+def _todo_mask(side, plan, out, Ndata):
+    """The catalogue rows a resumed fit still has to do: what each owner reads from its file,
+    and with one writer what rank 0 read, for everybody."""
+    state = np.zeros(Ndata, dtype=np.uint8)
+    if out is not None:
+        state[plan.my_first + np.asarray(out.todo, dtype=np.int64)] = 1
+    if not plan.per_rank:
+        side.broadcast_u8(state)
+    return state.astype(bool)
+
+
+def _resume_runs(todo_mask, lo, hi):
+    """The contiguous runs `[(a, b), ...]` of rows in `[lo, hi)` that this rank fits: all of them
+    (`todo_mask` None), or those the boolean mask over the catalogue marks.  Each run is one `_fit`
+    call seeded `seed0 + a` -- object i draws from stream `seed0 + i` as in the interrupted run,
+    so the completed file equals an uninterrupted one."""
+    if todo_mask is None:
+        return [(lo, hi)] if hi > lo else []
+    mine = np.flatnonzero(todo_mask[lo:hi]) + lo
+    cuts = np.flatnonzero(np.diff(mine) != 1) + 1
+    return [(int(r[0]), int(r[-1]) + 1) for r in np.split(mine, cuts) if r.size]
+
+
+def _fitted_rows(bf, runs, data, data_err, data_mask, per_object, lnprior_ext, seed0, fit_kw):
+    """(catalogue row, 13-tuple) of every row of `runs`, in row order.  `per_object`: keyword
+    arrays (or None) with a row per object, sliced like the data, as `lnprior_ext`'s are;
+    `fit_kw`: what is the same for every run.  Closing this generator closes the `_fit`
+    generator in flight, which shuts its scan-ahead helper thread down."""
+    for a, b in runs:
+        rkw = dict(fit_kw)
+        rkw.update((k, None if v is None else v[a:b]) for k, v in per_object.items())
+        if lnprior_ext is not None:
+            # per-object constraints: `_fit` sees objects a..b as 0..b-a
+            rkw["lnprior_ext"] = {k: np.asarray(v)[a:b] for k, v in lnprior_ext.items()}
+        g = bf._fit(data[a:b], data_err[a:b], data_mask[a:b], seed0=seed0 + a, **rkw)
+        try:
+            for k, res in enumerate(g):
+                yield a + k, res
+        finally:
+            if hasattr(g, "close"):
+                g.close()
+
+
+def _pack_blocks(rows, chunk, rowdt, positions):
+    """`(start, n, block)`: the `(row, 13-tuple)` pairs of `rows` packed `chunk` at a time into
+    structured arrays of the file's own dtypes (`h5io.ResultsFile.row_dtype`); the first `n`
+    entries of `block` are rows `start .. start + n`.  Every block is a fresh array (blocks sit
+    in the queue while the next is filled) and holds consecutive rows only."""
+    rows = iter(rows)
+    exhausted = False
+    pending = None                               # a row of the next run, already fitted
+    while not exhausted:
+        block = np.zeros(chunk, dtype=rowdt)
+        n, start = 0, None
+        with np.errstate(over="ignore"):
+            while n < chunk:
+                if pending is not None:
+                    row, res = pending
+                    pending = None
+                else:
+                    try:
+                        row, res = next(rows)
+                    except StopIteration:
+                        exhausted = True
+                        break
+                if start is None:
+                    start = row
+                elif row != start + n:           # a new run: blocks hold consecutive rows
+                    pending = (row, res)
+                    break
+                for name, pos in positions:
+                    block[name][n] = res[pos]
+                n += 1
+        if n:
+            yield start, n, block
+
+
+class _HandOff(object):
+    """The hand-off thread of one rank and its protocol.
+
+    * The fit (`BruteForce._fit`, the caller's thread) packs every `chunk` finished objects into
+      one block -- a structured array with the file's own dtypes (`h5io.ResultsFile.row_dtype`,
+      18 KB per object at the defaults) -- and `put`s it into a bounded queue (`queue_depth`
+      blocks: the only back-pressure is a writer slower than the fits).
+    * This thread drains that queue over the side group: a round is one tiny `all_gather` of
+      headers `(rows, first row, done, failed)` followed by point-to-point sends of exactly the
+      rows that are ready -- a rank with nothing ready sends nothing and holds nobody up, so
+      rank 0's shard, its unpacking and the writer's thread sit in no other rank's critical path.
+    * Rank 0's thread gives the blocks to the asynchronous `ResultsFile` writer at their
+      catalogue positions -- row `lo_r + ...`, the mapping of reference fitting.py:1734-1748.
+      No rank holds more than `queue_depth * chunk` finished rows, rank 0 no more than a round
+      of `world * chunk` on top, whatever the catalogue size.
+
+    A failure anywhere -- a fit (`fail`), the writer (its errors are sticky), a hand-off -- is
+    announced in the next round's headers; every rank's thread then ends with `error()` set and
+    the next `put` or `check` raises it: none is left waiting in a collective.  That includes
+    the writer's LAST blocks: when every rank has reported "done", the owners flush and close
+    their files inside the protocol and a closing round of headers carries the outcome
+    (`_close`).  With `writer="per_rank"` the queue carries nothing but "done": the fitting
+    thread writes its own blocks and only the headers cross the side group.
+    """
+
+    def __init__(self, side, plan, out, rowdt, positions, queue_depth, write_index):
+        self.side, self.plan, self.out = side, plan, out
+        self.rowdt, self.positions, self.write_index = rowdt, positions, write_index
+        self.q = queue.Queue(maxsize=max(1, int(queue_depth)))
+        self.abort = threading.Event()
+        self.local = self.remote = None          # this rank's own failure; the others', as told
+        self.done = False
+        self.thread = threading.Thread(target=self._run, name="brutus-shard-handoff", daemon=True)
+
+    def error(self):
+        """What stopped the protocol, this rank's own failure first; None while all is well.
+        (`remote` is only ever set while `local` is None, and `local` after `remote` only by
+        `fail`, i.e. when the fitting thread has an error of its own to raise.)"""
+        return self.local or self.remote
+
+    def check(self):
+        if self.abort.is_set():                  # somebody failed: stop fitting
+            raise self.error() or RuntimeError("fit_sharded aborted")
+
+    def put(self, item):
+        while True:
+            self.check()
+            try:
+                self.q.put(item, timeout=0.05)
+                return
+            except queue.Full:
+                continue
+
+    def fail(self, e):
+        """The fit raised `e`: tell the others, whatever the queue holds."""
+        if not self.abort.is_set():
+            self.local = self.local or e
+
+    def _run(self):
+        try:
+            while self._round():
+                pass
+        except BaseException as e:               # the collective itself failed
+            self.local = self.local or e
+        finally:
+            if self.error() is not None:
+                self.abort.set()
+
+    def _round(self):
+        """Header round, then the rows that are ready; False when the protocol has ended."""
+        # The failure state is read ONCE per round, before the queue: a block taken
+        # from the queue is handed over in this round even if the fit raises while it
+        # is on its way (the fitting thread runs on as soon as the queue has room), and
+        # the failure goes into the next round's header.  Read after the `get`, the flag
+        # could drop rows that were fitted before anything went wrong.
+        failed = self.local is not None
+        n, start, block, failed = self._take(failed)
+        hdrs = self.side.all_gather_i64(self._header(n, start, failed))
+        bad = np.flatnonzero(hdrs[:, 3])
+        if bad.size:
+            if self.local is None:
+                self.remote = RuntimeError("fit_sharded: rank(s) %s failed; this rank stops too"
+                                           % ", ".join(str(int(b)) for b in bad))
+            return False
+        try:
+            self._deliver(hdrs, n, block)
+        except BaseException as e:               # announced in the next round's headers: it
+            self.local = e                       # does not end the thread
+            return True
+        if np.all(hdrs[:, 2] == 1) and not np.any(hdrs[:, 0]):
+            self._close()
+            return False
+        return True
+
+    def _take(self, failed):
+        """`(n, start, block, failed)` of the next queue item, if there is one within 20 ms."""
+        item = None
+        if not self.done and not failed:
+            try:
+                item = self.q.get(timeout=0.02)
+            except queue.Empty:
+                pass
+        n, start, block = 0, 0, None
+        if item is not None:
+            if item[0] == "rows":
+                _, start, n, block = item
+            elif item[0] == "done":
+                self.done = True
+            else:
+                self.local = self.local or RuntimeError(item[1])
+                failed = True
+        return n, start, block, failed
+
+    def _header(self, n, start, failed):
+        return [n, start, 1 if self.done else 0, 1 if failed else 0]
+
+    def _deliver(self, hdrs, n, block):
+        if self.plan.rank == 0:
+            got = []
+            for r in range(self.side.world):     # every payload is received before any is
+                nr = int(hdrs[r, 0])             # written: a failing write strands no sender
+                if nr == 0:
+                    continue
+                if r == 0:
+                    rows = block[:nr]
+                else:
+                    rows = self.side.recv(nr * self.rowdt.itemsize, src=r).view(self.rowdt)
+                got.append((int(hdrs[r, 1]), rows))
+            for first, rows in got:
+                self.out.write_block(first, {name: rows[name] for name, _ in self.positions})
+        elif n:
+            self.side.send(block[:n].view(np.uint8).reshape(-1), dst=0)
+
+    def _close(self):
+        """Everything has been handed over -- but the writer is asynchronous: a failure in its
+        last blocks (a full disk) only shows when the file is flushed and closed.  The owner does
+        that HERE, and one more round of headers tells everybody how it went; otherwise it alone
+        would raise after the threads have ended and the others would wait in the closing
+        barrier."""
+        if self.out is not None:
+            try:
+                self.out.close()
+            except BaseException as e:
+                self.local = e
+        all_closed = self._closing_round()
+        if self.plan.per_rank and all_closed:
+            # every part is complete and closed: the index that presents them as the
+            # reference's one file, and a second closing round for ITS verdict
+            if self.plan.rank == 0:
+                try:
+                    self.write_index()
+                except BaseException as e:
+                    self.local = e
+            self._closing_round()
+
+    def _closing_round(self):
+        """Everybody's verdict on the step just taken; True if all went well."""
+        lasts = self.side.all_gather_i64([0, 0, 1, 0 if self.local is None else 1])
+        badr = np.flatnonzero(lasts[:, 3])
+        if badr.size and self.local is None:
+            self.remote = RuntimeError(
+                "fit_sharded: rank %s could not finish the results file; "
+                "this rank stops too" % ", ".join(str(int(r)) for r in badr))
+        return not badr.size
 
 
 def fit_sharded(bf, data, data_err, data_mask, data_labels, save_file,
@@ -93,29 +473,13 @@ def fit_sharded(bf, data, data_err, data_mask, data_labels, save_file,
 
     Every rank fits the contiguous shard `shard_bounds(Ndata, world, rank0_share)[rank]` on
     its own GPU (no collective on the data path) and hands its finished rows to rank 0 in
-    bounded pieces, WITHOUT the ranks ever waiting for each other's fits:
-
-    * the fit (`BruteForce._fit`, this thread) packs every `chunk` finished objects into one
-      block -- a structured array with the file's own dtypes (`h5io.ResultsFile.row_dtype`,
-      18 KB per object at the defaults) -- and puts it into a bounded queue
-      (`queue_depth` blocks: the only back-pressure is a writer slower than the fits);
-    * a hand-off thread per rank drains that queue over a gloo SIDE GROUP
-      (`dist.new_group(backend="gloo")`: host memory to host memory, nothing is pickled and
-      nothing passes through RCCL): a round is one tiny `all_gather` of headers
-      `(rows, first row, done, failed)` followed by point-to-point sends of exactly the
-      rows that are ready -- a rank with nothing ready sends nothing and holds nobody up,
-      so rank 0's shard, its unpacking and the writer's thread no longer sit in every other
-      rank's critical path (round 3 gathered fixed blocks in lock-step from the fit loop);
-    * rank 0's hand-off thread gives the blocks to the asynchronous `ResultsFile` writer at
-      their catalogue positions -- row `lo_r + ...`, the mapping of reference
-      fitting.py:1734-1748.  No rank holds more than `queue_depth * chunk` finished rows,
-      rank 0 no more than a round of `world * chunk` on top, whatever the catalogue size.
-
-    A failure anywhere -- a fit, the writer (its errors are sticky), a hand-off -- is
-    announced in the next round's headers; every rank then stops its generator and raises,
-    none is left waiting in a collective.  That includes the writer's LAST blocks: when every
-    rank has reported "done", rank 0 flushes and closes the file inside the protocol and a
-    closing round of headers carries the outcome.  The side group is destroyed on the way out.
+    bounded pieces of `chunk` objects, WITHOUT the ranks ever waiting for each other's fits: a
+    hand-off thread per rank drains a queue of `queue_depth` such blocks over a gloo side
+    group, and rank 0's gives them to the asynchronous `ResultsFile` writer at their catalogue
+    positions.  No rank holds more than `queue_depth * chunk` finished rows, rank 0 no more than
+    `world * chunk` on top, whatever the catalogue size.  A failure anywhere -- a fit, the
+    writer, a hand-off -- stops every rank: each raises, none is left waiting in a collective
+    (`_HandOff` has the protocol).
 
     With `running_io=True` (default) the file on disk is current up to the last flush and
     `model_idx` is the last dataset of a block to be written, so a crash leaves the rows in
@@ -151,327 +515,64 @@ def fit_sharded(bf, data, data_err, data_mask, data_labels, save_file,
     per rank it is 0.45 GB/s into a file of its own.  `resume=True` re-opens every rank's part
     (same number of ranks as the interrupted run).
     """
-    import os
-    import queue
-    import threading
-    import time
-    import torch
     import torch.distributed as dist
     from . import h5io
     rank, world = dist.get_rank(), dist.get_world_size()
-    kw = dict(fit_kwargs)
-    resume = bool(kw.pop("resume", False))
-    Ndraws = kw.pop("Ndraws", 250)
-    save_dar_draws = kw.pop("save_dar_draws", True)
-    running_io = kw.pop("running_io", True)
-    lnprior_ext = kw.pop("lnprior_ext", None)
-    kw.pop("verbose", None)
-    kw.pop("rstate", None)
+    opts, skw, fkw = _split_fit_kwargs(fit_kwargs)
     chunk = max(1, int(chunk))
-    setup_keys = ("phot_offsets", "parallax", "parallax_err", "av_gauss",
-                  "lnprior", "wt_thresh", "cdf_thresh", "apply_agewt",
-                  "apply_grad", "lngalprior", "lndustprior", "dustfile",
-                  "data_coords", "ltol_subthresh", "logl_initthresh", "mag_max",
-                  "merr_max")
-    skw = {k: kw[k] for k in setup_keys if k in kw}
     (data, data_err, data_mask, data_labels, data_coords, lnprior, lngalprior,
      lndustprior, av_gauss, wt_thresh, _) = bf._setup(
         data, data_err, data_mask, data_labels, **skw)
     Ndata = data.shape[0]
-    bounds = shard_bounds(Ndata, world, rank0_share)
-    lo, hi = bounds[rank]
-    fkw = {k: v for k, v in kw.items()
-           if k not in ("phot_offsets", "apply_agewt", "apply_grad", "mag_max",
-                        "merr_max", "parallax", "parallax_err", "data_coords",
-                        "lnprior", "lngalprior", "lndustprior", "av_gauss",
-                        "wt_thresh")}
-    if "logl_dim_prior" not in fkw:
-        fkw["logl_dim_prior"] = True
-    par = kw.get("parallax")
-    perr = kw.get("parallax_err")
     t_start = time.time()
-    if writer not in ("rank0", "per_rank"):
-        raise ValueError("fit_sharded: writer must be 'rank0' or 'per_rank'")
-    per_rank = writer == "per_rank"
-    side = dist.new_group(backend="gloo") if world > 1 else None     # host-to-host hand-off
-    out = None
-    todo = None
-    # Who writes what: one file on rank 0 (rows arrive over the side group), or a part per rank.
-    owner = rank == 0 or (per_rank and hi > lo)
-    my_path = ("{0}.r{1:02d}.h5".format(save_file, rank) if per_rank else "{0}.h5".format(save_file))
-    my_rows = (hi - lo) if per_rank else Ndata
-    my_first = lo if per_rank else 0
-    if per_rank and rank == 0 and hi == lo:
-        owner = False
-    open_error = None
-    if per_rank and rank == 0 and not resume and os.path.exists("{0}.h5".format(save_file)):
-        # the index is written LAST; that it cannot be created ("w-", reference fitting.py:1632)
-        # is said now, not after the whole catalogue has been fitted
-        open_error = OSError("fit_sharded: %s.h5 exists already" % save_file)
-        owner = False
-    if owner:
-        try:
-            if resume:
-                # the interrupted file(s): rows whose `model_idx[:, 0]` still holds the sentinel
-                # -99 were never fitted (reference fitting.py:1635)
-                out = h5io.ResultsFile.resume(my_path, my_rows, Ndraws, save_dar_draws)
-            else:
-                lab = data_labels
-                if per_rank and lab is not None:
-                    lab = np.asarray(lab)[lo:hi]
-                out = h5io.ResultsFile(my_path, my_rows, Ndraws, lab, save_dar_draws,
-                                       running_io=running_io)
-        except BaseException as e:
-            open_error = e
-    # One handshake for every way of opening: a rank that could not create / re-open its file
-    # says so before anybody enters the hand-off protocol, and EVERY rank raises (without it
-    # the others would wait for the failed rank in the first round of headers).
-    ok = torch.tensor([0 if open_error is not None else 1], dtype=torch.int64)
-    if world > 1:
-        oks = [torch.empty(1, dtype=torch.int64) for _ in range(world)]
-        dist.all_gather(oks, ok, group=side)
-        bad = [r for r in range(world) if not int(oks[r])]
-    else:
-        bad = [] if int(ok) else [0]
-    if bad:
-        if out is not None:
-            try:
-                out.close()
-                if not resume:
-                    os.remove(my_path)          # created a moment ago, holds nothing: a rerun must not trip over it
-            except BaseException:
-                pass
-        if side is not None:
-            dist.destroy_process_group(side)
-        raise open_error or RuntimeError(
-            "fit_sharded: rank(s) %s could not open their results file; this rank stops too"
-            % ", ".join(str(r) for r in bad))
-    if resume:
-        # every rank fits only the unfinished rows of ITS shard, each contiguous run of them as
-        # one `_fit` call seeded `seed0 + first row` -- object i draws from stream `seed0 + i` as
-        # in the interrupted run, so the completed file equals an uninterrupted one.
-        state = torch.zeros(Ndata, dtype=torch.uint8)
-        if out is not None:
-            state[my_first + torch.from_numpy(np.asarray(out.todo, dtype=np.int64))] = 1
-        if world > 1 and not per_rank:
-            dist.broadcast(state, src=0, group=side)
-        todo = state.numpy().astype(bool)
-    # the contiguous runs [a, b) of rows this rank fits
-    if todo is None:
-        runs = [(lo, hi)] if hi > lo else []
-    else:
-        mine = np.flatnonzero(todo[lo:hi]) + lo
-        cuts = np.flatnonzero(np.diff(mine) != 1) + 1
-        runs = [(int(r[0]), int(r[-1]) + 1) for r in np.split(mine, cuts) if r.size]
+    plan = _make_plan(rank, shard_bounds(Ndata, world, rank0_share), writer, save_file, opts.resume)
+    side = _SideGroup(world)                     # host-to-host hand-off
+    out, open_error = _open_results(plan, opts, data_labels)
+    _open_handshake(side, plan, out, open_error, opts.resume)
+    runs = _resume_runs(_todo_mask(side, plan, out, Ndata) if opts.resume else None,
+                        plan.lo, plan.hi)
     nmine = sum(b - a for a, b in runs)
-    current = [None]
-
-    def fitted_rows():
-        """(catalogue row, 13-tuple) of every row of this rank's runs, in row order."""
-        for a, b in runs:
-            rkw = dict(fkw)
-            if lnprior_ext is not None:
-                # per-object constraints: `_fit` sees objects a..b as 0..b-a
-                rkw["lnprior_ext"] = {k: np.asarray(v)[a:b] for k, v in lnprior_ext.items()}
-            g = bf._fit(
-                data[a:b], data_err[a:b], data_mask[a:b],
-                parallax=None if par is None else np.asarray(par)[a:b],
-                parallax_err=None if perr is None else np.asarray(perr)[a:b],
-                lnprior=lnprior, lngalprior=lngalprior, lndustprior=lndustprior,
-                av_gauss=av_gauss, wt_thresh=wt_thresh, data_coords=data_coords[a:b],
-                Ndraws=Ndraws, return_distreds=save_dar_draws,
-                seed0=seed0 + a,
-                rstate_per_object="philox" if rng == "philox" else None, **rkw)
-            current[0] = g
-            for k, res in enumerate(g):
-                yield a + k, res
-            current[0] = None
-
-    gen = fitted_rows()
-    rowdt, positions = h5io.ResultsFile.row_dtype(Ndraws, save_dar_draws)
-    rowbytes = rowdt.itemsize
-    q = queue.Queue(maxsize=max(1, int(queue_depth)))
-    abort = threading.Event()
-    failure = {"local": None, "remote": None}
-
-    def hand_off():
-        """Drains the queue: header round, then the rows that are ready (see above)."""
-        done = False
-        try:
-            while True:
-                item = None
-                # The failure state is read ONCE per round, before the queue: a block taken
-                # from the queue is handed over in this round even if the fit raises while it
-                # is on its way (the fitting thread runs on as soon as the queue has room), and
-                # the failure goes into the next round's header.  Read after the `get`, the flag
-                # could drop rows that were fitted before anything went wrong.
-                failed = failure["local"] is not None
-                if not done and not failed:
-                    try:
-                        item = q.get(timeout=0.02)
-                    except queue.Empty:
-                        pass
-                n, start, block = 0, 0, None
-                if item is not None:
-                    if item[0] == "rows":
-                        _, start, n, block = item
-                    elif item[0] == "done":
-                        done = True
-                    else:
-                        failure["local"] = failure["local"] or RuntimeError(item[1])
-                        failed = True
-                hdr = torch.tensor([n, start, 1 if done else 0, 1 if failed else 0],
-                                   dtype=torch.int64)
-                if world > 1:
-                    hdrs = [torch.empty(4, dtype=torch.int64) for _ in range(world)]
-                    dist.all_gather(hdrs, hdr, group=side)
-                    hdrs = torch.stack(hdrs).numpy()
-                else:
-                    hdrs = hdr.numpy()[None, :]
-                bad = np.flatnonzero(hdrs[:, 3])
-                if bad.size:
-                    if failure["local"] is None:
-                        failure["remote"] = RuntimeError(
-                            "fit_sharded: rank(s) %s failed; this rank stops too"
-                            % ", ".join(str(int(b)) for b in bad))
-                    return
-                try:
-                    if rank == 0:
-                        got = []
-                        for r in range(world):       # every payload is received before any is
-                            nr = int(hdrs[r, 0])     # written: a failing write strands no sender
-                            if nr == 0:
-                                continue
-                            if r == 0:
-                                rows = block[:nr]
-                            else:
-                                buf = torch.empty(nr * rowbytes, dtype=torch.uint8)
-                                dist.recv(buf, src=r, group=side)
-                                rows = buf.numpy().view(rowdt)
-                            got.append((int(hdrs[r, 1]), rows))
-                        for first, rows in got:
-                            out.write_block(first, {name: rows[name] for name, _ in positions})
-                    elif n:
-                        dist.send(torch.from_numpy(block[:n].view(np.uint8).reshape(-1)), dst=0,
-                                  group=side)
-                except BaseException as e:           # announced in the next round's headers
-                    failure["local"] = e
-                    continue
-                if np.all(hdrs[:, 2] == 1) and not np.any(hdrs[:, 0]):
-                    # Everything has been handed over -- but the writer is asynchronous: a
-                    # failure in its last blocks (a full disk) only shows when the file is
-                    # flushed and closed.  Rank 0 does that HERE, and one more round of headers
-                    # tells everybody how it went; otherwise rank 0 alone would raise after the
-                    # threads have ended and the others would wait in the closing barrier.
-                    def closing_round():
-                        """Everybody's verdict on the step just taken; True if all went well."""
-                        if world == 1:
-                            return failure["local"] is None
-                        last = torch.tensor([0, 0, 1, 0 if failure["local"] is None else 1],
-                                            dtype=torch.int64)
-                        lasts = [torch.empty(4, dtype=torch.int64) for _ in range(world)]
-                        dist.all_gather(lasts, last, group=side)
-                        badr = [r for r in range(world) if int(lasts[r][3])]
-                        if badr and failure["local"] is None:
-                            failure["remote"] = RuntimeError(
-                                "fit_sharded: rank %s could not finish the results file; "
-                                "this rank stops too" % ", ".join(str(r) for r in badr))
-                        return not badr
-                    if out is not None:
-                        try:
-                            out.close()
-                        except BaseException as e:
-                            failure["local"] = e
-                    all_closed = closing_round()
-                    if per_rank and all_closed:
-                        # every part is complete and closed: the index that presents them as
-                        # the reference's one file
-                        if rank == 0:
-                            try:
-                                h5io.write_virtual_index(
-                                    "{0}.h5".format(save_file), Ndata, Ndraws, save_dar_draws,
-                                    data_labels,
-                                    [(a, b, os.path.basename("{0}.r{1:02d}.h5".format(save_file, r)))
-                                     for r, (a, b) in enumerate(bounds) if b > a],
-                                    overwrite=resume)
-                            except BaseException as e:
-                                failure["local"] = e
-                        closing_round()
-                    return
-        except BaseException as e:                   # the collective itself failed
-            failure["local"] = failure["local"] or e
-        finally:
-            if failure["local"] is not None or failure["remote"] is not None:
-                abort.set()
-
-    def put(item):
-        while True:
-            if abort.is_set():
-                raise failure["remote"] or failure["local"] or RuntimeError("fit_sharded aborted")
-            try:
-                q.put(item, timeout=0.05)
-                return
-            except queue.Full:
-                continue
-
-    th = threading.Thread(target=hand_off, name="brutus-shard-handoff", daemon=True)
-    th.start()
-    fit_error = None
-    t_fit = None
+    per_object = {k: None if skw.get(k) is None else np.asarray(skw[k])
+                  for k in ("parallax", "parallax_err")}
+    gen = _fitted_rows(
+        bf, runs, data, data_err, data_mask, dict(per_object, data_coords=data_coords),
+        opts.lnprior_ext, seed0,
+        dict(fkw, lnprior=lnprior, lngalprior=lngalprior, lndustprior=lndustprior,
+             av_gauss=av_gauss, wt_thresh=wt_thresh, Ndraws=opts.Ndraws,
+             return_distreds=opts.save_dar_draws,
+             rstate_per_object="philox" if rng == "philox" else None))
+    rowdt, positions = h5io.ResultsFile.row_dtype(opts.Ndraws, opts.save_dar_draws)
+    handoff = _HandOff(side, plan, out, rowdt, positions, queue_depth, functools.partial(
+        h5io.write_virtual_index, plan.index_path, Ndata, opts.Ndraws, opts.save_dar_draws,
+        data_labels, plan.index_parts(), overwrite=opts.resume))
+    handoff.thread.start()
+    fit_error = t_fit = close_error = None
     try:
         bf._catalogue_mask = data_mask       # one band set for all ranks and runs (BruteForce._bands_for)
         try:
-            exhausted = False
-            pending = None                           # a row of the next run, already fitted
-            while not exhausted:
-                block = np.zeros(chunk, dtype=rowdt)
-                n, start = 0, None
-                with np.errstate(over="ignore"):
-                    while n < chunk:
-                        if pending is not None:
-                            row, res = pending
-                            pending = None
-                        else:
-                            try:
-                                row, res = next(gen)
-                            except StopIteration:
-                                exhausted = True
-                                break
-                        if start is None:
-                            start = row
-                        elif row != start + n:       # a new run: blocks hold consecutive rows
-                            pending = (row, res)
-                            break
-                        for name, pos in positions:
-                            block[name][n] = res[pos]
-                        n += 1
-                if n and per_rank:
-                    if abort.is_set():               # somebody else failed: stop fitting
-                        raise failure["remote"] or failure["local"] or RuntimeError("fit_sharded aborted")
-                    out.write_block(start - lo, {name: block[name][:n] for name, _ in positions})
-                elif n:
-                    put(("rows", start, n, block))
+            for start, n, block in _pack_blocks(gen, chunk, rowdt, positions):
+                if plan.per_rank:            # written here, at `start - lo` of this rank's part
+                    handoff.check()
+                    out.write_block(start - plan.lo,
+                                    {name: block[name][:n] for name, _ in positions})
+                else:
+                    handoff.put(("rows", start, n, block))
             t_fit = time.time() - t_start
-            put(("done",))
+            handoff.put(("done",))
         except BaseException as e:
             fit_error = e
-            if not abort.is_set():                   # tell the others, whatever the queue holds
-                failure["local"] = failure["local"] or e
-        th.join()
+            handoff.fail(e)
+        handoff.thread.join()
     finally:
         bf._catalogue_mask = None
-        if current[0] is not None and hasattr(current[0], "close"):
-            current[0].close()              # shuts the scan-ahead helper thread down
-        gen.close()
-        close_error = None
+        gen.close()                          # and with it the `_fit` generator in flight
         if out is not None:
             try:
                 out.close()
-            except BaseException as e:      # (sticky writer error: reported below)
+            except BaseException as e:       # (sticky writer error: reported below)
                 close_error = e
-        if side is not None:
-            dist.destroy_process_group(side)
-    err = fit_error or failure["local"] or failure["remote"] or close_error
+        side.destroy()
+    err = fit_error or handoff.error() or close_error
     if err is not None:
         raise err
     fit_sharded.last_stats = {"fit_s": t_fit, "total_s": time.time() - t_start,

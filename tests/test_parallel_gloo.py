@@ -1,5 +1,5 @@
 """CPU, world_size 2, gloo: the star-sharding plumbing of brutus_amd.parallel
-(the N > 1 path of bench.py / fit_sharded).  The HIP engine itself cannot run
+(`fit_sharded`; bench.py's N > 1 path does not go through it).  The HIP engine itself cannot run
 here, so `_fit` is replaced by a deterministic stand-in; what is under test is
 the partition, the rank-ordered gather, the per-object seeding and the HDF5
 assembly."""
