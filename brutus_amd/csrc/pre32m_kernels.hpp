@@ -37,7 +37,7 @@
 // Layout.  v_mfma_f32_16x16x4_f32: A operand lane l = A[i = l & 15][k = l >> 4], B operand lane
 // l = B[k = l >> 4][j = l & 15], result register r of lane l = D[4 (l >> 4) + r][l & 15].  Rows
 // i = 16 models of a tile, columns j = the wave's 16 stars: a lane ends up with ITS star (lane &
-// 15) and four consecutive models (4 (lane >> 4) + r) -- the per-pair code of k_pre32s runs
+// 15) and four consecutive models (4 (lane >> 4) + r) -- the per-pair code of pre32_pair.hpp runs
 // unchanged with lane = (star, model quarter), reads the model-only values (mcC_j, R_j) from the
 // tile's LDS rows with quarter-wave-uniform addresses, and stores its four models as ONE 16-byte
 // word per plane (no LDS transposition).
@@ -50,7 +50,7 @@
 // pdf.py:209-218; float32 only ever classifies.
 #pragma once
 
-#include "pre32s_kernels.hpp"
+#include "pre32_pair.hpp"
 
 namespace {
 
@@ -91,8 +91,6 @@ k_pre32m(const float *__restrict__ grid, int64_t nmodel, int64_t nmodel_pad, int
     constexpr int OFF_A = NB, OFF_B = 2 * NB, OFF_MBAR = (RVF ? 2 : 3) * NB;
     __shared__ __attribute__((aligned(16))) float s_row[4][4 * GS];
     __shared__ float s_mx[4][NV32][16];
-    const float C10 = -1.32877123795494494f;      // c = -0.4 log2(10)
-    const float NINF = -INFINITY;
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int sj = lane & 15, g = lane >> 4;      // pair code: star column, model quarter; operands: k = g
@@ -115,7 +113,7 @@ k_pre32m(const float *__restrict__ grid, int64_t nmodel, int64_t nmodel_pad, int
     float U0 = 0.f, G2 = 0.f;
 #pragma unroll
     for (int j = 0; j < NB; ++j) {
-        const float gcC = C10 * sp.gc[j], w = sp.w[j];
+        const float gcC = PS_C10 * sp.gc[j], w = sp.w[j];
         U0 = fmaf(w, gcC, U0);
         G2 = fmaf(w * gcC, gcC, G2);
     }
@@ -123,7 +121,7 @@ k_pre32m(const float *__restrict__ grid, int64_t nmodel, int64_t nmodel_pad, int
     for (int t = 0; t < NQ; ++t) {
         const int b = 2 * t + par;
         const float w = sp.w[b];
-        bw2[t] = odd ? w : w * (C10 * sp.gc[b]);
+        bw2[t] = odd ? w : w * (PS_C10 * sp.gc[b]);
     }
 #pragma unroll
     for (int t = 0; t < NT; ++t) bw1[t] = sp.w[par + 4 * t + 2 * odd];
@@ -133,17 +131,10 @@ k_pre32m(const float *__restrict__ grid, int64_t nmodel, int64_t nmodel_pad, int
         dd[j] = sp.dd[j];
         iv[j] = sp.iv[j];
     }
-    const float S = sp.S, rS = __builtin_amdgcn_rcpf(sp.S), gbarC = C10 * sp.gbar, DD2 = sp.DD2;
-    const bool has_par = sp.has_par != 0, sp_on = sp.sp_on != 0;
-    const float eps4 = sp.ok ? 4.f * sp.eps : INFINITY, chi2_lo = sp.ok ? sp.chi2_lo : INFINITY;
-    const float parx = has_par ? sp.par : 0.f, par_hiv = has_par ? 0.5f * sp.par_ivar : 0.f;
-    const float sp_mean = sp.sp_mean, sp_var = sp.sp_var, c0 = sp.c0, c1 = sp.c1;
-    const bool any_par = __ballot(has_par) != 0ull, any_sp = __ballot(sp_on) != 0ull;     // wave-uniform
-    const float avm = C10 * p.av_mean, av_lo = C10 * p.avmax, av_hi = C10 * p.avmin;
-    const float tol_hi = -C10 * p.mtol_hi, tol_lo = -C10 * p.mtol_lo;
-    const float lw_scale = -0.5f / (C10 * C10);
-    float mx0 = NINF, mx1 = NINF, mx2 = NINF, mx3 = NINF, mx4 = NINF, mx5 = NINF, mx6 = NINF, mx7 = NINF,
-          mx8 = NINF, mx9 = NINF;
+    const PairStar cst = pair_star(&sp, p);
+    // (written out: a loop is unrolled too late for the maxima a kernel never updates to fold away)
+    const float NINF = -INFINITY;
+    float mx[NV32] = {NINF, NINF, NINF, NINF, NINF, NINF, NINF, NINF, NINF, NINF};
     const int64_t i0 = (int64_t)bx * (F2_T * PS_TILE) + (int64_t)wv * PS_WM;
     const int64_t i1 = i0 + PS_WM < nmodel ? i0 + PS_WM : nmodel;
     // ---- model side ----------------------------------------------------------------------------
@@ -184,7 +175,7 @@ k_pre32m(const float *__restrict__ grid, int64_t nmodel, int64_t nmodel_pad, int
 #pragma unroll
             for (int q = 0; q < NQ; ++q) {
                 const int b = 2 * q + par;
-                mc[q] = C10 * (cm[q] - mbar);
+                mc[q] = PS_C10 * (cm[q] - mbar);
                 if constexpr (RVF) A[q] = fmaf(p.rv_mean, cdr[q], cr0[q]);
                 else A[q] = cr0[q];
                 // the tile's rows for the per-pair code: even lanes the magnitudes, odd ones R
@@ -193,7 +184,7 @@ k_pre32m(const float *__restrict__ grid, int64_t nmodel, int64_t nmodel_pad, int
                 wrow[wsel + b] = odd ? A[q] : mc[q];
                 if constexpr (!RVF) wrow[OFF_B + b] = cdr[q];
             }
-            wrow[OFF_MBAR] = C10 * mbar;
+            wrow[OFF_MBAR] = PS_C10 * mbar;
             // two-term planes: band 2 t + par, first term from the even lanes, second from the odd
 #pragma unroll
             for (int t = 0; t < NQ; ++t) {
@@ -240,122 +231,17 @@ k_pre32m(const float *__restrict__ grid, int64_t nmodel, int64_t nmodel_pad, int
                     B[4 * k] = d.x; B[4 * k + 1] = d.y; B[4 * k + 2] = d.z; B[4 * k + 3] = d.w;
                 }
             }
-            const float dbar = gbarC - rrow[r * RS + OFF_MBAR];      // c (gbar - mbar)
-            float av = avm, rv = p.rv_mean;                          // av: c Av throughout
-            const float uy = a_uy[r], yy = a_yy[r];
-            if constexpr (RVF) {
-                const float uR = a_uR[r], RR = a_RR[r], yR = a_yR[r];
-                const float rs = uy - av * uR;
-                const float ra = (yR - av * RR) + (avm - av) * p.av_ivar;
-                const float a_den = RR + p.av_ivar;
-                float dav = (S * ra - uR * rs) * __builtin_amdgcn_rcpf(S * a_den - uR * uR);
-                dav = fminf(dav, av_hi - av);
-                dav = fmaxf(dav, av_lo - av);
-                av += dav;
-                const float oc = (uy - av * uR) * rS;
-                const float tt0 = dbar + oc;
-                const float lw = lw_scale * ((yy - av * (2.f * yR - av * RR)) + S * (tt0 * tt0 - oc * oc));
-                const float st = fabsf(dav);
-                mx0 = vmaxf(mx0, lw);
-                mx1 = vmaxf(mx1, st >= tol_hi ? lw : NINF);
-                mx2 = vmaxf(mx2, st >= tol_lo ? lw : NINF);
-                mx8 = lw != lw ? 1.f : mx8;
-            } else {
-                const float ua = a_uR[r], ub = a_ub[r], aa = a_RR[r], ab = a_ab[r], bb = a_bb[r], ay = a_yR[r],
-                            by = a_by[r];
-                const float c2 = C10 * C10;
-                auto sweep = [&](float &dav_o, float &drv_o) -> float {
-                    const float uR = ua + rv * ub;
-                    const float RR = aa + rv * (2.f * ab + rv * bb);
-                    const float yR = ay + rv * by;
-                    float rs = uy - av * uR;
-                    const float ra = (yR - av * RR) + (avm - av) * p.av_ivar;
-                    const float a_den = RR + p.av_ivar;
-                    float dav = (S * ra - uR * rs) * __builtin_amdgcn_rcpf(S * a_den - uR * uR);
-                    dav = fminf(dav, av_hi - av);
-                    dav = fmaxf(dav, av_lo - av);
-                    av += dav;
-                    const float r_den = bb * av * av + c2 * p.rv_ivar;
-                    const float sr = ub * av;
-                    rs = uy - av * uR;
-                    const float bres = by - av * (ab + rv * bb);
-                    const float rr = av * bres + c2 * ((p.rv_mean - rv) * p.rv_ivar);
-                    float drv = (S * rr - sr * rs) * __builtin_amdgcn_rcpf(S * r_den - sr * sr);
-                    drv = fmaxf(drv, p.rvmin - rv);
-                    drv = fminf(drv, p.rvmax - rv);
-                    rv += drv;
-                    const float RR2 = aa + rv * (2.f * ab + rv * bb);
-                    const float yR2 = ay + rv * by;
-                    dav_o = dav;
-                    drv_o = drv;
-                    const float uR2 = ua + rv * ub;
-                    const float oc = (uy - av * uR2) * rS;
-                    const float tt0 = dbar + oc;
-                    return lw_scale * ((yy - av * (2.f * yR2 - av * RR2)) + S * (tt0 * tt0 - oc * oc));
-                };
-                float d1, d2;
-                {
-                    const float lw = sweep(d1, d2);
-                    const float st = fmaxf(fabsf(d1) * (-1.f / C10), fabsf(d2));
-                    mx0 = vmaxf(mx0, lw);
-                    mx1 = vmaxf(mx1, st >= p.mtol_hi ? lw : NINF);
-                    mx2 = vmaxf(mx2, st >= p.mtol_lo ? lw : NINF);
-                    mx8 = lw != lw ? 1.f : mx8;
-                }
-                {
-                    const float lw = sweep(d1, d2);
-                    const float st = fmaxf(fabsf(d1) * (-1.f / C10), fabsf(d2));
-                    mx3 = vmaxf(mx3, lw);
-                    mx4 = vmaxf(mx4, st >= p.mtol_hi ? lw : NINF);
-                    mx5 = vmaxf(mx5, st >= p.mtol_lo ? lw : NINF);
-                    mx8 = lw != lw ? 1.f : mx8;
-                }
-            }
-            // MLE in scaled units: F = A f, A = 10^(-0.4 mbar), d = D dd
-            float num = 0.f, den = 0.f;
-#pragma unroll
-            for (int j = 0; j < NB; ++j) {
-                float Rj;
-                if constexpr (RVF) Rj = A[j];
-                else Rj = fmaf(rv, B[j], A[j]);
-                const float e = __builtin_amdgcn_exp2f(fmaf(av, Rj, mcC[j]));
-                const float fw = e * iv[j];
-                num = fmaf(dd[j], fw, num);
-                den = fmaf(e, fw, den);
-            }
-            const float q = __builtin_amdgcn_exp2f(dbar);       // D / A
-            const float rden = __builtin_amdgcn_rcpf(den);
-            float tt = num * rden;
-            float sc = tt * q;
-            {
-                const bool tiny = sc <= 1e-20f;
-                const float tt_lo = 1e-20f * __builtin_amdgcn_rcpf(q);
-                tt = tiny ? tt_lo : tt;
-                sc = tiny ? 1e-20f : sc;
-            }
-            const float chi2 = fmaf(tt, fmaf(tt, den, -2.f * num), DD2);
-            const float lnl = -0.5f * chi2;
-            float lnlp = lnl;
-            if (any_par) {
-                const float dp = __builtin_amdgcn_sqrtf(sc) - parx;
-                lnlp = has_par ? lnl - dp * dp * par_hiv : lnl;
-            }
-            float lnpr = lnl;
-            if (p.dim_prior) lnpr = c0 + c1 * ln_pos(chi2) - 0.5f * chi2;
-            if (any_sp) {
-                const float vt = sp_var + q * q * rden;
-                const float ds = sc - sp_mean;
-                const float t = -0.5f * (ds * ds * __builtin_amdgcn_rcpf(vt) + ln_pos(6.2831853071795865f * vt));
-                lnpr = sp_on ? lnpr + t : lnpr;
-            }
-            lnlp = chi2 > eps4 ? lnlp : NAN;
-            lnpr = fabsf(lnpr) < 0x1p-100f ? 0.f : lnpr;
-            lnpr = chi2 > chi2_lo ? lnpr : NAN;
+            const float dbar = cst.gbarC - rrow[r * RS + OFF_MBAR];      // c (gbar - mbar)
+            float av, rv = p.rv_mean;                                // av: c Av throughout
+            if constexpr (RVF)
+                av = pair_av_step(a_uR[r], a_RR[r], a_yR[r], a_uy[r], a_yy[r], dbar, cst, p, mx);
+            else
+                pair_sweeps(a_uR[r], a_ub[r], a_uy[r], a_RR[r], a_ab[r], a_bb[r], a_yR[r], a_by[r], a_yy[r], dbar,
+                            cst, p, av, rv, mx);
+            float lnlp, lnpr;
+            pair_tail<NB, RVF>(mcC, A, B, dd, iv, av, rv, dbar, cst, p, lnlp, lnpr, mx);
             o_lnlp[r] = lnlp;
             o_lnpr[r] = lnpr;
-            mx9 = (lnlp != lnlp || lnpr != lnpr) ? 1.f : mx9;
-            mx6 = vmaxf(mx6, lnlp);
-            mx7 = vmaxf(mx7, lnpr);
         }
         // four consecutive models of one star per lane: one 16-byte word per plane where the row
         // is aligned (s nmodel + ib + 4 g: nmodel a multiple of 4), scalars otherwise
@@ -376,14 +262,11 @@ k_pre32m(const float *__restrict__ grid, int64_t nmodel, int64_t nmodel_pad, int
         ps_wave_sync();
     }
     // a star's four lane quarters, then the four waves
-    {
-        float v[NV32] = {mx0, mx1, mx2, mx3, mx4, mx5, mx6, mx7, mx8, mx9};
 #pragma unroll
-        for (int k = 0; k < NV32; ++k) {
-            v[k] = vmaxf(v[k], __shfl_xor(v[k], 16, 64));
-            v[k] = vmaxf(v[k], __shfl_xor(v[k], 32, 64));
-            if (g == 0) s_mx[wv][k][sj] = v[k];
-        }
+    for (int k = 0; k < NV32; ++k) {
+        float v = vmaxf(mx[k], __shfl_xor(mx[k], 16, 64));
+        v = vmaxf(v, __shfl_xor(v, 32, 64));
+        if (g == 0) s_mx[wv][k][sj] = v;
     }
     __syncthreads();
     if (wv == 0 && g == 0 && slive) {

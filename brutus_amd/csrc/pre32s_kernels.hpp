@@ -43,36 +43,15 @@
 // classifies (see fit2_kernels.hpp).
 #pragma once
 
-#include "pre32_types.hpp"
+#include "pre32_pair.hpp"
 
 namespace {
 
 constexpr int PS_M = 16;                      // models per tile (staging and transposition)
 constexpr int PS_STRIDE = 66;                 // floats per transposition row: (2 m + star) mod 32 is conflict-free
-constexpr int PS_WM = F2_T * PS_TILE / 4;        // models per wave: a block of F2_T tiles over four waves
 constexpr int ps_row(int nb) { return 3 * nb + 4; }
 // (16 bands: 168 registers + 72-160 bytes of scratch at three waves per SIMD -- k_pre32 keeps them)
 constexpr bool ps_bands(int nb) { return nb <= 12; }
-
-// v_max_f32 as the hardware defines it: a NaN operand yields the other one (fmaxf compiles to
-// two canonicalising v_max per call on top)
-__device__ __forceinline__ float vmaxf(float a, float b) {
-    float r;
-    asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-// ln x for a normal-range positive argument: v_log_f32 (log2, 1 ulp) times ln 2 -- __logf's
-// denormal rescue and its extended-precision multiplication are ten more instructions, and the
-// arguments here (chi2 above chi2_lo >= 0.5, variances) never need them
-__device__ __forceinline__ float ln_pos(float x) { return 0.69314718055994531f * __builtin_amdgcn_logf(x); }
-// LDS hand-over between the lanes of ONE wave (its instructions reach the LDS in order: no
-// hardware wait is needed, but the compiler must not move the reads of other lanes' words
-// across the writes, in either direction)
-__device__ __forceinline__ void ps_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    asm volatile("" ::: "memory");
-}
 
 // One workgroup = one block of F2_T tiles (the unit of part32) x one group of 64 stars; wave w
 // takes a quarter of the block's models, in tiles of 16.  Per tile: the wave's lanes (model m =
@@ -99,8 +78,6 @@ k_pre32s(const float *__restrict__ grid, int64_t nmodel, int64_t nmodel_pad, int
     __shared__ float s_t[4][2][PS_M][PS_STRIDE];
     __shared__ __attribute__((aligned(16))) float s_row[4][PS_M][ROW];
     __shared__ int64_t s_base[64];
-    const float C10 = -1.32877123795494494f;      // c = -0.4 log2(10)
-    const float NINF = -INFINITY;
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int ngroup = (nrun + 63) >> 6;
@@ -114,24 +91,15 @@ k_pre32s(const float *__restrict__ grid, int64_t nmodel, int64_t nmodel_pad, int
     float gcC[NB], w[NB], dd[NB], iv[NB];
 #pragma unroll
     for (int j = 0; j < NB; ++j) {
-        gcC[j] = C10 * sp.gc[j];
+        gcC[j] = PS_C10 * sp.gc[j];
         w[j] = sp.w[j];
         dd[j] = sp.dd[j];
         iv[j] = sp.iv[j];
     }
-    const float S = sp.S, rS = __builtin_amdgcn_rcpf(sp.S), gbarC = C10 * sp.gbar, DD2 = sp.DD2;
-    const bool has_par = sp.has_par != 0, sp_on = sp.sp_on != 0;
-    // (a star float32 cannot represent: both limits at +inf turn every value into NaN)
-    const float eps4 = sp.ok ? 4.f * sp.eps : INFINITY, chi2_lo = sp.ok ? sp.chi2_lo : INFINITY;
-    const float par = has_par ? sp.par : 0.f, par_hiv = has_par ? 0.5f * sp.par_ivar : 0.f;
-    const float sp_mean = sp.sp_mean, sp_var = sp.sp_var, c0 = sp.c0, c1 = sp.c1;
-    const bool any_par = __ballot(has_par) != 0ull, any_sp = __ballot(sp_on) != 0ull;     // wave-uniform
-    // the Av solve in av' = c av (c < 0: the clamps trade places)
-    const float avm = C10 * p.av_mean, av_lo = C10 * p.avmax, av_hi = C10 * p.avmin;
-    const float tol_hi = -C10 * p.mtol_hi, tol_lo = -C10 * p.mtol_lo;
-    const float lw_scale = -0.5f / (C10 * C10);
-    float mx0 = NINF, mx1 = NINF, mx2 = NINF, mx3 = NINF, mx4 = NINF, mx5 = NINF, mx6 = NINF, mx7 = NINF,
-          mx8 = NINF, mx9 = NINF;
+    const PairStar cst = pair_star(&sp, p);
+    // (written out: a loop is unrolled too late for the maxima a kernel never updates to fold away)
+    const float NINF = -INFINITY;
+    float mx[NV32] = {NINF, NINF, NINF, NINF, NINF, NINF, NINF, NINF, NINF, NINF};
     const int64_t i0 = (int64_t)bx * (F2_T * PS_TILE) + (int64_t)wv * PS_WM;
     const int64_t i1 = i0 + PS_WM < nmodel ? i0 + PS_WM : nmodel;
     // staging role of this lane
@@ -165,7 +133,7 @@ k_pre32s(const float *__restrict__ grid, int64_t nmodel, int64_t nmodel_pad, int
 #pragma unroll
             for (int k = 0; k < NBG; ++k) {
                 const int j = bg * NBG + k;
-                rw[j] = C10 * (cm[k] - mbar);
+                rw[j] = PS_C10 * (cm[k] - mbar);
                 if constexpr (RVF) {
                     const float R = fmaf(p.rv_mean, cdr[k], cr0[k]);
                     rw[NB + j] = R;
@@ -178,7 +146,7 @@ k_pre32s(const float *__restrict__ grid, int64_t nmodel, int64_t nmodel_pad, int
                     rw[NF * NB + 4 + 2 * NB + j] = cdr[k] * cdr[k];
                 }
             }
-            if (bg == 0) rw[NF * NB] = C10 * mbar;
+            if (bg == 0) rw[NF * NB] = PS_C10 * mbar;
         }
         if (ib + PS_M < i1) fetch(ib + PS_M);        // the next tile's coefficients: a whole tile of latency cover
         ps_wave_sync();
@@ -193,8 +161,8 @@ k_pre32s(const float *__restrict__ grid, int64_t nmodel, int64_t nmodel_pad, int
                 A[4 * k] = c.x; A[4 * k + 1] = c.y; A[4 * k + 2] = c.z; A[4 * k + 3] = c.w;
                 B[4 * k] = d.x; B[4 * k + 1] = d.y; B[4 * k + 2] = d.z; B[4 * k + 3] = d.w;
             }
-            const float dbar = gbarC - s_row[wv][u][NF * NB];      // c (gbar - mbar)
-            float av = avm, rv = p.rv_mean;                       // av: c Av throughout
+            const float dbar = cst.gbarC - s_row[wv][u][NF * NB];      // c (gbar - mbar)
+            float av, rv = p.rv_mean;                                  // av: c Av throughout
             if constexpr (RVF) {
                 float uR = 0.f, RR = 0.f, yR = 0.f, uy = 0.f, yy = 0.f;
 #pragma unroll
@@ -207,21 +175,7 @@ k_pre32s(const float *__restrict__ grid, int64_t nmodel, int64_t nmodel_pad, int
                     uy += yw;
                     yy = fmaf(y, yw, yy);
                 }
-                const float rs = uy - av * uR;
-                const float ra = (yR - av * RR) + (avm - av) * p.av_ivar;
-                const float a_den = RR + p.av_ivar;
-                float dav = (S * ra - uR * rs) * __builtin_amdgcn_rcpf(S * a_den - uR * uR);
-                dav = fminf(dav, av_hi - av);
-                dav = fmaxf(dav, av_lo - av);
-                av += dav;
-                const float oc = (uy - av * uR) * rS;
-                const float tt0 = dbar + oc;
-                const float lw = lw_scale * ((yy - av * (2.f * yR - av * RR)) + S * (tt0 * tt0 - oc * oc));
-                const float st = fabsf(dav);
-                mx0 = vmaxf(mx0, lw);
-                mx1 = vmaxf(mx1, st >= tol_hi ? lw : NINF);
-                mx2 = vmaxf(mx2, st >= tol_lo ? lw : NINF);
-                mx8 = lw != lw ? 1.f : mx8;
+                av = pair_av_step(uR, RR, yR, uy, yy, dbar, cst, p, mx);
             } else {
                 float ua = 0.f, ub = 0.f, uy = 0.f, aa = 0.f, ab = 0.f, bb = 0.f, ay = 0.f, by = 0.f, yy = 0.f;
 #pragma unroll
@@ -246,107 +200,12 @@ k_pre32s(const float *__restrict__ grid, int64_t nmodel, int64_t nmodel_pad, int
                         yy = fmaf(y, yw, yy);
                     }
                 }
-                // one sweep of fitting.py:176-243 with av -> c av: the Av half as above; in the
-                // Rv half every product av x (a y-free sum) carries one c and every product
-                // av x (a y sum) two, so its numerator and denominator are both c^2 times the
-                // reference's once the prior terms are scaled likewise: drv comes out unscaled
-                const float c2 = C10 * C10;
-                auto sweep = [&](float &dav_o, float &drv_o) -> float {
-                    const float uR = ua + rv * ub;
-                    const float RR = aa + rv * (2.f * ab + rv * bb);
-                    const float yR = ay + rv * by;
-                    float rs = uy - av * uR;
-                    const float ra = (yR - av * RR) + (avm - av) * p.av_ivar;
-                    const float a_den = RR + p.av_ivar;
-                    float dav = (S * ra - uR * rs) * __builtin_amdgcn_rcpf(S * a_den - uR * uR);
-                    dav = fminf(dav, av_hi - av);
-                    dav = fmaxf(dav, av_lo - av);
-                    av += dav;
-                    const float r_den = bb * av * av + c2 * p.rv_ivar;
-                    const float sr = ub * av;
-                    rs = uy - av * uR;
-                    const float bres = by - av * (ab + rv * bb);
-                    const float rr = av * bres + c2 * ((p.rv_mean - rv) * p.rv_ivar);
-                    float drv = (S * rr - sr * rs) * __builtin_amdgcn_rcpf(S * r_den - sr * sr);
-                    drv = fmaxf(drv, p.rvmin - rv);
-                    drv = fminf(drv, p.rvmax - rv);
-                    rv += drv;
-                    const float RR2 = aa + rv * (2.f * ab + rv * bb);
-                    const float yR2 = ay + rv * by;
-                    dav_o = dav;
-                    drv_o = drv;
-                    const float uR2 = ua + rv * ub;
-                    const float oc = (uy - av * uR2) * rS;
-                    const float tt0 = dbar + oc;
-                    return lw_scale * ((yy - av * (2.f * yR2 - av * RR2)) + S * (tt0 * tt0 - oc * oc));
-                };
-                float d1, d2;
-                {
-                    const float lw = sweep(d1, d2);
-                    const float st = fmaxf(fabsf(d1) * (-1.f / C10), fabsf(d2));
-                    mx0 = vmaxf(mx0, lw);
-                    mx1 = vmaxf(mx1, st >= p.mtol_hi ? lw : NINF);
-                    mx2 = vmaxf(mx2, st >= p.mtol_lo ? lw : NINF);
-                    mx8 = lw != lw ? 1.f : mx8;
-                }
-                {
-                    const float lw = sweep(d1, d2);
-                    const float st = fmaxf(fabsf(d1) * (-1.f / C10), fabsf(d2));
-                    mx3 = vmaxf(mx3, lw);
-                    mx4 = vmaxf(mx4, st >= p.mtol_hi ? lw : NINF);
-                    mx5 = vmaxf(mx5, st >= p.mtol_lo ? lw : NINF);
-                    mx8 = lw != lw ? 1.f : mx8;
-                }
+                pair_sweeps(ua, ub, uy, aa, ab, bb, ay, by, yy, dbar, cst, p, av, rv, mx);
             }
-            // MLE in scaled units: F = A f, A = 10^(-0.4 mbar), d = D dd
-            float num = 0.f, den = 0.f;
-#pragma unroll
-            for (int j = 0; j < NB; ++j) {
-                float Rj;
-                if constexpr (RVF) Rj = A[j];
-                else Rj = fmaf(rv, B[j], A[j]);
-                const float e = __builtin_amdgcn_exp2f(fmaf(av, Rj, mcC[j]));
-                const float fw = e * iv[j];
-                num = fmaf(dd[j], fw, num);
-                den = fmaf(e, fw, den);
-            }
-            const float q = __builtin_amdgcn_exp2f(dbar);       // D / A
-            const float rden = __builtin_amdgcn_rcpf(den);
-            float tt = num * rden;
-            float sc = tt * q;
-            {
-                const bool tiny = sc <= 1e-20f;
-                const float tt_lo = 1e-20f * __builtin_amdgcn_rcpf(q);
-                tt = tiny ? tt_lo : tt;
-                sc = tiny ? 1e-20f : sc;
-            }
-            const float chi2 = fmaf(tt, fmaf(tt, den, -2.f * num), DD2);
-            const float lnl = -0.5f * chi2;
-            float lnlp = lnl;
-            if (any_par) {
-                const float dp = __builtin_amdgcn_sqrtf(sc) - par;
-                lnlp = has_par ? lnl - dp * dp * par_hiv : lnl;
-            }
-            float lnpr = lnl;
-            if (p.dim_prior) lnpr = c0 + c1 * ln_pos(chi2) - 0.5f * chi2;
-            if (any_sp) {
-                const float vt = sp_var + q * q * rden;
-                const float ds = sc - sp_mean;
-                const float t = -0.5f * (ds * ds * __builtin_amdgcn_rcpf(vt) + ln_pos(6.2831853071795865f * vt));
-                lnpr = sp_on ? lnpr + t : lnpr;
-            }
-            // a chi2 the cancellation cannot resolve, or a star float32 cannot represent:
-            // NaN = "re-evaluate in float64"
-            lnlp = chi2 > eps4 ? lnlp : NAN;
-            // (|lnprob~| < 2^-100 is stored as +0: that range of bit patterns marks survivors in
-            // this plane, fit_kernels.hpp surv_tag)
-            lnpr = fabsf(lnpr) < 0x1p-100f ? 0.f : lnpr;
-            lnpr = chi2 > chi2_lo ? lnpr : NAN;
+            float lnlp, lnpr;
+            pair_tail<NB, RVF>(mcC, A, B, dd, iv, av, rv, dbar, cst, p, lnlp, lnpr, mx);
             s_t[wv][0][u][lane] = lnlp;
             s_t[wv][1][u][lane] = lnpr;
-            mx9 = (lnlp != lnlp || lnpr != lnpr) ? 1.f : mx9;
-            mx6 = vmaxf(mx6, lnlp);
-            mx7 = vmaxf(mx7, lnpr);
         }
         // the tile leaves transposed: a store covers four stars x sixteen models (64-byte row
         // segments; the next tile of this wave completes the lines)
@@ -372,11 +231,8 @@ k_pre32s(const float *__restrict__ grid, int64_t nmodel, int64_t nmodel_pad, int
     // the four waves' maxima meet in LDS (the transposition tiles are free now)
     __syncthreads();
     float *s_mx = &s_t[0][0][0][0];                      // [4][NV32][64]
-    {
-        const float v[NV32] = {mx0, mx1, mx2, mx3, mx4, mx5, mx6, mx7, mx8, mx9};
 #pragma unroll
-        for (int k = 0; k < NV32; ++k) s_mx[(wv * NV32 + k) * 64 + lane] = v[k];
-    }
+    for (int k = 0; k < NV32; ++k) s_mx[(wv * NV32 + k) * 64 + lane] = mx[k];
     __syncthreads();
     if (wv == 0 && slive) {
 #pragma unroll

@@ -18,43 +18,47 @@
 
 namespace {
 
-template <int NB>
-int launch_nb(int mfma, int rvf, const float *grid, int64_t nmodel, int64_t nmodel_pad, int nstar, int nrun,
-              const int32_t *star_ids, const Star32 *stars, const P32 &p, float *lnlp32,
-              float *lnpr32, float *part32, hipStream_t st) {
-    const int ntile = (int)(nmodel_pad / PS_TILE);
-    const int nblkx = (ntile + F2_T - 1) / F2_T;
-#ifdef BRUTUS_DEV_PRE32M_DIAG
-    if (mfma == 2) {
-        const dim3 gm(8 * ((nblkx + 7) / 8) * ((nrun + 15) / 16)), bm(PS_TILE);
-        if (rvf)
-            hipLaunchKernelGGL((k_pre32m<NB, true, 1>), gm, bm, 0, st, grid, nmodel, nmodel_pad, nblkx, nstar, nrun,
-                               star_ids, stars, p, lnlp32, lnpr32, part32);
-        else
-            hipLaunchKernelGGL((k_pre32m<NB, false, 1>), gm, bm, 0, st, grid, nmodel, nmodel_pad, nblkx, nstar, nrun,
-                               star_ids, stars, p, lnlp32, lnpr32, part32);
-        return hipGetLastError() == hipSuccess ? 0 : -2;
-    }
-#endif
-    if (mfma) {
-        // (k_pre32m: 16 stars per wave, the band contractions on the matrix pipe)
-        const dim3 gm(8 * ((nblkx + 7) / 8) * ((nrun + 15) / 16)), bm(PS_TILE);
-        if (rvf)
-            hipLaunchKernelGGL((k_pre32m<NB, true>), gm, bm, 0, st, grid, nmodel, nmodel_pad, nblkx, nstar, nrun,
-                               star_ids, stars, p, lnlp32, lnpr32, part32);
-        else
-            hipLaunchKernelGGL((k_pre32m<NB, false>), gm, bm, 0, st, grid, nmodel, nmodel_pad, nblkx, nstar, nrun,
-                               star_ids, stars, p, lnlp32, lnpr32, part32);
-        return hipGetLastError() == hipSuccess ? 0 : -2;
-    }
-    const dim3 g(nblkx * ((nrun + 63) / 64)), b(PS_TILE);
-    if (rvf)
-        hipLaunchKernelGGL((k_pre32s<NB, true>), g, b, 0, st, grid, nmodel, nmodel_pad, nstar, nrun,
-                           star_ids, stars, p, lnlp32, lnpr32, part32);
-    else
-        hipLaunchKernelGGL((k_pre32s<NB, false>), g, b, 0, st, grid, nmodel, nmodel_pad, nstar, nrun,
-                           star_ids, stars, p, lnlp32, lnpr32, part32);
+// What a launch of either form is given
+struct Pre32Args {
+    const float *grid;
+    int64_t nmodel, nmodel_pad;
+    int nstar, nrun;
+    const int32_t *star_ids;
+    const Star32 *stars;
+    const P32 &p;
+    float *lnlp32, *lnpr32, *part32;
+    hipStream_t st;
+    // model blocks of F2_T tiles: the unit of part32
+    int nblkx() const { return ((int)(nmodel_pad / PS_TILE) + F2_T - 1) / F2_T; }
+};
+
+// k_pre32s: 64 stars per wave, the star group the fast block index
+template <int NB, bool RVF>
+int launch_s(const Pre32Args &a) {
+    const dim3 g(a.nblkx() * ((a.nrun + 63) / 64)), b(PS_TILE);
+    hipLaunchKernelGGL((k_pre32s<NB, RVF>), g, b, 0, a.st, a.grid, a.nmodel, a.nmodel_pad, a.nstar, a.nrun,
+                       a.star_ids, a.stars, a.p, a.lnlp32, a.lnpr32, a.part32);
     return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+// k_pre32m: 16 stars per wave, the band contractions on the matrix pipe; the model blocks rounded
+// up to the eight XCDs (see the kernel's block numbering)
+template <int NB, bool RVF, int DIAG>
+int launch_m(const Pre32Args &a) {
+    const int nblkx = a.nblkx();
+    const dim3 g(8 * ((nblkx + 7) / 8) * ((a.nrun + 15) / 16)), b(PS_TILE);
+    hipLaunchKernelGGL((k_pre32m<NB, RVF, DIAG>), g, b, 0, a.st, a.grid, a.nmodel, a.nmodel_pad, nblkx, a.nstar,
+                       a.nrun, a.star_ids, a.stars, a.p, a.lnlp32, a.lnpr32, a.part32);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+template <int NB>
+int launch_nb(int mfma, int rvf, const Pre32Args &a) {
+#ifdef BRUTUS_DEV_PRE32M_DIAG
+    if (mfma == 2) return rvf ? launch_m<NB, true, 1>(a) : launch_m<NB, false, 1>(a);
+#endif
+    if (mfma) return rvf ? launch_m<NB, true, 0>(a) : launch_m<NB, false, 0>(a);
+    return rvf ? launch_s<NB, true>(a) : launch_s<NB, false>(a);
 }
 
 }  // namespace
@@ -83,14 +87,13 @@ extern "C" int brutus_i_pre32s_launch(int nb, int mfma, int rvf, const float *gr
                                       const int32_t *star_ids, const void *stars32,
                                       const void *p32, float *lnlp32, float *lnpr32,
                                       float *part32, void *stream) {
-    const Star32 *stars = static_cast<const Star32 *>(stars32);
-    const P32 &p = *static_cast<const P32 *>(p32);
-    hipStream_t st = (hipStream_t)stream;
+    const Pre32Args a = {grid, nmodel, nmodel_pad, nstar, nrun, star_ids, static_cast<const Star32 *>(stars32),
+                         *static_cast<const P32 *>(p32), lnlp32, lnpr32, part32, (hipStream_t)stream};
     switch (nb) {
 #ifndef BRUTUS_DEV_NB12_ONLY
-        case 8: return launch_nb<8>(mfma, rvf, grid, nmodel, nmodel_pad, nstar, nrun, star_ids, stars, p, lnlp32, lnpr32, part32, st);
+        case 8: return launch_nb<8>(mfma, rvf, a);
 #endif
-        case 12: return launch_nb<12>(mfma, rvf, grid, nmodel, nmodel_pad, nstar, nrun, star_ids, stars, p, lnlp32, lnpr32, part32, st);
+        case 12: return launch_nb<12>(mfma, rvf, a);
         default: return -1;
     }
 }

@@ -295,6 +295,44 @@ def test_matrix_pipe_form_of_the_float32_pass_agrees():
             _vs_full_grid(fitting.DeviceGrid(models), st, kw, tol=tol, audit_frac=1.0)
 
 
+FORMS = [("tile", dict(BRUTUS_PRE32_STAR_LANES_MIN=1000)),
+         ("star_lanes", dict(BRUTUS_PRE32_STAR_LANES_MIN=1)),
+         ("matrix", dict(BRUTUS_PRE32_STAR_LANES_MIN=1, BRUTUS_PRE32_MFMA=1))]
+# (nmodel, nfilt, nstar) at which the star-lane passes take their other paths
+EDGE_SHAPES = [
+    (257, 8, 1),                    # one full tile plus one model; a single live lane
+    (257, 8, 17),                   # a second 16-star group (k_pre32m) with a single star
+    (4099, 12, 65),                 # 4099 % 16 == 3 and % 4 == 3: the ragged last tile, k_pre32m's word-by-word
+                                    # stores (rows not 16-byte aligned); a second 64-star group with one live lane
+    (2048 + 512 + 16, 12, 33),      # a second model block: its first wave has one tile, the other three none
+]
+_edge_cache = {}
+
+
+def _edge_inputs(nmodel, nfilt, nstar):
+    from brutus_amd import fitting, synth
+    key = (nmodel, nfilt, nstar)
+    if key not in _edge_cache:
+        models, _, _ = synth.make_grid(nmodel, nfilt, seed=nmodel)
+        _edge_cache[key] = (fitting.DeviceGrid(models), synth.make_stars(models, nstar, seed=nmodel + 1))
+    return _edge_cache[key]
+
+
+@pytest.mark.parametrize("rvlim", [(1., 8.), (3.32, 3.32)], ids=["general", "rv_pinned"])
+@pytest.mark.parametrize("form", FORMS, ids=[f[0] for f in FORMS])
+@pytest.mark.parametrize("shape", EDGE_SHAPES, ids=["%dx%d_%dstars" % s for s in EDGE_SHAPES])
+def test_float32_pass_forms_at_tile_and_group_edges(shape, form, rvlim):
+    """The three float32 passes (k_pre32, k_pre32s, k_pre32m) where their index arithmetic can go
+    wrong: partial tiles, partial star groups, rows of the planes that are not 16-byte aligned, waves
+    without any model.  The two star-lane kernels share their per-pair code (csrc/pre32_pair.hpp)
+    and differ exactly in what these shapes reach: staging, the stores, the final reduction.
+    (The audit is held to eps itself, the bound the library enforces, as for the same grids in
+    `test_random_order_grid_and_tiny_shapes` and for the matrix form above.)"""
+    grid, st = _edge_inputs(*shape)
+    with _Env(**form[1]):
+        _vs_full_grid(grid, st, dict(rvlim=rvlim), audit_frac=1.0)
+
+
 def test_random_order_grid_and_tiny_shapes():
     """A grid without any index locality, and shapes around the tile / chunk sizes."""
     from brutus_amd import fitting, synth
