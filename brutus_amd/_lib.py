@@ -307,6 +307,16 @@ SUMMARY_SIGNATURES = {
 }
 SUMMARY_MAX_DRAWS, SUMMARY_MAX_LABELS, SUMMARY_MAX_Q, SUMMARY_MAX_OBJ = 4096, 32, 64, 1 << 21
 
+# and for include/brutus_amd_predictive.h (pdf.PosteriorPredictive; tests/test_predictive_host.py
+# compares this table with that header parameter by parameter)
+PREDICTIVE_SIGNATURES = {
+    "brutus_predictive_seds": (C.c_int, [_i64, _i32, _di32, _df64, _df64, _df64, _i64, _i32, _df32, _i32,
+                                         _df64, _stream]),
+    "brutus_predictive_quantiles": (C.c_int, [_i64, _i32, _di32, _df64, _df64, _df64, _df64, _i64, _i32,
+                                              _df32, _i32, _i32, _df64, _df64, _stream]),
+}
+PREDICTIVE_MAX_DRAWS, PREDICTIVE_MAX_FILT, PREDICTIVE_MAX_Q, PREDICTIVE_MAX_OBJ = 4096, MAX_FILT, 64, 1 << 21
+
 
 def lib():
     """Load (once) and return the shared library; raise loudly if absent."""
@@ -325,7 +335,8 @@ def lib():
     import torch  # noqa: F401
     L = C.CDLL(LIB_PATH)
     for name, (res, args) in (list(SIGNATURES.items()) + list(BATCH_SIGNATURES.items())
-                              + list(DUST_SIGNATURES.items()) + list(SUMMARY_SIGNATURES.items())):
+                              + list(DUST_SIGNATURES.items()) + list(SUMMARY_SIGNATURES.items())
+                              + list(PREDICTIVE_SIGNATURES.items())):
         fn = getattr(L, name)   # AttributeError if the .so is stale
         fn.restype = res
         fn.argtypes = args

@@ -5,7 +5,8 @@
 // k_summary_quantiles<WEIGHTED>: one workgroup per object, objects along grid.x.  The workgroup has
 // T = min(P, 1024) lanes, P = the draw count padded to a power of two (64 at the least), and lane
 // t owns the samples e = m T + t, m < P / T <= 4, in registers for the whole object: their model
-// indices are read once, then the columns are walked.  Per column:
+// indices are read once, then the columns are walked.  Per column (summary_column, which
+// k_predictive_quantiles of predictive_kernels.hpp calls too):
 //   - the sample becomes an order-preserving 64-bit key (NaNs made canonical first, so a NaN of
 //     either sign sorts last; -0 becomes +0, numpy sorts them as equal; the padding is the
 //     all-ones key, above every NaN);
@@ -60,6 +61,134 @@ __device__ __forceinline__ double summary_knot(const double *sinc, int j, double
     return j ? sinc[j - 1] / norm : 0.;
 }
 
+// One column of one object, from the lanes' keys to its nq quantiles: `key` / `pos` hold the
+// column (sample e = m T + t in slot m, the padding as the all-ones key), `wrow` the object's
+// weights, `dst` the column's nq results.  Sort, scan, knot search, interpolation and store as
+// the head of this file has them; ends at a barrier, after which xk / sinc are free again.
+// Called by every lane of the workgroup (k_summary_quantiles, k_predictive_quantiles).
+template <bool WEIGHTED>
+__device__ __forceinline__ void summary_column(uint64_t (&key)[SUMMARY_MAX_E], uint32_t (&pos)[SUMMARY_MAX_E],
+                                               int nsamps, int npad, int T, int t, int E, uint64_t *xk,
+                                               double *sinc, uint32_t *xp, const double *__restrict__ wrow,
+                                               int nq, const double *__restrict__ qs,
+                                               double *__restrict__ dst) {
+    // ---- bitonic sort of (key, pos), ascending ----
+    for (int k = 2; k <= npad; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            if (j < 64) {
+#pragma unroll
+                for (int m = 0; m < SUMMARY_MAX_E; ++m)
+                    if (m < E) {
+                        const uint64_t ok = (uint64_t)__shfl_xor((unsigned long long)key[m], j);
+                        const uint32_t op = WEIGHTED ? (uint32_t)__shfl_xor((int)pos[m], j) : 0u;
+                        summary_keep<WEIGHTED>(m * T + t, k, j, key[m], pos[m], ok, op);
+                    }
+            } else {
+#pragma unroll
+                for (int m = 0; m < SUMMARY_MAX_E; ++m)
+                    if (m < E) {
+                        xk[m * T + t] = key[m];
+                        if (WEIGHTED) xp[m * T + t] = pos[m];
+                    }
+                __syncthreads();
+#pragma unroll
+                for (int m = 0; m < SUMMARY_MAX_E; ++m)
+                    if (m < E) {
+                        const int e = m * T + t;
+                        const uint64_t ok = xk[e ^ j];
+                        const uint32_t op = WEIGHTED ? xp[e ^ j] : 0u;
+                        summary_keep<WEIGHTED>(e, k, j, key[m], pos[m], ok, op);
+                    }
+                __syncthreads();
+            }
+        }
+    }
+#pragma unroll
+    for (int m = 0; m < SUMMARY_MAX_E; ++m)
+        if (m < E) xk[m * T + t] = key[m];
+
+    // ---- WEIGHTED: inclusive scan of the sorted weights, in the order e = 0 .. npad - 1 ----
+    if (WEIGHTED) {
+        const int lane = t & 63, wv = t >> 6, nw = (T + 63) >> 6;
+        double inc[SUMMARY_MAX_E];
+#pragma unroll
+        for (int m = 0; m < SUMMARY_MAX_E; ++m) {
+            inc[m] = 0.;
+            if (m < E) {
+                double w = (m * T + t) < nsamps && pos[m] < (uint32_t)nsamps ? wrow[pos[m]] : 0.;
+                for (int d = 1; d < 64; d <<= 1) {
+                    const double up = __shfl_up(w, d);
+                    if (lane >= d) w += up;
+                }
+                inc[m] = w;
+            }
+        }
+        // (every pass of the sort that read xp ended at a barrier: its place is free)
+#pragma unroll
+        for (int m = 0; m < SUMMARY_MAX_E; ++m)
+            if (m < E && lane == 63) sinc[m * nw + wv] = inc[m];
+        __syncthreads();
+        double before[SUMMARY_MAX_E];
+#pragma unroll
+        for (int m = 0; m < SUMMARY_MAX_E; ++m) {
+            before[m] = 0.;
+            if (m < E)
+                for (int i = 0; i < m * nw + wv; ++i) before[m] += sinc[i];
+        }
+        __syncthreads();                     // the wave totals are read: their place is the scan's
+#pragma unroll
+        for (int m = 0; m < SUMMARY_MAX_E; ++m)
+            if (m < E) sinc[m * T + t] = before[m] + inc[m];
+    }
+    __syncthreads();
+
+    // ---- one lane per q: the knot search and the interpolation of numpy.interp ----
+    if (t < nq) {
+        const double q = qs[t];
+        const int last = nsamps - 1;
+        const double norm = WEIGHTED ? sinc[nsamps - 2] : (double)last;
+        int j;
+        if (WEIGHTED) {
+            int lo = 0, hi = last;           // the rightmost knot <= q (c_0 = 0)
+            while (lo < hi) {
+                const int mid = (lo + hi + 1) >> 1;
+                if (summary_knot(sinc, mid, norm) <= q)
+                    lo = mid;
+                else
+                    hi = mid - 1;
+            }
+            j = lo;
+        } else {
+            const double g = q * norm;
+            j = g >= 0. ? (g < (double)last ? (int)g : last) : 0;
+            while (j < last && (double)(j + 1) / norm <= q) ++j;
+            while (j > 0 && (double)j / norm > q) --j;
+        }
+        double r;
+        if (WEIGHTED && !(norm > 0.)) {
+            r = __longlong_as_double(0x7ff8000000000000ll);
+        } else if (j == last) {
+            r = summary_unkey(xk[last]);
+        } else {
+            const double cj = WEIGHTED ? summary_knot(sinc, j, norm) : (double)j / norm;
+            const double cn = WEIGHTED ? summary_knot(sinc, j + 1, norm) : (double)(j + 1) / norm;
+            const double x0 = summary_unkey(xk[j]), x1 = summary_unkey(xk[j + 1]);
+            if (cj == q) {
+                r = x0;
+            } else {
+                const double slope = (x1 - x0) / (cn - cj);
+                r = slope * (q - cj) + x0;
+                if (r != r) {
+                    r = slope * (q - cn) + x1;
+                    if (r != r && x0 == x1) r = x0;
+                }
+            }
+        }
+        dst[t] = r;
+    }
+    __syncthreads();                         // the next column overwrites xk / sinc
+}
+
 template <bool WEIGHTED>
 __global__ void __launch_bounds__(SUMMARY_MAX_T)
 k_summary_quantiles(int nsamps, int npad, const int32_t *__restrict__ idx, const double *__restrict__ dist,
@@ -112,121 +241,9 @@ k_summary_quantiles(int nsamps, int npad, const int32_t *__restrict__ idx, const
             }
         }
 
-        // ---- bitonic sort of (key, pos), ascending ----
-        for (int k = 2; k <= npad; k <<= 1) {
-            for (int j = k >> 1; j > 0; j >>= 1) {
-                if (j < 64) {
-#pragma unroll
-                    for (int m = 0; m < SUMMARY_MAX_E; ++m)
-                        if (m < E) {
-                            const uint64_t ok = (uint64_t)__shfl_xor((unsigned long long)key[m], j);
-                            const uint32_t op = WEIGHTED ? (uint32_t)__shfl_xor((int)pos[m], j) : 0u;
-                            summary_keep<WEIGHTED>(m * T + t, k, j, key[m], pos[m], ok, op);
-                        }
-                } else {
-#pragma unroll
-                    for (int m = 0; m < SUMMARY_MAX_E; ++m)
-                        if (m < E) {
-                            xk[m * T + t] = key[m];
-                            if (WEIGHTED) xp[m * T + t] = pos[m];
-                        }
-                    __syncthreads();
-#pragma unroll
-                    for (int m = 0; m < SUMMARY_MAX_E; ++m)
-                        if (m < E) {
-                            const int e = m * T + t;
-                            const uint64_t ok = xk[e ^ j];
-                            const uint32_t op = WEIGHTED ? xp[e ^ j] : 0u;
-                            summary_keep<WEIGHTED>(e, k, j, key[m], pos[m], ok, op);
-                        }
-                    __syncthreads();
-                }
-            }
-        }
-#pragma unroll
-        for (int m = 0; m < SUMMARY_MAX_E; ++m)
-            if (m < E) xk[m * T + t] = key[m];
-
-        // ---- WEIGHTED: inclusive scan of the sorted weights, in the order e = 0 .. npad - 1 ----
-        if (WEIGHTED) {
-            const int lane = t & 63, wv = t >> 6, nw = (T + 63) >> 6;
-            double inc[SUMMARY_MAX_E];
-#pragma unroll
-            for (int m = 0; m < SUMMARY_MAX_E; ++m) {
-                inc[m] = 0.;
-                if (m < E) {
-                    double w = (m * T + t) < nsamps && pos[m] < (uint32_t)nsamps ? weights[row + pos[m]] : 0.;
-                    for (int d = 1; d < 64; d <<= 1) {
-                        const double up = __shfl_up(w, d);
-                        if (lane >= d) w += up;
-                    }
-                    inc[m] = w;
-                }
-            }
-            // (every pass of the sort that read xp ended at a barrier: its place is free)
-#pragma unroll
-            for (int m = 0; m < SUMMARY_MAX_E; ++m)
-                if (m < E && lane == 63) sinc[m * nw + wv] = inc[m];
-            __syncthreads();
-            double before[SUMMARY_MAX_E];
-#pragma unroll
-            for (int m = 0; m < SUMMARY_MAX_E; ++m) {
-                before[m] = 0.;
-                if (m < E)
-                    for (int i = 0; i < m * nw + wv; ++i) before[m] += sinc[i];
-            }
-            __syncthreads();                     // the wave totals are read: their place is the scan's
-#pragma unroll
-            for (int m = 0; m < SUMMARY_MAX_E; ++m)
-                if (m < E) sinc[m * T + t] = before[m] + inc[m];
-        }
-        __syncthreads();
-
-        // ---- one lane per q: the knot search and the interpolation of numpy.interp ----
-        if (t < nq) {
-            const double q = qs[t];
-            const int last = nsamps - 1;
-            const double norm = WEIGHTED ? sinc[nsamps - 2] : (double)last;
-            int j;
-            if (WEIGHTED) {
-                int lo = 0, hi = last;           // the rightmost knot <= q (c_0 = 0)
-                while (lo < hi) {
-                    const int mid = (lo + hi + 1) >> 1;
-                    if (summary_knot(sinc, mid, norm) <= q)
-                        lo = mid;
-                    else
-                        hi = mid - 1;
-                }
-                j = lo;
-            } else {
-                const double g = q * norm;
-                j = g >= 0. ? (g < (double)last ? (int)g : last) : 0;
-                while (j < last && (double)(j + 1) / norm <= q) ++j;
-                while (j > 0 && (double)j / norm > q) --j;
-            }
-            double r;
-            if (WEIGHTED && !(norm > 0.)) {
-                r = __longlong_as_double(0x7ff8000000000000ll);
-            } else if (j == last) {
-                r = summary_unkey(xk[last]);
-            } else {
-                const double cj = WEIGHTED ? summary_knot(sinc, j, norm) : (double)j / norm;
-                const double cn = WEIGHTED ? summary_knot(sinc, j + 1, norm) : (double)(j + 1) / norm;
-                const double x0 = summary_unkey(xk[j]), x1 = summary_unkey(xk[j + 1]);
-                if (cj == q) {
-                    r = x0;
-                } else {
-                    const double slope = (x1 - x0) / (cn - cj);
-                    r = slope * (q - cj) + x0;
-                    if (r != r) {
-                        r = slope * (q - cn) + x1;
-                        if (r != r && x0 == x1) r = x0;
-                    }
-                }
-            }
-            out[((int64_t)blockIdx.x * ncol + c) * nq + t] = r;
-        }
-        __syncthreads();                         // the next column overwrites xk / sinc
+        summary_column<WEIGHTED>(key, pos, nsamps, npad, T, t, E, xk, sinc, xp,
+                                 WEIGHTED ? weights + row : nullptr, nq, qs,
+                                 out + ((int64_t)blockIdx.x * ncol + c) * nq);
     }
 }
 

@@ -17,7 +17,7 @@ from .galprior import (gal_lnprior, logn_disk, logn_halo, logp_age_from_feh,   #
                        logp_feh)
 
 # the reference's `brutus.pdf.__all__` (pdf.py:30-35), plus the table type of the Bayestar-free
-# dust interface and the per-object posterior summaries
+# dust interface, the per-object posterior summaries and the posterior-predictive check
 __all__ = ["imf_lnprior", "ps1_MrLF_lnprior", "parallax_lnprior",
            "scale_parallax_lnprior", "parallax_to_scale",
            "logn_disk", "logn_halo",
@@ -25,7 +25,8 @@ __all__ = ["imf_lnprior", "ps1_MrLF_lnprior", "parallax_lnprior",
            "gal_lnprior", "dust_lnprior",
            "bin_pdfs_distred",
            "LOSTable", "DistancePriorTable", "dist_tables",
-           "posterior_quantiles", "PosteriorSummary"]
+           "posterior_quantiles", "PosteriorSummary",
+           "posterior_predictive", "predictive_seds", "PosteriorPredictive", "observed_sed"]
 
 
 def _kroupa_segment(m, alpha_low, alpha_high, mass_break):
@@ -715,9 +716,37 @@ def _summary_shapes(idxs, data, weights):
     return shape
 
 
+def _column_quantiles(x, w, q, check_norm):
+    """`utils.quantile(x, q, weights=w)` of one column on the host; with `check_norm` a
+    normaliser that is not positive gives NaNs."""
+    from .utils import quantile
+    if check_norm:
+        # the sum without the last sorted sample's weight has to be > 0
+        nan = np.flatnonzero(np.isnan(x))
+        last = nan[-1] if nan.size else x.size - 1 - int(np.argmax(x[::-1]))
+        if not np.delete(w, last).sum() > 0.:
+            return np.full(q.size, np.nan)
+    with np.errstate(all="ignore"):
+        return quantile(x, q, weights=w)
+
+
+def _table_indices(torch, idxs, nmodel, device):
+    """A chunk's indices as an int32 device tensor; what does not fit a table of `nmodel` rows
+    becomes -1 BEFORE the narrowing, which would otherwise wrap."""
+    if isinstance(idxs, torch.Tensor):
+        if idxs.dtype != torch.int32:
+            idxs = torch.where((idxs >= 0) & (idxs < nmodel), idxs, -1)
+    else:
+        idxs = np.asarray(idxs)
+        if idxs.dtype.kind not in "iu":
+            raise ValueError("`idxs` must be integers; got %s" % idxs.dtype)
+        if idxs.dtype != np.int32:
+            idxs = np.where((idxs >= 0) & (idxs < nmodel), idxs, -1)
+    return to_device(idxs, np.int32, device)
+
+
 def _summary_host(idxs, data, weights, table, q):
     """The host form: `utils.quantile`, weighted branch, over objects and columns."""
-    from .utils import quantile
     idxs = np.asarray(idxs)
     dists, reds, dreds = (np.asarray(a, dtype=np.float64) for a in data)
     weights = None if weights is None else np.asarray(weights, dtype=np.float64)
@@ -734,16 +763,7 @@ def _summary_host(idxs, data, weights, table, q):
             cols[nlab:] = reds[o], dreds[o], 1. / dists[o], dists[o]
         w = ones if weights is None else weights[o]
         for c in range(nlab + 4):
-            x = cols[c]
-            if weights is not None:
-                # the sum without the last sorted sample's weight has to be > 0
-                nan = np.flatnonzero(np.isnan(x))
-                last = nan[-1] if nan.size else nsamps - 1 - int(np.argmax(x[::-1]))
-                if not np.delete(w, last).sum() > 0.:
-                    out[o, c] = np.nan
-                    continue
-            with np.errstate(all="ignore"):
-                out[o, c] = quantile(x, q, weights=w)
+            out[o, c] = _column_quantiles(cols[c], w, q, weights is not None)
     return out
 
 
@@ -791,21 +811,6 @@ class PosteriorSummary(object):
         self._table = to_device(table, np.float64, self.device) if self.nlab else None
         self._q = to_device(self.q, np.float64, self.device)
 
-    def _indices(self, idxs):
-        """A chunk's indices as an int32 device tensor; what does not fit the table becomes -1
-        BEFORE the narrowing, which would otherwise wrap."""
-        torch = self._torch
-        if isinstance(idxs, torch.Tensor):
-            if idxs.dtype != torch.int32:
-                idxs = torch.where((idxs >= 0) & (idxs < self.nmodel), idxs, -1)
-        else:
-            idxs = np.asarray(idxs)
-            if idxs.dtype.kind not in "iu":
-                raise ValueError("`idxs` must be integers; got %s" % idxs.dtype)
-            if idxs.dtype != np.int32:
-                idxs = np.where((idxs >= 0) & (idxs < self.nmodel), idxs, -1)
-        return to_device(idxs, np.int32, self.device)
-
     def __call__(self, idxs, data, weights=None, device_out=False):
         from . import _lib
         torch = self._torch
@@ -828,7 +833,7 @@ class PosteriorSummary(object):
                                                         device=self.device)
             for a in range(0, nobj, chunk):
                 b = min(nobj, a + chunk)
-                t_idx = self._indices(idxs[a:b])
+                t_idx = _table_indices(torch, idxs[a:b], self.nmodel, self.device)
                 t_d, t_r, t_dr = (to_device(x[a:b], np.float64, self.device) for x in data)
                 t_w = None if weights is None else to_device(weights[a:b], np.float64, self.device)
                 dst = out[a:b] if device_out else t_out[:b - a]
@@ -862,3 +867,249 @@ def posterior_quantiles(idxs, data, params, q=_SUMMARY_Q, weights=None, names=No
     q = _summary_q(q)
     _summary_shapes(idxs, data, weights)
     return _summary_host(idxs, data, weights, table, q), list(labels) + list(_SUMMARY_DRAW_NAMES)
+
+
+# ---- the posterior-predictive check: the computing half of `plotting.posterior_predictive` ----
+#: bytes of input AND output a chunk of objects may take on the device
+_PREDICTIVE_CHUNK_LIMIT = 1 << 30
+
+
+def _predictive_grid(models, exact):
+    """The checks of a `(Nmodel, Nfilt, 3)` grid, numpy array or tensor; with `exact` (the device
+    form) also that float32 holds every coefficient, and the grid comes back as float32."""
+    if not hasattr(models, "dtype") or not hasattr(models, "shape"):
+        models = np.asarray(models)
+    shape = tuple(models.shape)
+    if len(shape) != 3 or shape[2] != 3 or shape[1] < 1:
+        raise ValueError("`models` must have shape (Nmodel, Nfilt, 3); got %s" % (shape,))
+    if not 1 <= shape[0] < 1 << 31:
+        raise ValueError("the model grid must have 1 to 2**31 - 1 rows; got %d" % shape[0])
+    if not exact:
+        return np.asarray(models)
+    if isinstance(models, np.ndarray):
+        if models.dtype != np.float32:
+            if models.dtype.kind != "f":
+                raise ValueError("`models` must be a float array; got %s" % models.dtype)
+            m32 = models.astype(np.float32)
+            if not np.array_equal(m32.astype(models.dtype), models, equal_nan=True):
+                raise ValueError("the device path needs float32 magnitude coefficients "
+                                 "(as `load_models` returns them)")
+            models = m32
+        return models
+    import torch
+    if models.dtype != torch.float32:
+        if not models.dtype.is_floating_point:
+            raise ValueError("`models` must be a float tensor; got %s" % models.dtype)
+        m32 = models.to(torch.float32)
+        back = m32.to(models.dtype)
+        if not bool(((back == models) | (torch.isnan(back) & torch.isnan(models))).all()):
+            raise ValueError("the device path needs float32 magnitude coefficients "
+                             "(as `load_models` returns them)")
+        models = m32
+    return models
+
+
+def _predictive_chunk(nobj, per_obj, limit):
+    """Objects per device call: `per_obj` bytes of input and output each, under the chunk limit."""
+    return int(max(1, min(nobj, limit, _PREDICTIVE_CHUNK_LIMIT // per_obj)))
+
+
+def _predictive_host_seds(models, idxs, data, flux):
+    """The host form of the `seds` array: `utils.get_seds` at the gathered rows, moved to the
+    draws' distances as reference plotting.py:887-893 does; NaN where the index is outside the
+    grid."""
+    from .utils import get_seds
+    idxs = np.asarray(idxs)
+    if idxs.dtype.kind not in "iu":
+        raise ValueError("`idxs` must be integers; got %s" % idxs.dtype)
+    dists, reds, dreds = (np.asarray(a, dtype=np.float64) for a in data)
+    nobj, nsamps = idxs.shape
+    nmodel, nfilt = models.shape[:2]
+    out = np.empty((nobj, nsamps, nfilt), dtype=np.float64)
+    step = max(1, (1 << 16) // nsamps)
+    for a in range(0, nobj, step):
+        sl = slice(a, min(nobj, a + step))
+        ok = (idxs[sl] >= 0) & (idxs[sl] < nmodel)
+        rows = np.where(ok, idxs[sl], 0).astype(np.int64).ravel()
+        with np.errstate(all="ignore"):
+            seds = get_seds(models[rows], av=reds[sl].ravel(), rv=dreds[sl].ravel(), return_flux=flux)
+            if flux:
+                seds /= dists[sl].ravel()[:, None] ** 2
+            else:
+                seds += 5. * np.log10(dists[sl].ravel())[:, None]
+        seds[~ok.ravel()] = np.nan
+        out[sl] = seds.reshape(ok.shape + (nfilt,))
+    return out
+
+
+def _predictive_host(models, idxs, data, weights, flux, q):
+    """The host form of the quantiles: the loop of `utils.quantile`, weighted branch, over
+    objects and bands."""
+    seds = _predictive_host_seds(models, idxs, data, flux)
+    weights = None if weights is None else np.asarray(weights, dtype=np.float64)
+    nobj, nsamps, nfilt = seds.shape
+    out = np.empty((nobj, nfilt, q.size), dtype=np.float64)
+    ones = np.ones(nsamps)
+    for o in range(nobj):
+        w = ones if weights is None else weights[o]
+        for b in range(nfilt):
+            out[o, b] = _column_quantiles(seds[o, :, b], w, q, weights is not None)
+    return out
+
+
+class PosteriorPredictive(object):
+    """The posterior-predictive check of a whole catalogue on the device: per object and band,
+    the quantiles of the model SEDs of the saved draws -- what reference
+    `plotting.posterior_predictive` (plotting.py:868-893) draws as violins for one object.
+
+    `PosteriorPredictive(models, q, device)` copies the `(Nmodel, Nfilt, 3)` grid of
+    `load_models` to `device` once (a numpy array or a tensor; float32, or values float32 holds
+    exactly -- anything else raises `ValueError`).  With `data = (dists, reds, dreds)` as
+    `fit(save_dar_draws=True)` saves them,
+
+        P = pdf.PosteriorPredictive(models)
+        quants = P(idxs, (dists, reds, dreds))                # (Nobj, Nfilt, 5), magnitudes
+        seds = P.seds(idxs, (dists, reds, dreds), flux=True)  # (Nobj, Nsamps, Nfilt), fluxes
+
+    `P.seds` is the reference's array `seds`: `get_seds(models[idxs], av=reds, rv=dreds)` in
+    float64 on the float32 coefficients, every product rounded before it is added, plus
+    `5 log10(dists)` -- or, with `flux=True`, `10**(-0.4 sed) / dists**2`.  `P(...)` gives the
+    quantiles `q` of `seds[o, :, b]` as `PosteriorSummary` computes them for its columns:
+    `utils.quantile(x, q, weights=w)`, always the weighted branch, ones by default; equal samples
+    keep the order they came in, NaN sorts last, a normaliser that is not positive gives a NaN
+    column.  The reference draws the violin of the UNWEIGHTED `seds`: it resamples indices by
+    weight (plotting.py:902-907) and then never uses them.  Here the weights are applied as
+    `utils.quantile` applies them, which is what that resampling was meant to do.
+
+    Two rules are not the reference's.  A draw whose index lies outside `[0, Nmodel)` (`fit()`
+    writes -99 for an object it did not fit) is NaN in every band; numpy's wrap-around would
+    silently show another model.  The rule is applied before any narrowing to int32.
+    Non-finite results follow IEEE as numpy gives them and are sorted like any other value:
+    `dist == 0` gives -inf magnitudes and inf fluxes, `dist < 0` NaN magnitudes, a NaN draw NaN.
+
+    The inputs are numpy arrays or tensors already on the device, `idxs` of any integer type;
+    `device_out=True` leaves the result on the device.  Objects go in chunks whose inputs and
+    outputs stay under about 1 GiB.  An object's values do not depend on the batch it is in.
+    At most 4096 draws, 64 bands and 64 quantiles.  There is no host fallback: without the
+    library or a GPU the constructor raises `BrutusError`; the host forms are
+    `posterior_predictive(device=None)` and `predictive_seds(device=None)`.
+    """
+
+    def __init__(self, models, q=_SUMMARY_Q, device="cuda"):
+        from . import _lib
+        from ._dev import _torch
+        models = _predictive_grid(models, exact=True)
+        self.q = _summary_q(q)
+        self.nmodel, self.nfilt = int(models.shape[0]), int(models.shape[1])
+        if self.nfilt > _lib.PREDICTIVE_MAX_FILT or self.q.size > _lib.PREDICTIVE_MAX_Q:
+            raise ValueError("PosteriorPredictive takes at most %d bands and %d quantiles; got %d and %d"
+                             % (_lib.PREDICTIVE_MAX_FILT, _lib.PREDICTIVE_MAX_Q, self.nfilt, self.q.size))
+        self._L = _lib.lib()
+        self._torch = torch = _torch("PosteriorPredictive only runs on the HIP path. The host form is "
+                                     "posterior_predictive(device=None).")
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise ValueError("PosteriorPredictive needs a GPU device; got %r" % (device,))
+        self._models = to_device(models, np.float32, self.device)
+        self._q = to_device(self.q, np.float64, self.device)
+
+    def _run(self, idxs, data, weights, shape_of, device_out, call):
+        """The chunk loop of both calls: an object's result has the shape `shape_of(nsamps)`, and
+        `call(n, nsamps, t_idx, t_d, t_r, t_dr, t_w, dst, stream)` fills `dst` for a chunk of `n`
+        objects."""
+        from . import _lib
+        torch = self._torch
+        nobj, nsamps = _summary_shapes(idxs, data, weights)
+        if nsamps > _lib.PREDICTIVE_MAX_DRAWS:
+            raise ValueError("PosteriorPredictive: at most %d draws per object; got %d"
+                             % (_lib.PREDICTIVE_MAX_DRAWS, nsamps))
+        shape = shape_of(nsamps)
+        if device_out:
+            out = torch.empty((nobj,) + shape, dtype=torch.float64, device=self.device)
+        else:
+            out = np.empty((nobj,) + shape, dtype=np.float64)
+        if nobj == 0:
+            return out
+        per_obj = nsamps * (4 + 3 * 8 + (0 if weights is None else 8)) + 8 * int(np.prod(shape))
+        chunk = _predictive_chunk(nobj, per_obj, _lib.PREDICTIVE_MAX_OBJ)
+        with torch.cuda.device(self.device):
+            stream = _stream_ptr(torch)
+            t_out = None if device_out else torch.empty((chunk,) + shape, dtype=torch.float64,
+                                                        device=self.device)
+            for a in range(0, nobj, chunk):
+                b = min(nobj, a + chunk)
+                t_idx = _table_indices(torch, idxs[a:b], self.nmodel, self.device)
+                t_d, t_r, t_dr = (to_device(x[a:b], np.float64, self.device) for x in data)
+                t_w = None if weights is None else to_device(weights[a:b], np.float64, self.device)
+                dst = out[a:b] if device_out else t_out[:b - a]
+                _lib.check(call(b - a, nsamps, t_idx, t_d, t_r, t_dr, t_w, dst, stream))
+                if not device_out:
+                    torch.from_numpy(out[a:b]).copy_(dst)         # (straight into the result: no staging copy)
+            if device_out:
+                torch.cuda.current_stream().synchronize()
+        return out
+
+    def __call__(self, idxs, data, weights=None, flux=False, device_out=False):
+        """`(Nobj, Nfilt, Nq)` float64: the quantiles of every band's predicted values."""
+        def call(n, nsamps, t_idx, t_d, t_r, t_dr, t_w, dst, stream):
+            return self._L.brutus_predictive_quantiles(
+                n, nsamps, t_idx, t_d, t_r, t_dr, t_w, self.nmodel, self.nfilt, self._models,
+                int(bool(flux)), self.q.size, self._q, dst, stream)
+        return self._run(idxs, data, weights, lambda nsamps: (self.nfilt, self.q.size), device_out, call)
+
+    def seds(self, idxs, data, flux=False, device_out=False):
+        """`(Nobj, Nsamps, Nfilt)` float64: the predicted value of every draw and band."""
+        def call(n, nsamps, t_idx, t_d, t_r, t_dr, t_w, dst, stream):
+            return self._L.brutus_predictive_seds(
+                n, nsamps, t_idx, t_d, t_r, t_dr, self.nmodel, self.nfilt, self._models,
+                int(bool(flux)), dst, stream)
+        return self._run(idxs, data, None, lambda nsamps: (nsamps, self.nfilt), device_out, call)
+
+
+def posterior_predictive(models, idxs, data, q=_SUMMARY_Q, weights=None, flux=False, device=None,
+                         device_out=False):
+    """`(Nobj, Nfilt, Nq)` float64: per object and band the quantiles `q` of the model SEDs of the
+    saved draws `idxs (Nobj, Nsamps)`, `data = (dists, reds, dreds)`, at the draws' distances --
+    magnitudes, or flux densities with `flux=True`; see `PosteriorPredictive` for the rules
+    (weights as `utils.quantile` applies them; an index outside the grid is NaN in every band).
+
+    `device=None`: numpy on the host, `utils.get_seds` and a loop of `utils.quantile` over
+    objects and bands, for a grid of any float type.  Otherwise a one-shot `PosteriorPredictive`
+    on that GPU; a catalogue in pieces keeps one `PosteriorPredictive`, whose grid travels once."""
+    if device is not None:
+        P = PosteriorPredictive(models, q=q, device=device)
+        return P(idxs, data, weights=weights, flux=flux, device_out=device_out)
+    models = _predictive_grid(models, exact=False)
+    q = _summary_q(q)
+    _summary_shapes(idxs, data, weights)
+    return _predictive_host(models, idxs, data, weights, flux, q)
+
+
+def predictive_seds(models, idxs, data, flux=False, device=None, device_out=False):
+    """`(Nobj, Nsamps, Nfilt)` float64: the model SED of every saved draw at the draw's distance,
+    the array `seds` of reference `plotting.posterior_predictive` (plotting.py:887-893) and the
+    `mpred` that opens `plotting.photometric_offsets` and `photometric_offsets_2d`.  `device` as
+    in `posterior_predictive`."""
+    if device is not None:
+        return PosteriorPredictive(models, device=device).seds(idxs, data, flux=flux, device_out=device_out)
+    models = _predictive_grid(models, exact=False)
+    _summary_shapes(idxs, data, None)
+    return _predictive_host_seds(models, idxs, data, flux)
+
+
+def observed_sed(data, data_err, data_mask=None, offset=None, flux=False):
+    """The photometry in the space of the prediction, `(m, e)` of shape `(..., Nfilt)`, as
+    reference plotting.py:915-921 puts it beside the violins: `data * offset` and
+    `data_err * offset` with `flux=True`, `utils.magnitude` of those otherwise; NaN where
+    `data_mask` is False.  A residual is `observed_sed(...)[0] - quantiles[..., k]`."""
+    from .utils import magnitude
+    data = np.asarray(data, dtype=np.float64)
+    data_err = np.asarray(data_err, dtype=np.float64)
+    offset = np.ones(data.shape[-1]) if offset is None else np.asarray(offset, dtype=np.float64)
+    m, e = data * offset, data_err * offset
+    if not flux:
+        m, e = magnitude(m, e)
+    if data_mask is not None:
+        keep = np.asarray(data_mask, dtype=bool)
+        m, e = np.where(keep, m, np.nan), np.where(keep, e, np.nan)
+    return m, e

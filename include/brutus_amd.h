@@ -636,6 +636,9 @@ void brutus_enable_timing(int on);
 /* ---- per-object posterior summaries: quantiles of the saved draws (reference plotting.py) ---- */
 #include "brutus_amd_summary.h"
 
+/* ---- posterior-predictive check: the draws' model SEDs and their quantiles per band ---- */
+#include "brutus_amd_predictive.h"
+
 #ifdef __cplusplus
 }
 #endif

@@ -1386,6 +1386,107 @@ def gen_post_quantiles():
              os.path.getsize(os.path.join(OUT, "post_quantiles.npz"))))
 
 
+def gen_post_predictive():
+    """tests/golden/post_predictive.npz: the computing half of `plotting.posterior_predictive`
+    (plotting.py:868-893) -- `seds = get_seds(models[idxs], av=reds, rv=dreds, return_flux=flux)`
+    moved to the draws' distances, in both spaces, and `utils.quantile(seds[:, b], q, weights)`
+    per object and band with unit weights, with dyadic weights and, at 250 draws, with weights
+    uniform in [0.5, 1.5].  The `seds` arrays are kept for 2, 65 and 250 draws only (the size of
+    the file), the quantiles for every draw count of tests/summary_helpers.py.
+
+    The grid is `synth.make_mist_like_grid(500, 8, seed=7)`, float32, promoted to float64 before
+    the reference sees it (the head of this file).  Objects are drawn as `gen_post_quantiles`
+    draws them -- from a pool of distinct models, each with ONE distance, Av, Rv and weight, so
+    equal samples are copies of one pool entry -- and redrawn until, in every band and both
+    spaces, the normaliser is positive, no quantile lies within `MARGIN` of a knot where the
+    result jumps, and two distinct values of a column differ by more than 1e-9 of the column's
+    largest |x| (rounding cannot then reorder them on the device).  The reference's result is
+    checked to be the same for the reversed sample order."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import predictive_helpers as PH
+    import summary_helpers as H
+    rng = np.random.RandomState(20261021)
+    models, _, _ = synth.make_mist_like_grid(PH.NMODEL, PH.NFILT, seed=PH.GRID_SEED)
+    assert models.dtype == np.float32 and models.shape == (PH.NMODEL, PH.NFILT, 3)
+    m64 = models.astype(np.float64)
+    q = np.array(PH.Q)
+    res = dict(models=models, q=q)
+    tries, gap = 0, np.inf
+
+    def draw_object(n):
+        k = n if n < 8 else min(max(8, n // 3), 400)       # pool size: ties from 8 draws on
+        pool = rng.choice(PH.NMODEL, k, replace=False)
+        pd = np.exp(rng.normal(0., 0.6, k))
+        pr, pdr = rng.uniform(0., 3., k), rng.uniform(2.5, 4.5, k)
+        wd = rng.randint(0, 33, k) / 8.
+        wd[rng.uniform(size=k) < 0.2] = 0.
+        wf = rng.uniform(0.5, 1.5, k)
+        if k >= 8:
+            order = np.argsort(pd)
+            start = rng.randint(1, k - 4)
+            wd[order[0]] = wd[order[-1]] = 0.
+            wd[order[start:start + 3]] = 0.
+        pick = rng.randint(0, k, n)
+        return pool[pick].astype(np.int32), pd[pick], pr[pick], pdr[pick], wd[pick], wf[pick]
+
+    def reference_seds(idx, d, r, dr, flux):
+        seds = U.get_seds(m64[idx], av=r, rv=dr, return_flux=flux)
+        if flux:
+            seds /= d[:, None]**2
+        else:
+            seds += 5. * np.log10(d)[:, None]
+        return seds
+
+    def smallest_gap(cols):
+        g = np.inf
+        for x in cols:
+            u = np.unique(x)
+            if u.size > 1:
+                g = min(g, float(np.min(np.diff(u)) / np.max(np.abs(x))))
+        return g
+
+    def acceptable(cols, weights):
+        try:
+            return all(H.margin(x, w, q) > H.MARGIN for w in weights for x in cols)
+        except AssertionError:
+            return False
+
+    for n in H.NSAMPS:
+        objs = []
+        while len(objs) < H.nobj_of(n):
+            tries += 1
+            idx, d, r, dr, wd, wf = draw_object(n)
+            seds = [reference_seds(idx, d, r, dr, flux) for flux in (False, True)]
+            cols = [x for s in seds for x in s.T]
+            g = smallest_gap(cols)
+            if g > 1e-9 and acceptable(cols, [np.ones(n), wd] + ([wf] if n == H.NFLOAT else [])):
+                gap = min(gap, g)
+                objs.append((idx, d, r, dr, wd, wf, seds))
+        for key, k in (("idx", 0), ("dist", 1), ("red", 2), ("dred", 3), ("wd", 4)):
+            res["%s_%d" % (key, n)] = np.stack([o[k] for o in objs])
+        kinds = [("unit", lambda o: np.ones(n)), ("dyad", lambda o: o[4])]
+        if n == H.NFLOAT:
+            res["wf_%d" % n] = np.stack([o[5] for o in objs])
+            kinds.append(("float", lambda o: o[5]))
+        for f, space in enumerate(PH.SPACES):
+            if n in PH.SEDS_NSAMPS:
+                res["seds_%s_%d" % (space, n)] = np.stack([o[6][f] for o in objs])
+            for kind, wof in kinds:
+                ref = np.empty((len(objs), PH.NFILT, q.size))
+                for i, o in enumerate(objs):
+                    w = wof(o)
+                    for b in range(PH.NFILT):
+                        x = o[6][f][:, b]
+                        ref[i, b] = U.quantile(x, q, weights=w)
+                        back = U.quantile(x[::-1], q, weights=w[::-1])
+                        assert np.array_equal(ref[i, b], back), (n, space, kind, i, b)
+                assert np.all(np.isfinite(ref))
+                res["ref_%s_%s_%d" % (kind, space, n)] = ref
+    np.savez_compressed(PH.FIXTURE, **res)
+    print("wrote post_predictive.npz: %d objects drawn for %d kept, smallest relative gap %.1e, %d bytes"
+          % (tries, sum(H.nobj_of(n) for n in H.NSAMPS), gap, os.path.getsize(PH.FIXTURE)))
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     which = sys.argv[1:] or ["loglike", "fit", "helpers", "setup", "galprior",
@@ -1440,4 +1541,5 @@ if __name__ == "__main__":
         gen_offsets_edges()
     if "post_quantiles" in which:
         gen_post_quantiles()
-
+    if "post_predictive" in which:
+        gen_post_predictive()
