@@ -317,6 +317,21 @@ PREDICTIVE_SIGNATURES = {
 }
 PREDICTIVE_MAX_DRAWS, PREDICTIVE_MAX_FILT, PREDICTIVE_MAX_Q, PREDICTIVE_MAX_OBJ = 4096, MAX_FILT, 64, 1 << 21
 
+# and for include/brutus_amd_offdiag.h (pdf.OffsetDiagnostics; tests/test_offdiag_host.py compares
+# this table with that header parameter by parameter)
+OFFDIAG_SIGNATURES = {
+    "brutus_offdiag_residuals": (C.c_int, [_i64, _i32, _di32, _df64, _df64, _df64, _df64, _i64, _i32, _df32,
+                                           _df64, _df64, _du8, _i32, _df64, _df64, _du8, _stream]),
+    "brutus_offdiag_pooled_quantiles": (C.c_int, [_i64, _i64, _i32, _di32, _df64, _i32, _df64, _i32, _df64,
+                                                  _df64, _stream]),
+    "brutus_offdiag_hist": (C.c_int, [_i64, _i64, _i32, _di32, _df64, _i32, _df64, _df64, _i32, _i32, _df64,
+                                      _df64, _df64, _stream]),
+    "brutus_offdiag_cell_medians": (C.c_int, [_i64, _i64, _i32, _di32, _di32, _df64, _df64, _i32, _i32, _df64,
+                                              _di32, _stream]),
+}
+OFFDIAG_MAX_DRAWS, OFFDIAG_MAX_FILT, OFFDIAG_MAX_SAMPLES, OFFDIAG_MAX_BINS, OFFDIAG_MAX_Q = (
+    4096, MAX_FILT, 1 << 27, 1024, 8)
+
 
 def lib():
     """Load (once) and return the shared library; raise loudly if absent."""
@@ -336,7 +351,7 @@ def lib():
     L = C.CDLL(LIB_PATH)
     for name, (res, args) in (list(SIGNATURES.items()) + list(BATCH_SIGNATURES.items())
                               + list(DUST_SIGNATURES.items()) + list(SUMMARY_SIGNATURES.items())
-                              + list(PREDICTIVE_SIGNATURES.items())):
+                              + list(PREDICTIVE_SIGNATURES.items()) + list(OFFDIAG_SIGNATURES.items())):
         fn = getattr(L, name)   # AttributeError if the .so is stale
         fn.restype = res
         fn.argtypes = args

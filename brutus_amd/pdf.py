@@ -17,7 +17,8 @@ from .galprior import (gal_lnprior, logn_disk, logn_halo, logp_age_from_feh,   #
                        logp_feh)
 
 # the reference's `brutus.pdf.__all__` (pdf.py:30-35), plus the table type of the Bayestar-free
-# dust interface, the per-object posterior summaries and the posterior-predictive check
+# dust interface, the per-object posterior summaries, the posterior-predictive check and the
+# photometric-offset residual maps
 __all__ = ["imf_lnprior", "ps1_MrLF_lnprior", "parallax_lnprior",
            "scale_parallax_lnprior", "parallax_to_scale",
            "logn_disk", "logn_halo",
@@ -26,7 +27,8 @@ __all__ = ["imf_lnprior", "ps1_MrLF_lnprior", "parallax_lnprior",
            "bin_pdfs_distred",
            "LOSTable", "DistancePriorTable", "dist_tables",
            "posterior_quantiles", "PosteriorSummary",
-           "posterior_predictive", "predictive_seds", "PosteriorPredictive", "observed_sed"]
+           "posterior_predictive", "predictive_seds", "PosteriorPredictive", "observed_sed",
+           "offset_residuals", "offset_hist", "offset_map", "OffsetDiagnostics"]
 
 
 def _kroupa_segment(m, alpha_low, alpha_high, mass_break):
@@ -1113,3 +1115,425 @@ def observed_sed(data, data_err, data_mask=None, offset=None, flux=False):
         keep = np.asarray(data_mask, dtype=bool)
         m, e = np.where(keep, m, np.nan), np.where(keep, e, np.nan)
     return m, e
+
+
+# ---- photometric-offset residual maps: the computing half of `plotting.photometric_offsets` ----
+# ---- and `plotting.photometric_offsets_2d` ------------------------------------------------------
+_OFFDIAG_Q_SPAN = (0.02, 0.98)        # the default spans of the histogram (plotting.py:1124)
+
+
+class _OffdiagInputs(object):
+    """The arguments the three calls share, checked and brought into one form on the host -- no
+    array the size of the draws is touched: `nobj, nsamps, nfilt`, `magobs, mageobs (Nobj, Nfilt)`
+    (the reference's rule, plotting.py:1079-1084), `mask` bool, `weights` (Nobj, Nsamps) or None."""
+
+    def __init__(self, nfilt, phot, err, mask, idxs, data, weights, offset, flux):
+        from . import _lib
+        from .utils import magnitude
+        self.nobj, self.nsamps = nobj, nsamps = _summary_shapes(idxs, data, None)
+        self.nfilt = nfilt
+        if nsamps > _lib.OFFDIAG_MAX_DRAWS:
+            raise ValueError("OffsetDiagnostics: at most %d draws per object; got %d"
+                             % (_lib.OFFDIAG_MAX_DRAWS, nsamps))
+        if nobj * nsamps > _lib.OFFDIAG_MAX_SAMPLES:
+            raise ValueError("OffsetDiagnostics: at most 2**27 samples (Nobj * Nsamps) per call; got %d x %d. "
+                             "Split the catalogue and give `xspan` and `yspan`: the `H` of the pieces "
+                             "then add" % (nobj, nsamps))
+        if nobj < 1:
+            raise ValueError("OffsetDiagnostics needs at least one object")
+        phot, err = np.asarray(phot, dtype=np.float64), np.asarray(err, dtype=np.float64)
+        self.mask = mask = np.asarray(mask).astype(bool)
+        for a, name in ((phot, "phot"), (err, "err"), (mask, "mask")):
+            if a.shape != (nobj, nfilt):
+                raise ValueError("`%s` must have shape (Nobj, Nfilt) = %s; got %s"
+                                 % (name, (nobj, nfilt), a.shape))
+        if weights is not None:
+            if not hasattr(weights, "shape"):
+                weights = np.asarray(weights, dtype=np.float64)
+            wshape = tuple(weights.shape)
+            if wshape not in ((nobj,), (nobj, nsamps)):
+                raise ValueError("`weights` must have shape (Nobj,) or (Nobj, Nsamps); got %s" % (wshape,))
+        self.weights = weights
+        offset = np.ones(nfilt) if offset is None else np.asarray(offset, dtype=np.float64)
+        if offset.shape != (nfilt,):
+            raise ValueError("`offset` must have shape (Nfilt,); got %s" % (offset.shape,))
+        with np.errstate(all="ignore"):
+            if flux:
+                self.magobs, self.mageobs = magnitude(phot * offset, err * offset)
+            else:
+                self.magobs, self.mageobs = phot + offset, err
+        self.magobs = np.ascontiguousarray(self.magobs)
+        self.mageobs = np.ascontiguousarray(self.mageobs)
+
+
+def _offdiag_bins(bins):
+    """`(nx, ny)` of `bins`, an int or a pair, each in [1, 1024]."""
+    from . import _lib
+    try:
+        nx, ny = (int(b) for b in bins)
+    except TypeError:
+        nx = ny = int(bins)
+    except ValueError:
+        raise ValueError("`bins` must be an int or an (nx, ny) pair (per-band bin counts would give "
+                         "ragged outputs)")
+    if not (1 <= nx <= _lib.OFFDIAG_MAX_BINS and 1 <= ny <= _lib.OFFDIAG_MAX_BINS):
+        raise ValueError("`bins` must lie in [1, %d] per axis; got %r" % (_lib.OFFDIAG_MAX_BINS, bins))
+    return nx, ny
+
+
+def _offdiag_x(x, nobj, nsamps, name="x"):
+    """`(per_sample, shape ok)` of the abscissa of `hist`."""
+    shape = tuple(x.shape)
+    if shape == (nobj, nsamps):
+        return True
+    if shape == (nobj,):
+        return False
+    raise ValueError("`%s` must have shape (Nobj,) or (Nobj, Nsamps); got %s" % (name, shape))
+
+
+def _offdiag_spans(span, nfilt, name):
+    if span is None:
+        return None
+    span = np.asarray(span, dtype=np.float64)
+    if span.shape != (nfilt, 2):
+        raise ValueError("`%s` must have shape (Nfilt, 2); got %s" % (name, span.shape))
+    return span
+
+
+def _offdiag_edges(lo_hi, spans, col, nb):
+    """The `(Nfilt, nb + 1)` edges: `np.linspace` between the quantiles `lo_hi[:, col:col + 2]` of
+    every band, or its given span."""
+    nfilt = lo_hi.shape[0]
+    out = np.empty((nfilt, nb + 1))
+    for i in range(nfilt):
+        lo, hi = lo_hi[i, col:col + 2] if spans is None else spans[i]
+        out[i] = np.linspace(lo, hi, nb + 1)
+    return out
+
+
+def _offdiag_cells(x, y, bins, align, nobj):
+    """`(cell (Nobj,) int32, xedges, yedges, nx, ny)`: the flat cell `cx * ny + cy` every object's
+    residuals are shown in, -1 for none.  Edges: `np.histogram2d(x, y, bins)`; bins:
+    `np.digitize`.  `align="reference"` shows bin k in cell k + 1 and loses the last bin, as the
+    reference does by comparing `digitize`'s numbers (from 1) with cell numbers (from 0),
+    plotting.py:1335 and 1355; `align="bins"` shows bin k in cell k, the last edge inclusive."""
+    if align not in ("reference", "bins"):
+        raise ValueError("`align` must be 'reference' or 'bins'; got %r" % (align,))
+    nx, ny = _offdiag_bins(bins)
+    x, y = np.asarray(x), np.asarray(y)
+    if x.shape != (nobj,) or y.shape != (nobj,):
+        raise ValueError("`x` and `y` must have shape (Nobj,) = (%d,) in `map` (the reference cannot run "
+                         "with (Nobj, Nsamps) either); got %s and %s" % (nobj, x.shape, y.shape))
+    x, y = x.astype(np.float64), y.astype(np.float64)
+    if not (np.all(np.isfinite(x)) and np.all(np.isfinite(y))):
+        raise ValueError("`x` and `y` must be finite")
+    _, xedges, yedges = np.histogram2d(x, y, bins=(nx, ny))
+    shift = 1 if align == "reference" else 0
+    cx, cy = np.digitize(x, xedges) - 1, np.digitize(y, yedges) - 1       # the bin, from 0; n: on the last edge
+    if not shift:
+        cx, cy = np.minimum(cx, nx - 1), np.minimum(cy, ny - 1)
+    cx, cy = cx + shift, cy + shift
+    ok = (cx < nx) & (cy < ny)
+    return np.where(ok, cx * ny + cy, -1).astype(np.int32), xedges, yedges, nx, ny
+
+
+def _offdiag_host_residuals(models, inp, idxs, data, dim_prior):
+    from scipy.special import logsumexp
+    from .utils import phot_loglike
+    nobj, nsamps, nfilt = inp.nobj, inp.nsamps, inp.nfilt
+    idxs = np.asarray(idxs)
+    mpred = _predictive_host_seds(models, idxs, data, False)
+    good = np.all((idxs >= 0) & (idxs < models.shape[0]), axis=1)
+    weights = np.ones((nobj, nsamps)) if inp.weights is None else np.asarray(inp.weights, dtype=np.float64)
+    if weights.shape != (nobj, nsamps):
+        weights = np.repeat(weights, nsamps).reshape(nobj, nsamps)
+    magobs, mageobs, mask = inp.magobs, inp.mageobs, inp.mask
+    dm = np.full((nfilt, nobj, nsamps), np.nan)
+    wt = np.zeros((nfilt, nobj, nsamps))
+    use = np.zeros((nfilt, nobj), dtype=bool)
+    finite = np.all(np.isfinite(magobs), axis=1)
+    for i in range(nfilt):
+        mtemp = np.array(mask)
+        mtemp[:, i] = False
+        s = mask[:, i] & (np.sum(mtemp, axis=1) > 3) & finite & good
+        for o in np.flatnonzero(s):
+            with np.errstate(all="ignore"):
+                lnl = phot_loglike(magobs[o], mageobs[o], mtemp[o], mpred[o], dim_prior=dim_prior)
+                levid = logsumexp(lnl)
+                w = np.exp(lnl - levid)
+                w = w / w.sum()
+                w = weights[o] * w
+                tot = w.sum()
+            if np.isfinite(levid) and np.isfinite(tot) and tot > 0.:
+                use[i, o] = True
+                wt[i, o] = w
+                dm[i, o] = mpred[o, :, i] - magobs[o, i]
+    return dm, wt, use
+
+
+def _offdiag_host_x(x, inp, i, sel):
+    """The pooled abscissa of band `i` over the used objects `sel`."""
+    if x is None:
+        return np.repeat(inp.magobs[sel, i], inp.nsamps)
+    x = np.asarray(x, dtype=np.float64)
+    return x[sel].ravel() if _offdiag_x(x, inp.nobj, inp.nsamps) else np.repeat(x[sel], inp.nsamps)
+
+
+def _offdiag_host_quantile(v, q, w):
+    """`utils.quantile(v, q, weights=w)` of a pooled column; NaN for fewer than 2 samples or a
+    normaliser that is not positive, as on the device."""
+    q = np.asarray(q, dtype=np.float64)
+    return _column_quantiles(v, w, q, True) if v.size >= 2 else np.full(q.size, np.nan)
+
+
+class OffsetDiagnostics(object):
+    """The two diagnostics that follow `utils.photometric_offsets`, for a whole catalogue on the
+    device: where in magnitude, colour or position a band disagrees with the models.
+
+    `OffsetDiagnostics(models, device)` copies the `(Nmodel, Nfilt, 3)` grid to `device` once,
+    under the float32 rule of `PosteriorPredictive`.  `phot, err, mask` are `(Nobj, Nfilt)` as
+    given to `fit`; `idxs` and `data = (dists, reds, dreds)` are what `fit(save_dar_draws=True)`
+    saves.
+
+        D = pdf.OffsetDiagnostics(models)
+        dm, wt, use = D.residuals(phot, err, mask, idxs, data)
+        H, xedges, yedges = D.hist(phot, err, mask, idxs, data)                  # photometric_offsets
+        med, count, xedges, yedges = D.map(phot, err, mask, idxs, data, x, y)    # photometric_offsets_2d
+
+    `residuals` is the stage both share (reference plotting.py:1073-1110).  `mpred` is
+    `PosteriorPredictive.seds(flux=False)` bit for bit; `magobs, mageobs` are
+    `utils.magnitude(phot * offset, err * offset)` with `flux=True` and `(phot + offset, err)`
+    otherwise -- the reference's rule, kept as it is.  In band i an object is USED when
+    `mask[o, i]` is set, more than 3 other bands are masked in, and every `magobs[o, :]` is finite
+    (masked-out bands included, as the reference has it).  Its draws are re-weighted by the
+    likelihood of the OTHER bands, `utils.phot_loglike(..., dim_prior)`:
+    `wt = weights * e / sum_k e`, `e = exp(lnl - logsumexp_k lnl)`; `weights` is `(Nobj,)` or
+    `(Nobj, Nsamps)`, ones by default, and multiplies after the normalisation (plotting.py:1122).
+    Returns `dm (Nfilt, Nobj, Nsamps) = mpred - magobs` (NaN where not used), `wt` of that shape
+    (0 where not used) and `use (Nfilt, Nobj)` bool; `device_out=True` leaves them on the device.
+
+    Two rules are not the reference's.  An object is dropped from every band when any of its draw
+    indices lies outside `[0, Nmodel)`: `fit()` writes -99 for an object it did not fit, and numpy
+    would wrap it to another model.  An object is dropped from a band when that band's
+    log-evidence is not finite, or its weights do not sum to a finite value > 0 (a row of zero
+    `weights`): the reference would carry NaN into the pooled quantiles.
+
+    `hist` (plotting.py:1112-1134) pools, per band, the draws of the used objects: abscissa
+    `magobs[o, i]`, or `x` of shape `(Nobj,)` or `(Nobj, Nsamps)`; ordinate `dm`; weight `wt`.
+    The edges are `np.linspace(lo, hi, bins + 1)` with `(lo, hi)` the pooled
+    `utils.quantile(., [0.02, 0.98], weights)` or `xspan[i]` / `yspan[i]`; `H[i]` is
+    `np.histogram2d(xp, yp, bins=(bx, by), weights=w)[0]`.  `bins`: an int or `(nx, ny)`, at most
+    1024 each.  Returns `H (Nfilt, nx, ny)`, `xedges (Nfilt, nx + 1)`, `yedges (Nfilt, ny + 1)`.
+    A band without a used object has NaN edges (unless given) and an empty histogram.
+
+    `map` (plotting.py:1330-1363): `x, y (Nobj,)`, finite.  The edges are those of
+    `np.histogram2d(x, y, bins)` over all objects, the same for every band; `med[i, cx, cy]` is
+    the weighted median `utils.quantile(dm, [0.5], wt)` over the draws of the used objects of the
+    cell, NaN where fewer than `min_count` (the reference's `plot_thresh`; at least 1) fall in it;
+    `count (Nfilt, nx, ny)` int32 is that number.  `align="reference"` reproduces the reference's
+    off-by-one: it compares `np.digitize` results, which start at 1, with cell numbers that start
+    at 0, so row and column 0 are always empty, cell k shows bin k - 1 and the last bin is lost.
+    `align="bins"` shows bin k in cell k, the last edge inclusive.  Returns
+    `med, count, xedges (nx + 1,), yedges (ny + 1,)`.
+
+    Every sum runs in a fixed order, without atomics: a result has the same bytes from call to
+    call, and an object's `dm` and `wt` do not depend on the catalogue it is in.  The
+    leave-one-band-out variant of the `PosteriorPredictive` quantiles is
+    `P(idxs, data, weights=wt[i])`.  At most 4096 draws, 64 bands and `Nobj * Nsamps <= 2**27`
+    per call: split a larger catalogue and give `xspan` and `yspan`, the `H` of the pieces then
+    add.  There is no host fallback: without the library or a GPU the constructor raises
+    `BrutusError`; the host forms are `offset_residuals`, `offset_hist` and
+    `offset_map(device=None)`.
+    """
+
+    def __init__(self, models, device="cuda"):
+        from . import _lib
+        from ._dev import _torch
+        models = _predictive_grid(models, exact=True)
+        self.nmodel, self.nfilt = int(models.shape[0]), int(models.shape[1])
+        if self.nfilt > _lib.OFFDIAG_MAX_FILT:
+            raise ValueError("OffsetDiagnostics takes at most %d bands; got %d"
+                             % (_lib.OFFDIAG_MAX_FILT, self.nfilt))
+        self._L = _lib.lib()
+        self._torch = torch = _torch("OffsetDiagnostics only runs on the HIP path. The host forms are "
+                                     "offset_residuals, offset_hist and offset_map(device=None).")
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise ValueError("OffsetDiagnostics needs a GPU device; got %r" % (device,))
+        self._models = to_device(models, np.float32, self.device)
+        self._q = to_device(np.array(_OFFDIAG_Q_SPAN), np.float64, self.device)
+
+    def _residuals(self, inp, idxs, data, dim_prior):
+        """`(dm, wt, use)` on the device; the caller holds `torch.cuda.device`."""
+        from . import _lib
+        torch = self._torch
+        nobj, nsamps, nfilt = inp.nobj, inp.nsamps, inp.nfilt
+        t_idx = _table_indices(torch, idxs, self.nmodel, self.device)
+        t_d, t_r, t_dr = (to_device(a, np.float64, self.device) for a in data)
+        t_w = None
+        if inp.weights is not None:
+            t_w = to_device(inp.weights, np.float64, self.device)
+            if t_w.dim() == 1:
+                t_w = t_w[:, None].expand(nobj, nsamps).contiguous()
+        t_mo = to_device(inp.magobs, np.float64, self.device)
+        t_me = to_device(inp.mageobs, np.float64, self.device)
+        t_mk = to_device(inp.mask.astype(np.uint8), np.uint8, self.device)
+        dm = torch.empty((nfilt, nobj, nsamps), dtype=torch.float64, device=self.device)
+        wt = torch.empty((nfilt, nobj, nsamps), dtype=torch.float64, device=self.device)
+        use = torch.empty((nfilt, nobj), dtype=torch.uint8, device=self.device)
+        _lib.check(self._L.brutus_offdiag_residuals(
+            nobj, nsamps, t_idx, t_d, t_r, t_dr, t_w, self.nmodel, nfilt, self._models, t_mo, t_me, t_mk,
+            int(bool(dim_prior)), dm, wt, use, _stream_ptr(torch)))
+        return dm, wt, use
+
+    def _objs(self, use):
+        """Per band the used objects, as int32 device tensors (one copy of `use` to the host)."""
+        use = use.cpu().numpy().astype(bool)
+        return use, [to_device(np.flatnonzero(u).astype(np.int32), np.int32, self.device) for u in use]
+
+    def residuals(self, phot, err, mask, idxs, data, weights=None, offset=None, flux=True, dim_prior=True,
+                  device_out=False):
+        inp = _OffdiagInputs(self.nfilt, phot, err, mask, idxs, data, weights, offset, flux)
+        torch = self._torch
+        with torch.cuda.device(self.device):
+            dm, wt, use = self._residuals(inp, idxs, data, dim_prior)
+            torch.cuda.current_stream().synchronize()
+            if device_out:
+                return dm, wt, use.to(torch.bool)
+            return dm.cpu().numpy(), wt.cpu().numpy(), use.cpu().numpy().astype(bool)
+
+    def hist(self, phot, err, mask, idxs, data, x=None, weights=None, bins=100, offset=None, flux=True,
+             dim_prior=True, xspan=None, yspan=None):
+        from . import _lib
+        inp = _OffdiagInputs(self.nfilt, phot, err, mask, idxs, data, weights, offset, flux)
+        nobj, nsamps, nfilt = inp.nobj, inp.nsamps, inp.nfilt
+        nx, ny = _offdiag_bins(bins)
+        xspan, yspan = _offdiag_spans(xspan, nfilt, "xspan"), _offdiag_spans(yspan, nfilt, "yspan")
+        x_per_sample = False if x is None else _offdiag_x(x, nobj, nsamps)
+        torch, L = self._torch, self._L
+        with torch.cuda.device(self.device):
+            stream = _stream_ptr(torch)
+            dm, wt, use = self._residuals(inp, idxs, data, dim_prior)
+            use, objs = self._objs(use)
+            if x is None:       # band-major, so that a band's column is contiguous
+                t_x = to_device(np.ascontiguousarray(inp.magobs.T), np.float64, self.device)
+            else:
+                t_x = to_device(x, np.float64, self.device)
+            x_of = (lambda i: t_x[i]) if x is None else (lambda i: t_x)
+            lo_hi = torch.full((nfilt, 4), float("nan"), dtype=torch.float64, device=self.device)
+            for i in range(nfilt):
+                nuse = int(objs[i].shape[0])
+                if xspan is None:
+                    _lib.check(L.brutus_offdiag_pooled_quantiles(
+                        nobj, nuse, nsamps, objs[i], x_of(i), int(x_per_sample), wt[i], 2, self._q,
+                        lo_hi[i, 0:2], stream))
+                if yspan is None:
+                    _lib.check(L.brutus_offdiag_pooled_quantiles(
+                        nobj, nuse, nsamps, objs[i], dm[i], 1, wt[i], 2, self._q, lo_hi[i, 2:4], stream))
+            lo_hi = lo_hi.cpu().numpy()
+            xedges, yedges = _offdiag_edges(lo_hi, xspan, 0, nx), _offdiag_edges(lo_hi, yspan, 2, ny)
+            t_xe = to_device(xedges, np.float64, self.device)
+            t_ye = to_device(yedges, np.float64, self.device)
+            H = torch.empty((nfilt, nx, ny), dtype=torch.float64, device=self.device)
+            for i in range(nfilt):
+                _lib.check(L.brutus_offdiag_hist(
+                    nobj, int(objs[i].shape[0]), nsamps, objs[i], x_of(i), int(x_per_sample), dm[i], wt[i],
+                    nx, ny, t_xe[i], t_ye[i], H[i], stream))
+            return H.cpu().numpy(), xedges, yedges
+
+    def map(self, phot, err, mask, idxs, data, x, y, weights=None, bins=100, offset=None, flux=True,
+            dim_prior=True, min_count=10, align="reference"):
+        from . import _lib
+        inp = _OffdiagInputs(self.nfilt, phot, err, mask, idxs, data, weights, offset, flux)
+        nobj, nsamps, nfilt = inp.nobj, inp.nsamps, inp.nfilt
+        cell, xedges, yedges, nx, ny = _offdiag_cells(x, y, bins, align, nobj)
+        torch, L = self._torch, self._L
+        with torch.cuda.device(self.device):
+            stream = _stream_ptr(torch)
+            dm, wt, use = self._residuals(inp, idxs, data, dim_prior)
+            use, objs = self._objs(use)
+            t_cell = to_device(cell, np.int32, self.device)
+            med = torch.empty((nfilt, nx, ny), dtype=torch.float64, device=self.device)
+            count = torch.empty((nfilt, nx, ny), dtype=torch.int32, device=self.device)
+            for i in range(nfilt):
+                _lib.check(L.brutus_offdiag_cell_medians(
+                    nobj, int(objs[i].shape[0]), nsamps, objs[i], t_cell, dm[i], wt[i], nx * ny,
+                    int(min_count), med[i], count[i], stream))
+            return med.cpu().numpy(), count.cpu().numpy(), xedges, yedges
+
+
+def offset_residuals(models, phot, err, mask, idxs, data, weights=None, offset=None, flux=True,
+                     dim_prior=True, device=None, device_out=False):
+    """`(dm, wt, use)`: per band the residuals `mag_pred - mag_obs` of every saved draw, their
+    leave-one-band-out weights and the objects used; see `OffsetDiagnostics.residuals`.
+
+    `device=None`: numpy on the host -- `utils.get_seds`, `utils.magnitude`, `utils.phot_loglike`
+    per object and band -- for a grid of any float type.  Otherwise a one-shot `OffsetDiagnostics`
+    on that GPU."""
+    if device is not None:
+        return OffsetDiagnostics(models, device=device).residuals(
+            phot, err, mask, idxs, data, weights=weights, offset=offset, flux=flux, dim_prior=dim_prior,
+            device_out=device_out)
+    models = _predictive_grid(models, exact=False)
+    inp = _OffdiagInputs(models.shape[1], phot, err, mask, idxs, data, weights, offset, flux)
+    return _offdiag_host_residuals(models, inp, idxs, data, dim_prior)
+
+
+def offset_hist(models, phot, err, mask, idxs, data, x=None, weights=None, bins=100, offset=None,
+                flux=True, dim_prior=True, xspan=None, yspan=None, device=None):
+    """`(H (Nfilt, nx, ny), xedges (Nfilt, nx + 1), yedges (Nfilt, ny + 1))`: per band the weighted
+    2-D histogram of (x, `mag_pred - mag_obs`) that reference `plotting.photometric_offsets`
+    hands to `hist2d`; see `OffsetDiagnostics.hist`.  `device` as in `offset_residuals`; the host
+    form uses `utils.quantile` and `np.histogram2d`."""
+    if device is not None:
+        return OffsetDiagnostics(models, device=device).hist(
+            phot, err, mask, idxs, data, x=x, weights=weights, bins=bins, offset=offset, flux=flux,
+            dim_prior=dim_prior, xspan=xspan, yspan=yspan)
+    models = _predictive_grid(models, exact=False)
+    inp = _OffdiagInputs(models.shape[1], phot, err, mask, idxs, data, weights, offset, flux)
+    nfilt = inp.nfilt
+    nx, ny = _offdiag_bins(bins)
+    xspan, yspan = _offdiag_spans(xspan, nfilt, "xspan"), _offdiag_spans(yspan, nfilt, "yspan")
+    if x is not None:
+        _offdiag_x(np.asarray(x), inp.nobj, inp.nsamps)
+    dm, wt, use = _offdiag_host_residuals(models, inp, idxs, data, dim_prior)
+    pooled, lo_hi = [], np.full((nfilt, 4), np.nan)
+    for i in range(nfilt):
+        sel = np.flatnonzero(use[i])
+        xp, yp, w = _offdiag_host_x(x, inp, i, sel), dm[i, sel].ravel(), wt[i, sel].ravel()
+        pooled.append((xp, yp, w))
+        if xspan is None:
+            lo_hi[i, 0:2] = _offdiag_host_quantile(xp, _OFFDIAG_Q_SPAN, w)
+        if yspan is None:
+            lo_hi[i, 2:4] = _offdiag_host_quantile(yp, _OFFDIAG_Q_SPAN, w)
+    xedges, yedges = _offdiag_edges(lo_hi, xspan, 0, nx), _offdiag_edges(lo_hi, yspan, 2, ny)
+    H = np.zeros((nfilt, nx, ny))
+    for i, (xp, yp, w) in enumerate(pooled):
+        if xp.size and np.all(np.isfinite(xedges[i])) and np.all(np.isfinite(yedges[i])):
+            H[i] = np.histogram2d(xp, yp, bins=(xedges[i], yedges[i]), weights=w)[0]
+    return H, xedges, yedges
+
+
+def offset_map(models, phot, err, mask, idxs, data, x, y, weights=None, bins=100, offset=None,
+               flux=True, dim_prior=True, min_count=10, align="reference", device=None):
+    """`(med (Nfilt, nx, ny), count (Nfilt, nx, ny) int32, xedges, yedges)`: per band the weighted
+    median `mag_pred - mag_obs` in bins of two per-object quantities, the image reference
+    `plotting.photometric_offsets_2d` draws; see `OffsetDiagnostics.map` (and there for `align`).
+    `device` as in `offset_residuals`; the host form uses `utils.quantile` per cell."""
+    if device is not None:
+        return OffsetDiagnostics(models, device=device).map(
+            phot, err, mask, idxs, data, x, y, weights=weights, bins=bins, offset=offset, flux=flux,
+            dim_prior=dim_prior, min_count=min_count, align=align)
+    models = _predictive_grid(models, exact=False)
+    inp = _OffdiagInputs(models.shape[1], phot, err, mask, idxs, data, weights, offset, flux)
+    cell, xedges, yedges, nx, ny = _offdiag_cells(x, y, bins, align, inp.nobj)
+    dm, wt, use = _offdiag_host_residuals(models, inp, idxs, data, dim_prior)
+    med = np.full((inp.nfilt, nx * ny), np.nan)
+    count = np.zeros((inp.nfilt, nx * ny), dtype=np.int32)
+    for i in range(inp.nfilt):
+        for c in np.unique(cell[use[i] & (cell >= 0)]):
+            sel = np.flatnonzero(use[i] & (cell == c))
+            count[i, c] = sel.size
+            if sel.size >= max(1, min_count):
+                med[i, c] = _offdiag_host_quantile(dm[i, sel].ravel(), [0.5], wt[i, sel].ravel())[0]
+    return med.reshape(-1, nx, ny), count.reshape(-1, nx, ny), xedges, yedges

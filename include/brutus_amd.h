@@ -639,6 +639,9 @@ void brutus_enable_timing(int on);
 /* ---- posterior-predictive check: the draws' model SEDs and their quantiles per band ---- */
 #include "brutus_amd_predictive.h"
 
+/* ---- photometric-offset residual maps: leave-one-band-out residuals, histograms, medians ---- */
+#include "brutus_amd_offdiag.h"
+
 #ifdef __cplusplus
 }
 #endif

@@ -1487,6 +1487,246 @@ def gen_post_predictive():
           % (tries, sum(H.nobj_of(n) for n in H.NSAMPS), gap, os.path.getsize(PH.FIXTURE)))
 
 
+def gen_offset_diag():
+    """tests/golden/offset_diag.npz: what reference `plotting.photometric_offsets` hands to
+    `Axes.hist2d` and `plotting.photometric_offsets_2d` to `Axes.imshow` (both methods and
+    `phot_loglike` are wrapped for the duration of the call; nothing is drawn to a file), for the
+    cases of tests/offdiag_helpers.py: 48 objects at 2, 65, 250 and 100 draws on
+    `synth.make_mist_like_grid(500, 8, seed=7)`, float32 promoted to float64.
+
+    An object's draws are picks from a pool of `npool(n)` distinct (distance, Av, Rv) entries of
+    one model, so ties exist, and the file keeps every per-draw quantity per pool entry.  The
+    pool has 3 entries (nearly every knot interval of a pooled column is then a tie, which
+    condition (e) needs) except at 100 draws, where it has 16 and every histogram has given
+    spans.  Photometry is one pool entry plus 5 % noise.  Objects 0-4: exactly 4 masked-in bands
+    (never used), exactly 5 (used in each of its bands), all 8, a negative flux in a masked-out
+    band and one in a masked-in band (both dropped everywhere); object LONER sits alone in its
+    cell of the maps.
+
+    The catalogue is redrawn until, against the reference alone:
+    (a) no pooled sample lies within 1e-9 (hi - lo) of a bin edge without being equal to it (a
+        quantile that falls on a tie, which (e) asks for, IS a sample, bit for bit, on the host
+        and on the device alike);
+    (b) `summary_helpers.margin` of every pooled quantile and cell median exceeds MARGIN;
+    (c) distinct values of a pooled column differ by more than 1e-9 of its largest magnitude;
+    (d) with the objects in reverse order the reference gives the same bytes for ln L, the edges
+        and the medians; H is allowed the rounding of a bin's sum taken in another order,
+        Nobj Nsamps eps of the bin, since `np.histogram2d` adds a bin's weights in sample order;
+    (e) for every pooled quantile of a default-span case the bracket at delta = 1e-8 is narrower
+        than 1e-10 (hi - lo).
+    At 2 draws and with the pool of 16 (e) cannot hold, so every histogram there has given
+    spans."""
+    import warnings
+    import matplotlib
+    matplotlib.use("Agg")
+    from matplotlib import pyplot as plt
+    from matplotlib.axes import Axes
+    from brutus import plotting as RP
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import offdiag_helpers as OH
+    import summary_helpers as H
+    rng = np.random.RandomState(20261022)
+    models, _, _ = synth.make_mist_like_grid(OH.NMODEL, OH.NFILT, seed=OH.GRID_SEED)
+    m64 = models.astype(np.float64)
+    nobj, nfilt = OH.NOBJ, OH.NFILT
+    res = dict(models=models)
+
+    def draw(n):
+        k = OH.npool(n)
+        c = dict()
+        # (entries 1.. are entry 0's model a little nearer, farther or redder: residuals of a tenth
+        # of a magnitude, as after a fit -- models picked at random would sit 1000 in ln L away,
+        # where the bound tau on a weight's error exceeds the 1e-8 the bracket rule allows)
+        c["pool_idx"] = np.repeat(rng.choice(OH.NMODEL, nobj, replace=False)[:, None], k, axis=1).astype(np.int32)
+        c["pool_dist"] = np.exp(rng.normal(0., 0.6, (nobj, 1))) * np.exp(rng.normal(0., 0.02, (nobj, k)))
+        c["pool_red"] = rng.uniform(0.1, 3., (nobj, 1)) + rng.normal(0., 0.02, (nobj, k))
+        c["pool_dred"] = rng.uniform(2.5, 4.5, (nobj, 1)) + rng.normal(0., 0.05, (nobj, k))
+        c["pool_x2"], c["pool_w2"] = rng.uniform(-1., 1., (nobj, k)), rng.uniform(0.5, 1.5, (nobj, k))
+        pick = rng.randint(0, k, (nobj, n))
+        pick[:, :k] = np.arange(k)                       # every entry is drawn
+        c["pick"] = pick.astype(np.uint8)
+        sed = U.get_seds(m64[c["pool_idx"].ravel()], av=c["pool_red"].ravel(), rv=c["pool_dred"].ravel())
+        sed += 5. * np.log10(c["pool_dist"].ravel())[:, None]
+        c["pool_mpred"] = sed.reshape(nobj, k, nfilt)
+        truth = 10. ** (-0.4 * c["pool_mpred"][:, 0])
+        c["phot"] = truth * (1. + 0.05 * rng.normal(size=truth.shape))
+        c["err"] = 0.05 * truth
+        mask = rng.uniform(size=(nobj, nfilt)) < 0.85
+        for o in range(nobj):
+            while mask[o].sum() < 6:
+                mask[o, rng.randint(nfilt)] = True
+        mask[0] = False
+        mask[0, rng.choice(nfilt, 4, replace=False)] = True
+        mask[1] = False
+        mask[1, rng.choice(nfilt, 5, replace=False)] = True
+        mask[2] = True
+        mask[3, 2], mask[4, 2] = False, True
+        c["phot"][3, 2] = -abs(c["phot"][3, 2])
+        c["phot"][4, 2] = -abs(c["phot"][4, 2])
+        c["mask"] = mask
+        with np.errstate(all="ignore"):
+            c["photmag"], c["errmag"] = U.magnitude(c["phot"], c["err"])
+        c["x1"], c["y"] = rng.uniform(-1., 1., nobj), rng.uniform(-1., 1., nobj)
+        c["x1"][OH.LONER], c["y"][OH.LONER] = -2., -2.
+        c["w1"] = rng.uniform(0.5, 1.5, nobj)
+        c["w1"][[7, 11]] = 0.
+        c["offset_mul"], c["offset_add"] = rng.uniform(0.97, 1.03, nfilt), rng.uniform(-0.03, 0.03, nfilt)
+        c["yspan"] = np.tile([-0.3, 0.3], (nfilt, 1))
+        return c
+
+    reasons = dict()
+
+    def why(k):
+        reasons[k] = reasons.get(k, 0) + 1
+        if sum(reasons.values()) % 25 == 0:
+            print("offset_diag: rejections by check so far:", sorted(reasons.items()), flush=True)
+        return None
+
+    def run_reference(c, n, order):
+        """Every case on the catalogue with its objects in `order`; None if a condition fails."""
+        full = OH.catalogue({"%s_%d" % (k, n): v[order] if v.shape[:1] == (nobj,) else v
+                             for k, v in c.items()}, n)
+        out, captured = dict(), dict(lnl=[], hist=[], img=[])
+        orig = (Axes.hist2d, Axes.imshow, RP.phot_loglike)
+
+        def hist2d(self, x, y, bins=10, weights=None, **kw):
+            r = orig[0](self, x, y, bins=bins, weights=weights, **kw)
+            captured["hist"].append((np.array(x), np.array(y), np.array(weights), np.array(r[0]),
+                                     np.array(r[1]), np.array(r[2])))
+            return r
+
+        def imshow(self, X, **kw):
+            captured["img"].append(np.array(X).T)
+            return orig[1](self, X, **kw)
+
+        def phot_loglike(*a, **kw):
+            r = orig[2](*a, **kw)
+            captured["lnl"].append(np.array(r))
+            return r
+
+        Axes.hist2d, Axes.imshow, RP.phot_loglike = hist2d, imshow, phot_loglike
+        try:
+            for table, names in ((OH.HIST_CASES, "hist"), (OH.MAP_CASES, "map")):
+                for case in sorted(table):
+                    for v in captured.values():
+                        del v[:]
+                    (phot, err), kw = OH.call_args(full, case, table)
+                    magobs, mageobs = OH.magobs_of(full, case, table)
+                    kw.pop("bins")
+                    args = (phot, err, full["mask"], m64, full["idxs"], full["reds"], full["dreds"], full["dists"])
+                    with warnings.catch_warnings():
+                        warnings.simplefilter("ignore")
+                        if names == "hist":
+                            sp = OH.spans_of(full, case) if OH.explicit_spans(case, n) else (None, None)
+                            RP.photometric_offsets(*args, bins=table[case]["bins"], plot_thresh=0.,
+                                                   xspan=sp[0], yspan=sp[1], **kw)
+                        else:
+                            RP.photometric_offsets_2d(*args, full["x1"], full["y"], bins=table[case]["bins"],
+                                                      plot_thresh=OH.MIN_COUNT, **kw)
+                    plt.close("all")
+                    finite = np.all(np.isfinite(magobs), axis=1)
+                    lnl_pool = np.full((nfilt, nobj, OH.npool(n)), np.nan)
+                    calls = iter(captured["lnl"])
+                    for i in range(nfilt):
+                        mt = full["mask"].copy()
+                        mt[:, i] = False
+                        s = full["mask"][:, i] & (mt.sum(axis=1) > 3) & finite
+                        for o in (np.flatnonzero(s) if names == "hist" else range(nobj)):
+                            lnl = next(calls)
+                            if s[o]:
+                                lnl_pool[i, o, full["pick"][o]] = lnl
+                                assert np.array_equal(lnl_pool[i, o, full["pick"][o]], lnl)
+                    assert next(calls, None) is None
+                    key = "%s_%s_%d" % (names, case, n)
+                    out["lnl_" + key] = lnl_pool
+                    wt, s, _ = OH.reference_weights(lnl_pool, full["pick"], kw["weights"])
+                    if names == "hist":
+                        assert len(captured["hist"]) == nfilt
+                        for i, (xp, yp, w, Hh, xe, ye) in enumerate(captured["hist"]):
+                            assert np.array_equal(w, wt[i, s[i]].ravel()), (key, i)
+                            for col, e in ((xp, xe), (yp, ye)):
+                                gap = np.abs(col[:, None] - e[None, :])
+                                if np.any((gap > 0.) & (gap <= 1e-9 * (e[-1] - e[0]))):
+                                    return why(1)                                   # (a)
+                                u = np.unique(col)
+                                if u.size > 1 and np.min(np.diff(u)) <= 1e-9 * np.max(np.abs(col)):
+                                    return why(2)                                   # (c)
+                                if not OH.explicit_spans(case, n):
+                                    try:
+                                        if not H.margin(col, w, OH.Q_SPAN) > H.MARGIN:
+                                            return why(3)                           # (b)
+                                    except AssertionError:
+                                        return why(4)
+                                    for q in OH.Q_SPAN:                           # (e)
+                                        lo, hi = U.quantile(col, [q - 1e-8, q + 1e-8], weights=w)
+                                        if not hi - lo < 1e-10 * (e[-1] - e[0]):
+                                            return why(5)
+                        out["H_" + key] = np.stack([h[3] for h in captured["hist"]])
+                        out["xedges_" + key] = np.stack([h[4] for h in captured["hist"]])
+                        out["yedges_" + key] = np.stack([h[5] for h in captured["hist"]])
+                    else:
+                        assert len(captured["img"]) == nfilt
+                        med = np.stack(captured["img"])
+                        _, xe, ye = np.histogram2d(full["x1"], full["y"], bins=table[case]["bins"])
+                        xl, yl = np.digitize(full["x1"], xe), np.digitize(full["y"], ye)
+                        for i in range(nfilt):
+                            for cx, cy in zip(*np.nonzero(~np.isnan(med[i]))):
+                                sel = np.flatnonzero((xl == cx) & (yl == cy) & s[i])
+                                col, w = (full["mpred"][sel, :, i] - magobs[sel, i][:, None]).ravel(), wt[i, sel].ravel()
+                                try:
+                                    if not H.margin(col, w, [0.5]) > H.MARGIN:
+                                        return why(6)                               # (b)
+                                except AssertionError:
+                                    return why(7)
+                                u = np.unique(col)
+                                if u.size > 1 and np.min(np.diff(u)) <= 1e-9 * np.max(np.abs(col)):
+                                    return why(8)                                   # (c)
+                        out["med_" + key] = med
+        finally:
+            Axes.hist2d, Axes.imshow, RP.phot_loglike = orig
+            plt.close("all")
+        return out
+
+    total = 0
+    for n in OH.NSAMPS:
+        tries = 0
+        while True:
+            tries += 1
+            c = draw(n)
+            xs = np.where(np.isfinite(c["photmag"]), c["photmag"], np.nan)
+            c["xspan_mag"] = np.stack([np.nanmean(xs, axis=0) - 1.5, np.nanmean(xs, axis=0) + 1.5], axis=1)
+            c["xspan"] = np.tile([-1.2, 1.2], (nfilt, 1))                         # against x1 or x2
+            fwd = run_reference(c, n, np.arange(nobj))
+            if fwd is None:
+                continue
+            back = run_reference(c, n, np.arange(nobj)[::-1])                     # (d)
+            if back is None:
+                continue
+            same = True
+            for k, v in fwd.items():
+                if k.startswith("H_"):
+                    same &= bool(np.all(np.abs(v - back[k]) <= nobj * n * OH.EPS * np.maximum(v, back[k])))
+                elif k.startswith("lnl_"):
+                    same &= np.array_equal(v, back[k][:, ::-1], equal_nan=True)
+                elif k.startswith("med_"):
+                    pass                                 # (the cells move with x1 and y: compared below)
+                else:
+                    same &= np.array_equal(v, back[k], equal_nan=True)
+            for k in fwd:
+                if k.startswith("med_"):
+                    same &= np.array_equal(fwd[k], back[k], equal_nan=True)
+            if same:
+                break
+        total += tries
+        print("offset_diag: %d draws: conditions (a)-(e) met after %d tries" % (n, tries))
+        for k, v in c.items():
+            res["%s_%d" % (k, n)] = v
+        res.update(fwd)
+    np.savez_compressed(OH.FIXTURE, **res)
+    print("wrote offset_diag.npz: %d catalogues drawn for %d kept, %d bytes"
+          % (total, len(OH.NSAMPS), os.path.getsize(OH.FIXTURE)))
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     which = sys.argv[1:] or ["loglike", "fit", "helpers", "setup", "galprior",
@@ -1543,3 +1783,5 @@ if __name__ == "__main__":
         gen_post_quantiles()
     if "post_predictive" in which:
         gen_post_predictive()
+    if "offset_diag" in which:
+        gen_offset_diag()
