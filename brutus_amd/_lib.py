@@ -332,6 +332,18 @@ OFFDIAG_SIGNATURES = {
 OFFDIAG_MAX_DRAWS, OFFDIAG_MAX_FILT, OFFDIAG_MAX_SAMPLES, OFFDIAG_MAX_BINS, OFFDIAG_MAX_Q = (
     4096, MAX_FILT, 1 << 27, 1024, 8)
 
+# and for include/brutus_amd_los_field.h (los.LOSField; tests/test_los_field_host.py compares this
+# table with that header parameter by parameter)
+LOS_FIELD_SIGNATURES = {
+    "brutus_los_field_plan": (C.c_int, [_i32, _hi32, _hi32, _hi64, _hi32, _i64, _hi64]),
+    "brutus_los_field_workspace_bytes": (_sz, [_i64, _i32]),
+    "brutus_los_field_loglike": (C.c_int, [_i32, _i64, _i64, _df64, _df64, _df64, _di64, _di32, _i32, _i32,
+                                           _df64, C.POINTER(LosParams), _i32, _df64, _df64, _dv, _sz,
+                                           _stream]),
+}
+LOSFIELD_MAX_SIGHTLINES, LOSFIELD_MAX_TILES, LOSFIELD_COLS = 1 << 20, (1 << 20) + (1 << 16), 6
+LOSFIELD_CHECK_THETA, LOSFIELD_MONOTONIC = 1, 2
+
 
 def lib():
     """Load (once) and return the shared library; raise loudly if absent."""
@@ -351,7 +363,8 @@ def lib():
     L = C.CDLL(LIB_PATH)
     for name, (res, args) in (list(SIGNATURES.items()) + list(BATCH_SIGNATURES.items())
                               + list(DUST_SIGNATURES.items()) + list(SUMMARY_SIGNATURES.items())
-                              + list(PREDICTIVE_SIGNATURES.items()) + list(OFFDIAG_SIGNATURES.items())):
+                              + list(PREDICTIVE_SIGNATURES.items()) + list(OFFDIAG_SIGNATURES.items())
+                              + list(LOS_FIELD_SIGNATURES.items())):
         fn = getattr(L, name)   # AttributeError if the .so is stale
         fn.restype = res
         fn.argtypes = args

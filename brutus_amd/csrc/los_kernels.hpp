@@ -11,6 +11,13 @@
 // order -- to one partial per (theta, tile), and k_los_final adds the partials of a theta in a
 // fixed order as well: no floating-point atomics, the same bytes for the same theta whatever
 // else is in the batch.
+//
+// k_los_field_terms / k_los_field_final are the same work over a ragged FIELD of sightlines
+// (include/brutus_amd_los_field.h): a tile never crosses a sightline, a workgroup finds its
+// sightline in a tile table and reads row k of that sightline's thetas.  The table in LDS
+// (los_build_table), the per-star arithmetic (los_star_term) and the wave's sum (los_wave_sum)
+// are ONE copy that both pairs call, so a sightline's values in a field are the bytes
+// k_los_terms / k_los_final give for it alone.
 #pragma once
 
 namespace {
@@ -29,6 +36,19 @@ struct LosCall {
     int nobj, ndraws, nclouds, ntiles;
 };
 
+struct LosFieldCall {
+    const double *ds, *rs;       // the sightlines' draw-major blocks, end to end
+    const double *templ;         // (nstars) or null
+    const double *theta;         // (nsight, ntheta, 4 + 2 nclouds)
+    const int64_t *sl;           // (nsight, BRUTUS_LOSFIELD_COLS): the plan's sightline table
+    const int32_t *tiles;        // (ntiles): the sightline of every tile
+    double *partial;             // (ntheta, ntiles)
+    double *loglike;             // (nsight, ntheta)
+    double *terms;               // per sightline (ntheta, nobj_s), or null
+    double area, ln_area_neg;
+    int ntheta, nclouds, ntiles, flags;
+};
+
 // ln of the kernel's norm (los.py:274, 307, 337) for the width w
 template <int KERNEL>
 __device__ __forceinline__ double los_lnnorm(double w) {
@@ -38,20 +58,16 @@ __device__ __forceinline__ double los_lnnorm(double w) {
     else return fast_log(2. * w);
 }
 
-// KERNEL 0 gauss, 1 lorentz, 2 tophat; TEMPL: cloud reddenings are multiples of the object's
-// template value; ADD: the foreground is added to every later bin's mean
+// The per-bin table of the row `th` in LDS, one lane per bin (bin 0: the foreground); the caller
+// synchronises.  s_mean: the mean (TEMPL: the rescaling) of the bin; s_w: the width for the top
+// hat, else 1 / width; s_ln: ln norm; s_xd: the cloud distances.
 template <int KERNEL, bool TEMPL, bool ADD>
-__global__ __launch_bounds__(LOS_TILE) void k_los_terms(const LosCall c) {
-#pragma clang fp contract(off)       // mean = r t, then + fred; z z; (1 - pb) e1 + pb e2: rounded one by one
-    __shared__ double s_xd[LOS_MAX_CLOUDS];          // cloud distances
-    __shared__ double s_mean[LOS_MAX_CLOUDS + 1];    // TEMPL: the rescaling of the bin (bin 0: fred)
-    __shared__ double s_w[LOS_MAX_CLOUDS + 1];       // tophat: width; else 1 / width
-    __shared__ double s_ln[LOS_MAX_CLOUDS + 1];      // ln norm
-    const int lane = threadIdx.x, nc = c.nclouds;
-    const double *th = c.theta + (size_t)blockIdx.y * (size_t)(4 + 2 * nc);
-    const double pb = th[0], fred = th[3];
+__device__ __forceinline__ void los_build_table(const double *th, double area, int nc, int lane, double *s_xd,
+                                                double *s_mean, double *s_w, double *s_ln) {
+#pragma clang fp contract(off)
     if (lane <= nc) {
-        const double w = (lane == 0 ? th[1] : th[2]) * c.area;
+        const double fred = th[3];
+        const double w = (lane == 0 ? th[1] : th[2]) * area;
         double mean = th[3 + 2 * lane];
         if (!TEMPL && ADD && lane > 0) mean = mean + fred;
         s_mean[lane] = mean;
@@ -59,16 +75,21 @@ __global__ __launch_bounds__(LOS_TILE) void k_los_terms(const LosCall c) {
         s_ln[lane] = los_lnnorm<KERNEL>(w);
         if (lane > 0) s_xd[lane - 1] = th[2 + 2 * lane];
     }
-    __syncthreads();
+}
 
-    const int i = blockIdx.x * LOS_TILE + lane;
-    const bool live = i < c.nobj;
-    const size_t col = live ? (size_t)i : (size_t)(c.nobj - 1);   // lanes past the end reread the last object
-    const double t = TEMPL ? c.templ[col] : 1.;
-
+// The term of one star, from the bin search through the outlier mixture: its draws are
+// ds[n * nobj + col], rs[n * nobj + col], n < ndraws; t its template value (TEMPL).
+// KERNEL 0 gauss, 1 lorentz, 2 tophat; TEMPL: cloud reddenings are multiples of the object's
+// template value; ADD: the foreground is added to every later bin's mean
+template <int KERNEL, bool TEMPL, bool ADD>
+__device__ __forceinline__ double los_star_term(const double *ds, const double *rs, size_t nobj, size_t col,
+                                                int ndraws, int nc, double t, double pb, double fred,
+                                                double ln_nsamps, double ln_area_neg, const double *s_xd,
+                                                const double *s_mean, const double *s_w, const double *s_ln) {
+#pragma clang fp contract(off)       // mean = r t, then + fred; z z; (1 - pb) e1 + pb e2: rounded one by one
     auto logw = [&](int n) -> double {
 #pragma clang fp contract(off)
-        const double d = c.ds[(size_t)n * c.nobj + col], r = c.rs[(size_t)n * c.nobj + col];
+        const double d = ds[(size_t)n * nobj + col], r = rs[(size_t)n * nobj + col];
         int bin = 0;
         for (int q = 0; q < nc; ++q) bin += s_xd[q] <= d ? 1 : 0;
         double mean = s_mean[bin];
@@ -92,7 +113,7 @@ __global__ __launch_bounds__(LOS_TILE) void k_los_terms(const LosCall c) {
 
     double m = -INFINITY;
     bool isnan_ = false;
-    for (int n = 0; n < c.ndraws; ++n) {
+    for (int n = 0; n < ndraws; ++n) {
         const double lw = logw(n);
         isnan_ = isnan_ || lw != lw;
         m = lw > m ? lw : m;
@@ -100,22 +121,47 @@ __global__ __launch_bounds__(LOS_TILE) void k_los_terms(const LosCall c) {
     double l = -INFINITY;
     if (m > -INFINITY) {
         double s = 0.;
-        for (int n = 0; n < c.ndraws; ++n) s += fast_exp(logw(n) - m);
-        l = (fast_log(s) + m) - c.ln_nsamps;
+        for (int n = 0; n < ndraws; ++n) s += fast_exp(logw(n) - m);
+        l = (fast_log(s) + m) - ln_nsamps;
     }
     if (isnan_) l = nan("");
     // outlier mixture ln((1 - pb) e^l + pb / area), shifted by the larger of the two; a part whose
     // weight is zero adds nothing, whatever its value (scipy's logsumexp with `b`)
-    const double a1 = 1. - pb == 0. ? -INFINITY : l, a2 = pb == 0. ? -INFINITY : c.ln_area_neg;
+    const double a1 = 1. - pb == 0. ? -INFINITY : l, a2 = pb == 0. ? -INFINITY : ln_area_neg;
     const double mx = a1 > a2 ? a1 : a2;
     const double shift = mx > -INFINITY ? mx : 0.;
     const double e1 = fast_exp(a1 - shift), e2 = fast_exp(a2 - shift);
-    const double term = fast_log((1. - pb) * e1 + pb * e2) + mx;
-    if (live && c.terms) c.terms[(size_t)blockIdx.y * (size_t)c.nobj + (size_t)i] = term;
+    return fast_log((1. - pb) * e1 + pb * e2) + mx;
+}
 
-    double v = live ? term : 0.;
+// the sum over the wave in a fixed order: every lane ends with the total
+__device__ __forceinline__ double los_wave_sum(double v) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+template <int KERNEL, bool TEMPL, bool ADD>
+__global__ __launch_bounds__(LOS_TILE) void k_los_terms(const LosCall c) {
+    __shared__ double s_xd[LOS_MAX_CLOUDS];          // cloud distances
+    __shared__ double s_mean[LOS_MAX_CLOUDS + 1];    // TEMPL: the rescaling of the bin (bin 0: fred)
+    __shared__ double s_w[LOS_MAX_CLOUDS + 1];       // tophat: width; else 1 / width
+    __shared__ double s_ln[LOS_MAX_CLOUDS + 1];      // ln norm
+    const int lane = threadIdx.x, nc = c.nclouds;
+    const double *th = c.theta + (size_t)blockIdx.y * (size_t)(4 + 2 * nc);
+    const double pb = th[0], fred = th[3];
+    los_build_table<KERNEL, TEMPL, ADD>(th, c.area, nc, lane, s_xd, s_mean, s_w, s_ln);
+    __syncthreads();
+
+    const int i = blockIdx.x * LOS_TILE + lane;
+    const bool live = i < c.nobj;
+    const size_t col = live ? (size_t)i : (size_t)(c.nobj - 1);   // lanes past the end reread the last object
+    const double t = TEMPL ? c.templ[col] : 1.;
+    const double term = los_star_term<KERNEL, TEMPL, ADD>(c.ds, c.rs, (size_t)c.nobj, col, c.ndraws, nc, t, pb, fred,
+                                                          c.ln_nsamps, c.ln_area_neg, s_xd, s_mean, s_w, s_ln);
+    if (live && c.terms) c.terms[(size_t)blockIdx.y * (size_t)c.nobj + (size_t)i] = term;
+
+    const double v = los_wave_sum(live ? term : 0.);
     if (lane == 0) c.partial[(size_t)blockIdx.y * (size_t)c.ntiles + blockIdx.x] = v;
 }
 
@@ -126,9 +172,80 @@ __global__ __launch_bounds__(64) void k_los_final(const double *__restrict__ par
     const double *p = partial + (size_t)blockIdx.x * (size_t)ntiles;
     double v = 0.;
     for (int q = threadIdx.x; q < ntiles; q += 64) v += p[q];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    v = los_wave_sum(v);
     if (threadIdx.x == 0) loglike[blockIdx.x] = v;
+}
+
+// The field: workgroup (tile, k).  The tile's sightline comes from the tile table, everything
+// about the sightline from its row of the sightline table; tile j of a sightline holds its stars
+// 64 j ... 64 j + 63, the last tile is partial and its dead lanes reread the sightline's last star.
+template <int KERNEL, bool TEMPL, bool ADD>
+__global__ __launch_bounds__(LOS_TILE) void k_los_field_terms(const LosFieldCall c) {
+    __shared__ double s_xd[LOS_MAX_CLOUDS];
+    __shared__ double s_mean[LOS_MAX_CLOUDS + 1];
+    __shared__ double s_w[LOS_MAX_CLOUDS + 1];
+    __shared__ double s_ln[LOS_MAX_CLOUDS + 1];
+    const int lane = threadIdx.x, nc = c.nclouds;
+    const int s = c.tiles[blockIdx.x];
+    const int64_t *row = c.sl + (size_t)s * BRUTUS_LOSFIELD_COLS;
+    const size_t star0 = (size_t)row[BRUTUS_LOSFIELD_STAR0], draw0 = (size_t)row[BRUTUS_LOSFIELD_DRAW0];
+    const int tile = (int)((int64_t)blockIdx.x - row[BRUTUS_LOSFIELD_TILE0]);
+    const int nobj = (int)row[BRUTUS_LOSFIELD_NOBJ], ndraws = (int)row[BRUTUS_LOSFIELD_NDRAWS];
+    const double ln_nsamps = __longlong_as_double(row[BRUTUS_LOSFIELD_LNDRAWS]);
+    const double *th = c.theta + ((size_t)s * (size_t)c.ntheta + blockIdx.y) * (size_t)(4 + 2 * nc);
+    const double pb = th[0], fred = th[3];
+    los_build_table<KERNEL, TEMPL, ADD>(th, c.area, nc, lane, s_xd, s_mean, s_w, s_ln);
+    __syncthreads();
+
+    const int i = tile * LOS_TILE + lane;
+    const bool live = i < nobj;
+    const size_t col = live ? (size_t)i : (size_t)(nobj - 1);
+    const double t = TEMPL ? c.templ[star0 + col] : 1.;
+    const double term = los_star_term<KERNEL, TEMPL, ADD>(c.ds + draw0, c.rs + draw0, (size_t)nobj, col, ndraws, nc, t,
+                                                          pb, fred, ln_nsamps, c.ln_area_neg, s_xd, s_mean, s_w, s_ln);
+    if (live && c.terms)
+        c.terms[((size_t)c.ntheta * star0 + (size_t)blockIdx.y * (size_t)nobj) + (size_t)i] = term;
+
+    const double v = los_wave_sum(live ? term : 0.);
+    if (lane == 0) c.partial[(size_t)blockIdx.y * (size_t)c.ntiles + blockIdx.x] = v;
+}
+
+// loglike[s, k]: workgroup (s, k) adds the partials of the sightline's own tiles as k_los_final
+// does -- lane q its tiles q, q + 64, ..., then the butterfly.  With BRUTUS_LOSFIELD_CHECK_THETA it
+// then decides the rows the host decides for brutus_los_loglike (brutus_amd_los_field.h), and
+// the row's terms with them.
+__global__ __launch_bounds__(64) void k_los_field_final(const LosFieldCall c) {
+    const int lane = threadIdx.x, s = blockIdx.x, k = blockIdx.y, nc = c.nclouds;
+    const int64_t *row = c.sl + (size_t)s * BRUTUS_LOSFIELD_COLS;
+    const int nobj = (int)row[BRUTUS_LOSFIELD_NOBJ];
+    const int ntiles = (nobj + LOS_TILE - 1) / LOS_TILE;
+    const double *p = c.partial + ((size_t)k * (size_t)c.ntiles + (size_t)row[BRUTUS_LOSFIELD_TILE0]);
+    double v = 0.;
+    for (int q = lane; q < ntiles; q += 64) v += p[q];
+    v = los_wave_sum(v);
+    bool fixed = false;
+    if (c.flags & BRUTUS_LOSFIELD_CHECK_THETA) {
+        const double *th = c.theta + ((size_t)s * (size_t)c.ntheta + k) * (size_t)(4 + 2 * nc);
+        // lane j: cloud distance j against the next one, reddening j (0: fred) against the next
+        // one; a NaN fails every comparison (numpy: sort(x) == x is False there)
+        bool bad_d = false, bad_r = false;
+        if (lane < nc) {
+            const double d = th[4 + 2 * lane];
+            bad_d = d != d || (lane + 1 < nc && !(d <= th[6 + 2 * lane]));
+        }
+        if (lane <= nc) {
+            const double r = th[3 + 2 * lane];
+            bad_r = r != r || (lane < nc && !(r <= th[5 + 2 * lane]));
+        }
+        if (!(th[1] > 0. && th[2] > 0.)) { v = nan(""); fixed = true; }
+        if (__any(bad_d)) { v = nan(""); fixed = true; }
+        if ((c.flags & BRUTUS_LOSFIELD_MONOTONIC) && __any(bad_r)) { v = -INFINITY; fixed = true; }
+    }
+    if (lane == 0) c.loglike[(size_t)s * (size_t)c.ntheta + k] = v;
+    if (fixed && c.terms) {
+        double *t = c.terms + ((size_t)c.ntheta * (size_t)row[BRUTUS_LOSFIELD_STAR0] + (size_t)k * (size_t)nobj);
+        for (int i = lane; i < nobj; i += 64) t[i] = v;
+    }
 }
 
 }  // namespace

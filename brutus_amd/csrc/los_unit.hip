@@ -1,9 +1,11 @@
 // los_unit.hip -- translation unit of libbrutus_amd.so: the line-of-sight cloud likelihood
-// (brutus_los_*; reference los.py:119-248, los_kernels.hpp).
+// (brutus_los_*; reference los.py:119-248, los_kernels.hpp), for one sightline per call and for a
+// ragged field of them (brutus_los_field_*; include/brutus_amd_los_field.h).
 
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
+#include <string.h>
 
 #include "../../include/brutus_amd.h"
 
@@ -23,6 +25,16 @@ static void los_launch(bool templ, bool add, dim3 grid, hipStream_t st, const Lo
     else if (templ) hipLaunchKernelGGL((k_los_terms<KERNEL, true, false>), grid, dim3(LOS_TILE), 0, st, c);
     else if (add) hipLaunchKernelGGL((k_los_terms<KERNEL, false, true>), grid, dim3(LOS_TILE), 0, st, c);
     else hipLaunchKernelGGL((k_los_terms<KERNEL, false, false>), grid, dim3(LOS_TILE), 0, st, c);
+}
+template <int KERNEL>
+static void los_field_launch(bool templ, bool add, dim3 grid, hipStream_t st, const LosFieldCall &c) {
+    if (templ && add) hipLaunchKernelGGL((k_los_field_terms<KERNEL, true, true>), grid, dim3(LOS_TILE), 0, st, c);
+    else if (templ) hipLaunchKernelGGL((k_los_field_terms<KERNEL, true, false>), grid, dim3(LOS_TILE), 0, st, c);
+    else if (add) hipLaunchKernelGGL((k_los_field_terms<KERNEL, false, true>), grid, dim3(LOS_TILE), 0, st, c);
+    else hipLaunchKernelGGL((k_los_field_terms<KERNEL, false, false>), grid, dim3(LOS_TILE), 0, st, c);
+}
+static bool los_field_dims_ok(int64_t ntiles, int ntheta) {
+    return ntiles >= 1 && ntiles <= BRUTUS_LOSFIELD_MAX_TILES && ntheta >= 1 && ntheta <= BRUTUS_LOS_MAX_THETA;
 }
 }  // namespace
 
@@ -79,6 +91,116 @@ int brutus_los_loglike(int nobj, int ndraws, const double *d_dsamps, const doubl
     tm.begin("k_los_final");
     hipLaunchKernelGGL(k_los_final, dim3(ntheta), dim3(64), 0, st, (const double *)c.partial, c.ntiles,
                        d_loglike);
+    tm.end();
+    HIP_TRY(hipGetLastError());
+    tm.collect();
+    return 0;
+}
+
+// ---- a ragged field of sightlines (include/brutus_amd_los_field.h) ----------------------------
+
+int brutus_los_field_plan(int nsight, const int32_t *h_nobj, const int32_t *h_ndraws, int64_t *h_sightlines,
+                          int32_t *h_tiles, int64_t ntiles_cap, int64_t *h_totals) {
+    if (nsight < 1 || nsight > BRUTUS_LOSFIELD_MAX_SIGHTLINES)
+        return fail(BRUTUS_EINVAL, "bad los field dimensions (nsight=%d)", nsight);
+    if (!h_nobj || !h_ndraws || !h_totals) return fail(BRUTUS_EINVAL, "NULL pointer");
+    if ((h_sightlines == nullptr) != (h_tiles == nullptr))
+        return fail(BRUTUS_EINVAL, "the sightline table and the tile table go together (both or neither)");
+    int64_t nstars = 0, ndraw_el = 0, ntiles = 0;
+    for (int s = 0; s < nsight; ++s) {
+        if (h_nobj[s] < 1 || h_ndraws[s] < 1 || h_ndraws[s] > BRUTUS_LOS_MAX_DRAWS)
+            return fail(BRUTUS_EINVAL, "bad los field sightline %d (nobj=%d, ndraws=%d)", s, h_nobj[s], h_ndraws[s]);
+        nstars += h_nobj[s];
+        ndraw_el += (int64_t)h_nobj[s] * h_ndraws[s];
+        ntiles += los_tiles(h_nobj[s]);
+        if (nstars > BRUTUS_LOS_MAX_OBJ)
+            return fail(BRUTUS_EINVAL, "bad los field dimensions (more than %d stars by sightline %d)",
+                        BRUTUS_LOS_MAX_OBJ, s);
+    }
+    if (h_sightlines) {
+        if (ntiles_cap < ntiles)
+            return fail(BRUTUS_EINVAL, "los field tile table too small (%lld < %lld)", (long long)ntiles_cap,
+                        (long long)ntiles);
+        int64_t star0 = 0, draw0 = 0, tile0 = 0;
+        for (int s = 0; s < nsight; ++s) {
+            int64_t *row = h_sightlines + (size_t)s * BRUTUS_LOSFIELD_COLS;
+            const double ln_n = log((double)h_ndraws[s]);
+            row[BRUTUS_LOSFIELD_STAR0] = star0;
+            row[BRUTUS_LOSFIELD_DRAW0] = draw0;
+            row[BRUTUS_LOSFIELD_TILE0] = tile0;
+            row[BRUTUS_LOSFIELD_NOBJ] = h_nobj[s];
+            row[BRUTUS_LOSFIELD_NDRAWS] = h_ndraws[s];
+            memcpy(&row[BRUTUS_LOSFIELD_LNDRAWS], &ln_n, sizeof(double));
+            const int nt = los_tiles(h_nobj[s]);
+            for (int j = 0; j < nt; ++j) h_tiles[tile0 + j] = s;
+            star0 += h_nobj[s];
+            draw0 += (int64_t)h_nobj[s] * h_ndraws[s];
+            tile0 += nt;
+        }
+    }
+    h_totals[0] = nstars;
+    h_totals[1] = ndraw_el;
+    h_totals[2] = ntiles;
+    return 0;
+}
+
+size_t brutus_los_field_workspace_bytes(int64_t ntiles, int ntheta) {
+    if (!los_field_dims_ok(ntiles, ntheta)) return 0;
+    return align_up(sizeof(double) * (size_t)ntheta * (size_t)ntiles);
+}
+
+int brutus_los_field_loglike(int nsight, int64_t nstars, int64_t ntiles, const double *d_dsamps,
+                             const double *d_rsamps, const double *d_template, const int64_t *d_sightlines,
+                             const int32_t *d_tiles, int ntheta, int nclouds, const double *d_theta,
+                             const brutus_los_params *params, int flags, double *d_loglike, double *d_terms,
+                             void *d_workspace, size_t workspace_bytes, void *stream) {
+    if (nsight < 1 || nsight > BRUTUS_LOSFIELD_MAX_SIGHTLINES || nstars < nsight || nstars > BRUTUS_LOS_MAX_OBJ ||
+        !los_field_dims_ok(ntiles, ntheta) || ntiles < nsight || ntiles < (nstars + LOS_TILE - 1) / LOS_TILE ||
+        ntiles > nsight + nstars / LOS_TILE || nclouds < 0 || nclouds > BRUTUS_LOS_MAX_CLOUDS)
+        return fail(BRUTUS_EINVAL,
+                    "bad los field dimensions (nsight=%d, nstars=%lld, ntiles=%lld, ntheta=%d, nclouds=%d)", nsight,
+                    (long long)nstars, (long long)ntiles, ntheta, nclouds);
+    if (flags & ~(BRUTUS_LOSFIELD_CHECK_THETA | BRUTUS_LOSFIELD_MONOTONIC))
+        return fail(BRUTUS_EINVAL, "bad los field flags %d", flags);
+    if (!params) return fail(BRUTUS_EINVAL, "NULL los parameters");
+    if (params->kernel < 0 || params->kernel > 2)
+        return fail(BRUTUS_EINVAL, "bad los kernel %d (0 gauss, 1 lorentz, 2 tophat)", params->kernel);
+    const double area = params->rlims[1] - params->rlims[0];
+    if (!(area > 0.) || !(area < INFINITY))
+        return fail(BRUTUS_EINVAL, "bad los rlims (%g, %g)", params->rlims[0], params->rlims[1]);
+    if (!d_dsamps || !d_rsamps || !d_sightlines || !d_tiles || !d_theta || !d_loglike || !d_workspace)
+        return fail(BRUTUS_EINVAL, "NULL pointer");
+    if (workspace_bytes < brutus_los_field_workspace_bytes(ntiles, ntheta))
+        return fail(BRUTUS_ENOMEM, "los field workspace too small");
+
+    LosFieldCall c;
+    c.ds = d_dsamps;
+    c.rs = d_rsamps;
+    c.templ = d_template;
+    c.theta = d_theta;
+    c.sl = d_sightlines;
+    c.tiles = d_tiles;
+    c.partial = (double *)d_workspace;
+    c.loglike = d_loglike;
+    c.terms = d_terms;
+    c.area = area;
+    c.ln_area_neg = -log(area);
+    c.ntheta = ntheta;
+    c.nclouds = nclouds;
+    c.ntiles = (int)ntiles;
+    c.flags = flags;
+
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)ntiles, ntheta);
+    const bool templ = d_template != nullptr, add = params->additive_foreground != 0;
+    Timer tm(st);
+    tm.begin("k_los_field_terms");
+    if (params->kernel == 0) los_field_launch<0>(templ, add, grid, st, c);
+    else if (params->kernel == 1) los_field_launch<1>(templ, add, grid, st, c);
+    else los_field_launch<2>(templ, add, grid, st, c);
+    tm.end();
+    tm.begin("k_los_field_final");
+    hipLaunchKernelGGL(k_los_field_final, dim3(nsight, ntheta), dim3(64), 0, st, c);
     tm.end();
     HIP_TRY(hipGetLastError());
     tm.collect();

@@ -5,7 +5,11 @@ reddening draws of the stars of one sightline (`fit(save_dar_draws=True)`); a ne
 calls `LOS_clouds_loglike_samples` 10^5 - 10^6 times per sightline on data that never changes.
 `LOSSamples` keeps the sub-sampled draws on the GPU and evaluates one `theta` or a batch per
 call (`brutus_los_loglike`); the function of the reference's name is the host form (numpy) and,
-with `device=`, a one-shot wrapper of the class.
+with `device=`, a one-shot wrapper of the class.  `LOSField` and `LOS_clouds_loglike_field` are
+the same pair for MANY sightlines that are fitted with one model and advance together (a dust
+map): all sightlines' draws on the GPU, K profiles per sightline in one call
+(`brutus_los_field_loglike`).  The two are not in `__all__`, which lists the reference's names
+and `LOSSamples`.
 
 Both forms weigh every sample against the ONE cloud bin its distance falls in, instead of the
 reference's `(Nclouds + 1, Nobj, Ndraws)` temporaries; the result is the reference's up to the
@@ -160,16 +164,24 @@ def _check_theta(theta, monotonic, device):
     if device and nclouds > _lib.LOS_MAX_CLOUDS:
         raise ValueError("%d clouds: the device form takes at most %d; use the host path "
                          "(device=None)." % (nclouds, _lib.LOS_MAX_CLOUDS))
-    reds, dists = th[:, 3::2], th[:, 4::2]
-    bad = np.nonzero(~np.all(np.sort(dists, axis=1) == dists, axis=1))[0]
+    bad, preset = _decide_rows(th, monotonic)
     if bad.size:
         raise ValueError("Distances must be monotonically increasing." if single else
                          "Distances must be monotonically increasing. (row %d of theta)" % bad[0])
+    return th, single, preset
+
+
+def _decide_rows(th, monotonic):
+    """Of the rows `(N, Nparams)`: the indices of those whose cloud distances do not ascend, and
+    per row -inf where `monotonic` forbids the reddenings, else NaN where a width is not
+    positive, else 0."""
+    reds, dists = th[:, 3::2], th[:, 4::2]
+    bad = np.nonzero(~np.all(np.sort(dists, axis=1) == dists, axis=1))[0]
     preset = np.zeros(th.shape[0])
     preset[~((th[:, 1] > 0.) & (th[:, 2] > 0.))] = np.nan
     if monotonic:
         preset[~np.all(np.sort(reds, axis=1) == reds, axis=1)] = -np.inf
-    return th, single, preset
+    return bad, preset
 
 
 def _host_row(th, ds, rs, kern, rlims, template_reds, additive_foreground):
@@ -408,3 +420,339 @@ class LOSSamples(object):
         """`(loglike, terms)`: the per-object values after the outlier mixture, `(Nobj,)` or
         `(K, Nobj)`; `loglike` is the value of `S(theta)`."""
         return self._eval(theta, True)
+
+
+# ---- many sightlines at once -------------------------------------------------------------------
+def _check_sightlines(sightlines, template_reds, Ndraws):
+    """[(ds, rs, template or None)] of a sequence of `(dsamps_s, rsamps_s)`, each checked and
+    sub-sampled like a single sightline; `template_reds` is None or one array per sightline."""
+    try:
+        pairs = [(p[0], p[1]) for p in sightlines]
+    except (TypeError, IndexError):
+        raise ValueError("sightlines must be a sequence of (dsamps, rsamps) pairs")
+    if not pairs:
+        raise ValueError("sightlines must hold at least one (dsamps, rsamps) pair")
+    if template_reds is not None and (not hasattr(template_reds, "__len__")
+                                      or len(template_reds) != len(pairs)):
+        raise ValueError("template_reds must be one array (Nobj_s,) per sightline: %d of them"
+                         % len(pairs))
+    out = []
+    for s, (d, r) in enumerate(pairs):
+        try:
+            out.append(_check_samples(d, r, None if template_reds is None else template_reds[s], Ndraws))
+        except ValueError as e:
+            raise ValueError("sightline %d: %s" % (s, e))
+    return out
+
+
+def _check_field_thetas(thetas, nsight, monotonic, device):
+    """`thetas` as `(S, K, Nparams)` float64, whether it was `(S, Nparams)`, and the rows the host
+    decides as `(S, K)` (`_decide_rows`).  ValueError, naming sightline and row, for cloud
+    distances that do not ascend."""
+    try:
+        th = np.asarray(thetas, dtype=np.float64)
+    except (ValueError, TypeError):
+        raise ValueError("thetas must be one array (S, Nparams) or (S, K, Nparams): the same number of "
+                         "rows and of parameters for every sightline")
+    single = th.ndim == 2
+    if single:
+        th = th[:, None, :]
+    if th.ndim != 3 or th.shape[1] < 1 or th.shape[2] < 4 or th.shape[2] % 2:
+        raise ValueError("thetas must have shape (S, Nparams) or (S, K, Nparams) with Nparams = 4 + 2 "
+                         "Nclouds: [pb, s0, s, fred, d1, r1, ...]; got %s" % (np.shape(thetas),))
+    if th.shape[0] != nsight:
+        raise ValueError("thetas has rows for %d sightlines; the field has %d" % (th.shape[0], nsight))
+    nclouds = (th.shape[2] - 4) // 2
+    if device and nclouds > _lib.LOS_MAX_CLOUDS:
+        raise ValueError("%d clouds: the device form takes at most %d; use the host path "
+                         "(device=None)." % (nclouds, _lib.LOS_MAX_CLOUDS))
+    th = np.ascontiguousarray(th)
+    bad, preset = _decide_rows(th.reshape(-1, th.shape[2]), monotonic)
+    if bad.size:
+        raise ValueError("Distances must be monotonically increasing. (sightline %d, row %d of its thetas)"
+                         % divmod(int(bad[0]), th.shape[1]))
+    return th, single, preset.reshape(th.shape[:2])
+
+
+def LOS_clouds_loglike_field(thetas, sightlines, kernel='gauss', rlims=(0., 6.), template_reds=None,
+                             Ndraws=25, additive_foreground=False, monotonic=True, device=None,
+                             return_terms=False):
+    """
+    `LOS_clouds_loglike_samples` for many sightlines that are fitted with the same model: `K`
+    profiles for each of `S` sightlines, every sightline with its own stars and its own profiles.
+
+    Parameters
+    ----------
+    thetas : `~numpy.ndarray` of shape `(S, Nparams)` or `(S, K, Nparams)`
+        The profiles of sightline `s` are `thetas[s]`, laid out as `theta` of
+        `LOS_clouds_loglike_samples`; the same `K` and the same number of clouds for all.
+
+    sightlines : sequence of `(dsamps_s, rsamps_s)`, each of shape `(Nobj_s, Nsamps_s)`
+        The draws of every sightline; the divisor of sightline `s` is `min(Ndraws, Nsamps_s)`.
+
+    template_reds : sequence of `S` arrays `(Nobj_s,)`, optional
+
+    kernel, rlims, Ndraws, additive_foreground, monotonic
+        As in `LOS_clouds_loglike_samples`, common to the field.
+
+    device : None, str or `torch.device`, optional
+        `None` (default): the host path, a loop of `LOS_clouds_loglike_samples` over the
+        sightlines.  Otherwise a one-shot `LOSField` is built on that GPU and called; a sampler
+        builds `LOSField` once.
+
+    return_terms : bool, optional
+        Also return the per-star values: a list of `S` arrays `(Nobj_s,)` or `(K, Nobj_s)`.
+
+    Returns
+    -------
+    loglike : `~numpy.ndarray` of shape `(S,)` or `(S, K)`
+        `ValueError` if the cloud distances of a row do not ascend: sightline and row are named
+        and nothing is evaluated.
+    """
+    kern = _check_kernel(kernel, device is not None)
+    cats = _check_sightlines(sightlines, template_reds, Ndraws)
+    th, single, _ = _check_field_thetas(thetas, len(cats), monotonic, device is not None)
+    if device is not None:
+        F = LOSField([(d, r) for d, r, _ in cats], template_reds=template_reds, Ndraws=Ndraws,
+                     kernel=kernel, rlims=rlims, additive_foreground=additive_foreground,
+                     monotonic=monotonic, device=device)
+        return F.terms(thetas) if return_terms else F(thetas)
+    out = np.empty(th.shape[:2])
+    terms = []
+    for s, (ds, rs, tm) in enumerate(cats):
+        out[s], t = LOS_clouds_loglike_samples(th[s], ds, rs, kernel=kern, rlims=rlims, template_reds=tm,
+                                               Ndraws=Ndraws, additive_foreground=additive_foreground,
+                                               monotonic=monotonic, return_terms=True)
+        terms.append(t[0] if single else t)
+    if single:
+        out = out[:, 0]
+    return (out, terms) if return_terms else out
+
+
+class LOSField(object):
+    """The draws of MANY sightlines on the device, callable with one batch of profiles per
+    sightline: the shape of a dust map, 10^3 - 10^5 sightlines that a sampler advances together.
+
+    `LOSField(sightlines, ...)` takes a sequence of `(dsamps_s, rsamps_s)`, sub-samples each
+    (`[:, :Ndraws]`), transposes it once to draw-major float64 and keeps all of them, end to end,
+    on `device`.  `F(thetas)` with `thetas` of shape `(S, Nparams)` or `(S, K, Nparams)` is
+    `LOS_clouds_loglike_field(thetas, sightlines, ...)`: `(S,)` or `(S, K)` float64, one device
+    call for all sightlines (chunks of 65535 rows per sightline).  The values of sightline `s`
+    are, byte for byte, those of `LOSSamples` built on that sightline alone, wherever it stands
+    in the field and whatever else the field holds.  `F.terms(thetas)` returns
+    `(loglike, terms)` with `terms` a list of `S` arrays `(Nobj_s,)` / `(K, Nobj_s)`.
+
+    `F(thetas, device_out=True)` takes a float64 tensor on the field's device and returns a
+    tensor, without any synchronisation with the host.  The rows the host decides for numpy
+    input are then decided on the device, in this order, a later rule overriding an earlier
+    one: NaN where `s0` or `s` is not `> 0`; NaN where the cloud distances do not ascend --
+    the numpy path raises `ValueError` there, which a call that does not wait for the device
+    cannot; `-inf` where `monotonic` forbids the reddenings.
+
+    `F.nsightlines`, `F.nobj` (stars per sightline) and `F.offsets` (`S + 1`: the first star of
+    every sightline among all stars).  `template_reds` is one array per sightline.  There is no
+    host fallback: without the library or a GPU the constructor raises `BrutusError`.
+    """
+
+    def __init__(self, sightlines, template_reds=None, Ndraws=25, kernel='gauss', rlims=(0., 6.),
+                 additive_foreground=False, monotonic=True, device="cuda"):
+        _check_kernel(kernel, True)
+        cats = _check_sightlines(sightlines, template_reds, Ndraws)
+        rlims = (float(rlims[0]), float(rlims[1]))
+        if not (np.isfinite(rlims[0]) and np.isfinite(rlims[1]) and rlims[1] > rlims[0]):
+            raise ValueError("rlims must be finite and increasing; got %s" % (rlims,))
+        self.nsightlines = len(cats)
+        self.nobj = np.array([c[0].shape[0] for c in cats], dtype=np.int64)
+        self.nsamps = np.array([c[0].shape[1] for c in cats], dtype=np.int64)
+        self.offsets = np.concatenate([[0], np.cumsum(self.nobj)])
+        if (self.nsightlines > _lib.LOSFIELD_MAX_SIGHTLINES or self.offsets[-1] > _lib.LOS_MAX_OBJ
+                or self.nsamps.max() > _lib.LOS_MAX_DRAWS):
+            raise ValueError("the device form takes at most %d sightlines, %d stars in all and %d draws "
+                             "each; got %d sightlines, %d stars, %d draws"
+                             % (_lib.LOSFIELD_MAX_SIGHTLINES, _lib.LOS_MAX_OBJ, _lib.LOS_MAX_DRAWS,
+                                self.nsightlines, self.offsets[-1], self.nsamps.max()))
+        self.kernel, self.rlims, self.monotonic = kernel, rlims, bool(monotonic)
+        self._L = L = _lib.lib()
+        self._torch = torch = _torch("LOSField only runs on the HIP path. The host form is "
+                                     "LOS_clouds_loglike_field(device=None).")
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise ValueError("LOSField needs a GPU device; got %r" % (device,))
+        self._p = _lib.LosParams()
+        self._p.kernel = _KERNEL_CODES[kernel]
+        self._p.additive_foreground = int(bool(additive_foreground))
+        self._p.rlims[0], self._p.rlims[1] = rlims
+        # the tables: the library lays them out (brutus_los_field_plan), first the sizes alone
+        nobj32, nsamps32 = self.nobj.astype(np.int32), self.nsamps.astype(np.int32)
+        totals = np.zeros(3, dtype=np.int64)
+        _lib.check(L.brutus_los_field_plan(self.nsightlines, nobj32, nsamps32, None, None, 0, totals))
+        self.nstars, self.ntiles = int(totals[0]), int(totals[2])
+        table = np.zeros((self.nsightlines, _lib.LOSFIELD_COLS), dtype=np.int64)
+        tiles = np.zeros(self.ntiles, dtype=np.int32)
+        _lib.check(L.brutus_los_field_plan(self.nsightlines, nobj32, nsamps32, table, tiles, tiles.size,
+                                           totals))
+        # (draw-major blocks end to end)
+        ds = np.concatenate([np.asarray(c[0].T, order='C').reshape(-1) for c in cats])
+        rs = np.concatenate([np.asarray(c[1].T, order='C').reshape(-1) for c in cats])
+        assert ds.size == rs.size == totals[1]
+        self._ds = to_device(ds, np.float64, self.device)
+        self._rs = to_device(rs, np.float64, self.device)
+        self.device = self._ds.device               # ("cuda" has become the card it meant)
+        self._templ = (None if template_reds is None else
+                       to_device(np.concatenate([c[2] for c in cats]), np.float64, self.device))
+        self._table = to_device(table, np.int64, self.device)
+        self._tiles = to_device(tiles, np.int32, self.device)
+        # the buffers of a call are the same from call to call (`LOSSamples._buffers`)
+        self._fixed = (_lib.fixed(self._ds, "d", "float64"), _lib.fixed(self._rs, "d", "float64"),
+                       _lib.fixed(self._templ, "d", "float64"), _lib.fixed(self._table, "d", "int64"),
+                       _lib.fixed(self._tiles, "d", "int32"))
+        self._cap, self._ncol = 0, 0
+
+    @property
+    def live_lane_share(self):
+        """Stars per lane of the tiles: 1 when every sightline is a multiple of 64 stars."""
+        return self.nstars / (64. * self.ntiles)
+
+    @staticmethod
+    def group_pixels(coords, nside, min_stars=1):
+        """Group stars by nested HEALPix pixel (host numpy): `coords` is `(N, 2)` Galactic
+        `(l, b)` in degrees.  Returns the ids of the pixels that hold at least `min_stars` stars,
+        ascending, and for each the indices of its stars in their original order.  Stars that
+        `dust.lb2pix` cannot place (-1) belong to no pixel."""
+        from .dust import lb2pix
+        coords = np.asarray(coords, dtype=np.float64)
+        if coords.ndim != 2 or coords.shape[1] != 2:
+            raise ValueError("coords must have shape (N, 2): Galactic (l, b) in degrees; got %s"
+                             % (coords.shape,))
+        pix = np.asarray(lb2pix(nside, coords[:, 0], coords[:, 1]), dtype=np.int64).reshape(-1)
+        order = np.argsort(pix, kind='stable')
+        ids, first, counts = np.unique(pix[order], return_index=True, return_counts=True)
+        keep = (ids >= 0) & (counts >= int(min_stars))
+        return ids[keep], [order[a:a + n] for a, n in zip(first[keep], counts[keep])]
+
+    @classmethod
+    def from_pixels(cls, coords, dsamps, rsamps, nside, min_stars=1, **kw):
+        """The field of a catalogue (`fit(save_dar_draws=True)`: `dsamps`, `rsamps` of shape
+        `(N, Nsamps)`, `coords` `(N, 2)` Galactic degrees), one sightline per nested HEALPix pixel
+        of `nside` with at least `min_stars` stars; the pixels ascend and a pixel's stars keep
+        their order.  `template_reds`, if given, is `(N,)` and is split with the stars.  Returns
+        `(field, pixel ids)`; `(None, empty)` if no pixel qualifies."""
+        dsamps, rsamps = np.asarray(dsamps), np.asarray(rsamps)
+        ids, groups = cls.group_pixels(coords, nside, min_stars)
+        if dsamps.ndim != 2 or dsamps.shape != rsamps.shape or dsamps.shape[0] != np.shape(coords)[0]:
+            raise ValueError("dsamps and rsamps must both have shape (N, Nsamps) with N = %d stars; got "
+                             "%s and %s" % (np.shape(coords)[0], dsamps.shape, rsamps.shape))
+        templ = kw.pop("template_reds", None)
+        if templ is not None:
+            templ = np.asarray(templ, dtype=np.float64)
+            if templ.shape != (dsamps.shape[0],):
+                raise ValueError("template_reds must have shape (N,) = (%d,); got %s"
+                                 % (dsamps.shape[0], templ.shape))
+        if not groups:
+            return None, ids
+        return cls([(dsamps[g], rsamps[g]) for g in groups],
+                   template_reds=None if templ is None else [templ[g] for g in groups], **kw), ids
+
+    def _buffers(self, k, ncol):
+        """Device theta / workspace for `k` rows per sightline of `ncol` parameters; they grow,
+        and are otherwise kept from call to call."""
+        if k > self._cap or ncol != self._ncol:
+            torch = self._torch
+            cap = max(k, self._cap if ncol == self._ncol else 0)
+            self._theta = torch.empty(self.nsightlines * cap * ncol, dtype=torch.float64, device=self.device)
+            self._out = torch.empty(self.nsightlines * cap, dtype=torch.float64, device=self.device)
+            self._ws_bytes = int(self._L.brutus_los_field_workspace_bytes(self.ntiles, cap))
+            self._ws = torch.empty(self._ws_bytes, dtype=torch.uint8, device=self.device)
+            self._bufs = (_lib.fixed(self._theta, "d", "float64"), _lib.fixed(self._out, "d", "float64"),
+                          _lib.fixed(self._ws, "d"))
+            self._cap, self._ncol = cap, ncol
+        return self._theta, self._out
+
+    def _launch(self, theta, k, ncol, flags, out, terms, stream):
+        """One device call: `theta` and `out` are `_lib.fixed` addresses or tensors of `k` rows per
+        sightline."""
+        _lib.check(self._L.brutus_los_field_loglike(
+            self.nsightlines, self.nstars, self.ntiles, *self._fixed, k, (ncol - 4) // 2, theta,
+            C.byref(self._p), flags, out, terms, self._bufs[2], self._ws_bytes, stream))
+
+    def _run(self, th, want_terms):
+        """Values (S, K) and, if wanted, the terms as a list of (K, Nobj_s), of checked rows."""
+        torch = self._torch
+        nsight, ktot, ncol = th.shape
+        out = np.empty((nsight, ktot))
+        terms = [np.empty((ktot, n)) for n in self.nobj] if want_terms else None
+        chunk = _lib.LOS_MAX_THETA
+        if want_terms:
+            chunk = int(max(1, min(chunk, _TERMS_CHUNK_BYTES // (8 * self.nstars))))
+        with torch.cuda.device(self.device):
+            stream = _stream_ptr(torch)
+            for a in range(0, ktot, chunk):
+                k = min(chunk, ktot - a)
+                t_theta, t_out = self._buffers(k, ncol)
+                t_theta[:nsight * k * ncol].view(nsight, k, ncol).copy_(torch.from_numpy(th[:, a:a + k]))
+                t_terms = (torch.empty(k * self.nstars, dtype=torch.float64, device=self.device)
+                           if want_terms else None)
+                self._launch(self._bufs[0], k, ncol, 0, self._bufs[1], t_terms, stream)
+                out[:, a:a + k] = t_out[:nsight * k].cpu().numpy().reshape(nsight, k)
+                if want_terms:
+                    flat = t_terms.cpu().numpy()
+                    for s, n in enumerate(self.nobj):
+                        terms[s][a:a + k] = flat[k * self.offsets[s]:k * self.offsets[s + 1]].reshape(k, n)
+        return out, terms
+
+    def _run_tensor(self, theta):
+        """`(S, K)` tensor of a float64 tensor `(S, K, Nparams)` on the device; every row is
+        decided on the device, nothing waits for it."""
+        torch = self._torch
+        nsight, ktot, ncol = theta.shape
+        out = torch.empty((nsight, ktot), dtype=torch.float64, device=self.device)
+        flags = _lib.LOSFIELD_CHECK_THETA | (_lib.LOSFIELD_MONOTONIC if self.monotonic else 0)
+        with torch.cuda.device(self.device):
+            stream = _stream_ptr(torch)
+            for a in range(0, ktot, _lib.LOS_MAX_THETA):
+                k = min(_lib.LOS_MAX_THETA, ktot - a)
+                self._buffers(k, ncol)                   # (the workspace)
+                whole = k == ktot
+                part = torch.empty((nsight, k), dtype=torch.float64, device=self.device) if not whole else out
+                self._launch(theta[:, a:a + k].contiguous(), k, ncol, flags, part, None, stream)
+                if not whole:
+                    out[:, a:a + k] = part
+        return out
+
+    def _eval(self, thetas, want_terms):
+        th, single, preset = _check_field_thetas(thetas, self.nsightlines, self.monotonic, True)
+        out, terms = self._run(th, want_terms)
+        fixed = preset != 0.
+        if fixed.any():
+            out[fixed] = preset[fixed]
+            if want_terms:
+                for s, k in zip(*np.nonzero(fixed)):
+                    terms[s][k] = preset[s, k]
+        if single:
+            out = out[:, 0]
+            terms = [t[0] for t in terms] if want_terms else None
+        return (out, terms) if want_terms else out
+
+    def __call__(self, thetas, device_out=False):
+        torch = self._torch
+        if not device_out:
+            if isinstance(thetas, torch.Tensor):
+                thetas = thetas.detach().cpu().numpy()
+            return self._eval(thetas, False)
+        if not (isinstance(thetas, torch.Tensor) and thetas.dtype == torch.float64
+                and thetas.device == self.device):
+            raise TypeError("device_out=True takes a float64 tensor on %s" % (self.device,))
+        single = thetas.dim() == 2
+        th = thetas[:, None, :] if single else thetas
+        if th.dim() != 3 or th.shape[0] != self.nsightlines or th.shape[1] < 1 or th.shape[2] < 4 \
+                or th.shape[2] % 2 or (th.shape[2] - 4) // 2 > _lib.LOS_MAX_CLOUDS:
+            raise ValueError("thetas must have shape (S, Nparams) or (S, K, Nparams) with S = %d and "
+                             "Nparams = 4 + 2 Nclouds, at most %d clouds; got %s"
+                             % (self.nsightlines, _lib.LOS_MAX_CLOUDS, tuple(thetas.shape)))
+        out = self._run_tensor(th.contiguous())
+        return out[:, 0] if single else out
+
+    def terms(self, thetas):
+        """`(loglike, terms)`: `terms[s]` holds the per-star values of sightline `s` after the
+        outlier mixture, `(Nobj_s,)` or `(K, Nobj_s)`; `loglike` is the value of `F(thetas)`."""
+        return self._eval(thetas, True)
