@@ -8,16 +8,16 @@
 // own.  The per-theta table (mean, width or 1 / width, ln norm per bin) is built once per
 // workgroup.  The log-sum over an object's samples is max-shifted in two passes over the draws,
 // like scipy's logsumexp; the objects' terms are summed by a butterfly over the wave -- a fixed
-// order -- to one partial per (theta, tile), and k_los_final adds the partials of a theta in a
-// fixed order as well: no floating-point atomics, the same bytes for the same theta whatever
-// else is in the batch.
+// order -- to one partial per (theta, tile), and the partials of a theta are added in a fixed
+// order as well: no floating-point atomics, the same bytes for the same theta whatever else is
+// in the batch.
 //
-// k_los_field_terms / k_los_field_final are the same work over a ragged FIELD of sightlines
-// (include/brutus_amd_los_field.h): a tile never crosses a sightline, a workgroup finds its
-// sightline in a tile table and reads row k of that sightline's thetas.  The table in LDS
-// (los_build_table), the per-star arithmetic (los_star_term) and the wave's sum (los_wave_sum)
-// are ONE copy that both pairs call, so a sightline's values in a field are the bytes
-// k_los_terms / k_los_final give for it alone.
+// All of that is ONE tile body, los_tile, over a LosTile, which says where the sightline's draws
+// and template, the row of theta, its terms and its partial lie.  k_los_terms fills the LosTile
+// from its arguments, k_los_field_terms from the tile and sightline tables of a ragged FIELD of
+// sightlines (include/brutus_amd_los_field.h: a tile never crosses a sightline); neither has
+// arithmetic of its own, and both final kernels add a row's partials with los_partials_sum.  So
+// a sightline's values in a field are the bytes k_los_terms / k_los_final give for it alone.
 #pragma once
 
 namespace {
@@ -25,28 +25,36 @@ namespace {
 constexpr int LOS_TILE = 64;         // objects per workgroup = one wave
 constexpr int LOS_MAX_CLOUDS = 32;
 
-struct LosCall {
-    const double *ds, *rs;       // (ndraws, nobj)
+// What both calls pass: of the one sightline, or (LosFieldCall) the sightlines' blocks end to end
+struct LosCommon {
+    const double *ds, *rs;       // (ndraws, nobj), draw-major
     const double *templ;         // (nobj) or null
-    const double *theta;         // (ntheta, 4 + 2 nclouds)
+    const double *theta;         // (ntheta, 4 + 2 nclouds); field: (nsight, ntheta, 4 + 2 nclouds)
     double *partial;             // (ntheta, ntiles)
-    double *terms;               // (ntheta, nobj) or null
+    double *terms;               // (ntheta, nobj) or null; field: per sightline (ntheta, nobj_s)
     double area, ln_area_neg;    // rlims[1] - rlims[0], -ln(area)
-    double ln_nsamps;            // ln(ndraws)
-    int nobj, ndraws, nclouds, ntiles;
+    int nclouds, ntiles;
 };
 
-struct LosFieldCall {
-    const double *ds, *rs;       // the sightlines' draw-major blocks, end to end
-    const double *templ;         // (nstars) or null
-    const double *theta;         // (nsight, ntheta, 4 + 2 nclouds)
+struct LosCall : LosCommon {
+    double ln_nsamps;            // ln(ndraws)
+    int nobj, ndraws;
+};
+
+struct LosFieldCall : LosCommon {
     const int64_t *sl;           // (nsight, BRUTUS_LOSFIELD_COLS): the plan's sightline table
     const int32_t *tiles;        // (ntiles): the sightline of every tile
-    double *partial;             // (ntheta, ntiles)
     double *loglike;             // (nsight, ntheta)
-    double *terms;               // per sightline (ntheta, nobj_s), or null
-    double area, ln_area_neg;
-    int ntheta, nclouds, ntiles, flags;
+    int ntheta, flags;
+};
+
+// The work of one workgroup, everything relative to its sightline and its row of theta
+struct LosTile {
+    const double *ds, *rs;       // the sightline's draws (ndraws, nobj)
+    const double *templ, *th;    // its template (nobj) or null; the row of theta
+    double *terms, *partial;     // the row's terms (nobj) or null; the slot of (row, tile)
+    double ln_nsamps;            // ln(ndraws)
+    int nobj, ndraws, tile;      // tile within the sightline: its objects 64 tile ... 64 tile + 63
 };
 
 // ln of the kernel's norm (los.py:274, 307, 337) for the width w
@@ -141,88 +149,80 @@ __device__ __forceinline__ double los_wave_sum(double v) {
     return v;
 }
 
+// The tile body: the row's table in LDS, one lane per object of the tile (the dead lanes of a
+// sightline's last tile reread its last object), the term store, the wave's sum, the partial
 template <int KERNEL, bool TEMPL, bool ADD>
-__global__ __launch_bounds__(LOS_TILE) void k_los_terms(const LosCall c) {
+__device__ __forceinline__ void los_tile(const LosTile &d, const LosCommon &c) {
     __shared__ double s_xd[LOS_MAX_CLOUDS];          // cloud distances
     __shared__ double s_mean[LOS_MAX_CLOUDS + 1];    // TEMPL: the rescaling of the bin (bin 0: fred)
     __shared__ double s_w[LOS_MAX_CLOUDS + 1];       // tophat: width; else 1 / width
     __shared__ double s_ln[LOS_MAX_CLOUDS + 1];      // ln norm
     const int lane = threadIdx.x, nc = c.nclouds;
-    const double *th = c.theta + (size_t)blockIdx.y * (size_t)(4 + 2 * nc);
-    const double pb = th[0], fred = th[3];
-    los_build_table<KERNEL, TEMPL, ADD>(th, c.area, nc, lane, s_xd, s_mean, s_w, s_ln);
+    const double pb = d.th[0], fred = d.th[3];
+    los_build_table<KERNEL, TEMPL, ADD>(d.th, c.area, nc, lane, s_xd, s_mean, s_w, s_ln);
     __syncthreads();
-
-    const int i = blockIdx.x * LOS_TILE + lane;
-    const bool live = i < c.nobj;
-    const size_t col = live ? (size_t)i : (size_t)(c.nobj - 1);   // lanes past the end reread the last object
-    const double t = TEMPL ? c.templ[col] : 1.;
-    const double term = los_star_term<KERNEL, TEMPL, ADD>(c.ds, c.rs, (size_t)c.nobj, col, c.ndraws, nc, t, pb, fred,
-                                                          c.ln_nsamps, c.ln_area_neg, s_xd, s_mean, s_w, s_ln);
-    if (live && c.terms) c.terms[(size_t)blockIdx.y * (size_t)c.nobj + (size_t)i] = term;
-
+    const int i = d.tile * LOS_TILE + lane;
+    const bool live = i < d.nobj;
+    const size_t col = live ? (size_t)i : (size_t)(d.nobj - 1);
+    const double t = TEMPL ? d.templ[col] : 1.;
+    const double term = los_star_term<KERNEL, TEMPL, ADD>(d.ds, d.rs, (size_t)d.nobj, col, d.ndraws, nc, t, pb, fred,
+                                                          d.ln_nsamps, c.ln_area_neg, s_xd, s_mean, s_w, s_ln);
+    if (live && d.terms) d.terms[i] = term;
     const double v = los_wave_sum(live ? term : 0.);
-    if (lane == 0) c.partial[(size_t)blockIdx.y * (size_t)c.ntiles + blockIdx.x] = v;
+    if (lane == 0) *d.partial = v;
 }
 
-// loglike[theta] = sum of its partials: lane q adds tiles q, q + 64, ... in that order, then the
-// same butterfly
+// the sum of a row's partials p[0 .. ntiles): lane q adds tiles q, q + 64, ... in that order, then
+// the same butterfly
+__device__ __forceinline__ double los_partials_sum(const double *p, int ntiles, int lane) {
+    double v = 0.;
+    for (int q = lane; q < ntiles; q += 64) v += p[q];
+    return los_wave_sum(v);
+}
+
+// One sightline: workgroup (tile, k)
+template <int KERNEL, bool TEMPL, bool ADD>
+__global__ __launch_bounds__(LOS_TILE) void k_los_terms(const LosCall c) {
+    const size_t k = blockIdx.y;
+    const LosTile d{c.ds, c.rs, c.templ, c.theta + k * (size_t)(4 + 2 * c.nclouds),
+                    c.terms ? c.terms + k * (size_t)c.nobj : nullptr,
+                    c.partial + (k * (size_t)c.ntiles + blockIdx.x), c.ln_nsamps, c.nobj, c.ndraws, (int)blockIdx.x};
+    los_tile<KERNEL, TEMPL, ADD>(d, c);
+}
+
+// loglike[theta] = the sum of its partials
 __global__ __launch_bounds__(64) void k_los_final(const double *__restrict__ partial, int ntiles,
                                                   double *__restrict__ loglike) {
-    const double *p = partial + (size_t)blockIdx.x * (size_t)ntiles;
-    double v = 0.;
-    for (int q = threadIdx.x; q < ntiles; q += 64) v += p[q];
-    v = los_wave_sum(v);
+    const double v = los_partials_sum(partial + (size_t)blockIdx.x * (size_t)ntiles, ntiles, threadIdx.x);
     if (threadIdx.x == 0) loglike[blockIdx.x] = v;
 }
 
 // The field: workgroup (tile, k).  The tile's sightline comes from the tile table, everything
-// about the sightline from its row of the sightline table; tile j of a sightline holds its stars
-// 64 j ... 64 j + 63, the last tile is partial and its dead lanes reread the sightline's last star.
+// about the sightline from its row of the sightline table.
 template <int KERNEL, bool TEMPL, bool ADD>
 __global__ __launch_bounds__(LOS_TILE) void k_los_field_terms(const LosFieldCall c) {
-    __shared__ double s_xd[LOS_MAX_CLOUDS];
-    __shared__ double s_mean[LOS_MAX_CLOUDS + 1];
-    __shared__ double s_w[LOS_MAX_CLOUDS + 1];
-    __shared__ double s_ln[LOS_MAX_CLOUDS + 1];
-    const int lane = threadIdx.x, nc = c.nclouds;
+    const size_t k = blockIdx.y;
     const int s = c.tiles[blockIdx.x];
     const int64_t *row = c.sl + (size_t)s * BRUTUS_LOSFIELD_COLS;
     const size_t star0 = (size_t)row[BRUTUS_LOSFIELD_STAR0], draw0 = (size_t)row[BRUTUS_LOSFIELD_DRAW0];
-    const int tile = (int)((int64_t)blockIdx.x - row[BRUTUS_LOSFIELD_TILE0]);
-    const int nobj = (int)row[BRUTUS_LOSFIELD_NOBJ], ndraws = (int)row[BRUTUS_LOSFIELD_NDRAWS];
-    const double ln_nsamps = __longlong_as_double(row[BRUTUS_LOSFIELD_LNDRAWS]);
-    const double *th = c.theta + ((size_t)s * (size_t)c.ntheta + blockIdx.y) * (size_t)(4 + 2 * nc);
-    const double pb = th[0], fred = th[3];
-    los_build_table<KERNEL, TEMPL, ADD>(th, c.area, nc, lane, s_xd, s_mean, s_w, s_ln);
-    __syncthreads();
-
-    const int i = tile * LOS_TILE + lane;
-    const bool live = i < nobj;
-    const size_t col = live ? (size_t)i : (size_t)(nobj - 1);
-    const double t = TEMPL ? c.templ[star0 + col] : 1.;
-    const double term = los_star_term<KERNEL, TEMPL, ADD>(c.ds + draw0, c.rs + draw0, (size_t)nobj, col, ndraws, nc, t,
-                                                          pb, fred, ln_nsamps, c.ln_area_neg, s_xd, s_mean, s_w, s_ln);
-    if (live && c.terms)
-        c.terms[((size_t)c.ntheta * star0 + (size_t)blockIdx.y * (size_t)nobj) + (size_t)i] = term;
-
-    const double v = los_wave_sum(live ? term : 0.);
-    if (lane == 0) c.partial[(size_t)blockIdx.y * (size_t)c.ntiles + blockIdx.x] = v;
+    const int nobj = (int)row[BRUTUS_LOSFIELD_NOBJ];
+    const LosTile d{c.ds + draw0, c.rs + draw0, TEMPL ? c.templ + star0 : nullptr,
+                    c.theta + ((size_t)s * (size_t)c.ntheta + k) * (size_t)(4 + 2 * c.nclouds),
+                    c.terms ? c.terms + ((size_t)c.ntheta * star0 + k * (size_t)nobj) : nullptr,
+                    c.partial + (k * (size_t)c.ntiles + blockIdx.x), __longlong_as_double(row[BRUTUS_LOSFIELD_LNDRAWS]),
+                    nobj, (int)row[BRUTUS_LOSFIELD_NDRAWS], (int)((int64_t)blockIdx.x - row[BRUTUS_LOSFIELD_TILE0])};
+    los_tile<KERNEL, TEMPL, ADD>(d, c);
 }
 
-// loglike[s, k]: workgroup (s, k) adds the partials of the sightline's own tiles as k_los_final
-// does -- lane q its tiles q, q + 64, ..., then the butterfly.  With BRUTUS_LOSFIELD_CHECK_THETA it
-// then decides the rows the host decides for brutus_los_loglike (brutus_amd_los_field.h), and
-// the row's terms with them.
+// loglike[s, k]: workgroup (s, k) adds the partials of the sightline's own tiles, as k_los_final
+// does.  With BRUTUS_LOSFIELD_CHECK_THETA it then decides the rows the host decides for
+// brutus_los_loglike (brutus_amd_los_field.h), and the row's terms with them.
 __global__ __launch_bounds__(64) void k_los_field_final(const LosFieldCall c) {
     const int lane = threadIdx.x, s = blockIdx.x, k = blockIdx.y, nc = c.nclouds;
     const int64_t *row = c.sl + (size_t)s * BRUTUS_LOSFIELD_COLS;
     const int nobj = (int)row[BRUTUS_LOSFIELD_NOBJ];
-    const int ntiles = (nobj + LOS_TILE - 1) / LOS_TILE;
-    const double *p = c.partial + ((size_t)k * (size_t)c.ntiles + (size_t)row[BRUTUS_LOSFIELD_TILE0]);
-    double v = 0.;
-    for (int q = lane; q < ntiles; q += 64) v += p[q];
-    v = los_wave_sum(v);
+    double v = los_partials_sum(c.partial + ((size_t)k * (size_t)c.ntiles + (size_t)row[BRUTUS_LOSFIELD_TILE0]),
+                                (nobj + LOS_TILE - 1) / LOS_TILE, lane);
     bool fixed = false;
     if (c.flags & BRUTUS_LOSFIELD_CHECK_THETA) {
         const double *th = c.theta + ((size_t)s * (size_t)c.ntheta + k) * (size_t)(4 + 2 * nc);

@@ -17,24 +17,42 @@ namespace {
 static bool los_dims_ok(int nobj, int ntheta) {
     return nobj >= 1 && nobj <= BRUTUS_LOS_MAX_OBJ && ntheta >= 1 && ntheta <= BRUTUS_LOS_MAX_THETA;
 }
-static int los_tiles(int nobj) { return (nobj + LOS_TILE - 1) / LOS_TILE; }
-
-template <int KERNEL>
-static void los_launch(bool templ, bool add, dim3 grid, hipStream_t st, const LosCall &c) {
-    if (templ && add) hipLaunchKernelGGL((k_los_terms<KERNEL, true, true>), grid, dim3(LOS_TILE), 0, st, c);
-    else if (templ) hipLaunchKernelGGL((k_los_terms<KERNEL, true, false>), grid, dim3(LOS_TILE), 0, st, c);
-    else if (add) hipLaunchKernelGGL((k_los_terms<KERNEL, false, true>), grid, dim3(LOS_TILE), 0, st, c);
-    else hipLaunchKernelGGL((k_los_terms<KERNEL, false, false>), grid, dim3(LOS_TILE), 0, st, c);
-}
-template <int KERNEL>
-static void los_field_launch(bool templ, bool add, dim3 grid, hipStream_t st, const LosFieldCall &c) {
-    if (templ && add) hipLaunchKernelGGL((k_los_field_terms<KERNEL, true, true>), grid, dim3(LOS_TILE), 0, st, c);
-    else if (templ) hipLaunchKernelGGL((k_los_field_terms<KERNEL, true, false>), grid, dim3(LOS_TILE), 0, st, c);
-    else if (add) hipLaunchKernelGGL((k_los_field_terms<KERNEL, false, true>), grid, dim3(LOS_TILE), 0, st, c);
-    else hipLaunchKernelGGL((k_los_field_terms<KERNEL, false, false>), grid, dim3(LOS_TILE), 0, st, c);
-}
 static bool los_field_dims_ok(int64_t ntiles, int ntheta) {
     return ntiles >= 1 && ntiles <= BRUTUS_LOSFIELD_MAX_TILES && ntheta >= 1 && ntheta <= BRUTUS_LOS_MAX_THETA;
+}
+static int los_tiles(int nobj) { return (nobj + LOS_TILE - 1) / LOS_TILE; }
+
+// the checks of `params` of both calls; *area = rlims[1] - rlims[0]
+static int los_check_params(const brutus_los_params *params, double *area) {
+    if (!params) return fail(BRUTUS_EINVAL, "NULL los parameters");
+    if (params->kernel < 0 || params->kernel > 2)
+        return fail(BRUTUS_EINVAL, "bad los kernel %d (0 gauss, 1 lorentz, 2 tophat)", params->kernel);
+    *area = params->rlims[1] - params->rlims[0];
+    if (!(*area > 0.) || !(*area < INFINITY))
+        return fail(BRUTUS_EINVAL, "bad los rlims (%g, %g)", params->rlims[0], params->rlims[1]);
+    return 0;
+}
+
+// the fields the two calls share
+static LosCommon los_common(const double *ds, const double *rs, const double *templ, const double *theta,
+                            void *workspace, double *terms, double area, int nclouds, int ntiles) {
+    return LosCommon{ds, rs, templ, theta, (double *)workspace, terms, area, -log(area), nclouds, ntiles};
+}
+
+// f(integral_constant<int, KERNEL>, bool_constant<TEMPL>, bool_constant<ADD>) for the options of
+// the call: the way to the 12 instantiations of a terms kernel
+template <class F>
+static void los_dispatch(const brutus_los_params *params, bool templ, F f) {
+    auto flags = [&](auto kernel) {
+        const bool add = params->additive_foreground != 0;
+        if (templ && add) f(kernel, std::true_type{}, std::true_type{});
+        else if (templ) f(kernel, std::true_type{}, std::false_type{});
+        else if (add) f(kernel, std::false_type{}, std::true_type{});
+        else f(kernel, std::false_type{}, std::false_type{});
+    };
+    if (params->kernel == 0) flags(std::integral_constant<int, 0>{});
+    else if (params->kernel == 1) flags(std::integral_constant<int, 1>{});
+    else flags(std::integral_constant<int, 2>{});
 }
 }  // namespace
 
@@ -53,40 +71,24 @@ int brutus_los_loglike(int nobj, int ndraws, const double *d_dsamps, const doubl
         nclouds > BRUTUS_LOS_MAX_CLOUDS)
         return fail(BRUTUS_EINVAL, "bad los dimensions (nobj=%d, ndraws=%d, ntheta=%d, nclouds=%d)", nobj,
                     ndraws, ntheta, nclouds);
-    if (!params) return fail(BRUTUS_EINVAL, "NULL los parameters");
-    if (params->kernel < 0 || params->kernel > 2)
-        return fail(BRUTUS_EINVAL, "bad los kernel %d (0 gauss, 1 lorentz, 2 tophat)", params->kernel);
-    const double area = params->rlims[1] - params->rlims[0];
-    if (!(area > 0.) || !(area < INFINITY))
-        return fail(BRUTUS_EINVAL, "bad los rlims (%g, %g)", params->rlims[0], params->rlims[1]);
+    double area;
+    if (int rc = los_check_params(params, &area)) return rc;
     if (!d_dsamps || !d_rsamps || !d_theta || !d_loglike || !d_workspace)
         return fail(BRUTUS_EINVAL, "NULL pointer");
     if (workspace_bytes < brutus_los_workspace_bytes(nobj, ntheta))
         return fail(BRUTUS_ENOMEM, "los workspace too small");
 
-    LosCall c;
-    c.ds = d_dsamps;
-    c.rs = d_rsamps;
-    c.templ = d_template;
-    c.theta = d_theta;
-    c.partial = (double *)d_workspace;
-    c.terms = d_terms;
-    c.area = area;
-    c.ln_area_neg = -log(area);
-    c.ln_nsamps = log((double)ndraws);
-    c.nobj = nobj;
-    c.ndraws = ndraws;
-    c.nclouds = nclouds;
-    c.ntiles = los_tiles(nobj);
-
+    const LosCall c{los_common(d_dsamps, d_rsamps, d_template, d_theta, d_workspace, d_terms, area, nclouds,
+                               los_tiles(nobj)),
+                    log((double)ndraws), nobj, ndraws};
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid(c.ntiles, ntheta);
-    const bool templ = d_template != nullptr, add = params->additive_foreground != 0;
     Timer tm(st);
     tm.begin("k_los_terms");
-    if (params->kernel == 0) los_launch<0>(templ, add, grid, st, c);
-    else if (params->kernel == 1) los_launch<1>(templ, add, grid, st, c);
-    else los_launch<2>(templ, add, grid, st, c);
+    los_dispatch(params, d_template != nullptr, [&](auto k, auto t, auto a) {
+        hipLaunchKernelGGL((k_los_terms<decltype(k)::value, decltype(t)::value, decltype(a)::value>), grid,
+                           dim3(LOS_TILE), 0, st, c);
+    });
     tm.end();
     tm.begin("k_los_final");
     hipLaunchKernelGGL(k_los_final, dim3(ntheta), dim3(64), 0, st, (const double *)c.partial, c.ntiles,
@@ -162,42 +164,24 @@ int brutus_los_field_loglike(int nsight, int64_t nstars, int64_t ntiles, const d
                     (long long)nstars, (long long)ntiles, ntheta, nclouds);
     if (flags & ~(BRUTUS_LOSFIELD_CHECK_THETA | BRUTUS_LOSFIELD_MONOTONIC))
         return fail(BRUTUS_EINVAL, "bad los field flags %d", flags);
-    if (!params) return fail(BRUTUS_EINVAL, "NULL los parameters");
-    if (params->kernel < 0 || params->kernel > 2)
-        return fail(BRUTUS_EINVAL, "bad los kernel %d (0 gauss, 1 lorentz, 2 tophat)", params->kernel);
-    const double area = params->rlims[1] - params->rlims[0];
-    if (!(area > 0.) || !(area < INFINITY))
-        return fail(BRUTUS_EINVAL, "bad los rlims (%g, %g)", params->rlims[0], params->rlims[1]);
+    double area;
+    if (int rc = los_check_params(params, &area)) return rc;
     if (!d_dsamps || !d_rsamps || !d_sightlines || !d_tiles || !d_theta || !d_loglike || !d_workspace)
         return fail(BRUTUS_EINVAL, "NULL pointer");
     if (workspace_bytes < brutus_los_field_workspace_bytes(ntiles, ntheta))
         return fail(BRUTUS_ENOMEM, "los field workspace too small");
 
-    LosFieldCall c;
-    c.ds = d_dsamps;
-    c.rs = d_rsamps;
-    c.templ = d_template;
-    c.theta = d_theta;
-    c.sl = d_sightlines;
-    c.tiles = d_tiles;
-    c.partial = (double *)d_workspace;
-    c.loglike = d_loglike;
-    c.terms = d_terms;
-    c.area = area;
-    c.ln_area_neg = -log(area);
-    c.ntheta = ntheta;
-    c.nclouds = nclouds;
-    c.ntiles = (int)ntiles;
-    c.flags = flags;
-
+    const LosFieldCall c{los_common(d_dsamps, d_rsamps, d_template, d_theta, d_workspace, d_terms, area, nclouds,
+                                    (int)ntiles),
+                         d_sightlines, d_tiles, d_loglike, ntheta, flags};
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)ntiles, ntheta);
-    const bool templ = d_template != nullptr, add = params->additive_foreground != 0;
     Timer tm(st);
     tm.begin("k_los_field_terms");
-    if (params->kernel == 0) los_field_launch<0>(templ, add, grid, st, c);
-    else if (params->kernel == 1) los_field_launch<1>(templ, add, grid, st, c);
-    else los_field_launch<2>(templ, add, grid, st, c);
+    los_dispatch(params, d_template != nullptr, [&](auto k, auto t, auto a) {
+        hipLaunchKernelGGL((k_los_field_terms<decltype(k)::value, decltype(t)::value, decltype(a)::value>), grid,
+                           dim3(LOS_TILE), 0, st, c);
+    });
     tm.end();
     tm.begin("k_los_field_final");
     hipLaunchKernelGGL(k_los_field_final, dim3(nsight, ntheta), dim3(64), 0, st, c);

@@ -301,7 +301,99 @@ def LOS_clouds_loglike_samples(theta, dsamps, rsamps, kernel='gauss',
     return (out, terms) if return_terms else out
 
 
-class LOSSamples(object):
+def _check_rlims(rlims):
+    rlims = (float(rlims[0]), float(rlims[1]))
+    if not (np.isfinite(rlims[0]) and np.isfinite(rlims[1]) and rlims[1] > rlims[0]):
+        raise ValueError("rlims must be finite and increasing; got %s" % (rlims,))
+    return rlims
+
+
+class _LOSDevice(object):
+    """The driver under `LOSSamples` and `LOSField`: `_nsight` sightlines of `_nterms` stars in
+    all, sightline s holding the stars `_offsets[s]` to `_offsets[s + 1]`; thetas `(S, K, ncol)`,
+    values `(S, K)`, terms per sightline `(K, nobj_s)` -- in memory the single sightline's
+    `(K, ncol)`, `(K,)` and `(K, nobj)` at S = 1.  A subclass lays out its draws, names itself
+    (`_name`, `_host_form`) and has `_ws_size(cap)`, the workspace bytes of `cap` rows per
+    sightline, and `_launch(theta, k, ncol, out, terms, stream)`, the device call."""
+
+    def _open(self, kernel, rlims, additive_foreground, monotonic, device):
+        """The options, the library and the device, once the data is checked."""
+        self.kernel, self.rlims, self.monotonic = kernel, rlims, bool(monotonic)
+        self._L = _lib.lib()
+        self._torch = torch = _torch("%s only runs on the HIP path. The host form is %s(device=None)."
+                                     % (self._name, self._host_form))
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise ValueError("%s needs a GPU device; got %r" % (self._name, device))
+        self._p = _lib.LosParams()
+        self._p.kernel = _KERNEL_CODES[kernel]
+        self._p.additive_foreground = int(bool(additive_foreground))
+        self._p.rlims[0], self._p.rlims[1] = rlims
+        self._cap, self._ncol, self._k = 0, 0, 0
+
+    def _buffers(self, k, ncol):
+        """Device theta `(S, k, ncol)` and values `(S * k,)`: views of buffers that grow and are
+        otherwise kept from call to call, with the workspace."""
+        if k > self._cap or ncol != self._ncol:
+            torch = self._torch
+            cap = max(k, self._cap if ncol == self._ncol else 0)
+            self._theta = torch.empty(self._nsight * cap * ncol, dtype=torch.float64, device=self.device)
+            self._out = torch.empty(self._nsight * cap, dtype=torch.float64, device=self.device)
+            self._ws_bytes = self._ws_size(cap)
+            self._ws = torch.empty(self._ws_bytes, dtype=torch.uint8, device=self.device)
+            # the buffers of a call are the same from call to call: checked here, passed as
+            # `_lib.fixed` addresses (a single-theta call takes 70 us).  Each holds its tensor;
+            # whoever replaces one of the tensors replaces its address with it
+            self._bufs = (_lib.fixed(self._theta, "d", "float64"), _lib.fixed(self._out, "d", "float64"),
+                          _lib.fixed(self._ws, "d"))
+            self._cap, self._ncol, self._k = cap, ncol, 0
+        if k != self._k:
+            n = self._nsight * k
+            self._views = self._theta[:n * ncol].view(self._nsight, k, ncol), self._out[:n]
+            self._k = k
+        return self._views
+
+    def _run(self, th, want_terms):
+        """Values (S, K) and, if wanted, the terms as a list of (K, Nobj_s), of checked rows
+        (S, K, ncol), chunk by chunk."""
+        torch = self._torch
+        nsight, ktot, ncol = th.shape
+        out = np.empty((nsight, ktot))
+        terms = [np.empty((ktot, n)) for n in np.diff(self._offsets)] if want_terms else None
+        chunk = _lib.LOS_MAX_THETA
+        if want_terms:
+            chunk = int(max(1, min(chunk, _TERMS_CHUNK_BYTES // (8 * self._nterms))))
+        with torch.cuda.device(self.device):
+            stream = _stream_ptr(torch)
+            for a in range(0, ktot, chunk):
+                k = min(chunk, ktot - a)
+                t_theta, t_out = self._buffers(k, ncol)
+                t_theta.copy_(torch.from_numpy(th[:, a:a + k]))
+                t_terms = (torch.empty(k * self._nterms, dtype=torch.float64, device=self.device)
+                           if want_terms else None)
+                self._launch(self._bufs[0], k, ncol, self._bufs[1], t_terms, stream)
+                out[:, a:a + k] = t_out.cpu().numpy().reshape(nsight, k)
+                if want_terms:
+                    flat = t_terms.cpu().numpy()
+                    for t, b, e in zip(terms, self._offsets[:-1], self._offsets[1:]):
+                        t[a:a + k] = flat[k * b:k * e].reshape(k, e - b)
+        return out, terms
+
+    def _eval_rows(self, th, preset, want_terms):
+        # Rows the host decides (-inf under `monotonic`, NaN for a width that is not positive) are
+        # sent to the device with the rest and overwritten afterwards: rows do not influence one
+        # another, and a batch that is not compacted keeps one shape per call.
+        out, terms = self._run(th, want_terms)
+        fixed = preset != 0.
+        if fixed.any():
+            out[fixed] = preset[fixed]
+            if want_terms:
+                for s in np.nonzero(fixed.any(axis=1))[0]:
+                    terms[s][fixed[s]] = preset[s][fixed[s]][:, None]
+        return out, terms
+
+
+class LOSSamples(_LOSDevice):
     """The draws of one sightline on the device, callable with `theta`.
 
     `LOSSamples(dsamps, rsamps, ...)` sub-samples the draws (`[:, :Ndraws]`), transposes them
@@ -321,94 +413,39 @@ class LOSSamples(object):
     `BrutusError`.
     """
 
+    _name, _host_form, _nsight = "LOSSamples", "LOS_clouds_loglike_samples", 1
+
     def __init__(self, dsamps, rsamps, template_reds=None, Ndraws=25, kernel='gauss',
                  rlims=(0., 6.), additive_foreground=False, monotonic=True, device="cuda"):
         _check_kernel(kernel, True)
         ds, rs, template_reds = _check_samples(dsamps, rsamps, template_reds, Ndraws)
-        rlims = (float(rlims[0]), float(rlims[1]))
-        if not (np.isfinite(rlims[0]) and np.isfinite(rlims[1]) and rlims[1] > rlims[0]):
-            raise ValueError("rlims must be finite and increasing; got %s" % (rlims,))
+        rlims = _check_rlims(rlims)
         self.nobj, self.nsamps = ds.shape
         if self.nobj > _lib.LOS_MAX_OBJ or self.nsamps > _lib.LOS_MAX_DRAWS:
             raise ValueError("the device form takes at most %d objects and %d draws each; got %s"
                              % (_lib.LOS_MAX_OBJ, _lib.LOS_MAX_DRAWS, ds.shape))
-        self.kernel, self.rlims, self.monotonic = kernel, rlims, bool(monotonic)
-        self._L = _lib.lib()
-        self._torch = torch = _torch("LOSSamples only runs on the HIP path. The host form is "
-                                     "LOS_clouds_loglike_samples(device=None).")
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise ValueError("LOSSamples needs a GPU device; got %r" % (device,))
-        self._p = _lib.LosParams()
-        self._p.kernel = _KERNEL_CODES[kernel]
-        self._p.additive_foreground = int(bool(additive_foreground))
-        self._p.rlims[0], self._p.rlims[1] = rlims
+        self._nterms, self._offsets = self.nobj, np.array([0, self.nobj])
+        self._open(kernel, rlims, additive_foreground, monotonic, device)
         # (draw-major copies: the caller's arrays may be read-only)
         self._ds = to_device(np.array(ds.T, order='C'), np.float64, self.device)
         self._rs = to_device(np.array(rs.T, order='C'), np.float64, self.device)
         self._templ = (None if template_reds is None else
                        to_device(np.array(template_reds), np.float64, self.device))
-        # the six buffers of a call are the same from call to call: checked here and in
-        # `_buffers`, passed as `_lib.fixed` addresses (a single-theta call takes 70 us).  Each
-        # holds its tensor; whoever replaces one of the tensors replaces its address with it
-        self._draws = tuple(_lib.fixed(t, "d", "float64")
+        self._draws = tuple(_lib.fixed(t, "d", "float64")          # (as `_bufs`: built once)
                             for t in (self._ds, self._rs, self._templ))
-        self._cap, self._ncol = 0, 0
 
-    def _buffers(self, k, ncol):
-        """Device theta / result / workspace for `k` rows of `ncol` parameters; they grow, and are
-        otherwise kept from call to call."""
-        if k > self._cap or ncol != self._ncol:
-            torch = self._torch
-            cap = max(k, self._cap if ncol == self._ncol else 0)
-            self._theta = torch.empty((cap, ncol), dtype=torch.float64, device=self.device)
-            self._out = torch.empty(cap, dtype=torch.float64, device=self.device)
-            self._ws_bytes = int(self._L.brutus_los_workspace_bytes(self.nobj, cap))
-            self._ws = torch.empty(self._ws_bytes, dtype=torch.uint8, device=self.device)
-            # (with the tensors above, always: the call passes these, not the tensors)
-            self._bufs = (_lib.fixed(self._theta, "d", "float64"),
-                          _lib.fixed(self._out, "d", "float64"), _lib.fixed(self._ws, "d"))
-            self._cap, self._ncol = cap, ncol
-        return self._theta, self._out
+    def _ws_size(self, cap):
+        return int(self._L.brutus_los_workspace_bytes(self.nobj, cap))
 
-    def _run(self, th, want_terms):
-        """Values (K,) and, if wanted, terms (K, Nobj) of checked rows, chunk by chunk."""
-        torch = self._torch
-        ktot, ncol = th.shape
-        out = np.empty(ktot)
-        terms = np.empty((ktot, self.nobj)) if want_terms else None
-        chunk = _lib.LOS_MAX_THETA
-        if want_terms:
-            chunk = int(max(1, min(chunk, _TERMS_CHUNK_BYTES // (8 * self.nobj))))
-        with torch.cuda.device(self.device):
-            stream = _stream_ptr(torch)
-            for a in range(0, ktot, chunk):
-                k = min(chunk, ktot - a)
-                t_theta, t_out = self._buffers(k, ncol)
-                t_theta[:k].copy_(torch.from_numpy(th[a:a + k]))
-                t_terms = (torch.empty((k, self.nobj), dtype=torch.float64, device=self.device)
-                           if want_terms else None)
-                _lib.check(self._L.brutus_los_loglike(
-                    self.nobj, self.nsamps, *self._draws, k, (ncol - 4) // 2, self._bufs[0],
-                    C.byref(self._p), self._bufs[1], t_terms, self._bufs[2], self._ws_bytes,
-                    stream))
-                out[a:a + k] = t_out[:k].cpu().numpy()
-                if want_terms:
-                    terms[a:a + k] = t_terms.cpu().numpy()
-        return out, terms
+    def _launch(self, theta, k, ncol, out, terms, stream):
+        _lib.check(self._L.brutus_los_loglike(
+            self.nobj, self.nsamps, *self._draws, k, (ncol - 4) // 2, theta, C.byref(self._p), out,
+            terms, self._bufs[2], self._ws_bytes, stream))
 
     def _eval(self, theta, want_terms):
-        # Rows the host decides (-inf under `monotonic`, NaN for a width that is not positive) are
-        # sent to the device with the rest and overwritten afterwards: rows do not influence one
-        # another, and a batch that is not compacted keeps one shape per call.
         th, single, preset = _check_theta(theta, self.monotonic, True)
-        th = np.ascontiguousarray(th)
-        out, terms = self._run(th, want_terms)
-        fixed = preset != 0.
-        if fixed.any():
-            out[fixed] = preset[fixed]
-            if want_terms:
-                terms[fixed] = preset[fixed][:, None]
+        out, terms = self._eval_rows(np.ascontiguousarray(th)[None], preset[None], want_terms)
+        out, terms = out[0], terms[0] if want_terms else None
         if single:
             return (float(out[0]), terms[0]) if want_terms else float(out[0])
         return (out, terms) if want_terms else out
@@ -529,7 +566,7 @@ def LOS_clouds_loglike_field(thetas, sightlines, kernel='gauss', rlims=(0., 6.),
     return (out, terms) if return_terms else out
 
 
-class LOSField(object):
+class LOSField(_LOSDevice):
     """The draws of MANY sightlines on the device, callable with one batch of profiles per
     sightline: the shape of a dust map, 10^3 - 10^5 sightlines that a sampler advances together.
 
@@ -554,39 +591,31 @@ class LOSField(object):
     host fallback: without the library or a GPU the constructor raises `BrutusError`.
     """
 
+    _name, _host_form = "LOSField", "LOS_clouds_loglike_field"
+
     def __init__(self, sightlines, template_reds=None, Ndraws=25, kernel='gauss', rlims=(0., 6.),
                  additive_foreground=False, monotonic=True, device="cuda"):
         _check_kernel(kernel, True)
         cats = _check_sightlines(sightlines, template_reds, Ndraws)
-        rlims = (float(rlims[0]), float(rlims[1]))
-        if not (np.isfinite(rlims[0]) and np.isfinite(rlims[1]) and rlims[1] > rlims[0]):
-            raise ValueError("rlims must be finite and increasing; got %s" % (rlims,))
-        self.nsightlines = len(cats)
+        rlims = _check_rlims(rlims)
+        self.nsightlines = self._nsight = len(cats)
         self.nobj = np.array([c[0].shape[0] for c in cats], dtype=np.int64)
         self.nsamps = np.array([c[0].shape[1] for c in cats], dtype=np.int64)
-        self.offsets = np.concatenate([[0], np.cumsum(self.nobj)])
+        self.offsets = self._offsets = np.concatenate([[0], np.cumsum(self.nobj)])
         if (self.nsightlines > _lib.LOSFIELD_MAX_SIGHTLINES or self.offsets[-1] > _lib.LOS_MAX_OBJ
                 or self.nsamps.max() > _lib.LOS_MAX_DRAWS):
             raise ValueError("the device form takes at most %d sightlines, %d stars in all and %d draws "
                              "each; got %d sightlines, %d stars, %d draws"
                              % (_lib.LOSFIELD_MAX_SIGHTLINES, _lib.LOS_MAX_OBJ, _lib.LOS_MAX_DRAWS,
                                 self.nsightlines, self.offsets[-1], self.nsamps.max()))
-        self.kernel, self.rlims, self.monotonic = kernel, rlims, bool(monotonic)
-        self._L = L = _lib.lib()
-        self._torch = torch = _torch("LOSField only runs on the HIP path. The host form is "
-                                     "LOS_clouds_loglike_field(device=None).")
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise ValueError("LOSField needs a GPU device; got %r" % (device,))
-        self._p = _lib.LosParams()
-        self._p.kernel = _KERNEL_CODES[kernel]
-        self._p.additive_foreground = int(bool(additive_foreground))
-        self._p.rlims[0], self._p.rlims[1] = rlims
+        self._open(kernel, rlims, additive_foreground, monotonic, device)
+        L = self._L
         # the tables: the library lays them out (brutus_los_field_plan), first the sizes alone
         nobj32, nsamps32 = self.nobj.astype(np.int32), self.nsamps.astype(np.int32)
         totals = np.zeros(3, dtype=np.int64)
         _lib.check(L.brutus_los_field_plan(self.nsightlines, nobj32, nsamps32, None, None, 0, totals))
         self.nstars, self.ntiles = int(totals[0]), int(totals[2])
+        self._nterms = self.nstars
         table = np.zeros((self.nsightlines, _lib.LOSFIELD_COLS), dtype=np.int64)
         tiles = np.zeros(self.ntiles, dtype=np.int32)
         _lib.check(L.brutus_los_field_plan(self.nsightlines, nobj32, nsamps32, table, tiles, tiles.size,
@@ -602,11 +631,10 @@ class LOSField(object):
                        to_device(np.concatenate([c[2] for c in cats]), np.float64, self.device))
         self._table = to_device(table, np.int64, self.device)
         self._tiles = to_device(tiles, np.int32, self.device)
-        # the buffers of a call are the same from call to call (`LOSSamples._buffers`)
+        # (as `_bufs`: built once)
         self._fixed = (_lib.fixed(self._ds, "d", "float64"), _lib.fixed(self._rs, "d", "float64"),
                        _lib.fixed(self._templ, "d", "float64"), _lib.fixed(self._table, "d", "int64"),
                        _lib.fixed(self._tiles, "d", "int32"))
-        self._cap, self._ncol = 0, 0
 
     @property
     def live_lane_share(self):
@@ -653,52 +681,15 @@ class LOSField(object):
         return cls([(dsamps[g], rsamps[g]) for g in groups],
                    template_reds=None if templ is None else [templ[g] for g in groups], **kw), ids
 
-    def _buffers(self, k, ncol):
-        """Device theta / workspace for `k` rows per sightline of `ncol` parameters; they grow,
-        and are otherwise kept from call to call."""
-        if k > self._cap or ncol != self._ncol:
-            torch = self._torch
-            cap = max(k, self._cap if ncol == self._ncol else 0)
-            self._theta = torch.empty(self.nsightlines * cap * ncol, dtype=torch.float64, device=self.device)
-            self._out = torch.empty(self.nsightlines * cap, dtype=torch.float64, device=self.device)
-            self._ws_bytes = int(self._L.brutus_los_field_workspace_bytes(self.ntiles, cap))
-            self._ws = torch.empty(self._ws_bytes, dtype=torch.uint8, device=self.device)
-            self._bufs = (_lib.fixed(self._theta, "d", "float64"), _lib.fixed(self._out, "d", "float64"),
-                          _lib.fixed(self._ws, "d"))
-            self._cap, self._ncol = cap, ncol
-        return self._theta, self._out
+    def _ws_size(self, cap):
+        return int(self._L.brutus_los_field_workspace_bytes(self.ntiles, cap))
 
-    def _launch(self, theta, k, ncol, flags, out, terms, stream):
+    def _launch(self, theta, k, ncol, out, terms, stream, flags=0):
         """One device call: `theta` and `out` are `_lib.fixed` addresses or tensors of `k` rows per
         sightline."""
         _lib.check(self._L.brutus_los_field_loglike(
             self.nsightlines, self.nstars, self.ntiles, *self._fixed, k, (ncol - 4) // 2, theta,
             C.byref(self._p), flags, out, terms, self._bufs[2], self._ws_bytes, stream))
-
-    def _run(self, th, want_terms):
-        """Values (S, K) and, if wanted, the terms as a list of (K, Nobj_s), of checked rows."""
-        torch = self._torch
-        nsight, ktot, ncol = th.shape
-        out = np.empty((nsight, ktot))
-        terms = [np.empty((ktot, n)) for n in self.nobj] if want_terms else None
-        chunk = _lib.LOS_MAX_THETA
-        if want_terms:
-            chunk = int(max(1, min(chunk, _TERMS_CHUNK_BYTES // (8 * self.nstars))))
-        with torch.cuda.device(self.device):
-            stream = _stream_ptr(torch)
-            for a in range(0, ktot, chunk):
-                k = min(chunk, ktot - a)
-                t_theta, t_out = self._buffers(k, ncol)
-                t_theta[:nsight * k * ncol].view(nsight, k, ncol).copy_(torch.from_numpy(th[:, a:a + k]))
-                t_terms = (torch.empty(k * self.nstars, dtype=torch.float64, device=self.device)
-                           if want_terms else None)
-                self._launch(self._bufs[0], k, ncol, 0, self._bufs[1], t_terms, stream)
-                out[:, a:a + k] = t_out[:nsight * k].cpu().numpy().reshape(nsight, k)
-                if want_terms:
-                    flat = t_terms.cpu().numpy()
-                    for s, n in enumerate(self.nobj):
-                        terms[s][a:a + k] = flat[k * self.offsets[s]:k * self.offsets[s + 1]].reshape(k, n)
-        return out, terms
 
     def _run_tensor(self, theta):
         """`(S, K)` tensor of a float64 tensor `(S, K, Nparams)` on the device; every row is
@@ -714,20 +705,14 @@ class LOSField(object):
                 self._buffers(k, ncol)                   # (the workspace)
                 whole = k == ktot
                 part = torch.empty((nsight, k), dtype=torch.float64, device=self.device) if not whole else out
-                self._launch(theta[:, a:a + k].contiguous(), k, ncol, flags, part, None, stream)
+                self._launch(theta[:, a:a + k].contiguous(), k, ncol, part, None, stream, flags)
                 if not whole:
                     out[:, a:a + k] = part
         return out
 
     def _eval(self, thetas, want_terms):
         th, single, preset = _check_field_thetas(thetas, self.nsightlines, self.monotonic, True)
-        out, terms = self._run(th, want_terms)
-        fixed = preset != 0.
-        if fixed.any():
-            out[fixed] = preset[fixed]
-            if want_terms:
-                for s, k in zip(*np.nonzero(fixed)):
-                    terms[s][k] = preset[s, k]
+        out, terms = self._eval_rows(th, preset, want_terms)
         if single:
             out = out[:, 0]
             terms = [t[0] for t in terms] if want_terms else None

@@ -245,8 +245,9 @@ def test_los_kernels_use_no_scratch():
     import kernel_resources
     from brutus_amd import _lib
     ks = {n: v for n, v in kernel_resources.kernels(_lib.LIB_PATH).items() if n.startswith("k_los_")}
-    want = {"k_los_terms<%d, %s, %s>" % (k, t, a) for k in range(3) for t in ("false", "true")
-            for a in ("false", "true")} | {"k_los_final"}
+    want = {"%s<%d, %s, %s>" % (name, k, t, a) for name in ("k_los_terms", "k_los_field_terms")
+            for k in range(3) for t in ("false", "true") for a in ("false", "true")}
+    want |= {"k_los_final", "k_los_field_final"}
     assert want <= set(ks), sorted(ks)
     bad = {n: v for n, v in ks.items() if v["scratch"] > 0 or v.get("vgpr_spills", 0) > 0}
     assert not bad, bad

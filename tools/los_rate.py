@@ -74,8 +74,8 @@ def parts_of_a_call(S, thetas, n):
         t0 = time.perf_counter()
         th = np.ascontiguousarray(los._check_theta(thetas[q], True, True)[0])
         t1 = time.perf_counter()
-        dev_th, dev_out = S._buffers(1, th.shape[1])
-        dev_th[:1].copy_(torch.from_numpy(th))
+        dev_th, dev_out = S._buffers(1, th.shape[1])        # (views (1, 1, ncol) and (1,))
+        dev_th.copy_(torch.from_numpy(th[None]))
         torch.cuda.synchronize()
         t2 = time.perf_counter()
         _lib.check(L.brutus_los_loglike(S.nobj, S.nsamps, S._ds.data_ptr(), S._rs.data_ptr(), None, 1,
@@ -83,7 +83,7 @@ def parts_of_a_call(S, thetas, n):
                                         dev_out.data_ptr(), None, S._ws.data_ptr(), S._ws_bytes, stream))
         torch.cuda.synchronize()
         t3 = time.perf_counter()
-        dev_out[:1].cpu().numpy()
+        dev_out.cpu().numpy()
         t4 = time.perf_counter()
         for key, v in zip(t, (t1 - t0, t2 - t1, t3 - t2, t4 - t3)):
             t[key].append(1e6 * v)
