@@ -99,6 +99,12 @@ class LosParams(C.Structure):
     _fields_ = [("kernel", C.c_int32), ("additive_foreground", C.c_int32), ("rlims", C.c_double * 2)]
 
 
+class LosPriorParams(C.Structure):
+    """struct brutus_los_prior_params (include/brutus_amd_los_walk.h)."""
+    _fields_ = [("pb", C.c_double * 10), ("s", C.c_double * 10), ("rlims", C.c_double * 2),
+                ("dlims", C.c_double * 2), ("clims", C.c_double * 2)]
+
+
 LOS_MAX_CLOUDS, LOS_MAX_THETA, LOS_MAX_DRAWS, LOS_MAX_OBJ = 32, 65535, 4096, 1 << 22
 
 _i64, _i32, _sz, _dbl, _u64 = C.c_int64, C.c_int, C.c_size_t, C.c_double, C.c_uint64
@@ -344,6 +350,17 @@ LOS_FIELD_SIGNATURES = {
 LOSFIELD_MAX_SIGHTLINES, LOSFIELD_MAX_TILES, LOSFIELD_COLS = 1 << 20, (1 << 20) + (1 << 16), 6
 LOSFIELD_CHECK_THETA, LOSFIELD_MONOTONIC = 1, 2
 
+# and for include/brutus_amd_los_walk.h (los.LOSPrior, los.LOSFieldSampler; tests/test_los_walk_host.py
+# compares this table with that header parameter by parameter)
+LOS_WALK_SIGNATURES = {
+    "brutus_los_prior_transform": (C.c_int, [_i64, _i32, _df64, C.POINTER(LosPriorParams), _df64, _stream]),
+    "brutus_los_walk_propose": (C.c_int, [_i32, _i32, _i32, _i32, _i64, _u64, _di64, _df64,
+                                          C.POINTER(LosPriorParams), _df64, _df64, _di32, _di32, _stream]),
+    "brutus_los_walk_accept": (C.c_int, [_i32, _i32, _i32, _i32, _i64, _u64, _di64, _df64, _df64, _df64, _di32,
+                                         _df64, _df64, _df64, _di64, _df64, _df64, _stream]),
+}
+LOSWALK_MAX_WALKERS, LOSWALK_MAX_ID, LOSWALK_MAX_STEP, LOSWALK_MAX_ROWS = 1 << 16, (1 << 20) - 1, (1 << 26) - 1, 1 << 30
+
 
 def lib():
     """Load (once) and return the shared library; raise loudly if absent."""
@@ -364,7 +381,7 @@ def lib():
     for name, (res, args) in (list(SIGNATURES.items()) + list(BATCH_SIGNATURES.items())
                               + list(DUST_SIGNATURES.items()) + list(SUMMARY_SIGNATURES.items())
                               + list(PREDICTIVE_SIGNATURES.items()) + list(OFFDIAG_SIGNATURES.items())
-                              + list(LOS_FIELD_SIGNATURES.items())):
+                              + list(LOS_FIELD_SIGNATURES.items()) + list(LOS_WALK_SIGNATURES.items())):
         fn = getattr(L, name)   # AttributeError if the .so is stale
         fn.restype = res
         fn.argtypes = args

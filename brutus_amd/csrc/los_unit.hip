@@ -1,6 +1,8 @@
 // los_unit.hip -- translation unit of libbrutus_amd.so: the line-of-sight cloud likelihood
 // (brutus_los_*; reference los.py:119-248, los_kernels.hpp), for one sightline per call and for a
-// ragged field of them (brutus_los_field_*; include/brutus_amd_los_field.h).
+// ragged field of them (brutus_los_field_*; include/brutus_amd_los_field.h), and what fits such a
+// field on the device: the prior transform and the ensemble sampler's two kernels
+// (brutus_los_prior_transform, brutus_los_walk_*; include/brutus_amd_los_walk.h, los_walk_kernels.hpp).
 
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -12,6 +14,7 @@
 #include "host.hpp"
 #include "fastmath.hpp"
 #include "los_kernels.hpp"
+#include "los_walk_kernels.hpp"
 
 namespace {
 static bool los_dims_ok(int nobj, int ntheta) {
@@ -54,6 +57,46 @@ static void los_dispatch(const brutus_los_params *params, bool templ, F f) {
     else if (params->kernel == 1) flags(std::integral_constant<int, 1>{});
     else flags(std::integral_constant<int, 2>{});
 }
+
+// the checks of the transform's constants
+static int los_prior_check(const brutus_los_prior_params *pp) {
+    if (!pp) return fail(BRUTUS_EINVAL, "NULL los prior parameters");
+    const double *sets[2] = {pp->pb, pp->s};
+    for (int k = 0; k < 2; ++k) {
+        const double *t = sets[k];
+        const char *name = k == 0 ? "pb" : "s";
+        if (!(t[LOSPRIOR_STD] > 0.) || !(t[LOSPRIOR_STD] < INFINITY) || !(fabs(t[LOSPRIOR_MEAN]) < INFINITY) ||
+            !(t[LOSPRIOR_LOW] < t[LOSPRIOR_HIGH]))
+            return fail(BRUTUS_EINVAL, "bad los prior %s_params (mean=%g, std=%g, low=%g, high=%g)", name,
+                        t[LOSPRIOR_MEAN], t[LOSPRIOR_STD], t[LOSPRIOR_LOW], t[LOSPRIOR_HIGH]);
+        for (int q = LOSPRIOR_CDF_A; q <= LOSPRIOR_SF_B; ++q)
+            if (!(t[q] >= 0. && t[q] <= 1.))
+                return fail(BRUTUS_EINVAL, "bad los prior %s_params (Phi %d = %g outside [0, 1])", name, q, t[q]);
+        if (!(t[LOSPRIOR_CDF_A] <= t[LOSPRIOR_CDF_B]) || !(t[LOSPRIOR_SF_B] <= t[LOSPRIOR_SF_A]))
+            return fail(BRUTUS_EINVAL, "bad los prior %s_params (Phi(a) > Phi(b))", name);
+        if (!(t[LOSPRIOR_EXP_LOW] >= 0.) || !(t[LOSPRIOR_EXP_LOW] < t[LOSPRIOR_EXP_HIGH]) ||
+            !(t[LOSPRIOR_EXP_HIGH] < INFINITY))
+            return fail(BRUTUS_EINVAL, "bad los prior %s_params (exp(low)=%g, exp(high)=%g)", name, t[LOSPRIOR_EXP_LOW],
+                        t[LOSPRIOR_EXP_HIGH]);
+    }
+    const double *lims[3] = {pp->rlims, pp->dlims, pp->clims};
+    for (int k = 0; k < 3; ++k)
+        if (!(fabs(lims[k][0]) < INFINITY) || !(fabs(lims[k][1]) < INFINITY))
+            return fail(BRUTUS_EINVAL, "bad los prior limits (%g, %g)", lims[k][0], lims[k][1]);
+    return 0;
+}
+
+// the checks the two walk calls share; *nmoved = nsight nwalkers / 2
+static int los_walk_check(int nsight, int nwalkers, int nclouds, int half, int64_t step, int64_t *nmoved) {
+    if (nsight < 1 || nsight > BRUTUS_LOSFIELD_MAX_SIGHTLINES || nwalkers < 2 || nwalkers > BRUTUS_LOSWALK_MAX_WALKERS ||
+        nwalkers % 2 || (int64_t)nsight * (nwalkers / 2) > BRUTUS_LOSWALK_MAX_ROWS || nclouds < 0 ||
+        nclouds > BRUTUS_LOS_MAX_CLOUDS || half < 0 || half > 1 || step < 0 || step > BRUTUS_LOSWALK_MAX_STEP)
+        return fail(BRUTUS_EINVAL, "bad los walk dimensions (nsight=%d, nwalkers=%d, nclouds=%d, half=%d, step=%lld)",
+                    nsight, nwalkers, nclouds, half, (long long)step);
+    *nmoved = (int64_t)nsight * (nwalkers / 2);
+    return 0;
+}
+static unsigned los_walk_blocks(int64_t rows) { return (unsigned)((rows + LOSWALK_BLOCK - 1) / LOSWALK_BLOCK); }
 }  // namespace
 
 extern "C" {
@@ -185,6 +228,68 @@ int brutus_los_field_loglike(int nsight, int64_t nstars, int64_t ntiles, const d
     tm.end();
     tm.begin("k_los_field_final");
     hipLaunchKernelGGL(k_los_field_final, dim3(nsight, ntheta), dim3(64), 0, st, c);
+    tm.end();
+    HIP_TRY(hipGetLastError());
+    tm.collect();
+    return 0;
+}
+
+// ---- fitting a field: prior transform and ensemble sampler (include/brutus_amd_los_walk.h) ----
+
+int brutus_los_prior_transform(int64_t nrows, int nclouds, const double *d_u, const brutus_los_prior_params *params,
+                               double *d_theta, void *stream) {
+    if (nrows < 1 || nrows > BRUTUS_LOSWALK_MAX_ROWS || nclouds < 0 || nclouds > BRUTUS_LOS_MAX_CLOUDS)
+        return fail(BRUTUS_EINVAL, "bad los prior dimensions (nrows=%lld, nclouds=%d)", (long long)nrows, nclouds);
+    if (int rc = los_prior_check(params)) return rc;
+    if (!d_u || !d_theta) return fail(BRUTUS_EINVAL, "NULL pointer");
+    hipStream_t st = (hipStream_t)stream;
+    Timer tm(st);
+    tm.begin("k_los_prior_transform");
+    hipLaunchKernelGGL(k_los_prior_transform, dim3(los_walk_blocks(nrows)), dim3(LOSWALK_BLOCK), 0, st, nrows, nclouds,
+                       d_u, d_theta, *params);
+    tm.end();
+    HIP_TRY(hipGetLastError());
+    tm.collect();
+    return 0;
+}
+
+int brutus_los_walk_propose(int nsight, int nwalkers, int nclouds, int half, int64_t step, uint64_t seed,
+                            const int64_t *d_ids, const double *d_u, const brutus_los_prior_params *params,
+                            double *d_u_new, double *d_theta_new, int32_t *d_outside, int32_t *d_partner,
+                            void *stream) {
+    int64_t nmoved;
+    if (int rc = los_walk_check(nsight, nwalkers, nclouds, half, step, &nmoved)) return rc;
+    if (int rc = los_prior_check(params)) return rc;
+    if (!d_ids || !d_u || !d_u_new || !d_theta_new || !d_outside) return fail(BRUTUS_EINVAL, "NULL pointer");
+    const LosWalkCall c{d_ids, seed, step, nmoved, nwalkers, nclouds, half};
+    hipStream_t st = (hipStream_t)stream;
+    Timer tm(st);
+    tm.begin("k_los_walk_propose");
+    hipLaunchKernelGGL(k_los_walk_propose, dim3(los_walk_blocks(nmoved)), dim3(LOSWALK_BLOCK), 0, st, c, d_u, *params,
+                       d_u_new, d_theta_new, d_outside, d_partner);
+    tm.end();
+    HIP_TRY(hipGetLastError());
+    tm.collect();
+    return 0;
+}
+
+int brutus_los_walk_accept(int nsight, int nwalkers, int nclouds, int half, int64_t step, uint64_t seed,
+                           const int64_t *d_ids, const double *d_u_new, const double *d_theta_new,
+                           const double *d_lnl_new, const int32_t *d_outside, double *d_u, double *d_theta,
+                           double *d_lnl, int64_t *d_naccept, double *d_chain, double *d_chain_lnl, void *stream) {
+    int64_t nmoved;
+    if (int rc = los_walk_check(nsight, nwalkers, nclouds, half, step, &nmoved)) return rc;
+    if (!d_ids || !d_u_new || !d_theta_new || !d_lnl_new || !d_outside || !d_u || !d_theta || !d_lnl || !d_naccept)
+        return fail(BRUTUS_EINVAL, "NULL pointer");
+    if ((d_chain == nullptr) != (d_chain_lnl == nullptr))
+        return fail(BRUTUS_EINVAL, "the chain slot and its ln L go together (both or neither)");
+    const LosWalkCall c{d_ids, seed, step, nmoved, nwalkers, nclouds, half};
+    hipStream_t st = (hipStream_t)stream;
+    Timer tm(st);
+    tm.begin("k_los_walk_accept");
+    hipLaunchKernelGGL(k_los_walk_accept, dim3(los_walk_blocks(nmoved)), dim3(LOSWALK_BLOCK), 0, st, c, d_u_new,
+                       d_theta_new, d_lnl_new, d_outside, d_u, d_theta, d_lnl, (unsigned long long *)d_naccept, d_chain,
+                       d_chain_lnl);
     tm.end();
     HIP_TRY(hipGetLastError());
     tm.collect();

@@ -1,11 +1,12 @@
 // post_kernels.hpp -- device lnpost (second cut, MC prior integral, resampling) behind brutus_post_batch
-// Included by post_unit.hip only (it defines kernels); needs common.hpp, fastmath.hpp and
-// mt_kernels.hpp (ZMap: where the numpy stream left the normals).
+// Included by post_unit.hip only (it defines kernels); needs common.hpp, fastmath.hpp, philox.hpp
+// (the generator itself) and mt_kernels.hpp (ZMap: where the numpy stream left the normals).
 #pragma once
 
 #include "common.hpp"
 #include "fastmath.hpp"
 #include "mt_kernels.hpp"
+#include "philox.hpp"      // Philox4, philox4x32_7, u53, philox_at, STREAM_*
 
 namespace {
 
@@ -17,39 +18,9 @@ namespace {
 // integrated in parallel and the result still equals, deviate for deviate, a
 // sequential run of the reference with that `rstate` object.
 // ===========================================================================
-struct Philox4 {
-    uint32_t w[4];
-};
-
 #define ZIG_TABLE_QUAL __device__ const
 #include "zig_table.inc"      // ZIG_N, kZigX[ZIG_N + 1], kZigY[ZIG_N + 1]
 #undef ZIG_TABLE_QUAL
-
-__device__ __forceinline__ Philox4 philox4x32_7(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
-                                                uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 7; ++r) {
-        if (r > 0) {
-            k0 += 0x9E3779B9u;
-            k1 += 0xBB67AE85u;
-        }
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;   // v_mad_u64_u32
-        const uint32_t hi0 = (uint32_t)(p0 >> 32), lo0 = (uint32_t)p0;
-        const uint32_t hi1 = (uint32_t)(p1 >> 32), lo1 = (uint32_t)p1;
-        const uint32_t n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
-        c0 = n0;
-        c1 = lo1;
-        c2 = n2;
-        c3 = lo0;
-    }
-    Philox4 o;
-    o.w[0] = c0; o.w[1] = c1; o.w[2] = c2; o.w[3] = c3;
-    return o;
-}
-
-__device__ __forceinline__ double u53(uint32_t a, uint32_t b) {
-    return ((double)(a >> 5) * 67108864.0 + (double)(b >> 6)) / 9007199254740992.0;
-}
 
 // q-th uniform of the uniform stream (rng.py: philox_uniform)
 __device__ __forceinline__ double rng_uniform(uint64_t seed, uint64_t q) {
@@ -59,8 +30,6 @@ __device__ __forceinline__ double rng_uniform(uint64_t seed, uint64_t q) {
 }
 
 // ---- normal stream (rng.py: philox_normal): ziggurat, 1024 layers, two normals per call ----
-constexpr uint32_t STREAM_NORMAL = 0u, STREAM_UNIFORM = 1u, STREAM_RETRY = 2u, STREAM_TAIL = 3u;
-
 // 64 random bits -> layer i, sign and x = u X[i]; true inside the layer's rectangle (99.57 %:
 // the normal is then +-x).  One multiplication: host and device round alike, the decision is
 // bit-exact.  `X` is kZigX or an LDS copy of it (stage_zig_table).
@@ -76,10 +45,6 @@ __device__ __forceinline__ bool zig_try(uint32_t a, uint32_t b, const double *__
 // high word instead of a compare and two selects
 __device__ __forceinline__ double zig_signed(double x, uint32_t b) {
     return __hiloint2double(__double2hiint(x) | (int)((b << 21) & 0x80000000u), __double2loint(x));
-}
-__device__ __forceinline__ Philox4 philox_at(uint64_t seed, uint64_t idx, uint32_t c2, uint32_t stream) {
-    return philox4x32_7((uint32_t)idx, (uint32_t)(idx >> 32), c2, stream, (uint32_t)seed,
-                        (uint32_t)(seed >> 32));
 }
 // normal j whose attempt 0 (layer i, x, sign) fell outside the rectangle: wedge test or tail,
 // further attempts (rng.py).  0.43 % of the normals come here; ocml's exp / log.

@@ -9,7 +9,10 @@ with `device=`, a one-shot wrapper of the class.  `LOSField` and `LOS_clouds_log
 the same pair for MANY sightlines that are fitted with one model and advance together (a dust
 map): all sightlines' draws on the GPU, K profiles per sightline in one call
 (`brutus_los_field_loglike`).  The two are not in `__all__`, which lists the reference's names
-and `LOSSamples`.
+and `LOSSamples`.  `LOSPrior` and `LOSFieldSampler` take the step from the likelihood of a field to
+its posterior: the prior transform on the device and an affine-invariant ensemble sampler that
+advances all sightlines together in the unit cube (`brutus_los_prior_transform`,
+`brutus_los_walk_*`); `LOS_walk_field_host` is the same chain in numpy.
 
 Both forms weigh every sample against the ONE cloud bin its distance falls in, instead of the
 reference's `(Nclouds + 1, Nobj, Ndraws)` temporaries; the result is the reference's up to the
@@ -19,9 +22,11 @@ import ctypes as C
 import warnings
 
 import numpy as np
+from scipy.special import ndtr
 from scipy.stats import truncnorm
 
 from . import _lib
+from . import rng as _rng
 from ._dev import _stream_ptr, _torch, to_device
 
 __all__ = ["LOS_clouds_priortransform", "LOS_clouds_loglike_samples",
@@ -741,3 +746,350 @@ class LOSField(_LOSDevice):
         """`(loglike, terms)`: `terms[s]` holds the per-star values of sightline `s` after the
         outlier mixture, `(Nobj_s,)` or `(K, Nobj_s)`; `loglike` is the value of `F(thetas)`."""
         return self._eval(thetas, True)
+
+
+# ---- fitting a field: the prior on the device and the ensemble sampler ------------------------
+_CHAIN_BYTES = 4 << 30             # default limit of the chain one `run` returns
+
+
+def _truncnorm_constants(params, name):
+    """[Phi(a), Phi(b), Phi(-a), Phi(-b), mean, std, low, high, exp(low), exp(high)] of a truncated
+    normal: `brutus_los_prior_params::pb` / `s`."""
+    try:
+        mean, std, low, high = (float(v) for v in params)
+    except (TypeError, ValueError):
+        raise ValueError("%s must be (mean, std, low, high); got %r" % (name, params))
+    if not (np.isfinite(mean) and np.isfinite(std) and std > 0. and low < high):
+        raise ValueError("%s must be (mean, std, low, high) with finite mean, finite std > 0 and "
+                         "low < high; got %r" % (name, tuple(params)))
+    a, b = (low - mean) / std, (high - mean) / std
+    ends = np.exp([low, high])
+    if not (np.isfinite(ends[1]) and ends[0] < ends[1]):
+        raise ValueError("%s: exp(low) and exp(high) must differ and be finite; got %r" % (name, tuple(params)))
+    return [ndtr(a), ndtr(b), ndtr(-a), ndtr(-b), mean, std, low, high, ends[0], ends[1]]
+
+
+def _check_lims(lims, name):
+    try:
+        lo, hi = (float(v) for v in lims)
+    except (TypeError, ValueError):
+        raise ValueError("%s must be two numbers; got %r" % (name, lims))
+    if not (np.isfinite(lo) and np.isfinite(hi)):
+        raise ValueError("%s must be finite; got %r" % (name, tuple(lims)))
+    return lo, hi
+
+
+class LOSPrior(object):
+    """The prior transform of the LOS fit, on the host and on the device.
+
+    `LOSPrior(rlims, dlims, pb_params, s_params, dust_template, nlims)` takes the arguments and
+    defaults of `LOS_clouds_priortransform`.  `prior(u)` with numpy IS that function.
+    `prior(u, device_out=True)` takes a float64 tensor `(..., Nparams)` on a GPU and returns the
+    transformed tensor without synchronising (`brutus_los_prior_transform`): the uniform
+    coordinates have the host's bytes, the truncated log-normals agree with it to 1e-12 relative
+    (Wichura's AS 241 for the inverse normal, in the two-branch form that keeps the upper tail),
+    clouds with tied distance coordinates keep their order, and a row with a coordinate that is
+    NaN or outside `[0, 1]` is NaN throughout.  At most 32 clouds on the device.
+    """
+
+    def __init__(self, rlims=(0., 6.), dlims=(4., 19.), pb_params=(-3., 0.7, -np.inf, 0.),
+                 s_params=(-3., 0.3, -np.inf, 0.), dust_template=False, nlims=(0.2, 2)):
+        self.rlims, self.dlims = _check_lims(rlims, "rlims"), _check_lims(dlims, "dlims")
+        self.nlims = _check_lims(nlims, "nlims")
+        self.pb_params, self.s_params = tuple(pb_params), tuple(s_params)
+        self.dust_template = bool(dust_template)
+        self._p = p = _lib.LosPriorParams()
+        p.pb[:] = _truncnorm_constants(pb_params, "pb_params")
+        p.s[:] = _truncnorm_constants(s_params, "s_params")
+        p.rlims[:], p.dlims[:] = self.rlims, self.dlims
+        p.clims[:] = self.nlims if self.dust_template else self.rlims
+
+    @property
+    def kwargs(self):
+        """The keyword arguments of `LOS_clouds_priortransform` this prior stands for."""
+        return dict(rlims=self.rlims, dlims=self.dlims, pb_params=self.pb_params, s_params=self.s_params,
+                    dust_template=self.dust_template, nlims=self.nlims)
+
+    def __call__(self, u, device_out=False):
+        if not device_out:
+            if hasattr(u, "detach"):
+                u = u.detach().cpu().numpy()
+            return LOS_clouds_priortransform(u, **self.kwargs)
+        torch = _torch("LOSPrior(device_out=True) only runs on the HIP path. The host form is "
+                       "LOS_clouds_priortransform.")
+        if not (isinstance(u, torch.Tensor) and u.dtype == torch.float64 and u.is_cuda):
+            raise TypeError("device_out=True takes a float64 tensor on a GPU")
+        if u.dim() < 1 or u.shape[-1] < 4 or u.shape[-1] % 2 or (u.shape[-1] - 4) // 2 > _lib.LOS_MAX_CLOUDS \
+                or u.numel() == 0:
+            raise ValueError("u must have shape (..., Nparams) with Nparams = 4 + 2 Nclouds, at most %d "
+                             "clouds, and at least one row; got %s" % (_lib.LOS_MAX_CLOUDS, tuple(u.shape)))
+        u = u.contiguous()
+        theta = torch.empty_like(u)
+        with torch.cuda.device(u.device):
+            _lib.check(_lib.lib().brutus_los_prior_transform(
+                u.numel() // u.shape[-1], (u.shape[-1] - 4) // 2, u, C.byref(self._p), theta, _stream_ptr(torch)))
+        return theta
+
+
+def _check_walk(nsight, nwalkers, seed, ids, u0, nclouds, monotonic, prior):
+    """(W, seed, ids (S,) int64, u0 (S, W, P) float64) of a walk's arguments; `u0=None` is the
+    default start (`_walk_start`)."""
+    if not isinstance(prior, LOSPrior):
+        raise ValueError("prior must be a LOSPrior")
+    W = int(nwalkers)
+    if W != nwalkers or W < 2 or W % 2 or W > _lib.LOSWALK_MAX_WALKERS:
+        raise ValueError("nwalkers must be even, at least 2 and at most %d; got %r"
+                         % (_lib.LOSWALK_MAX_WALKERS, nwalkers))
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    ids = np.arange(nsight, dtype=np.int64) if ids is None else np.asarray(ids)
+    if ids.shape != (nsight,) or ids.dtype.kind not in "iu" or ids.min() < 0 or ids.max() > _lib.LOSWALK_MAX_ID:
+        raise ValueError("ids must be %d integers in [0, %d], one per sightline" % (nsight, _lib.LOSWALK_MAX_ID))
+    ids = ids.astype(np.int64)
+    if u0 is None:
+        if nclouds is None or int(nclouds) != nclouds or not 0 <= nclouds <= _lib.LOS_MAX_CLOUDS:
+            raise ValueError("without u0, nclouds must be given: an integer in [0, %d]" % _lib.LOS_MAX_CLOUDS)
+        if monotonic and prior.dust_template and nclouds:
+            raise ValueError("with dust_template=True and monotonic=True the caller supplies u0: the "
+                             "rescalings of a template do not order the reddenings")
+        u0 = _walk_start(seed, ids, W, int(nclouds), monotonic)
+    else:
+        u0 = np.array(u0, dtype=np.float64)
+        if u0.ndim != 3 or u0.shape[:2] != (nsight, W) or u0.shape[2] < 4 or u0.shape[2] % 2 \
+                or (u0.shape[2] - 4) // 2 > _lib.LOS_MAX_CLOUDS:
+            raise ValueError("u0 must have shape (S, nwalkers, Nparams) = (%d, %d, 4 + 2 Nclouds), at most "
+                             "%d clouds; got %s" % (nsight, W, _lib.LOS_MAX_CLOUDS, u0.shape))
+        if nclouds is not None and 4 + 2 * int(nclouds) != u0.shape[2]:
+            raise ValueError("u0 has %d columns; nclouds = %d needs %d" % (u0.shape[2], nclouds, 4 + 2 * int(nclouds)))
+        if not np.all((u0 >= 0.) & (u0 <= 1.)):
+            raise ValueError("u0 must lie in the unit cube")
+    return W, seed, ids, np.ascontiguousarray(u0)
+
+
+def _walk_start(seed, ids, nwalkers, nclouds, ascending):
+    """The default first state `(S, W, P)` in the unit cube: coordinate p of walker w of
+    sightline `id` is uniform 3 of the walk stream with p in the place of the step (`rng.py`).
+    `ascending` (a `monotonic` likelihood whose cloud coordinates are reddenings) then rearranges
+    every row's reddening coordinates: `fred` gets the smallest, the cloud with the k-th smallest
+    distance coordinate the (k + 1)-th -- every start is a row the likelihood allows."""
+    ncol = 4 + 2 * nclouds
+    u = _rng.walk_uniform(seed, ids[:, None, None], np.arange(ncol)[None, None, :],
+                          np.arange(nwalkers)[None, :, None], 3)
+    if ascending and nclouds:
+        reds = np.sort(u[..., 3::2], axis=-1)
+        order = np.argsort(u[..., 4::2], axis=-1, kind='stable')
+        u[..., 3] = reds[..., 0]
+        np.put_along_axis(u[..., 5::2], order, reds[..., 1:], axis=-1)
+    return u
+
+
+def _kept(step0, nsteps, thin):
+    """The steps of `step0 ... step0 + nsteps - 1` a chain keeps: step g (counted from the
+    sampler's first) is kept when g + 1 is a multiple of `thin`."""
+    g = np.arange(step0, step0 + nsteps)
+    return g[(g + 1) % thin == 0]
+
+
+def _check_run(step0, nsteps, thin):
+    if int(nsteps) != nsteps or nsteps < 1 or int(thin) != thin or thin < 1:
+        raise ValueError("nsteps and thin must be integers, at least 1; got %r, %r" % (nsteps, thin))
+    if step0 + nsteps - 1 > _lib.LOSWALK_MAX_STEP:
+        raise ValueError("a walk has at most %d steps" % (_lib.LOSWALK_MAX_STEP + 1))
+    return int(nsteps), int(thin)
+
+
+def _nonfinite_start(lnl):
+    bad = np.argwhere(~np.isfinite(lnl))
+    if bad.size:
+        raise ValueError("the initial ln L of sightline %d, walker %d is %r: every walker must start where the "
+                         "likelihood is finite" % (bad[0][0], bad[0][1], float(lnl[tuple(bad[0])])))
+
+
+def LOS_walk_field_host(sightlines, prior, nwalkers, nsteps, thin=1, seed=0, ids=None, u0=None, nclouds=None,
+                        return_walk=False, **kwargs):
+    """
+    The chain of `LOSFieldSampler` in numpy: the reference of the device form, with the same
+    Philox draws, `LOS_clouds_priortransform` and `LOS_clouds_loglike_field(device=None)`.
+
+    `W = nwalkers` (even) walkers per sightline live in the unit cube.  A step is two
+    half-steps; half `h` moves the walkers `w = h (mod 2)`, each with three uniforms of the walk
+    stream (`rng.walk_uniform`): `z = (r0 + 1)^2 / 2` (the stretch move with a = 2, Goodman &
+    Weare 2010), partner `j` = the `floor(r1 W / 2)`-th walker of the other half,
+    `u' = u_j + z (u_w - u_j)`; accepted iff `u'` lies in the cube and
+    `ln r2 < (P - 1) ln z + lnL' - lnL` (never for a NaN or `-inf` on the right).
+
+    Parameters
+    ----------
+    sightlines, **kwargs
+        As `LOS_clouds_loglike_field`: the draws and `kernel`, `rlims`, `template_reds`,
+        `Ndraws`, `additive_foreground`, `monotonic`.
+    prior : `LOSPrior`
+    nwalkers, seed, ids, u0, nclouds
+        As `LOSFieldSampler`.
+    nsteps, thin
+        As `LOSFieldSampler.run` from a new sampler.
+    return_walk : bool, optional
+        Also return `dict(u=(nsteps, S, W, P), accepted=(nsteps, S, W))`: the state in the cube
+        and the decisions after every step.
+
+    Returns
+    -------
+    chain `(nkept, S, W, P)` thetas, lnl `(nkept, S, W)`, accept_fraction `(S,)`, and the smallest
+    `|ln r2 - ln q|` over all decisions that were a comparison (`inf` if there was none): how
+    far the chain is from a different one under a perturbed likelihood.
+    """
+    cats = _check_sightlines(sightlines, kwargs.get("template_reds"), kwargs.get("Ndraws", 25))
+    nsight = len(cats)
+    monotonic = bool(kwargs.get("monotonic", True))
+    W, seed, ids, u = _check_walk(nsight, nwalkers, seed, ids, u0, nclouds, monotonic, prior)
+    nsteps, thin = _check_run(0, nsteps, thin)
+    ncol, nhalf = u.shape[2], W // 2
+    pkw = prior.kwargs
+    theta = LOS_clouds_priortransform(u.reshape(-1, ncol), **pkw).reshape(u.shape)
+    lnl = LOS_clouds_loglike_field(theta, sightlines, device=None, **kwargs)
+    _nonfinite_start(lnl)
+    kept = _kept(0, nsteps, thin)
+    chain, chain_lnl = np.empty((kept.size,) + u.shape), np.empty((kept.size, nsight, W))
+    walk_u, walk_acc = np.empty((nsteps,) + u.shape), np.zeros((nsteps, nsight, W), dtype=bool)
+    margin, nacc = np.inf, np.zeros(nsight, dtype=np.int64)
+    for g in range(nsteps):
+        for h in (0, 1):
+            w = np.arange(h, W, 2)
+            r = _rng.walk_uniform(seed, ids[:, None, None], g, w[None, :, None], np.arange(3)[None, None, :])
+            z = (r[..., 0] + 1.) ** 2 / 2.
+            j = 2 * np.minimum(np.floor(r[..., 1] * nhalf).astype(np.int64), nhalf - 1) + 1 - h
+            uj, uw = np.take_along_axis(u, j[:, :, None], axis=1), u[:, w]
+            un = uj + z[..., None] * (uw - uj)
+            inside = np.all((un >= 0.) & (un <= 1.), axis=2)
+            # (a proposal outside the cube is never accepted: the likelihood sees the walker's own
+            # theta in its place, and its value is dropped)
+            tn = theta[:, w].copy()
+            if inside.any():
+                tn[inside] = LOS_clouds_priortransform(un[inside], **pkw)
+            ln = LOS_clouds_loglike_field(tn, sightlines, device=None, **kwargs)
+            with np.errstate(all="ignore"):
+                lnq = ((ncol - 1) * np.log(z) + ln) - lnl[:, w]
+                lnr = np.log(r[..., 2])
+                acc = inside & (lnr < lnq)
+                compared = inside & np.isfinite(lnq) & np.isfinite(lnr)
+                if compared.any():
+                    margin = min(margin, float(np.min(np.abs(lnr - lnq)[compared])))
+            s_i, m_i = np.nonzero(acc)
+            u[s_i, w[m_i]], theta[s_i, w[m_i]], lnl[s_i, w[m_i]] = un[acc], tn[acc], ln[acc]
+            walk_acc[g][:, w] = acc
+            nacc += acc.sum(axis=1)
+        walk_u[g] = u
+        slot = np.nonzero(kept == g)[0]
+        if slot.size:
+            chain[slot[0]], chain_lnl[slot[0]] = theta, lnl
+    out = (chain, chain_lnl, nacc / float(nsteps * W), margin)
+    return out + (dict(u=walk_u, accepted=walk_acc),) if return_walk else out
+
+
+class LOSFieldSampler(object):
+    """An affine-invariant ensemble sampler (stretch move, Goodman & Weare 2010) that fits every
+    sightline of a `LOSField` together, on the device, in the unit cube of a `LOSPrior`.
+
+    `LOSFieldSampler(field, prior, nwalkers, seed=0, ids=None, u0=None, nclouds=None)` holds
+    `W = nwalkers` (even) walkers per sightline: `u (S, W, P)` in the cube, its transform and
+    `lnL (S, W)`.  `u0=None` draws the first state on the host from the walk stream of
+    `brutus_amd.rng` (`nclouds` says how many clouds); for a `monotonic` field it is rearranged
+    so that every start is allowed (`_walk_start`).  With `dust_template=True` and `monotonic`
+    the caller supplies `u0`.  A first state whose `lnL` is not finite raises `ValueError` -- the
+    one time the sampler waits for the device.
+
+    `run(nsteps, thin=1, device_out=False)` advances all sightlines `nsteps` steps; a half-step is
+    four launches (`brutus_los_walk_propose`, the two kernels of `brutus_los_field_loglike`,
+    `brutus_los_walk_accept`) and nothing inside `run` waits for the device.  The algorithm is
+    `LOS_walk_field_host`'s, which is its reference: same draws, same proposals byte for byte.
+    The chain of a sightline is a pure function of `(seed, ids[s])` and its data: the same bytes
+    alone or in a field, in any order, in one `run` or several.  `sampler.u`, `sampler.theta`,
+    `sampler.lnl` are the current state (tensors), `sampler.step` the steps taken.
+    """
+
+    def __init__(self, field, prior, nwalkers, seed=0, ids=None, u0=None, nclouds=None):
+        if not isinstance(field, LOSField):
+            raise ValueError("field must be a LOSField")
+        W, self.seed, ids, u0 = _check_walk(field.nsightlines, nwalkers, seed, ids, u0, nclouds, field.monotonic,
+                                            prior)
+        self.field, self.prior, self.nwalkers, self.step = field, prior, W, 0
+        if field.nsightlines * (W // 2) > _lib.LOSWALK_MAX_ROWS:
+            raise ValueError("at most %d moved walkers per half-step" % _lib.LOSWALK_MAX_ROWS)
+        self._torch = torch = field._torch
+        dev = field.device
+        S, _, P = u0.shape
+        self.nparams, self.nclouds = P, (P - 4) // 2
+        self.ids = to_device(ids, np.int64, dev)
+        self.u = to_device(u0, np.float64, dev)
+        self.theta = prior(self.u, device_out=True)
+        self.lnl = field(self.theta, device_out=True).contiguous()
+        _nonfinite_start(self.lnl.cpu().numpy())
+        f64 = dict(dtype=torch.float64, device=dev)
+        self._u_new, self._theta_new = torch.empty((S, W // 2, P), **f64), torch.empty((S, W // 2, P), **f64)
+        self._lnl_new = torch.empty((S, W // 2), **f64)
+        self._outside = torch.empty((S, W // 2), dtype=torch.int32, device=dev)
+        self._naccept = torch.zeros(S, dtype=torch.int64, device=dev)
+        # (the same buffers for every launch of a run: checked once, as `_LOSDevice._bufs`)
+        fx = _lib.fixed
+        self._fx_state = (fx(self.u, "d", "float64"), fx(self.theta, "d", "float64"), fx(self.lnl, "d", "float64"),
+                          fx(self._naccept, "d", "int64"))
+        self._fx_new = (fx(self._u_new, "d", "float64"), fx(self._theta_new, "d", "float64"),
+                        fx(self._lnl_new, "d", "float64"), fx(self._outside, "d", "int32"))
+        self._fx_ids = fx(self.ids, "d", "int64")
+
+    def chain_bytes(self, nsteps, thin=1):
+        """The bytes of the chain and its ln L that `run(nsteps, thin)` would return now."""
+        S, W, P = self.u.shape
+        return int(_kept(self.step, int(nsteps), int(thin)).size) * S * W * (P + 1) * 8
+
+    def _half_step(self, g, half, chain, chain_lnl, stream, after=None):
+        """The four launches of half-step `half` of step `g`; `chain`, `chain_lnl`: the slot of a
+        kept step or None.  `after(name)`, if given, is called after each of the three library
+        calls (tools/los_walk_rate.py reads the kernel times there)."""
+        F, L, pp = self.field, self.field._L, C.byref(self.prior._p)
+        S, W, P = self.u.shape
+        flags = _lib.LOSFIELD_CHECK_THETA | (_lib.LOSFIELD_MONOTONIC if F.monotonic else 0)
+        u, theta, lnl, naccept = self._fx_state
+        u_new, theta_new, lnl_new, outside = self._fx_new
+        _lib.check(L.brutus_los_walk_propose(S, W, self.nclouds, half, g, self.seed, self._fx_ids, u, pp, u_new,
+                                             theta_new, outside, None, stream))
+        if after:
+            after("propose")
+        F._launch(theta_new, W // 2, P, lnl_new, None, stream, flags)
+        if after:
+            after("loglike")
+        _lib.check(L.brutus_los_walk_accept(S, W, self.nclouds, half, g, self.seed, self._fx_ids, u_new, theta_new,
+                                            lnl_new, outside, u, theta, lnl, naccept, chain, chain_lnl, stream))
+        if after:
+            after("accept")
+
+    def run(self, nsteps, thin=1, device_out=False, max_bytes=_CHAIN_BYTES):
+        """Advance every sightline `nsteps` steps.  Returns `(chain (nkept, S, W, P)` thetas,
+        `lnl (nkept, S, W)`, `accept_fraction (S,))` of this run: step g, counted from the sampler's
+        first, is kept when `g + 1` is a multiple of `thin`.  Tensors with `device_out=True` (no
+        synchronisation), else numpy.  `ValueError`, before anything is launched, if chain and
+        ln L would take more than `max_bytes`."""
+        torch, F = self._torch, self.field
+        nsteps, thin = _check_run(self.step, nsteps, thin)
+        if self.chain_bytes(nsteps, thin) > max_bytes:
+            raise ValueError("the chain of %d steps (thin=%d) takes %d bytes, more than max_bytes=%d: thin it, "
+                             "or run fewer steps at a time" % (nsteps, thin, self.chain_bytes(nsteps, thin), max_bytes))
+        S, W, P = self.u.shape
+        kept = set(_kept(self.step, nsteps, thin).tolist())
+        chain = torch.empty((len(kept), S, W, P), dtype=torch.float64, device=F.device)
+        chain_lnl = torch.empty((len(kept), S, W), dtype=torch.float64, device=F.device)
+        self._naccept.zero_()
+        with torch.cuda.device(F.device):
+            stream = _stream_ptr(torch)
+            F._buffers(W // 2, P)                       # (the likelihood's workspace)
+            slot = 0
+            for g in range(self.step, self.step + nsteps):
+                keep = g in kept
+                for half in (0, 1):
+                    self._half_step(g, half, chain[slot] if keep else None, chain_lnl[slot] if keep else None,
+                                    stream)
+                slot += keep
+        self.step += nsteps
+        frac = self._naccept.to(torch.float64) / float(nsteps * W)
+        if device_out:
+            return chain, chain_lnl, frac
+        return chain.cpu().numpy(), chain_lnl.cpu().numpy(), frac.cpu().numpy()

@@ -23,6 +23,16 @@ q-th uniform are pure functions of `(seed, j)` / `(seed, q)`:
               is the wedge test Y[i] + u2 (Y[i+1] - Y[i]) < exp(-x**2 / 2) with u2 from
               words (2, 3) of the call (j, r, stream 2), and on failure attempt r + 1.
 
+The ensemble sampler of a field of sightlines (`los.LOSFieldSampler`) has a stream of its own,
+STREAM_WALK, so that the chain of a sightline is a pure function of `(seed, sightline id)`:
+
+    uniform c of walker w of sightline `id` at step `step` = the 53-bit uniform of the call with
+    counter (index lo, index hi, 0, STREAM_WALK), index = id * 2**44 + step * 2**18 + w * 2**2 + c,
+    id < 2**20, step < 2**26, w < 2**16, c < 4
+    c = 0: the stretch, 1: the partner, 2: the acceptance; c = 3 is the host's: coordinate p of
+    the first state of walker w, with p in the place of the step
+    (`walk_index`, `walk_uniform`; the same words head brutus_amd/csrc/los_walk_kernels.hpp)
+
 Because any deviate can be computed without the ones before it, the device can
 evaluate the Monte Carlo integral of every selected model of every object in
 parallel (`brutus_post_batch`) and still reproduce, deviate for deviate, what
@@ -33,13 +43,14 @@ import numpy as np
 
 from ._zigtab import X as ZIG_X, Y as ZIG_Y, ZIG_N
 
-__all__ = ["PhiloxRandomState", "philox4x32", "philox_uniform", "philox_normal"]
+__all__ = ["PhiloxRandomState", "philox4x32", "philox_uniform", "philox_normal", "walk_index", "walk_uniform"]
 
 _M0, _M1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57)
 _W0, _W1 = np.uint64(0x9E3779B9), np.uint64(0xBB67AE85)
 _MASK = np.uint64(0xFFFFFFFF)
 ROUNDS = 7
-STREAM_NORMAL, STREAM_UNIFORM, STREAM_RETRY, STREAM_TAIL = 0, 1, 2, 3
+STREAM_NORMAL, STREAM_UNIFORM, STREAM_RETRY, STREAM_TAIL, STREAM_WALK = 0, 1, 2, 3, 4
+WALK_MAX_ID, WALK_MAX_STEP, WALK_MAX_WALKERS = (1 << 20) - 1, (1 << 26) - 1, 1 << 16
 
 
 def philox4x32(c0, c1, c2, c3, k0, k1, rounds=ROUNDS):
@@ -76,6 +87,20 @@ def _philox_at(seed, lo64, c2, stream):
     seed = np.uint64(seed)
     return philox4x32(lo64 & _MASK, lo64 >> np.uint64(32), c2, np.full_like(lo64, stream),
                       seed & _MASK, seed >> np.uint64(32))
+
+
+def walk_index(ids, step, walker, c):
+    """The counter index of the walk stream (uint64, broadcast over the arguments): `ids` up to
+    WALK_MAX_ID, `step` up to WALK_MAX_STEP, `walker` below WALK_MAX_WALKERS, `c` below 4."""
+    ids, step, walker, c = (np.asarray(x, dtype=np.uint64) for x in (ids, step, walker, c))
+    return ((ids << np.uint64(44)) + (step << np.uint64(18))) + ((walker << np.uint64(2)) + c)
+
+
+def walk_uniform(seed, ids, step, walker, c):
+    """Uniform deviates in [0, 1) of the walk stream, broadcast over `(ids, step, walker, c)`."""
+    idx = walk_index(ids, step, walker, c)
+    o = _philox_at(seed, idx, np.zeros_like(idx), STREAM_WALK)
+    return _u53(o[0], o[1])
 
 
 def _zig_try(a, b):

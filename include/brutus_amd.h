@@ -645,6 +645,9 @@ void brutus_enable_timing(int on);
 /* ---- line-of-sight cloud likelihood of many sightlines per call (a ragged field of them) ---- */
 #include "brutus_amd_los_field.h"
 
+/* ---- fitting a field of sightlines: the LOS prior transform and the ensemble sampler's kernels ---- */
+#include "brutus_amd_los_walk.h"
+
 #ifdef __cplusplus
 }
 #endif
