@@ -361,6 +361,18 @@ LOS_WALK_SIGNATURES = {
 }
 LOSWALK_MAX_WALKERS, LOSWALK_MAX_ID, LOSWALK_MAX_STEP, LOSWALK_MAX_ROWS = 1 << 16, (1 << 20) - 1, (1 << 26) - 1, 1 << 30
 
+# and for include/brutus_amd_los_chain.h (los.LOSChainSummary; tests/test_los_chain_host.py compares
+# this table with that header parameter by parameter)
+LOS_CHAIN_SIGNATURES = {
+    "brutus_los_chain_quantiles": (C.c_int, [_i64, _i32, _i32, _i32, _df64, _i32, _df64, _df64, _stream]),
+    "brutus_los_chain_profile": (C.c_int, [_i64, _i32, _i32, _i32, _df64, _i32, _i32, _df64, _i32, _df64, _df64,
+                                           _stream]),
+    "brutus_los_chain_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "brutus_los_chain_moments": (C.c_int, [_i64, _i32, _i32, _i32, _df64, _df64, _df64, _df64, _df64, _df64, _df64,
+                                           _dv, _sz, _stream]),
+}
+LOSCHAIN_MAX_SAMPLES, LOSCHAIN_MAX_Q, LOSCHAIN_MAX_GRID = 1 << 24, 16, 4096
+
 
 def lib():
     """Load (once) and return the shared library; raise loudly if absent."""
@@ -381,7 +393,8 @@ def lib():
     for name, (res, args) in (list(SIGNATURES.items()) + list(BATCH_SIGNATURES.items())
                               + list(DUST_SIGNATURES.items()) + list(SUMMARY_SIGNATURES.items())
                               + list(PREDICTIVE_SIGNATURES.items()) + list(OFFDIAG_SIGNATURES.items())
-                              + list(LOS_FIELD_SIGNATURES.items()) + list(LOS_WALK_SIGNATURES.items())):
+                              + list(LOS_FIELD_SIGNATURES.items()) + list(LOS_WALK_SIGNATURES.items())
+                              + list(LOS_CHAIN_SIGNATURES.items())):
         fn = getattr(L, name)   # AttributeError if the .so is stale
         fn.restype = res
         fn.argtypes = args

@@ -2,7 +2,9 @@
 // (brutus_los_*; reference los.py:119-248, los_kernels.hpp), for one sightline per call and for a
 // ragged field of them (brutus_los_field_*; include/brutus_amd_los_field.h), and what fits such a
 // field on the device: the prior transform and the ensemble sampler's two kernels
-// (brutus_los_prior_transform, brutus_los_walk_*; include/brutus_amd_los_walk.h, los_walk_kernels.hpp).
+// (brutus_los_prior_transform, brutus_los_walk_*; include/brutus_amd_los_walk.h, los_walk_kernels.hpp),
+// and what turns the chains of such a fit into a map (brutus_los_chain_*;
+// include/brutus_amd_los_chain.h, los_chain_kernels.hpp).
 
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -15,6 +17,7 @@
 #include "fastmath.hpp"
 #include "los_kernels.hpp"
 #include "los_walk_kernels.hpp"
+#include "los_chain_kernels.hpp"
 
 namespace {
 static bool los_dims_ok(int nobj, int ntheta) {
@@ -97,6 +100,44 @@ static int los_walk_check(int nsight, int nwalkers, int nclouds, int half, int64
     return 0;
 }
 static unsigned los_walk_blocks(int64_t rows) { return (unsigned)((rows + LOSWALK_BLOCK - 1) / LOSWALK_BLOCK); }
+
+// the checks the chain calls share
+static int los_chain_check(int64_t nkept, int nsight, int nwalkers, int nclouds) {
+    if (nkept < 1 || nwalkers < 1 || nkept > BRUTUS_LOSCHAIN_MAX_SAMPLES ||
+        nkept * nwalkers > BRUTUS_LOSCHAIN_MAX_SAMPLES || nsight < 1 || nsight > BRUTUS_LOSFIELD_MAX_SIGHTLINES ||
+        nclouds < 0 || nclouds > BRUTUS_LOS_MAX_CLOUDS)
+        return fail(BRUTUS_EINVAL, "bad los chain dimensions (nkept=%lld, nsight=%d, nwalkers=%d, nclouds=%d)",
+                    (long long)nkept, nsight, nwalkers, nclouds);
+    return 0;
+}
+static int los_chain_check_q(int nq) {
+    if (nq < 1 || nq > BRUTUS_LOSCHAIN_MAX_Q) return fail(BRUTUS_EINVAL, "bad los chain quantiles (nq=%d)", nq);
+    return 0;
+}
+static LosChainDims los_chain_dims(int64_t nkept, int nsight, int nwalkers, int nclouds, const double *chain) {
+    return LosChainDims{chain, nkept, nsight, nwalkers, 4 + 2 * nclouds, (unsigned)(nkept * nwalkers)};
+}
+
+// the selection of `ncols` columns of `src` per sightline
+template <class Source>
+static int los_chain_select(const char *name, const LosChainDims &d, int ncols, int nq, const double *d_q,
+                            double *d_out, Source src, hipStream_t st) {
+    int tc = LOSCHAIN_HISTS / (2 * nq);
+    if (tc > LOSCHAIN_TC_MAX) tc = LOSCHAIN_TC_MAX;
+    const int ntiles = (ncols + tc - 1) / tc;
+    if ((int64_t)d.nsight * ntiles > INT32_MAX)
+        return fail(BRUTUS_EINVAL, "los chain: %d sightlines x %d column tiles are more workgroups than one launch takes",
+                    d.nsight, ntiles);
+    const LosChainSelect c{d, d_q, d_out, nq, ncols, tc, ntiles};
+    Timer tm(st);
+    tm.begin(name);
+    hipLaunchKernelGGL(k_los_chain_select<Source>, dim3((unsigned)((int64_t)d.nsight * ntiles)), dim3(LOSCHAIN_BLOCK), 0,
+                       st, c, src);
+    tm.end();
+    HIP_TRY(hipGetLastError());
+    tm.collect();
+    return 0;
+}
 }  // namespace
 
 extern "C" {
@@ -291,6 +332,68 @@ int brutus_los_walk_accept(int nsight, int nwalkers, int nclouds, int half, int6
                        d_theta_new, d_lnl_new, d_outside, d_u, d_theta, d_lnl, (unsigned long long *)d_naccept, d_chain,
                        d_chain_lnl);
     tm.end();
+    HIP_TRY(hipGetLastError());
+    tm.collect();
+    return 0;
+}
+
+// ---- a field's chains to its map (include/brutus_amd_los_chain.h) ------------------------------
+
+int brutus_los_chain_quantiles(int64_t nkept, int nsight, int nwalkers, int nclouds, const double *d_chain, int nq,
+                               const double *d_q, double *d_out, void *stream) {
+    if (int rc = los_chain_check(nkept, nsight, nwalkers, nclouds)) return rc;
+    if (int rc = los_chain_check_q(nq)) return rc;
+    if (!d_chain || !d_q || !d_out) return fail(BRUTUS_EINVAL, "NULL pointer");
+    const LosChainDims d = los_chain_dims(nkept, nsight, nwalkers, nclouds, d_chain);
+    return los_chain_select("k_los_chain_select_param", d, d.ncol, nq, d_q, d_out, ParamColumn{}, (hipStream_t)stream);
+}
+
+int brutus_los_chain_profile(int64_t nkept, int nsight, int nwalkers, int nclouds, const double *d_chain,
+                             int additive_foreground, int ngrid, const double *d_dgrid, int nq, const double *d_q,
+                             double *d_out, void *stream) {
+    if (int rc = los_chain_check(nkept, nsight, nwalkers, nclouds)) return rc;
+    if (int rc = los_chain_check_q(nq)) return rc;
+    if (ngrid < 1 || ngrid > BRUTUS_LOSCHAIN_MAX_GRID || additive_foreground < 0 || additive_foreground > 1)
+        return fail(BRUTUS_EINVAL, "bad los chain profile (ngrid=%d, additive_foreground=%d)", ngrid,
+                    additive_foreground);
+    if (!d_chain || !d_dgrid || !d_q || !d_out) return fail(BRUTUS_EINVAL, "NULL pointer");
+    const LosChainDims d = los_chain_dims(nkept, nsight, nwalkers, nclouds, d_chain);
+    ProfileColumn src{};
+    src.dgrid = d_dgrid;
+    src.nclouds = nclouds;
+    src.additive = additive_foreground;
+    return los_chain_select("k_los_chain_select_profile", d, ngrid, nq, d_q, d_out, src, (hipStream_t)stream);
+}
+
+size_t brutus_los_chain_workspace_bytes(int nsight, int nwalkers, int nclouds) {
+    if (nsight < 1 || nsight > BRUTUS_LOSFIELD_MAX_SIGHTLINES || nwalkers < 1 ||
+        nwalkers > BRUTUS_LOSCHAIN_MAX_SAMPLES || nclouds < 0 || nclouds > BRUTUS_LOS_MAX_CLOUDS)
+        return 0;
+    return align_up(sizeof(double) * (size_t)nsight * (size_t)(4 + 2 * nclouds) * 2 * (size_t)nwalkers);
+}
+
+int brutus_los_chain_moments(int64_t nkept, int nsight, int nwalkers, int nclouds, const double *d_chain,
+                             const double *d_lnl, double *d_mean, double *d_std, double *d_rhat, double *d_best,
+                             double *d_best_lnl, void *d_workspace, size_t workspace_bytes, void *stream) {
+    if (int rc = los_chain_check(nkept, nsight, nwalkers, nclouds)) return rc;
+    if (!d_chain || !d_mean || !d_std || !d_rhat || !d_workspace) return fail(BRUTUS_EINVAL, "NULL pointer");
+    if ((d_lnl == nullptr) != (d_best == nullptr) || (d_lnl == nullptr) != (d_best_lnl == nullptr))
+        return fail(BRUTUS_EINVAL, "ln L, the best sample and its ln L go together (all three or none)");
+    if (workspace_bytes < brutus_los_chain_workspace_bytes(nsight, nwalkers, nclouds))
+        return fail(BRUTUS_ENOMEM, "los chain workspace too small");
+    const LosChainDims d = los_chain_dims(nkept, nsight, nwalkers, nclouds, d_chain);
+    hipStream_t st = (hipStream_t)stream;
+    Timer tm(st);
+    tm.begin("k_los_chain_moments");
+    hipLaunchKernelGGL(k_los_chain_moments, dim3((unsigned)((int64_t)nsight * d.ncol)), dim3(LOSCHAIN_BLOCK), 0, st,
+                       LosChainMoments{d, d_mean, d_std, d_rhat, (double *)d_workspace});
+    tm.end();
+    if (d_lnl) {
+        tm.begin("k_los_chain_best");
+        hipLaunchKernelGGL(k_los_chain_best, dim3((unsigned)nsight), dim3(LOSCHAIN_BLOCK), 0, st,
+                           LosChainBest{d, d_lnl, d_best, d_best_lnl});
+        tm.end();
+    }
     HIP_TRY(hipGetLastError());
     tm.collect();
     return 0;

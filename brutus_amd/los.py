@@ -12,7 +12,10 @@ map): all sightlines' draws on the GPU, K profiles per sightline in one call
 and `LOSSamples`.  `LOSPrior` and `LOSFieldSampler` take the step from the likelihood of a field to
 its posterior: the prior transform on the device and an affine-invariant ensemble sampler that
 advances all sightlines together in the unit cube (`brutus_los_prior_transform`,
-`brutus_los_walk_*`); `LOS_walk_field_host` is the same chain in numpy.
+`brutus_los_walk_*`); `LOS_walk_field_host` is the same chain in numpy.  `LOSChainSummary` turns
+the chains of such a fit into the map on the device -- per sightline the quantiles of every
+parameter, the reddening profile with its credible band, mean / std / split-R-hat and the best
+sample (`brutus_los_chain_*`) --; `LOS_chain_summary_host` is its definition in numpy.
 
 Both forms weigh every sample against the ONE cloud bin its distance falls in, instead of the
 reference's `(Nclouds + 1, Nobj, Ndraws)` temporaries; the result is the reference's up to the
@@ -1093,3 +1096,283 @@ class LOSFieldSampler(object):
         if device_out:
             return chain, chain_lnl, frac
         return chain.cpu().numpy(), chain_lnl.cpu().numpy(), frac.cpu().numpy()
+
+
+# ---- a field's chains to its map ----------------------------------------------------------------
+_CHAIN_Q = (.025, .16, .5, .84, .975)
+
+
+def _check_chain(shape, lnl_shape, device):
+    """(nkept, S, W, P) of a chain's shape; `lnl_shape` None or that of its ln L."""
+    shape = tuple(int(n) for n in shape)
+    if len(shape) != 4 or min(shape) < 1:
+        raise ValueError("chain must have shape (nkept, S, W, Nparams), every one at least 1; got %s" % (shape,))
+    nkept, S, W, P = shape
+    if P < 4 or P % 2:
+        raise ValueError("chain must have Nparams = 4 + 2 Nclouds columns: [pb, s0, s, fred, d1, r1, ...]; got "
+                         "Nparams = %d" % P)
+    if device:
+        if (P - 4) // 2 > _lib.LOS_MAX_CLOUDS:
+            raise ValueError("%d clouds: the device form takes at most %d; the host form is "
+                             "LOS_chain_summary_host." % ((P - 4) // 2, _lib.LOS_MAX_CLOUDS))
+        if nkept * W > _lib.LOSCHAIN_MAX_SAMPLES or S > _lib.LOSFIELD_MAX_SIGHTLINES:
+            raise ValueError("the device form takes at most %d samples per column and %d sightlines; got "
+                             "nkept * W = %d, S = %d" % (_lib.LOSCHAIN_MAX_SAMPLES, _lib.LOSFIELD_MAX_SIGHTLINES,
+                                                         nkept * W, S))
+    if lnl_shape is not None and tuple(lnl_shape) != shape[:3]:
+        raise ValueError("lnl must have shape (nkept, S, W) = %s; got %s" % (shape[:3], tuple(lnl_shape)))
+    return shape
+
+
+def _check_q(q, device):
+    q = np.atleast_1d(np.asarray(q, dtype=np.float64))
+    if q.ndim != 1 or q.size < 1 or (device and q.size > _lib.LOSCHAIN_MAX_Q):
+        raise ValueError("q must be 1 to %d quantiles; got shape %s" % (_lib.LOSCHAIN_MAX_Q, q.shape))
+    bad = ~((q >= 0.) & (q <= 1.))
+    if bad.any():
+        raise ValueError("q must lie in [0, 1]; got %r" % (float(q[bad][0]),))
+    return np.ascontiguousarray(q)
+
+
+def _check_dgrid(dgrid, device):
+    dgrid = np.atleast_1d(np.asarray(dgrid, dtype=np.float64))
+    if dgrid.ndim != 1 or dgrid.size < 1 or (device and dgrid.size > _lib.LOSCHAIN_MAX_GRID):
+        raise ValueError("dgrid must be 1 to %d distance moduli; got shape %s" % (_lib.LOSCHAIN_MAX_GRID, dgrid.shape))
+    bad = ~np.isfinite(dgrid)
+    if bad.any():
+        raise ValueError("dgrid must be finite; got %r at %d" % (float(dgrid[bad][0]), int(np.nonzero(bad)[0][0])))
+    return np.ascontiguousarray(dgrid)
+
+
+def _chain_quantiles_host(cols, q):
+    """`(..., nq)` quantiles `q` of the columns `cols (..., N)`, as `LOS_chain_summary_host` defines
+    them."""
+    cols = np.ascontiguousarray(cols, dtype=np.float64)
+    N = cols.shape[-1]
+    # ascending with -0 before +0: as signed integers, the negative floats with their lower 63
+    # bits flipped (its own inverse)
+    keys = cols.view(np.int64)
+    keys = np.sort(np.where(keys < 0, keys ^ np.int64(0x7fffffffffffffff), keys), axis=-1)
+    xs = np.where(keys < 0, keys ^ np.int64(0x7fffffffffffffff), keys).view(np.float64)
+    pos = q * (N - 1)
+    j = np.floor(pos)
+    f = pos - j
+    j = j.astype(np.int64)
+    with np.errstate(all="ignore"):
+        x0, x1 = xs[..., j], xs[..., np.minimum(j + 1, N - 1)]
+        out = np.where(f == 0., x0, x0 + f * (x1 - x0))
+    out[np.isnan(cols).any(axis=-1)] = np.nan
+    return out
+
+
+def _chain_profile_host(th, dgrid, additive_foreground):
+    """`(ngrid, N)`: the model's reddening at `dgrid` of the samples `th (N, P)`."""
+    k = np.sum(th[:, None, 4::2] <= dgrid[None, :, None], axis=2)
+    vals = np.take_along_axis(th, 3 + 2 * k, axis=1)
+    if additive_foreground:
+        vals = np.where(k > 0, vals + th[:, 3:4], vals)
+    return np.ascontiguousarray(vals.T)
+
+
+def LOS_chain_summary_host(chain, lnl=None, q=_CHAIN_Q, dgrid=None, additive_foreground=False):
+    """
+    The summary of a field's chains in numpy: the definition of `LOSChainSummary` and the
+    reference of its device form.
+
+    With `N = nkept W`, sample `n = k W + w` of column `(s, p)` is `chain[k, s, w, p]`.
+
+    Parameters
+    ----------
+    chain : `~numpy.ndarray` of shape `(nkept, S, W, Nparams)`
+        The thetas `LOSFieldSampler.run` or `LOS_walk_field_host` returns (drop burn-in by slicing).
+    lnl : `~numpy.ndarray` of shape `(nkept, S, W)`, optional
+    q : sequence of floats in `[0, 1]`, optional
+    dgrid : `~numpy.ndarray` of shape `(ngrid,)`, optional
+        Finite distance moduli, in any order.
+    additive_foreground : bool, optional
+        The likelihood's flag.
+
+    Returns
+    -------
+    dict of
+    quantiles `(S, Nparams, nq)`
+        A column sorted ascending (`-0` before `+0`), `pos = q (N - 1)`, `j = floor(pos)`,
+        `f = pos - j`: `x_j` for `f == 0`, else `x_j + f (x_{j+1} - x_j)`, rounded as written --
+        `np.percentile` up to rounding.  NaN for every `q` of a column that holds a NaN.
+    profile `(S, ngrid, nq)`, with `dgrid`
+        Those quantiles of the model's reddening at every `mu` of `dgrid`: for a sample, with `k`
+        the number of cloud distances `theta[4 + 2 i] <= mu` (the bin the likelihood gives a star
+        at that distance), `theta[3]` for `k = 0`, else `theta[3 + 2 k]`, plus `theta[3]` (one
+        rounding) if `additive_foreground`.  With a dust template the cloud values are the
+        rescalings of the template and are returned as they are.
+    mean, std, rhat `(S, Nparams)`
+        Mean and standard deviation (ddof = 1) over the `N` samples of a column.  `rhat` is the
+        split-R-hat over `2 W` sequences, per walker its first and its last `L = nkept // 2`
+        kept steps (an odd middle step belongs to neither): with `Wv` the mean of the sequences'
+        variances and `B / L` the variance of their means (both ddof = 1),
+        `sqrt(((L - 1) / L Wv + B / L) / Wv)`; NaN for `nkept < 4`.  Every variance is two-pass
+        on values shifted by the first of them: equal values have variance exactly 0.  A
+        heuristic: the walkers of a stretch move are not independent chains, and values near 1
+        are necessary for convergence, not sufficient.
+    best_theta `(S, Nparams)`, best_lnl `(S,)`, with `lnl`
+        The sample with the largest `lnl` of a sightline, the first in the order of `n` among
+        equals; a NaN never wins, and a sightline of NaNs alone gives NaN throughout.
+    """
+    chain = np.asarray(chain, dtype=np.float64)
+    if lnl is not None:
+        lnl = np.asarray(lnl, dtype=np.float64)
+    nkept, S, W, P = _check_chain(chain.shape, None if lnl is None else lnl.shape, False)
+    q = _check_q(q, False)
+    N = nkept * W
+    cols = chain.transpose(1, 3, 0, 2)                     # (S, P, nkept, W): a column is its last two
+    out = dict(quantiles=_chain_quantiles_host(cols.reshape(S, P, N), q))
+    if dgrid is not None:
+        dgrid = _check_dgrid(dgrid, False)
+        rows = chain.transpose(1, 0, 2, 3).reshape(S, N, P)
+        out["profile"] = np.stack([_chain_quantiles_host(_chain_profile_host(rows[s], dgrid, additive_foreground), q)
+                                   for s in range(S)])
+    with np.errstate(all="ignore"):
+        x0 = cols[..., :1, :1]
+        d = cols - x0
+        m = d.sum(axis=(-2, -1), keepdims=True) / N
+        out["mean"] = (x0 + m)[..., 0, 0]
+        out["std"] = np.sqrt(np.square(d - m).sum(axis=(-2, -1)) / (N - 1))
+        L = nkept // 2
+        if nkept < 4:
+            out["rhat"] = np.full((S, P), np.nan)
+        else:
+            seqs = np.concatenate([cols[..., :L, :], cols[..., nkept - L:, :]], axis=-1)     # (S, P, L, 2 W)
+            first = seqs[..., :1, :]
+            d = seqs - first
+            sm = d.sum(axis=-2, keepdims=True) / L
+            var = np.square(d - sm).sum(axis=-2) / (L - 1)
+            means = (first + sm)[..., 0, :]
+            Wv = var.sum(axis=-1) / (2 * W)
+            dm = means - means[..., :1]
+            mm = dm.sum(axis=-1, keepdims=True) / (2 * W)
+            BL = np.square(dm - mm).sum(axis=-1) / (2 * W - 1)
+            out["rhat"] = np.sqrt(((L - 1) / L * Wv + BL) / Wv)
+    if lnl is not None:
+        out["best_theta"], out["best_lnl"] = np.full((S, P), np.nan), np.full(S, np.nan)
+        for s in range(S):
+            flat = lnl[:, s].reshape(N)
+            valid = np.nonzero(~np.isnan(flat))[0]
+            if valid.size:
+                n = valid[np.argmax(flat[valid])]
+                out["best_theta"][s], out["best_lnl"][s] = chain[n // W, s, n % W], flat[n]
+    return out
+
+
+class LOSChainSummary(object):
+    """The chains of a field on the device, reduced there to its map.
+
+    `LOSChainSummary(chain, lnl=None, additive_foreground=False, device="cuda", field=None)`:
+    `chain` is `(nkept, S, W, Nparams)` float64 thetas as `LOSFieldSampler.run` returns them -- a
+    tensor on a GPU, kept as it is (no copy, no synchronisation; made contiguous once if it is
+    not), or a numpy array, copied once to `device`.  Drop burn-in by slicing, `chain[k0:]`.
+    `lnl` is `(nkept, S, W)` or None.  `field=<LOSField>` takes `additive_foreground` (and, for a
+    numpy chain, the device) from the field.  Any `W >= 1`, at most 32 clouds, `nkept W <= 2^24`.
+
+    Every method is `LOS_chain_summary_host`'s entry of that name, which defines it: numpy out
+    with `device_out=False`, tensors with `device_out=True` (nothing waits for the device).
+      `quantiles(q)` -> `(S, Nparams, nq)` and `profile(dgrid, q)` -> `(S, ngrid, nq)`, at most 16
+        `q` and 4096 grid points: an exact selection (MSD radix select on order-preserving keys),
+        the host form's bytes.  `profile` is the reddening `E(mu)` with its credible band; with a
+        dust template the cloud values are the template's rescalings, returned as they are.
+      `moments()` -> `mean, std, rhat`, each `(S, Nparams)`, the host form's up to the order of
+        the sums.  `rhat` is a heuristic: the walkers of a stretch move are not independent chains.
+      `best()` -> `theta (S, Nparams), lnl (S,)`; `ValueError` without `lnl`.
+    A sightline's results are the same bytes alone or in a field, in any order, from call to call.
+    There is no host fallback: without the library or a GPU the constructor raises `BrutusError`.
+    """
+
+    def __init__(self, chain, lnl=None, additive_foreground=False, device="cuda", field=None):
+        if field is not None:
+            if not isinstance(field, LOSField):
+                raise ValueError("field must be a LOSField")
+            additive_foreground, device = bool(field._p.additive_foreground), field.device
+        self.additive_foreground = bool(additive_foreground)
+        on_gpu = lambda x: hasattr(x, "is_cuda") and x.is_cuda
+        as_host = lambda x: x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x)
+        if not on_gpu(chain):
+            chain = as_host(chain)
+        if lnl is not None and not on_gpu(lnl):
+            lnl = as_host(lnl)
+        self.nkept, self.nsightlines, self.nwalkers, self.nparams = _check_chain(
+            chain.shape, None if lnl is None else lnl.shape, True)
+        self.nclouds = (self.nparams - 4) // 2
+        self._L = _lib.lib()
+        self._torch = torch = _torch("LOSChainSummary only runs on the HIP path. The host form is "
+                                     "LOS_chain_summary_host.")
+        if on_gpu(chain):
+            if chain.dtype != torch.float64:
+                raise ValueError("chain must be float64; got %s" % (chain.dtype,))
+            self._chain = chain.detach().contiguous()
+        else:
+            if torch.device(device).type != "cuda":
+                raise ValueError("LOSChainSummary needs a GPU device; got %r" % (device,))
+            self._chain = to_device(np.ascontiguousarray(chain, dtype=np.float64), np.float64, device)
+        self.device = self._chain.device
+        if lnl is None:
+            self._lnl = None
+        elif on_gpu(lnl):
+            if lnl.dtype != torch.float64 or lnl.device != self.device:
+                raise ValueError("lnl must be float64 on %s; got %s on %s" % (self.device, lnl.dtype, lnl.device))
+            self._lnl = lnl.detach().contiguous()
+        else:
+            self._lnl = to_device(np.ascontiguousarray(lnl, dtype=np.float64), np.float64, self.device)
+
+    def _dims(self):
+        return self.nkept, self.nsightlines, self.nwalkers, self.nclouds, self._chain
+
+    def _new(self, *shape):
+        return self._torch.empty(shape, dtype=self._torch.float64, device=self.device)
+
+    def _give(self, device_out, *tensors):
+        out = tensors if device_out else tuple(t.cpu().numpy() for t in tensors)
+        return out[0] if len(out) == 1 else out
+
+    def quantiles(self, q=_CHAIN_Q, device_out=False):
+        """`(S, Nparams, nq)`: the quantiles `q` of every parameter of every sightline."""
+        torch = self._torch
+        q = _check_q(q, True)
+        out = self._new(self.nsightlines, self.nparams, q.size)
+        with torch.cuda.device(self.device):
+            _lib.check(self._L.brutus_los_chain_quantiles(
+                *self._dims(), q.size, to_device(q, np.float64, self.device), out, _stream_ptr(torch)))
+        return self._give(device_out, out)
+
+    def profile(self, dgrid, q=_CHAIN_Q, device_out=False):
+        """`(S, ngrid, nq)`: the quantiles `q`, over a sightline's samples, of the model's reddening
+        at every distance modulus of `dgrid` (finite, in any order)."""
+        torch = self._torch
+        q, dgrid = _check_q(q, True), _check_dgrid(dgrid, True)
+        out = self._new(self.nsightlines, dgrid.size, q.size)
+        with torch.cuda.device(self.device):
+            _lib.check(self._L.brutus_los_chain_profile(
+                *self._dims(), int(self.additive_foreground), dgrid.size, to_device(dgrid, np.float64, self.device),
+                q.size, to_device(q, np.float64, self.device), out, _stream_ptr(torch)))
+        return self._give(device_out, out)
+
+    def _moments(self, want_best):
+        torch = self._torch
+        S, P = self.nsightlines, self.nparams
+        mean, std, rhat = self._new(S, P), self._new(S, P), self._new(S, P)
+        best, best_lnl = (self._new(S, P), self._new(S)) if want_best else (None, None)
+        nbytes = int(self._L.brutus_los_chain_workspace_bytes(S, self.nwalkers, self.nclouds))
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self._L.brutus_los_chain_moments(
+                *self._dims(), self._lnl if want_best else None, mean, std, rhat, best, best_lnl, ws, nbytes,
+                _stream_ptr(torch)))
+        return mean, std, rhat, best, best_lnl
+
+    def moments(self, device_out=False):
+        """`mean, std, rhat`, each `(S, Nparams)`."""
+        return self._give(device_out, *self._moments(False)[:3])
+
+    def best(self, device_out=False):
+        """`theta (S, Nparams), lnl (S,)` of the sample with the largest `lnl` of every sightline."""
+        if self._lnl is None:
+            raise ValueError("best() needs lnl; got lnl=None")
+        return self._give(device_out, *self._moments(True)[3:])

@@ -648,6 +648,9 @@ void brutus_enable_timing(int on);
 /* ---- fitting a field of sightlines: the LOS prior transform and the ensemble sampler's kernels ---- */
 #include "brutus_amd_los_walk.h"
 
+/* ---- a field's chains to its dust map: quantiles, reddening profile, moments and R-hat ---- */
+#include "brutus_amd_los_chain.h"
+
 #ifdef __cplusplus
 }
 #endif
