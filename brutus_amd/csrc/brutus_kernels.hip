@@ -102,8 +102,9 @@ struct Workspace {
     int32_t *bandn;                    // (S * NCHUNK,) band-queue fill of k_sel_classify
     unsigned long long *mask, *dmask;  // (S, nmodel_pad / 64) selected / selected-and-derived
     unsigned long long *smask;         // candidate bit-mask, same layout
-    double *step_st, *lnprob_st;       // (S * nmodel,) worst case: flux-phase step size and final
-                                       // first-cut statistic, by candidate-list position
+    uint16_t *step_st;                 // (S * nmodel,) worst case, by candidate-list position: flux-phase step size as
+                                       // the number of its divisions by 1.2
+    double *lnprob_st;                 // (S * nmodel,) ... and final first-cut statistic
     Star32 *s32;                       // (S,)
     float *lnlp32, *lnpr32;            // (S, nmodel) float32 statistics
     float *part32, *st32;              // (nblk2, S, NV32), (S, NV32)
@@ -182,7 +183,8 @@ Workspace carve(char *base, int64_t nmodel, int nstar, bool fit) {
         w.lnlp32 = (float *)cv.take_big(sizeof(float) * pairs);
         w.lnpr32 = (float *)cv.take_big(sizeof(float) * pairs);
         w.surv_idx = (int32_t *)cv.take_big(sizeof(int32_t) * pairs);
-        w.step_st = (double *)cv.take_big(sizeof(double) * pairs);
+        // (eight bytes per pair as before the step became a count: brutus_workspace_bytes keeps its value)
+        w.step_st = (uint16_t *)cv.take_big(sizeof(double) * pairs);
         w.lnprob_st = (double *)cv.take_big(sizeof(double) * pairs);
     }
     w.bytes = align_big(cv.off) + (base ? 0 : (size_t)4 << 20);     // (sizing: room for the base's own offset)
@@ -366,6 +368,7 @@ struct FitCall {
     // set by dispatch_fit
     int flux_rounds = 4;    // BRUTUS_FLUX_ROUNDS (development switch): continuations of the device-driven flux phase
     bool list_fast = true;  // BRUTUS_LIST_FAST (development switch): the plane passes that skip dead blocks
+    bool top1_screen = true;        // BRUTUS_TOP1_SCREEN (development switch): k_top1's hot lists hold pairs with a nominee only
     int list_run = -LIST_RUN;       // BRUTUS_LIST_RUN (development switch): the list kernels' run length, see ItemWalk
     bool audited = false;   // this call's float32 bound is audited and ENFORCED (audit_verdict)
     float *aud = nullptr;   // w.aud on an audited call and with BRUTUS_AUDIT=1 (recorded for the caller to read)
@@ -551,7 +554,22 @@ int classify_on_host(FitCall &c) {
     return 0;
 }
 
-// exact cull threshold (k_hot_list + k_top1: the hot (block, star) pairs as a list), then the
+// The hot (block, star) list of a k_top1 launch into w.hot / *nhot.  mode 0: cull statistic (plane lnlp32, level nomA);
+// mode 1: first-cut statistic (plane lnpr32, level nomB = maxsurv - eps, formed here).
+void launch_hot_list(const FitCall &c, int mode, int32_t *nhot) {
+    const Workspace &w = c.w;
+    const double *nomA = mode == 0 ? w.nomA : nullptr, *maxsurv = mode == 0 ? nullptr : w.maxsurv;
+    double *nomB = mode == 0 ? nullptr : w.nomB;
+    if (c.top1_screen)
+        hipLaunchKernelGGL(k_hot_list_screened, dim3(c.nstar, HOT_SPLIT), dim3(HOT_T), 0, c.st, c.nblkx, c.nstar, mode,
+                           c.nmodel, w.part32, mode == 0 ? w.lnlp32 : w.lnpr32, nomA, maxsurv, w.s32, nomB, w.part,
+                           w.hot, nhot);
+    else
+        hipLaunchKernelGGL(k_hot_list, dim3(c.nstar), dim3(256), 0, c.st, c.nblkx, c.nstar, mode, w.part32, nomA,
+                           maxsurv, w.s32, nomB, w.part, w.hot, nhot);
+}
+
+// exact cull threshold (hot list + k_top1: the hot (block, star) pairs as a list), then the
 // candidates (lnl_p~ >= thr_cull - eps) as ordered lists
 template <int NB, bool RVF>
 void cull_candidates(FitCall &c) {
@@ -559,8 +577,7 @@ void cull_candidates(FitCall &c) {
     const int nstar = c.nstar;
     const dim3 blk(TILE);
     c.tm.begin("k_top");
-    hipLaunchKernelGGL(k_hot_list, dim3(nstar), dim3(256), 0, c.st, c.nblkx, nstar, 0, w.part32, w.nomA,
-                       (const double *)nullptr, w.s32, (double *)nullptr, w.part, w.hot, w.ctr + 4);
+    launch_hot_list(c, 0, w.ctr + 4);
     hipLaunchKernelGGL((k_top1<NB, RVF>), dim3(TOP_BLOCKS), blk, 0, c.st, c.grid, c.nmodel, c.nmodel_pad, nstar,
                        w.stars, c.p, w.k1, c.ntile, 0, w.lnlp32, w.nomA, w.hot, w.ctr + 4, w.part, c.aud);
     c.tm.end();
@@ -669,8 +686,7 @@ void select_and_derive(FitCall &c) {
     const int nstar = c.nstar;
     const dim3 blk(TILE);
     c.tm.begin("k_top");
-    hipLaunchKernelGGL(k_hot_list, dim3(nstar), dim3(256), 0, c.st, c.nblkx, nstar, 1, w.part32,
-                       (const double *)nullptr, w.maxsurv, w.s32, w.nomB, w.part, w.hot, w.ctr + 5);
+    launch_hot_list(c, 1, w.ctr + 5);
     hipLaunchKernelGGL((k_top1<NB, RVF>), dim3(TOP_BLOCKS), blk, 0, c.st, c.grid, c.nmodel, c.nmodel_pad, nstar,
                        w.stars, c.p, w.k1, c.ntile, 1, w.lnpr32, w.nomB, w.hot, w.ctr + 5, w.part,
                        c.aud ? c.aud + nstar : nullptr);
@@ -779,6 +795,8 @@ int dispatch_fit(int nb, FitCall &c) {
     c.flux_rounds = env_int("BRUTUS_FLUX_ROUNDS", 4);
     // BRUTUS_LIST_FAST=0: the plane passes of the cull and the first cut as they were, every block read (A/B, tests)
     c.list_fast = env_int("BRUTUS_LIST_FAST", 1) != 0;
+    // BRUTUS_TOP1_SCREEN=0: k_top1 walks every (block, star) pair whose float32 maximum is hot, as it did (A/B, tests)
+    c.top1_screen = env_int("BRUTUS_TOP1_SCREEN", 1) != 0;
     // BRUTUS_LIST_RUN=<n>: runs of exactly n work items in the list kernels, 1 = item by item (A/B, tests)
     c.list_run = env_int("BRUTUS_LIST_RUN", 0);
     if (c.list_run < 1 || c.list_run > 64) c.list_run = -LIST_RUN;
@@ -1092,6 +1110,8 @@ int brutus_debug_copy(void *d_workspace, size_t workspace_bytes, int64_t nmodel,
         case 9: src = w.status; have = 4 * (size_t)nstar; break;
         case 10: src = w.part32; have = 4 * (size_t)((pad_models(nmodel) / TILE + F2_T - 1) / F2_T) * nstar * NV32; break;
         case 11: src = w.candS; have = 8 * (size_t)nstar; break;
+        case 12: src = w.nomA; have = 8 * (size_t)nstar; break;       // nominee levels of the two k_top1 launches
+        case 13: src = w.nomB; have = 8 * (size_t)nstar; break;
         default: return fail(BRUTUS_EINVAL, "unknown array %d", which);
     }
     if (nbytes > have) return fail(BRUTUS_EINVAL, "array %d holds %zu bytes, %zu requested", which, have, nbytes);

@@ -613,6 +613,78 @@ k_hot_list(int nblkx, int nstar, int mode, const float *__restrict__ part32,
     }
 }
 
+// k_hot_list, screened (default; BRUTUS_TOP1_SCREEN=0 restores the kernel above).  A block maximum at
+// the nominee level says little in the second launch: the maximum was taken before the flux phase
+// tagged the survivors, and the survivors are exactly the models up there -- of the bench's 15 400
+// hot pairs of that launch NONE holds a nominee (tools/top1_density.py), and of the first launch's
+// 1 080 a quarter hold none (the NaN flag of column 9 speaks for both statistics).  k_top1, bound by
+// its float64 code to two waves per SIMD, paid one dependent chain of round trips per such pair, 30
+// pairs in a row per workgroup.  Here, at full occupancy, a wave reads a hot block's 2048 plane entries (all loads in
+// flight at once) and applies k_top1's own nominee test: only a pair that holds a nominee is
+// listed, the others' partials are -inf as k_top1 would have left them.  HOT_SPLIT workgroups per
+// star share its blocks; a workgroup lists its hot blocks in LDS and its waves take them in turn.
+constexpr int HOT_SPLIT = 8, HOT_T = 256;
+__global__ void __launch_bounds__(HOT_T)
+k_hot_list_screened(int nblkx, int nstar, int mode, int64_t nmodel, const float *__restrict__ part32,
+                    const float *__restrict__ plane32, const double *__restrict__ nomA,
+                    const double *__restrict__ maxsurv, const Star32 *__restrict__ s32,
+                    double *__restrict__ nomB, double *__restrict__ part, int32_t *__restrict__ hot,
+                    int32_t *__restrict__ nhot) {
+    constexpr int CAP = 4 * HOT_T;      // blocks of one workgroup: 8192 blocks = 16.8 M models per HOT_SPLIT-th of a star
+    __shared__ int s_blk[CAP];
+    __shared__ int s_nb;
+    const int s = blockIdx.x;
+    double nm;
+    if (mode == 0) {
+        nm = nomA[s];
+    } else {
+        nm = maxsurv[s] - (double)s32[s].eps;
+        if (threadIdx.x == 0 && blockIdx.y == 0) nomB[s] = nm;
+    }
+    const float *__restrict__ row = plane32 + (int64_t)s * nmodel;
+    const int lane = threadIdx.x & 63;
+    // the workgroup's blocks y, y + HOT_SPLIT, ... in passes of CAP
+    for (int base = blockIdx.y; base < nblkx; base += CAP * HOT_SPLIT) {
+        if (threadIdx.x == 0) s_nb = 0;
+        __syncthreads();
+        for (int k = threadIdx.x; k < CAP; k += HOT_T) {
+            const int b = base + k * HOT_SPLIT;
+            if (b >= nblkx) break;
+            const float *pp = part32 + ((int64_t)b * nstar + s) * NV32;
+            const bool is_hot = !((double)pp[6 + mode] < nm) || pp[9] > 0.f;
+            if (is_hot) s_blk[atomicAdd(&s_nb, 1)] = b;
+            else part[(int64_t)b * nstar + s] = -INFINITY;
+        }
+        __syncthreads();
+        const int nb = s_nb;
+        for (int q = threadIdx.x >> 6; q < nb; q += HOT_T / 64) {       // (wave-uniform)
+            const int b = s_blk[q];
+            const int64_t i0 = (int64_t)b * (F2_T * TILE) + lane;
+            constexpr int U = F2_T * TILE / 64;
+            float v[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int64_t i = i0 + 64 * u;
+                v[u] = row[i < nmodel ? i : nmodel - 1];        // (clamped address, see k_cmp_count32)
+            }
+            bool any = false;
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                // k_top1's test: not below the level (NaN counts); mode 1: and not a survivor (tagged)
+                bool mine = i0 + 64 * u < nmodel && !((double)v[u] < nm);
+                if (mode == 1 && mine) mine = !surv_is(v[u]);
+                any |= mine;
+            }
+            const bool listed = __ballot(any) != 0ull;
+            if (lane == 0) {
+                if (listed) hot[atomicAdd(nhot, 1)] = b * BRUTUS_MAX_BATCH + s;
+                else part[(int64_t)b * nstar + s] = -INFINITY;
+            }
+        }
+        __syncthreads();        // (the list is rebuilt by the next pass)
+    }
+}
+
 template <int NB, bool RVF>
 __global__ void __launch_bounds__(TILE, top_waves(NB))
 k_top1(const float *__restrict__ grid, int64_t nmodel, int64_t nmodel_pad, int nstar,

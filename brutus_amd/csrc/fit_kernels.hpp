@@ -975,18 +975,26 @@ struct RecPlanes {
 // (fitting.py:758-759) whose outcome is marked in the float32 plane (survivor tag / left
 // alone, see surv_tag), two iterations from lnl_old = -1e300 for the survivors;
 // continuation: one iteration from the stored state.  A survivor's results go to the
-// record planes at its LIST POSITION q (full-line writes), its step size and final
-// first-cut statistic lnprob to the workspace arrays step_st / lnprob_st at the same
-// position.  Per work item and wave: L = max lnl_new, T = max{lnl_new : |dlnl| > ltol},
+// record planes at its LIST POSITION q (full-line writes); at the same position of the
+// workspace arrays go
+//   step_st    how often its step size was divided by 1.2 (two bytes instead of the double: a
+//              continuation launch repeats the divisions and so rebuilds the same double; the
+//              count saturates at STEP_SHRUNK_MAX, long after the step has underflowed to 0),
+//   lnprob_st  its final first-cut statistic lnprob, which the classify passes read.  (Left out for
+//              the stars without a scale prior, whose lnprob is the record's lnlike with non-finite
+//              values mapped to -BIG, and read from that plane instead, k_sel_classify_live went from
+//              133 to 183 us alone on the device: profiles/top1_dense_ab.txt.)
+// Per work item and wave: L = max lnl_new, T = max{lnl_new : |dlnl| > ltol},
 // M = max final lnprob.  Entries at or beyond the record capacity are skipped (the host
 // sees ncand > capacity and reports BRUTUS_ENOMEM).
+constexpr int STEP_SHRUNK_MAX = 65535;
 template <int NB, bool RVF, bool FIRST>
 __global__ void __launch_bounds__(TILE, fflux_waves(NB, FIRST))
 k_fflux(const float *__restrict__ grid, int64_t nmodel, int64_t nmodel_pad, int nstar,
         const StarPrep *__restrict__ stars, DevParams p, const int32_t *__restrict__ k1,
         const int32_t *__restrict__ k2state, const int32_t *__restrict__ cand_idx,
         const int64_t *__restrict__ cand_off, const int32_t *__restrict__ wbase,
-        const ItemGeom *__restrict__ items, RecPlanes rec, double *__restrict__ step_st,
+        const ItemGeom *__restrict__ items, RecPlanes rec, uint16_t *__restrict__ step_st,
         double *__restrict__ lnprob_st, double *__restrict__ part, float *__restrict__ surv32,
         const double *__restrict__ thr_cull, const int32_t *__restrict__ act, int nact,
         const int32_t *__restrict__ nact_dev, int run) {
@@ -1046,7 +1054,8 @@ k_fflux(const float *__restrict__ grid, int64_t nmodel, int64_t nmodel_pad, int 
         const int64_t o = (int64_t)s * nmodel + i;
         if (!FIRST && live) go = surv_is(surv32[o]);
         Mle m;
-        double o_lnl = 0., o_lnprob = 0., o_av = 0., o_rv = 0., o_step = 0.;
+        double o_lnl = 0., o_lnprob = 0., o_av = 0., o_rv = 0.;
+        int o_shrunk = 0, shrunk = 0;
         bool store = false;
         if (go) {
             Coef<NB> c;
@@ -1092,7 +1101,11 @@ k_fflux(const float *__restrict__ grid, int64_t nmodel, int64_t nmodel_pad, int 
             } else {
                 av = r_av[q];
                 rv = RVF ? p.rv_mean : r_rv[q];       // pinned Rv is not stored
-                step = step_st[q];
+                // the step as the iterations before left it: 1.0 divided `shrunk` times by 1.2, the
+                // same divisions again (once it has reached zero it stays there)
+                shrunk = step_st[q];
+                step = 1.0;
+                for (int k = 0; k < shrunk && step > 0.; ++k) step /= 1.2;
                 lnl_old = -0.5 * r_chi2[q];
             }
             mle_list<NB, RVF, false>(c, R, F0, Fc, sp, p, av, rv, s_tbl, m);
@@ -1124,7 +1137,10 @@ k_fflux(const float *__restrict__ grid, int64_t nmodel, int64_t nmodel_pad, int 
                 }
                 lnl_new = -0.5 * m.chi2;
                 dl = fabs(lnl_new - lnl_old);
-                if (lnl_new < lnl_old) step /= 1.2;
+                if (lnl_new < lnl_old) {
+                    step /= 1.2;
+                    if constexpr (!FIRST) shrunk = shrunk < STEP_SHRUNK_MAX ? shrunk + 1 : shrunk;
+                }
                 lnl_old = lnl_new;
             }
             if (go) {
@@ -1132,7 +1148,10 @@ k_fflux(const float *__restrict__ grid, int64_t nmodel, int64_t nmodel_pad, int 
                 o_lnprob = first_cut_lnprob(sp, o_lnl, m.scale, m.i00);
                 o_av = av;
                 o_rv = rv;
-                o_step = step;
+                // (the opening launch's two iterations leave one of three steps: read the count off the
+                // step instead of carrying a counter through the register-critical loop)
+                if constexpr (FIRST) o_shrunk = step == 1.0 ? 0 : step == 1.0 / 1.2 ? 1 : 2;
+                else o_shrunk = shrunk;
                 M = o_lnprob;
                 if (lnl_new == lnl_new) {
                     L = lnl_new;
@@ -1160,7 +1179,7 @@ k_fflux(const float *__restrict__ grid, int64_t nmodel, int64_t nmodel_pad, int 
             FF_ST(rec.plane(8), m.i11);
             FF_ST(rec.plane(9), m.i12);
             FF_ST(rec.plane(10), m.i22);
-            FF_ST(step_st, o_step);
+            FF_ST(step_st, (uint16_t)o_shrunk);
             FF_ST(lnprob_st, o_lnprob);
 #undef FF_ST
         }

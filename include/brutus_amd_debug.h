@@ -112,7 +112,8 @@ int brutus_debug_math(int which, const double *d_x, double *d_y, int64_t n,
  * (BRUTUS_AUDIT=1); 5: per-star float32 block; 6, 7: exact cull / first-cut
  * thresholds (nstar,) f64; 8: float32 maxima (nstar, 10); 9: K1 status (nstar,) i32;
  * 10: float32 maxima per 2048-model block (nblock, nstar, 10) f32; 11: candidate level of the cull
- * (cull threshold - eps) (nstar,) f64. */
+ * (cull threshold - eps) (nstar,) f64; 12, 13: nominee levels of the exact maxima of the cull / first-cut
+ * statistic (k_top1) (nstar,) f64. */
 int brutus_debug_copy(void *d_workspace, size_t workspace_bytes, int64_t nmodel,
                       int nfilt, int nstar, int which, void *d_dst, size_t nbytes,
                       void *stream);
