@@ -338,6 +338,19 @@ OFFDIAG_SIGNATURES = {
 OFFDIAG_MAX_DRAWS, OFFDIAG_MAX_FILT, OFFDIAG_MAX_SAMPLES, OFFDIAG_MAX_BINS, OFFDIAG_MAX_Q = (
     4096, MAX_FILT, 1 << 27, 1024, 8)
 
+# and for include/brutus_amd_corner.h (pdf.PosteriorCorner; tests/test_corner_host.py compares this
+# table with that header parameter by parameter)
+CORNER_SIGNATURES = {
+    "brutus_corner_workspace_bytes": (_sz, [_i64, _i32, _i32]),
+    "brutus_corner_hist1d": (C.c_int, [_i64, _i32, _di32, _df64, _df64, _df64, _df64, _i64, _i32, _df64, _i32,
+                                       _i32, _dbl, _df64, _df64, _dv, _sz, _stream]),
+    "brutus_corner_hist2d": (C.c_int, [_i64, _i32, _di32, _df64, _df64, _df64, _df64, _i64, _i32, _df64, _i32,
+                                       _i32, _i32, _i32, _dbl, _dbl, _df64, _i32, _df64, _df64, _df64, _dv, _sz,
+                                       _stream]),
+}
+CORNER_MAX_BINS1D, CORNER_MAX_BINS2D, CORNER_MAX_LEVELS, CORNER_MAX_SIGMA, CORNER_MAX_OBJ, CORNER_MAX_CELLS = (
+    1024, 128, 16, 64., 1 << 21, 1 << 31)
+
 # and for include/brutus_amd_los_field.h (los.LOSField; tests/test_los_field_host.py compares this
 # table with that header parameter by parameter)
 LOS_FIELD_SIGNATURES = {
@@ -394,7 +407,7 @@ def lib():
                               + list(DUST_SIGNATURES.items()) + list(SUMMARY_SIGNATURES.items())
                               + list(PREDICTIVE_SIGNATURES.items()) + list(OFFDIAG_SIGNATURES.items())
                               + list(LOS_FIELD_SIGNATURES.items()) + list(LOS_WALK_SIGNATURES.items())
-                              + list(LOS_CHAIN_SIGNATURES.items())):
+                              + list(LOS_CHAIN_SIGNATURES.items()) + list(CORNER_SIGNATURES.items())):
         fn = getattr(L, name)   # AttributeError if the .so is stale
         fn.restype = res
         fn.argtypes = args

@@ -11,11 +11,10 @@
 #include "common.hpp"
 #include "fastmath.hpp"
 #include "post_kernels.hpp"
+#include "smooth_taps.hpp"
 
 namespace {
 
-constexpr int BP_NT = 256;
-constexpr int BP_MAXR = 2047;                       // largest smoothing radius, in bins
 constexpr double BP_FIX = 1125899906842624.0;       // 2^50: one unit of weight in the planes
 
 struct BinGrid {
@@ -44,12 +43,6 @@ __device__ __forceinline__ double bp_x(double d, int dist_type) {
     return 5. * log10(d) + 10.;
 }
 
-__device__ __forceinline__ double bp_wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 // saved draws: one lane per draw, one count per draw that falls on the grid
 __global__ void __launch_bounds__(BP_NT)
 k_binpdf_hist(int nobj, int nsamps, const double *__restrict__ dist, const double *__restrict__ red,
@@ -72,20 +65,10 @@ k_binpdf_convert(int64_t n, const unsigned long long *__restrict__ acc, double u
     if (i < n) out[i] = (float)((double)acc[i] * unit / nsamps);
 }
 
-// index j of a line of n values extended by `reflect`: (d c b a | a b c d | d c b a), repeated
-__device__ __forceinline__ int bp_reflect(int j, int n) {
-    if ((unsigned)j < (unsigned)n) return j;
-    const int p = 2 * n;
-    int m = j % p;
-    if (m < 0) m += p;
-    return m < n ? m : p - 1 - m;
-}
-
 // One axis of scipy.ndimage.gaussian_filter (order 0, mode `reflect`, truncate 4) on the float32
-// planes of all objects: the weights exp(-k^2 / (2 sigma^2)) / sum in float64 (LDS, made by the
-// workgroup), the symmetric sum of scipy's correlate1d accumulated in float64 from the far taps
-// inwards, stored as float32.  AXIS 0: along x with the object's own width sig_obj[o]; AXIS 1:
-// along y with sig_all.  A width <= 1e-15 (or NaN) copies the plane.  grid = (plane / 256, nobj).
+// planes of all objects: weights and taps as smooth_taps.hpp has them, stored as float32.
+// AXIS 0: along x with the object's own width sig_obj[o]; AXIS 1: along y with sig_all.  A width
+// <= 1e-15 (or NaN) copies the plane.  grid = (plane / 256, nobj).
 template <int AXIS>
 __global__ void __launch_bounds__(BP_NT)
 k_binpdf_smooth(int nx, int ny, const double *__restrict__ sig_obj, double sig_all,
@@ -102,34 +85,10 @@ k_binpdf_smooth(int nx, int ny, const double *__restrict__ sig_obj, double sig_a
         if (i < plane) dst[i] = src[i];
         return;
     }
-    const double r4 = 4. * sigma + 0.5;
-    const int r = r4 < (double)BP_MAXR ? (int)r4 : BP_MAXR;
-    const double a = -0.5 / (sigma * sigma);
-    double s = 0.;
-    for (int k = threadIdx.x; k <= r; k += BP_NT) {
-        const double v = exp(a * (double)(k * k));
-        w[k] = v;
-        s += k ? v + v : v;
-    }
-    s = bp_wave_sum(s);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
-    __syncthreads();
-    const double tot = (part[0] + part[1]) + (part[2] + part[3]);
-    for (int k = threadIdx.x; k <= r; k += BP_NT) w[k] = w[k] / tot;
-    __syncthreads();
+    const int r = bp_gauss_weights(sigma, w, part);
     if (i >= plane) return;
     const int x = (int)(i / ny), y = (int)(i - (int64_t)x * ny);
-    double t = (double)src[i] * w[0];
-    if (AXIS == 0) {
-        const float *col = src + y;
-        for (int k = r; k >= 1; --k)
-            t += ((double)col[(int64_t)bp_reflect(x - k, nx) * ny] +
-                  (double)col[(int64_t)bp_reflect(x + k, nx) * ny]) * w[k];
-    } else {
-        const float *row = src + (int64_t)x * ny;
-        for (int k = r; k >= 1; --k)
-            t += ((double)row[bp_reflect(y - k, ny)] + (double)row[bp_reflect(y + k, ny)]) * w[k];
-    }
+    const double t = bp_taps<AXIS>(src, i, x, y, nx, ny, r, w);
     dst[i] = (float)t;
 }
 

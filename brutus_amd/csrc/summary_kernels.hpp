@@ -61,18 +61,13 @@ __device__ __forceinline__ double summary_knot(const double *sinc, int j, double
     return j ? sinc[j - 1] / norm : 0.;
 }
 
-// One column of one object, from the lanes' keys to its nq quantiles: `key` / `pos` hold the
-// column (sample e = m T + t in slot m, the padding as the all-ones key), `wrow` the object's
-// weights, `dst` the column's nq results.  Sort, scan, knot search, interpolation and store as
-// the head of this file has them; ends at a barrier, after which xk / sinc are free again.
-// Called by every lane of the workgroup (k_summary_quantiles, k_predictive_quantiles).
+// The bitonic sort of (key, pos), ascending, as the head of this file has it: sample e = m T + t
+// in slot m of lane t, npad samples in all; xk (npad) and, WEIGHTED, xp (npad) are the exchange
+// buffers.  Every pass that touched LDS ends at a barrier.  Called by every lane of the workgroup
+// (summary_column; k_corner_hist of corner_kernels.hpp sorts its bin keys with it).
 template <bool WEIGHTED>
-__device__ __forceinline__ void summary_column(uint64_t (&key)[SUMMARY_MAX_E], uint32_t (&pos)[SUMMARY_MAX_E],
-                                               int nsamps, int npad, int T, int t, int E, uint64_t *xk,
-                                               double *sinc, uint32_t *xp, const double *__restrict__ wrow,
-                                               int nq, const double *__restrict__ qs,
-                                               double *__restrict__ dst) {
-    // ---- bitonic sort of (key, pos), ascending ----
+__device__ __forceinline__ void summary_sort(uint64_t (&key)[SUMMARY_MAX_E], uint32_t (&pos)[SUMMARY_MAX_E],
+                                             int npad, int T, int t, int E, uint64_t *xk, uint32_t *xp) {
     for (int k = 2; k <= npad; k <<= 1) {
         for (int j = k >> 1; j > 0; j >>= 1) {
             if (j < 64) {
@@ -103,6 +98,20 @@ __device__ __forceinline__ void summary_column(uint64_t (&key)[SUMMARY_MAX_E], u
             }
         }
     }
+}
+
+// One column of one object, from the lanes' keys to its nq quantiles: `key` / `pos` hold the
+// column (sample e = m T + t in slot m, the padding as the all-ones key), `wrow` the object's
+// weights, `dst` the column's nq results.  Sort, scan, knot search, interpolation and store as
+// the head of this file has them; ends at a barrier, after which xk / sinc are free again.
+// Called by every lane of the workgroup (k_summary_quantiles, k_predictive_quantiles).
+template <bool WEIGHTED>
+__device__ __forceinline__ void summary_column(uint64_t (&key)[SUMMARY_MAX_E], uint32_t (&pos)[SUMMARY_MAX_E],
+                                               int nsamps, int npad, int T, int t, int E, uint64_t *xk,
+                                               double *sinc, uint32_t *xp, const double *__restrict__ wrow,
+                                               int nq, const double *__restrict__ qs,
+                                               double *__restrict__ dst) {
+    summary_sort<WEIGHTED>(key, pos, npad, T, t, E, xk, xp);
 #pragma unroll
     for (int m = 0; m < SUMMARY_MAX_E; ++m)
         if (m < E) xk[m * T + t] = key[m];
@@ -189,6 +198,18 @@ __device__ __forceinline__ void summary_column(uint64_t (&key)[SUMMARY_MAX_E], u
     __syncthreads();                         // the next column overwrites xk / sinc
 }
 
+// sample `i` (object row + draw) of column c: the labels of model `mi` (-1: outside the table,
+// NaN) in table order, then Av, Rv, parallax = 1 / distance, distance
+__device__ __forceinline__ double summary_sample(int c, int nlab, int32_t mi, const double *__restrict__ labels,
+                                                 const double *__restrict__ dist, const double *__restrict__ red,
+                                                 const double *__restrict__ dred, int64_t i) {
+    if (c < nlab) return mi >= 0 ? labels[(int64_t)mi * nlab + c] : __longlong_as_double(0x7ff8000000000000ll);
+    if (c == nlab) return red[i];
+    if (c == nlab + 1) return dred[i];
+    if (c == nlab + 2) return 1. / dist[i];
+    return dist[i];
+}
+
 template <bool WEIGHTED>
 __global__ void __launch_bounds__(SUMMARY_MAX_T)
 k_summary_quantiles(int nsamps, int npad, const int32_t *__restrict__ idx, const double *__restrict__ dist,
@@ -226,17 +247,7 @@ k_summary_quantiles(int nsamps, int npad, const int32_t *__restrict__ idx, const
             key[m] = ~0ull;
             pos[m] = (uint32_t)e;
             if (m < E && e < nsamps) {
-                double x;
-                if (c < nlab)
-                    x = mi[m] >= 0 ? labels[(int64_t)mi[m] * nlab + c] : __longlong_as_double(0x7ff8000000000000ll);
-                else if (c == nlab)
-                    x = red[row + e];
-                else if (c == nlab + 1)
-                    x = dred[row + e];
-                else if (c == nlab + 2)
-                    x = 1. / dist[row + e];
-                else
-                    x = dist[row + e];
+                const double x = summary_sample(c, nlab, mi[m], labels, dist, red, dred, row + e);
                 key[m] = summary_key(x);
             }
         }

@@ -1,13 +1,17 @@
 // summary_unit.hip -- translation unit of libbrutus_amd.so: per-object posterior summaries
 // (brutus_summary_*; reference plotting.py:249-322, utils.py:718-762, summary_kernels.hpp) and the
 // posterior-predictive check (brutus_predictive_*; plotting.py:868-893, predictive_kernels.hpp) and
-// the photometric-offset residual maps (brutus_offdiag_*; plotting.py:939-1390, offdiag_kernels.hpp).
+// the photometric-offset residual maps (brutus_offdiag_*; plotting.py:939-1390, offdiag_kernels.hpp)
+// and the corner-plot marginals (brutus_corner_*; plotting.py:361-501, 1456-1543, corner_kernels.hpp).
 
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 
 #include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_segmented_radix_sort.hpp>
+#include <rocprim/iterator/counting_iterator.hpp>
+#include <rocprim/iterator/transform_iterator.hpp>
 
 #include "../../include/brutus_amd.h"
 
@@ -15,6 +19,8 @@
 #include "summary_kernels.hpp"
 #include "predictive_kernels.hpp"
 #include "offdiag_kernels.hpp"
+#include "smooth_taps.hpp"
+#include "corner_kernels.hpp"
 
 // the argument checks the two predictive calls share (seds: nq = 1, d_q = d_out)
 static int predictive_args(int64_t nobj, int nsamps, int64_t nmodel, int nfilt, int nq, const void *d_idx,
@@ -91,6 +97,75 @@ static int offdiag_pool_args(int64_t nobj, int64_t nuse, int nsamps) {
         nobj * nsamps > BRUTUS_OFFDIAG_MAX_SAMPLES || nuse * nsamps > BRUTUS_OFFDIAG_MAX_SAMPLES)
         return fail(BRUTUS_EINVAL, "bad offdiag pool dimensions (nobj=%lld, nuse=%lld, nsamps=%d)", (long long)nobj,
                     (long long)nuse, nsamps);
+    return 0;
+}
+
+// ---- the corner-plot marginals ----
+struct CornerOffsets {                           // where panel i of `cells` cells begins
+    unsigned cells;
+    __host__ __device__ unsigned operator()(unsigned i) const { return i * cells; }
+};
+
+static size_t corner_ws_bytes(int64_t nobj, int nbx, int nby) {
+    return 2 * align_up(sizeof(double) * (size_t)nobj * (size_t)nbx * (size_t)nby);
+}
+
+// the argument checks the two corner calls share (1-D: coly = -1, nby = 1)
+static int corner_args(int64_t nobj, int nsamps, int64_t nmodel, int nlab, int colx, int coly, int nbx, int nby,
+                       int maxbins, double sigx, double sigy, const void *d_idx, const void *d_dist,
+                       const void *d_red, const void *d_dred, const void *d_labels, const void *d_spans,
+                       const void *d_hist) {
+    const int ncol = nlab + 4;
+    if (nobj < 1 || nobj > BRUTUS_CORNER_MAX_OBJ || nsamps < 2 || nsamps > BRUTUS_SUMMARY_MAX_DRAWS || nlab < 0 ||
+        nlab > BRUTUS_SUMMARY_MAX_LABELS || nmodel < (nlab ? 1 : 0) || nmodel > INT32_MAX || colx < 0 ||
+        colx >= ncol || coly < -1 || coly >= ncol || nbx < 1 || nbx > maxbins || nby < 1 || nby > maxbins ||
+        nobj * nbx * nby > BRUTUS_CORNER_MAX_CELLS)
+        return fail(BRUTUS_EINVAL,
+                    "bad corner dimensions (nobj=%lld, nsamps=%d, nmodel=%lld, nlab=%d, columns %d and %d, bins %d x %d)",
+                    (long long)nobj, nsamps, (long long)nmodel, nlab, colx, coly, nbx, nby);
+    if (!(sigx >= 0. && sigx <= BRUTUS_CORNER_MAX_SIGMA && sigy >= 0. && sigy <= BRUTUS_CORNER_MAX_SIGMA))
+        return fail(BRUTUS_EINVAL, "bad corner smoothing widths (%g, %g bins)", sigx, sigy);
+    if (!d_idx || !d_dist || !d_red || !d_dred || !d_spans || !d_hist) return fail(BRUTUS_EINVAL, "NULL pointer");
+    if ((d_labels == nullptr) != (nlab == 0))
+        return fail(BRUTUS_EINVAL, "d_labels is NULL exactly when nlab is 0 (nlab=%d)", nlab);
+    return 0;
+}
+
+// histogram and smoothing of one panel of every object into d_hist; ws: two panels per object
+static int corner_panel(Timer &tm, int64_t nobj, int nsamps, const int32_t *d_idx, const double *d_dist,
+                        const double *d_red, const double *d_dred, const double *d_weights, int64_t nmodel,
+                        int nlab, const double *d_labels, int colx, int coly, int nbx, int nby, double sigx,
+                        double sigy, const double *d_spans, double *d_hist, double *ws, hipStream_t st) {
+    int npad = 64;
+    while (npad < nsamps) npad <<= 1;
+    const int threads = npad < SUMMARY_MAX_T ? npad : SUMMARY_MAX_T;
+    const size_t lds = (size_t)npad * (d_weights ? 16 : 8);
+    const bool fx = sigx > 1e-15, fy = sigy > 1e-15;
+    // (the last pass writes d_hist: with one filtered axis the histogram goes to the workspace)
+    double *first = fx != fy ? ws : d_hist;
+    tm.begin("k_corner_hist");
+    if (d_weights)
+        hipLaunchKernelGGL(k_corner_hist<true>, dim3((unsigned)nobj), dim3(threads), lds, st, nsamps, npad, d_idx,
+                           d_dist, d_red, d_dred, d_weights, nmodel, nlab, d_labels, colx, coly, nbx, nby, d_spans,
+                           first);
+    else
+        hipLaunchKernelGGL(k_corner_hist<false>, dim3((unsigned)nobj), dim3(threads), lds, st, nsamps, npad, d_idx,
+                           d_dist, d_red, d_dred, d_weights, nmodel, nlab, d_labels, colx, coly, nbx, nby, d_spans,
+                           first);
+    tm.end();
+    const int nblk = (nbx * nby + BP_NT - 1) / BP_NT;
+    const dim3 grid((unsigned)(nobj * nblk));                // <= 2^21 * 64
+    if (fx) {
+        tm.begin("k_corner_smooth");
+        hipLaunchKernelGGL(k_corner_smooth<0>, grid, dim3(BP_NT), 0, st, nbx, nby, nblk, sigx, first, fy ? ws : d_hist);
+        tm.end();
+    }
+    if (fy) {
+        tm.begin("k_corner_smooth");
+        hipLaunchKernelGGL(k_corner_smooth<1>, grid, dim3(BP_NT), 0, st, nbx, nby, nblk, sigy, ws, d_hist);
+        tm.end();
+    }
+    HIP_TRY(hipGetLastError());
     return 0;
 }
 
@@ -224,6 +299,79 @@ int brutus_offdiag_cell_medians(int64_t nobj, int64_t nuse, int nsamps, const in
     tm.begin("k_od_run_quantiles");
     hipLaunchKernelGGL(k_od_run_quantiles, dim3((unsigned)ncell), dim3(OD_RUN_T), 0, st, n, xs, ws, sckeys, nsamps,
                        min_count, 1, (const double *)nullptr, d_med, d_count);
+    tm.end();
+    HIP_TRY(hipGetLastError());
+    tm.collect();
+    return 0;
+}
+
+size_t brutus_corner_workspace_bytes(int64_t nobj, int nbx, int nby) {
+    if (nobj < 1 || nobj > BRUTUS_CORNER_MAX_OBJ || nbx < 1 || nbx > BRUTUS_CORNER_MAX_BINS1D || nby < 1 ||
+        nby > BRUTUS_CORNER_MAX_BINS2D || (nby > 1 && nbx > BRUTUS_CORNER_MAX_BINS2D) ||
+        nobj * nbx * nby > BRUTUS_CORNER_MAX_CELLS)
+        return 0;
+    return corner_ws_bytes(nobj, nbx, nby);
+}
+
+int brutus_corner_hist1d(int64_t nobj, int nsamps, const int32_t *d_idx, const double *d_dist,
+                         const double *d_red, const double *d_dred, const double *d_weights,
+                         int64_t nmodel, int nlab, const double *d_labels, int col, int nbins, double sigma,
+                         const double *d_spans, double *d_hist, void *d_ws, size_t ws_bytes, void *stream) {
+    if (int rc = corner_args(nobj, nsamps, nmodel, nlab, col, -1, nbins, 1, BRUTUS_CORNER_MAX_BINS1D, sigma, 0.,
+                             d_idx, d_dist, d_red, d_dred, d_labels, d_spans, d_hist))
+        return rc;
+    if (sigma > 1e-15 && (!d_ws || ws_bytes < corner_ws_bytes(nobj, nbins, 1)))
+        return fail(BRUTUS_EINVAL, "corner workspace too small: %zu < %zu bytes", d_ws ? ws_bytes : (size_t)0,
+                    corner_ws_bytes(nobj, nbins, 1));
+    hipStream_t st = (hipStream_t)stream;
+    Timer tm(st);
+    if (int rc = corner_panel(tm, nobj, nsamps, d_idx, d_dist, d_red, d_dred, d_weights, nmodel, nlab, d_labels, col,
+                              -1, nbins, 1, sigma, 0., d_spans, d_hist, (double *)d_ws, st))
+        return rc;
+    tm.collect();
+    return 0;
+}
+
+int brutus_corner_hist2d(int64_t nobj, int nsamps, const int32_t *d_idx, const double *d_dist,
+                         const double *d_red, const double *d_dred, const double *d_weights,
+                         int64_t nmodel, int nlab, const double *d_labels, int colx, int coly, int nbx,
+                         int nby, double sigx, double sigy, const double *d_spans, int nlev,
+                         const double *d_levels, double *d_hist, double *d_lev, void *d_ws, size_t ws_bytes,
+                         void *stream) {
+    if (int rc = corner_args(nobj, nsamps, nmodel, nlab, colx, coly, nbx, nby, BRUTUS_CORNER_MAX_BINS2D, sigx, sigy,
+                             d_idx, d_dist, d_red, d_dred, d_labels, d_spans, d_hist))
+        return rc;
+    if (coly < 0) return fail(BRUTUS_EINVAL, "bad corner dimensions (column %d)", coly);
+    if (nlev < 1 || nlev > BRUTUS_CORNER_MAX_LEVELS) return fail(BRUTUS_EINVAL, "bad corner level count (nlev=%d)", nlev);
+    if (!d_levels || !d_lev) return fail(BRUTUS_EINVAL, "NULL pointer");
+    if (!d_ws || ws_bytes < corner_ws_bytes(nobj, nbx, nby))
+        return fail(BRUTUS_EINVAL, "corner workspace too small: %zu < %zu bytes", d_ws ? ws_bytes : (size_t)0,
+                    corner_ws_bytes(nobj, nbx, nby));
+    hipStream_t st = (hipStream_t)stream;
+    Timer tm(st);
+    const int cells = nbx * nby;
+    double *ws = (double *)d_ws;
+    double *sorted = (double *)((char *)d_ws + corner_ws_bytes(nobj, nbx, nby) / 2);
+    if (int rc = corner_panel(tm, nobj, nsamps, d_idx, d_dist, d_red, d_dred, d_weights, nmodel, nlab, d_labels, colx,
+                              coly, nbx, nby, sigx, sigy, d_spans, d_hist, ws, st))
+        return rc;
+    // every panel's cells in descending order, then the levels (the first half of ws is free again)
+    const auto begin = rocprim::make_transform_iterator(rocprim::make_counting_iterator(0u),
+                                                        CornerOffsets{(unsigned)cells});
+    size_t need = 0;
+    HIP_TRY(rocprim::segmented_radix_sort_keys_desc((void *)nullptr, need, (const double *)d_hist, sorted,
+                                                    (unsigned)(nobj * cells), (unsigned)nobj, begin, begin + 1, 0u,
+                                                    64u, st));
+    if (int rc = od_reserve(g_od_tmp, need, st)) return rc;
+    tm.begin("corner_segmented_sort");
+    const hipError_t e = rocprim::segmented_radix_sort_keys_desc(
+        (void *)g_od_tmp.p, need, (const double *)d_hist, sorted, (unsigned)(nobj * cells), (unsigned)nobj, begin,
+        begin + 1, 0u, 64u, st);
+    tm.end();
+    HIP_TRY(e);
+    tm.begin("k_corner_levels");
+    hipLaunchKernelGGL(k_corner_levels, dim3((unsigned)nobj), dim3(CORNER_LEV_T), 0, st, cells,
+                       (const double *)sorted, ws, nlev, d_levels, d_lev);
     tm.end();
     HIP_TRY(hipGetLastError());
     tm.collect();

@@ -17,8 +17,8 @@ from .galprior import (gal_lnprior, logn_disk, logn_halo, logp_age_from_feh,   #
                        logp_feh)
 
 # the reference's `brutus.pdf.__all__` (pdf.py:30-35), plus the table type of the Bayestar-free
-# dust interface, the per-object posterior summaries, the posterior-predictive check and the
-# photometric-offset residual maps
+# dust interface, the per-object posterior summaries, the posterior-predictive check, the
+# photometric-offset residual maps and the corner-plot marginals
 __all__ = ["imf_lnprior", "ps1_MrLF_lnprior", "parallax_lnprior",
            "scale_parallax_lnprior", "parallax_to_scale",
            "logn_disk", "logn_halo",
@@ -28,7 +28,8 @@ __all__ = ["imf_lnprior", "ps1_MrLF_lnprior", "parallax_lnprior",
            "LOSTable", "DistancePriorTable", "dist_tables",
            "posterior_quantiles", "PosteriorSummary",
            "posterior_predictive", "predictive_seds", "PosteriorPredictive", "observed_sed",
-           "offset_residuals", "offset_hist", "offset_map", "OffsetDiagnostics"]
+           "offset_residuals", "offset_hist", "offset_map", "OffsetDiagnostics",
+           "posterior_corner", "PosteriorCorner", "CornerResult"]
 
 
 def _kroupa_segment(m, alpha_low, alpha_high, mass_break):
@@ -660,7 +661,8 @@ def _bin_pdfs_device(data, regenerate, cdf, ebv, dist_type, lndistprior, coord, 
     return out, xbins, ybins
 
 
-# ---- per-object posterior summaries: the quantile half of `plotting.cornerplot` --------------
+# ---- per-object posterior summaries: the quantile half of `plotting.cornerplot` (the histogram
+# half: PosteriorCorner, below) ----
 #: the four columns that follow the labels (reference plotting.py:302)
 _SUMMARY_DRAW_NAMES = ("av", "rv", "parallax", "dist")
 _SUMMARY_Q = (0.025, 0.16, 0.5, 0.84, 0.975)
@@ -869,6 +871,392 @@ def posterior_quantiles(idxs, data, params, q=_SUMMARY_Q, weights=None, names=No
     q = _summary_q(q)
     _summary_shapes(idxs, data, weights)
     return _summary_host(idxs, data, weights, table, q), list(labels) + list(_SUMMARY_DRAW_NAMES)
+
+
+# ---- corner-plot marginals: the histogram half of `plotting.cornerplot` ----------------------
+#: bytes of OUTPUT a chunk of objects may take on the device (a 2-D panel's workspace is twice
+#: that panel again)
+_CORNER_CHUNK_LIMIT = 1 << 30
+_CORNER_SIGMA_1D, _CORNER_SIGMA_2D = 10., 2.      # reference plotting.py:405, 1509
+
+
+def _corner_levels_default():
+    return 1.0 - np.exp(-0.5 * np.arange(0.5, 2.1, 0.5) ** 2)       # plotting.py:1475
+
+
+def _corner_bins(s, per_sigma, sigma, cap, what):
+    """`(bins, sigma)` of one `smooth` value: an int is a bin count, a float `s` gives
+    `int(round(per_sigma / s))` bins filtered with `sigma` bins."""
+    if isinstance(s, (int, np.integer)) and not isinstance(s, (bool, np.bool_)):
+        n, sig = int(s), 0.
+    elif isinstance(s, (float, np.floating)):
+        if not s > 0.:
+            raise ValueError("a float `smooth` must be > 0; got %r" % (s,))
+        n, sig = int(round(per_sigma / float(s))), sigma
+    else:
+        raise ValueError("`smooth` takes ints (bins) and floats (a fraction of the span); got %r" % (s,))
+    if not 1 <= n <= cap:
+        raise ValueError("smooth = %r gives %d bins for %s; it takes 1 to %d" % (s, n, what, cap))
+    return n, sig
+
+
+def _corner_plan(names, smooth, span, pairs, levels):
+    """The arguments of `PosteriorCorner` resolved against the columns `names`, with every
+    caller mistake reported: a dict of `smooth` (per column), `bins1d`, `sigma1d`, `pairs`
+    [(i, j)], `bins2d` [(nbx, nby)], `sigma2d` [(sx, sy)], `span` [(lo, hi) or fraction],
+    `levels`."""
+    from . import _lib
+    ncol = len(names)
+    if isinstance(smooth, (int, float, np.integer, np.floating)):
+        smooth = [smooth] * ncol
+    smooth = list(smooth)
+    if len(smooth) != ncol:
+        raise ValueError("`smooth` must be one value or one per column (%d: %s); got %d: %r"
+                         % (ncol, ", ".join(names), len(smooth), smooth))
+    one = [_corner_bins(s, 10., _CORNER_SIGMA_1D, _lib.CORNER_MAX_BINS1D, "a 1-D panel") for s in smooth]
+    if span is None:
+        span = [0.99] * ncol
+    span = list(span)
+    if len(span) != ncol:
+        raise ValueError("`span` must hold one entry per column (%d: %s); got %d: %r"
+                         % (ncol, ", ".join(names), len(span), span))
+    spans = []
+    for sp in span:
+        try:
+            lo, hi = sp
+        except (TypeError, ValueError):
+            f = float(sp)
+            if not 0. <= f <= 1.:
+                raise ValueError("a fractional `span` must lie in [0, 1]; got %r" % (sp,))
+            spans.append(f)
+        else:
+            lo, hi = np.sort(np.asarray([lo, hi], dtype=np.float64))      # plotting.py:397
+            spans.append((float(lo), float(hi)))
+
+    def column(c):
+        if isinstance(c, str):
+            if c not in names:
+                raise ValueError("unknown column %r in `pairs`; the columns are %s" % (c, ", ".join(names)))
+            return names.index(c)
+        if isinstance(c, (int, np.integer)) and not isinstance(c, bool) and -ncol <= c < ncol:
+            return int(c) % ncol
+        raise ValueError("unknown column %r in `pairs`; the columns are %s" % (c, ", ".join(names)))
+
+    if pairs is None:
+        pairs = [(i, j) for i in range(ncol) for j in range(i)]           # plotting.py:361, 444
+    else:
+        got = []
+        for pr in pairs:
+            if isinstance(pr, str) or len(pr) != 2:
+                raise ValueError("`pairs` holds (column, column) entries; got %r" % (pr,))
+            i, j = column(pr[0]), column(pr[1])
+            if i == j:
+                raise ValueError("a pair needs two different columns; got %r" % (pr,))
+            got.append((i, j))
+        pairs = got
+    two = [tuple(_corner_bins(smooth[c], 2., _CORNER_SIGMA_2D, _lib.CORNER_MAX_BINS2D, "an axis of a 2-D panel")
+                 for c in (j, i)) for i, j in pairs]
+    levels = _corner_levels_default() if levels is None else np.atleast_1d(np.asarray(levels, dtype=np.float64))
+    if levels.ndim != 1 or not 1 <= levels.size <= _lib.CORNER_MAX_LEVELS or np.isnan(levels).any():
+        raise ValueError("`levels` must hold 1 to %d values; got %r" % (_lib.CORNER_MAX_LEVELS, levels))
+    return dict(smooth=smooth, bins1d=[n for n, _ in one], sigma1d=[s for _, s in one], pairs=pairs,
+                bins2d=[(x[0], y[0]) for x, y in two], sigma2d=[(x[1], y[1]) for x, y in two], span=spans,
+                levels=np.ascontiguousarray(levels))
+
+
+def _corner_levels(H, levels):
+    """The contour levels of one panel, reference plotting.py:1525-1536 without the nudge."""
+    flat = H.flatten()
+    flat = flat[np.argsort(flat)[::-1]]
+    with np.errstate(all="ignore"):
+        sm = np.cumsum(flat)
+        sm /= sm[-1]
+        V = np.empty(len(levels))
+        for i, v0 in enumerate(levels):
+            below = flat[sm <= v0]
+            V[i] = below[-1] if below.size else flat[0]
+    V.sort()
+    return V
+
+
+def _corner_span_ok(spans):
+    """Where `(lo, hi)` of `spans (..., 2)` is a range to bin in: finite and lo < hi."""
+    lo, hi = spans[..., 0], spans[..., 1]
+    if isinstance(spans, np.ndarray):
+        with np.errstate(all="ignore"):
+            return np.isfinite(lo) & np.isfinite(hi) & (lo < hi)
+    import torch
+    return torch.isfinite(lo) & torch.isfinite(hi) & (lo < hi)
+
+
+class CornerResult(object):
+    """What `PosteriorCorner` and `posterior_corner` return, as numpy arrays or device tensors:
+    `names` (the columns), `pairs` [(i, j)] (x is column j), `spans (Nobj, Ncol, 2)`,
+    `valid (Nobj, Ncol)`, `hist1d` (one `(Nobj, nbins_c)` per column), `hist2d` (one
+    `(Nobj, nbx, nby)` per pair), `levels (Nobj, Npairs, Nlev)`, `bins1d`, `bins2d`."""
+
+    def __init__(self, names, plan, spans, valid, hist1d, hist2d, levels):
+        self.names, self.pairs = list(names), list(plan["pairs"])
+        self.bins1d, self.bins2d = list(plan["bins1d"]), list(plan["bins2d"])
+        self.spans, self.valid, self.hist1d, self.hist2d, self.levels = spans, valid, hist1d, hist2d, levels
+
+    def edges(self, col, nbins=None):
+        """`(Nobj, nbins + 1)`: every object's bin edges of column `col` (a name or an index),
+        `numpy.linspace(lo, hi, nbins + 1)`; `nbins` defaults to the column's 1-D panel (an axis
+        of a 2-D panel has `bins2d[p]`)."""
+        c = self.names.index(col) if isinstance(col, str) else int(col)
+        n = self.bins1d[c] if nbins is None else int(nbins)
+        lo, hi = self.spans[:, c, 0], self.spans[:, c, 1]
+        if isinstance(self.spans, np.ndarray):
+            with np.errstate(all="ignore"):
+                step = (hi - lo) / n
+                e = np.arange(n + 1)[None, :] * step[:, None]
+                e += lo[:, None]
+        else:
+            import torch
+            # (a tensor divisor: torch divides by a Python number as a product with its reciprocal)
+            step = (hi - lo) / torch.full_like(lo, n)
+            e = torch.arange(n + 1, dtype=torch.float64, device=lo.device)[None, :] * step[:, None]
+            e += lo[:, None]
+        e[:, -1] = hi
+        return e
+
+
+def _corner_host(idxs, data, weights, table, names, plan):
+    """The host form: `numpy.histogram`, `numpy.histogram2d` and `scipy.ndimage.gaussian_filter`
+    per object and panel inside spans from `utils.quantile`."""
+    from scipy.ndimage import gaussian_filter
+    idxs = np.asarray(idxs)
+    dists, reds, dreds = (np.asarray(a, dtype=np.float64) for a in data)
+    weights = None if weights is None else np.asarray(weights, dtype=np.float64)
+    nobj, nsamps = idxs.shape
+    nlab, ncol, levels = table.shape[1], table.shape[1] + 4, plan["levels"]
+    spans = np.empty((nobj, ncol, 2))
+    hist1d = [np.empty((nobj, n)) for n in plan["bins1d"]]
+    hist2d = [np.empty((nobj,) + b) for b in plan["bins2d"]]
+    lev = np.empty((nobj, len(plan["pairs"]), levels.size))
+    ones = np.ones(nsamps)
+    cols = np.empty((ncol, nsamps))
+    for o in range(nobj):
+        ok = (idxs[o] >= 0) & (idxs[o] < table.shape[0])
+        cols[:nlab] = np.nan
+        cols[:nlab, ok] = table[idxs[o][ok].astype(np.int64)].T
+        with np.errstate(all="ignore"):
+            cols[nlab:] = reds[o], dreds[o], 1. / dists[o], dists[o]
+        w = ones if weights is None else weights[o]
+        for c, sp in enumerate(plan["span"]):
+            if isinstance(sp, tuple):
+                spans[o, c] = sp
+            else:
+                spans[o, c] = _column_quantiles(cols[c], w, np.array([0.5 - 0.5 * sp, 0.5 + 0.5 * sp]),
+                                                weights is not None)
+        good = _corner_span_ok(spans[o])
+        with np.errstate(all="ignore"):
+            for c in range(ncol):
+                if not good[c]:
+                    hist1d[c][o] = np.nan
+                    continue
+                n, _ = np.histogram(cols[c], bins=plan["bins1d"][c], range=tuple(spans[o, c]), weights=w)
+                hist1d[c][o] = gaussian_filter(n, plan["sigma1d"][c]) if plan["sigma1d"][c] else n
+            for p, (i, j) in enumerate(plan["pairs"]):
+                if not (good[i] and good[j]):
+                    hist2d[p][o], lev[o, p] = np.nan, np.nan
+                    continue
+                H, _, _ = np.histogram2d(cols[j], cols[i], bins=list(plan["bins2d"][p]),
+                                         range=[tuple(spans[o, j]), tuple(spans[o, i])], weights=w)
+                if any(plan["sigma2d"][p]):
+                    H = gaussian_filter(H, plan["sigma2d"][p])
+                hist2d[p][o], lev[o, p] = H, _corner_levels(H, levels)
+    return CornerResult(names, plan, spans, _corner_span_ok(spans), hist1d, hist2d, lev)
+
+
+class PosteriorCorner(object):
+    """The corner-plot marginals of a whole catalogue on the device: per object the weighted 1-D
+    histogram of every column and the 2-D histogram of chosen pairs of columns, their Gaussian
+    smoothing and the contour levels -- what the second half of reference `plotting.cornerplot`
+    (plotting.py:361-501 with `_hist2d`) computes for one object before it draws.
+
+        C = pdf.PosteriorCorner(labels, smooth=0.02, pairs=[("av", "dist"), ("feh", "mini")])
+        R = C(idxs, (dists, reds, dreds))                 # a CornerResult
+        stack = R.hist2d[0].sum(0)                        # given common spans: a population diagram
+
+    The columns are those of `PosteriorSummary`: the labels in table order without `agewt`, then
+    Av, Rv, parallax and distance -- `C.names`.
+
+    `span`: one entry per column (None: 0.99 everywhere), a `(lo, hi)` pair (sorted) or a
+    fraction `f`, the weighted quantiles `0.5 -+ 0.5 f` of that object's column as
+    `PosteriorSummary` computes them.  `smooth`: one value or one per column; an int `n` gives
+    `n` bins and no smoothing; a float `s` gives `int(round(10 / s))` bins filtered with sigma
+    10 in a 1-D panel, `int(round(2 / s))` bins and sigma 2 along its axis of a 2-D panel
+    (`scipy.ndimage.gaussian_filter`, mode reflect, truncate 4, float64, x first).  `pairs`:
+    None for every `(i, j)` with `j < i` in the reference's order, or a list of `(i, j)`, names
+    or indices; the panel is `numpy.histogram2d(col[j], col[i])`, so x is column j and
+    `R.hist2d[p]` has shape `(Nobj, nbx, nby)`; `[]` gives the 1-D panels only.  `levels`: the
+    enclosed shares of the contours, by default the 0.5, 1, 1.5 and 2 sigma ones.
+
+    Edges are `numpy.linspace(lo, hi, n + 1)` and decide a draw's bin as `numpy.histogram` has
+    it: an interior edge belongs to the bin on its right, `hi` to the last bin; draws outside
+    `[lo, hi]` and NaN draws are dropped.  A bin's weights are added in draw order, so with given
+    spans an unsmoothed histogram has numpy's bytes.  The smoothed ones agree with scipy to a
+    few ulp per tap.  `R.levels[o, p]` are, ascending, the values of the (smoothed) panel at
+    which the cells above enclose each share, by the reference's rule (the last cell of the
+    descending cumulative sum whose share is <= the level; the largest cell if there is none,
+    0 for an empty panel).  The reference's `*= 1 - 1e-4` nudge, which separates equal levels for
+    matplotlib, is drawing and is NOT applied: equal levels come back equal.
+
+    Where the reference raises ("no dynamic range"), a catalogue call marks: an object whose
+    span of a column is not finite with `lo < hi` -- Rv of an Av-only fit, labels of an object
+    `fit()` did not fit (-99) under a fractional span, weights that sum to nothing -- has
+    `R.valid[o, c]` False and NaN in every panel and level that involves the column.  Weights
+    are taken to be finite and not negative.
+
+    The inputs are numpy arrays or tensors already on the device; `device_out=True` leaves the
+    result on the device.  Objects go in chunks whose OUTPUT stays under about 1 GiB (a 100 x 100
+    panel is 80 KB per object and pair); an object's values do not depend on its chunk.  At most
+    4096 draws, 32 labels, 1024 bins in a 1-D panel, 128 per axis of a 2-D one and 16 levels.
+    The 4-tuple `data` that would regenerate draws, the parallax-prior overlay and everything
+    drawn are out of scope.  There is no host fallback: without the library or a GPU the
+    constructor raises `BrutusError`; the host form is `posterior_corner(device=None)`.
+    """
+
+    def __init__(self, params, smooth=10, span=None, pairs=None, levels=None, names=None, device="cuda"):
+        from . import _lib
+        from ._dev import _torch
+        table, labels = _summary_table(params, names)
+        if table.shape[1] > _lib.SUMMARY_MAX_LABELS:
+            raise ValueError("PosteriorCorner takes at most %d labels; got %d"
+                             % (_lib.SUMMARY_MAX_LABELS, table.shape[1]))
+        if table.shape[0] >= 1 << 31 or (table.shape[1] and not table.shape[0]):
+            raise ValueError("PosteriorCorner: the label table must have 1 to 2**31 - 1 rows")
+        self.names = list(labels) + list(_SUMMARY_DRAW_NAMES)
+        self.plan = _corner_plan(self.names, smooth, span, pairs, levels)
+        self.pairs = list(self.plan["pairs"])
+        self.nmodel, self.nlab = table.shape
+        self._L = _lib.lib()
+        self._torch = torch = _torch("PosteriorCorner only runs on the HIP path. The host form is "
+                                     "posterior_corner(device=None).")
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise ValueError("PosteriorCorner needs a GPU device; got %r" % (device,))
+        self._table = to_device(table, np.float64, self.device) if self.nlab else None
+        self._levels = to_device(self.plan["levels"], np.float64, self.device)
+        # the tails the fractional spans need, once: one quantile call serves every column
+        tails = sorted({q for sp in self.plan["span"] if not isinstance(sp, tuple)
+                        for q in (0.5 - 0.5 * sp, 0.5 + 0.5 * sp)})
+        self._tails = tails
+        self._q = to_device(np.array(tails), np.float64, self.device) if tails else None
+
+    def _spans(self, n, nsamps, ins, stream):
+        """`(n, Ncol, 2)` on the device: the given pairs, and `brutus_summary_quantiles` at the
+        tails of the fractional ones."""
+        from . import _lib
+        torch = self._torch
+        ncol = self.nlab + 4
+        spans = torch.empty((n, ncol, 2), dtype=torch.float64, device=self.device)
+        quants = None
+        if self._tails:
+            quants = torch.empty((n, ncol, len(self._tails)), dtype=torch.float64, device=self.device)
+            _lib.check(self._L.brutus_summary_quantiles(n, nsamps, *ins, self.nmodel, self.nlab, self._table,
+                                                        len(self._tails), self._q, quants, stream))
+        for c, sp in enumerate(self.plan["span"]):
+            if isinstance(sp, tuple):
+                spans[:, c, 0], spans[:, c, 1] = sp
+            else:
+                spans[:, c, 0] = quants[:, c, self._tails.index(0.5 - 0.5 * sp)]
+                spans[:, c, 1] = quants[:, c, self._tails.index(0.5 + 0.5 * sp)]
+        return spans
+
+    def __call__(self, idxs, data, weights=None, device_out=False):
+        from . import _lib
+        torch, L, plan = self._torch, self._L, self.plan
+        nobj, nsamps = _summary_shapes(idxs, data, weights)
+        if nsamps > _lib.SUMMARY_MAX_DRAWS:
+            raise ValueError("PosteriorCorner: at most %d draws per object; got %d"
+                             % (_lib.SUMMARY_MAX_DRAWS, nsamps))
+        ncol, nlev = self.nlab + 4, plan["levels"].size
+        shapes = [(ncol, 2)] + [(n,) for n in plan["bins1d"]] + list(plan["bins2d"]) + [(len(self.pairs), nlev)]
+
+        def empty(shape):
+            if device_out:
+                return torch.empty((nobj,) + shape, dtype=torch.float64, device=self.device)
+            return np.empty((nobj,) + shape, dtype=np.float64)
+
+        outs = [empty(sh) for sh in shapes]
+        spans, hist1d, hist2d, levels = outs[0], outs[1:1 + ncol], outs[1 + ncol:-1], outs[-1]
+        if nobj:
+            per_obj = 8 * sum(int(np.prod(sh)) for sh in shapes)
+            cells = max([n for n in plan["bins1d"]] + [nx * ny for nx, ny in plan["bins2d"]])
+            chunk = int(max(1, min(nobj, _lib.CORNER_MAX_OBJ, _CORNER_CHUNK_LIMIT // per_obj,
+                                   _lib.CORNER_MAX_CELLS // cells)))
+            with torch.cuda.device(self.device):
+                stream = _stream_ptr(torch)
+                ws_bytes = max([L.brutus_corner_workspace_bytes(chunk, n, 1)
+                                for n, s in zip(plan["bins1d"], plan["sigma1d"]) if s]
+                               + [L.brutus_corner_workspace_bytes(chunk, nx, ny) for nx, ny in plan["bins2d"]]
+                               + [0])
+                ws = torch.empty(ws_bytes, dtype=torch.uint8, device=self.device) if ws_bytes else None
+
+                def run(dst_all, a, b, shape, call):
+                    """One panel of the chunk [a, b): straight into the result on the device, or
+                    through a staging tensor into the host array."""
+                    dst = dst_all[a:b] if device_out else torch.empty((b - a,) + shape, dtype=torch.float64,
+                                                                      device=self.device)
+                    call(dst)
+                    if not device_out:
+                        torch.from_numpy(dst_all[a:b]).copy_(dst)
+
+                for a in range(0, nobj, chunk):
+                    b = min(nobj, a + chunk)
+                    t_idx = _table_indices(torch, idxs[a:b], self.nmodel, self.device)
+                    t_d, t_r, t_dr = (to_device(x[a:b], np.float64, self.device) for x in data)
+                    t_w = None if weights is None else to_device(weights[a:b], np.float64, self.device)
+                    ins = (t_idx, t_d, t_r, t_dr, t_w)
+                    t_sp = self._spans(b - a, nsamps, ins, stream)
+                    head = (b - a, nsamps) + ins + (self.nmodel, self.nlab, self._table)
+                    for c in range(ncol):
+                        run(hist1d[c], a, b, shapes[1 + c], lambda dst: _lib.check(L.brutus_corner_hist1d(
+                            *head, c, plan["bins1d"][c], plan["sigma1d"][c], t_sp, dst, ws, ws_bytes, stream)))
+                    t_lev = levels[a:b] if device_out else torch.empty((b - a,) + shapes[-1], dtype=torch.float64,
+                                                                       device=self.device)
+                    for p, (i, j) in enumerate(self.pairs):
+                        (nx, ny), (sx, sy) = plan["bins2d"][p], plan["sigma2d"][p]
+                        one = torch.empty((b - a, nlev), dtype=torch.float64, device=self.device)
+                        run(hist2d[p], a, b, shapes[1 + ncol + p], lambda dst: _lib.check(L.brutus_corner_hist2d(
+                            *head, j, i, nx, ny, sx, sy, t_sp, nlev, self._levels, dst, one, ws, ws_bytes, stream)))
+                        t_lev[:, p] = one
+                    if device_out:
+                        spans[a:b] = t_sp
+                    else:
+                        torch.from_numpy(spans[a:b]).copy_(t_sp)
+                        torch.from_numpy(levels[a:b]).copy_(t_lev)
+                if device_out:
+                    torch.cuda.current_stream().synchronize()
+        return CornerResult(self.names, plan, spans, _corner_span_ok(spans), hist1d, hist2d, levels)
+
+
+def posterior_corner(idxs, data, params, smooth=10, span=None, pairs=None, levels=None, weights=None,
+                     names=None, device=None, device_out=False):
+    """The corner-plot marginals of every object as a `CornerResult`: 1-D histograms of every
+    column, 2-D histograms of `pairs`, smoothed as `smooth` says, inside `span`, with the contour
+    `levels` -- see `PosteriorCorner` for the rules.
+
+    `device=None`: numpy on the host, a loop of `numpy.histogram`, `numpy.histogram2d` and
+    `scipy.ndimage.gaussian_filter` over objects and panels.  Otherwise a one-shot
+    `PosteriorCorner` on that GPU; a catalogue in pieces keeps one, whose label table travels
+    once."""
+    if len(data) == 4:
+        raise ValueError("posterior_corner takes the saved draws `(dists, reds, dreds)`; a 4-tuple "
+                         "`(scales, avs, rvs, covs_sar)` would have to be regenerated -- fit with "
+                         "fit(save_dar_draws=True)")
+    if device is not None:
+        C = PosteriorCorner(params, smooth=smooth, span=span, pairs=pairs, levels=levels, names=names,
+                            device=device)
+        return C(idxs, data, weights=weights, device_out=device_out)
+    table, labels = _summary_table(params, names)
+    cols = list(labels) + list(_SUMMARY_DRAW_NAMES)
+    plan = _corner_plan(cols, smooth, span, pairs, levels)
+    _summary_shapes(idxs, data, weights)
+    return _corner_host(idxs, data, weights, table, cols, plan)
 
 
 # ---- the posterior-predictive check: the computing half of `plotting.posterior_predictive` ----

@@ -642,6 +642,9 @@ void brutus_enable_timing(int on);
 /* ---- photometric-offset residual maps: leave-one-band-out residuals, histograms, medians ---- */
 #include "brutus_amd_offdiag.h"
 
+/* ---- corner-plot marginals: per-object 1-D and 2-D histograms, smoothing, contour levels ---- */
+#include "brutus_amd_corner.h"
+
 /* ---- line-of-sight cloud likelihood of many sightlines per call (a ragged field of them) ---- */
 #include "brutus_amd_los_field.h"
 

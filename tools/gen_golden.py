@@ -1727,6 +1727,170 @@ def gen_offset_diag():
           % (total, len(OH.NSAMPS), os.path.getsize(OH.FIXTURE)))
 
 
+def gen_corner():
+    """tests/golden/corner.npz: what reference `plotting.cornerplot` computes before it draws --
+    the 1-D histograms `Axes.hist` returns (`h1hist`) and, for a float `smooth`, the filtered
+    histogram it hands to that call (`h1`: the return of `norm_kde` at plotting.py:405; `hist`
+    bins those values again through `numpy.histogram` with explicit edges, which takes
+    differences of a cumulative sum and so returns them with that sum's rounding), the 2-D panels (`H2[2:-2, 2:-2]` of the first
+    `Axes.contourf` call of a panel) and the contour levels (the fourth argument of
+    `Axes.contour`) -- one object at a time under the Agg backend, the three methods wrapped for
+    the duration of the call; nothing is drawn to a file.  The cases are those of
+    tests/corner_helpers.py: 3 objects at 65 and at 250 draws on a 400-model table of two labels
+    and `agewt`, general weights with zeros, `smooth` an int, a float and a mixed list, spans
+    given and default, four of the fifteen pairs kept.  `plot_contours=True` is passed so that
+    the all-int panels get their levels too.
+
+    An object's draws are picks from a pool of distinct models with one distance, Av, Rv and
+    weight each (ties, as in `post_quantiles`).  The catalogue is redrawn until, against the
+    reference alone:
+    (a) no sample lies within 1e-9 (hi - lo) of a bin edge without being equal to it, for the
+        1-D and the 2-D bin counts of its column;
+    (b) every default-span quantile clears `summary_helpers.margin`;
+    (c) for every stored panel and level |cumulative share - level| > 1e-9;
+    (d) the reference's levels are distinct in every stored panel: its `*= 1 - 1e-4` nudge never
+        fired."""
+    import logging
+    import warnings
+    import matplotlib
+    matplotlib.use("Agg")
+    from matplotlib import pyplot as plt
+    from matplotlib.axes import Axes
+    from brutus import plotting as RP
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import corner_helpers as CH
+    import summary_helpers as H
+    rng = np.random.RandomState(20261021)
+    nmodel = 400
+    params = np.empty(nmodel, dtype=[(n, np.float64) for n in ("mini", "feh", "agewt")])
+    params["mini"], params["feh"] = rng.uniform(0.1, 8., nmodel), rng.uniform(-4., 0.5, nmodel)
+    params["agewt"] = rng.uniform(0., 1., nmodel)
+    res = dict(params=params)
+    logging.disable(logging.WARNING)           # "Too few points to create valid contours."
+
+    def draw_object(n):
+        k = min(max(8, n // 3), 400)
+        pool = rng.choice(nmodel, k, replace=False)
+        pd = np.exp(rng.normal(0., 0.6, k))
+        pr, pdr = rng.uniform(0., 3., k), rng.uniform(2.5, 4.5, k)
+        w = rng.uniform(0.5, 1.5, k)
+        w[rng.uniform(size=k) < 0.2] = 0.
+        pick = rng.randint(0, k, n)
+        return pool[pick].astype(np.int32), pd[pick], pr[pick], pdr[pick], w[pick]
+
+    def run_reference(obj, smooth, span):
+        """`(hist1d [Ncol], panels {(i, j): H}, levels {(i, j): V})` of one object."""
+        idx, d, r, dr, w = obj
+        got = dict(hist=[], contourf=[], contour=[], kde=[])
+        orig = (Axes.hist, Axes.contourf, Axes.contour, RP.norm_kde)
+
+        def norm_kde(a, *args, **kw):
+            out = orig[3](a, *args, **kw)
+            if np.ndim(a) == 1:
+                got["kde"].append(np.array(out))
+            return out
+
+        def hist(self, x, *a, **kw):
+            out = orig[0](self, x, *a, **kw)
+            got["hist"].append((self, np.array(out[0]), np.array(out[1])))
+            return out
+
+        def contourf(self, X, Y, Z, *a, **kw):
+            got["contourf"].append((self, np.array(Z).T[2:-2, 2:-2]))
+            return orig[1](self, X, Y, Z, *a, **kw)
+
+        def contour(self, X, Y, Z, V, *a, **kw):
+            got["contour"].append((self, np.array(V)))
+            return orig[2](self, X, Y, Z, V, *a, **kw)
+
+        Axes.hist, Axes.contourf, Axes.contour, RP.norm_kde = hist, contourf, contour, norm_kde
+        try:
+            with warnings.catch_warnings():
+                warnings.simplefilter("ignore")
+                fig, axes = RP.cornerplot(idx, (d, r, dr), params, weights=w, smooth=smooth, applied_parallax=False,
+                                          span=None if span is None else [tuple(s) for s in span],
+                                          hist2d_kwargs=dict(plot_contours=True))
+        finally:
+            Axes.hist, Axes.contourf, Axes.contour, RP.norm_kde = orig
+        h1, kde = [], iter(got["kde"])
+        for c in range(CH.NCOL):
+            mine = [g for g in got["hist"] if g[0] is axes[c, c]]
+            assert len(mine) == 1
+            filtered = next(kde) if CH.bins_of(smooth, c, False)[1] else mine[0][1]
+            h1.append((filtered, mine[0][2], mine[0][1]))
+        assert next(kde, None) is None
+        panels, levs = dict(), dict()
+        for i, j in CH.PAIRS:
+            panels[i, j] = [g for g in got["contourf"] if g[0] is axes[i, j]][0][1]
+            levs[i, j] = [g for g in got["contour"] if g[0] is axes[i, j]][0][1]
+        plt.close("all")
+        return h1, panels, levs
+
+    reasons = dict()
+
+    def acceptable(obj, n):
+        idx, d, r, dr, w = obj
+        cols = CH.columns(params, idx, d, r, dr)
+        try:
+            if not all(H.margin(x, w, CH.Q_DEFAULT) > H.MARGIN for x in cols):      # (b)
+                return "b"
+        except AssertionError:
+            return "b"
+        default = [U.quantile(x, CH.Q_DEFAULT, weights=w) for x in cols]
+        out = dict()
+        for sname in sorted(CH.SMOOTH):
+            smooth = CH.SMOOTH[sname]
+            for spname, span in (("given", CH.GIVEN), ("default", default)):
+                for c, x in enumerate(cols):                                          # (a)
+                    for two_d in (False, True):
+                        if CH.edge_gap(x, span[c][0], span[c][1], CH.bins_of(smooth, c, two_d)[0]) <= CH.EDGE_GAP:
+                            return "a"
+                h1, panels, levs = run_reference(obj, smooth, None if spname == "default" else span)
+                for pr in CH.PAIRS:
+                    # (d): the rule of plotting.py:1525-1536 on the reference's own panel gives distinct
+                    # values, and they are what it handed to `contour`
+                    raw = CH.levels_direct(panels[pr], CH.LEVELS)
+                    if np.any(np.diff(raw) == 0.) or not np.array_equal(raw, levs[pr]):
+                        return "d"
+                    sh = CH.shares(panels[pr])
+                    if np.min(np.abs(sh[:, None] - CH.LEVELS[None, :])) <= CH.SHARE_GAP:  # (c)
+                        return "c"
+                out[sname, spname] = (h1, panels, levs, np.array(default))
+        return out
+
+    tries = 0
+    for n in CH.NSAMPS:
+        objs, refs = [], []
+        while len(objs) < CH.NOBJ:
+            tries += 1
+            obj = draw_object(n)
+            got = acceptable(obj, n)
+            if isinstance(got, str):
+                reasons[got] = reasons.get(got, 0) + 1
+                print("corner: rejected by (%s); so far %s" % (got, sorted(reasons.items())), flush=True)
+                continue
+            objs.append(obj)
+            refs.append(got)
+        for k, name in enumerate(("idx", "dist", "red", "dred", "w")):
+            res["%s_%d" % (name, n)] = np.stack([o[k] for o in objs])
+        res["spans_%d" % n] = np.stack([r["int", "default"][3] for r in refs])
+        for sname in sorted(CH.SMOOTH):
+            for spname in CH.SPANS:
+                for c in range(CH.NCOL):
+                    res[CH.key("h1_%d" % c, n, sname, spname)] = np.stack([r[sname, spname][0][c][0] for r in refs])
+                    res[CH.key("e1_%d" % c, n, sname, spname)] = np.stack([r[sname, spname][0][c][1] for r in refs])
+                    if CH.bins_of(CH.SMOOTH[sname], c, False)[1]:
+                        res[CH.key("h1hist_%d" % c, n, sname, spname)] = np.stack([r[sname, spname][0][c][2]
+                                                                                  for r in refs])
+                for p, pr in enumerate(CH.PAIRS):
+                    res[CH.key("h2_%d" % p, n, sname, spname)] = np.stack([r[sname, spname][1][pr] for r in refs])
+                    res[CH.key("lev_%d" % p, n, sname, spname)] = np.stack([r[sname, spname][2][pr] for r in refs])
+    logging.disable(logging.NOTSET)
+    np.savez_compressed(CH.FIXTURE, **res)
+    print("wrote corner.npz: %d objects drawn for %d kept (rejections %s): conditions (a)-(d) hold, %d bytes"
+          % (tries, CH.NOBJ * len(CH.NSAMPS), sorted(reasons.items()), os.path.getsize(CH.FIXTURE)))
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     which = sys.argv[1:] or ["loglike", "fit", "helpers", "setup", "galprior",
@@ -1785,3 +1949,5 @@ if __name__ == "__main__":
         gen_post_predictive()
     if "offset_diag" in which:
         gen_offset_diag()
+    if "corner" in which:
+        gen_corner()
